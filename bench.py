@@ -8,10 +8,18 @@ residuals, synthetic window (seed 20260925), forced iterations (canbreak ignored
 step in one launch -> k_linearize with the point step fused in).  N > 1: points are sharded across the ranks,
 one RCCL all-reduce of the stitched system per iteration, replicated solve (strong scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_linearize): algorithmic bytes per launch
-(436 B per residual + 112 B per point) / average launch duration measured with HIP events on the
-launch stream in a separate profiled pass of the same process.  `cpu_baseline` times the oracle (CPU restatement
-of the reference, "port") on this box's host cores with the reference's 6-worker IndexThreadReduce schedule.
+Prints ONE JSON line (rank 0).  A plain run sets the window up, runs --warmup iterations, times ONE block of exactly --steps
+iterations between two fences (`ms_per_step` = that block / --steps), writes the outputs if --dump-outputs is given and prints
+the line.  --dump-outputs DIR: the state the timed iterations left behind (frame states and poses, calibration, inverse depths
+and their Hessians, residual energies and states) as DIR/<name>.npy, float32 / float64, taken right after the first timed block
+so that a plain and a --full run of the same arguments write the same arrays.
+
+--full adds everything else, as before: the timed block repeated until --min-timed-s (default 2 s) has been measured (median
+block reported), the parity checks against the oracle, the kernel timings, `roofline`, `cpu_baseline` and the other windows
+and components (C4 / C5, batched windows, adapter, tracker, tracer, initialiser).  `roofline` is for the dominant kernel
+(k_linearize): algorithmic bytes per launch (436 B per residual + 112 B per point) / average launch duration
+measured with HIP events on the launch stream in a separate profiled pass of the same process.  `cpu_baseline` times the oracle
+(CPU restatement of the reference, "port") on this box's host cores with the reference's 6-worker IndexThreadReduce schedule.
 """
 import argparse
 import json
@@ -186,8 +194,45 @@ def parity_check_dist(win, ba, rank, world, dist, pb, pe, stream, device):
     return out
 
 
-def measure(args, config, rank, local_rank, world, dist, steps, warmup, min_timed_s=2.0, with_parity=True):
-    """One BASELINE window: median time of blocks of EXACTLY `steps` forced GN iterations + the live roofline of k_linearize."""
+GRAPH_CHUNK = 1000          # iterations per enqueue of the timed path at most (see measure: run_steps)
+
+
+def collect_outputs(win, ba, world, dist, pb, pe):
+    """What a caller of the timed path receives after it: frame states and poses, calibration, inverse depths, residual energies and
+    states (float32 / float64).  N > 1: the frame states are replicated, the points and residuals of the other ranks' shards are
+    gathered (all ranks call this).  -> {name: array} on rank 0, None elsewhere."""
+    fr, pts, res = ba.get_frames(), ba.get_points(), ba.get_residuals()
+    idepth, hess = pts["idepth"].copy(), pts["idepth_hessian"].copy()
+    energy, state = res["out"]["state_NewEnergy"].copy(), res["state_state"].copy()
+    if world > 1:
+        mine = (win.residuals["point"] >= pb) & (win.residuals["point"] < pe)
+        parts = [None] * world
+        dist.all_gather_object(parts, {"pb": pb, "pe": pe, "idepth": idepth[pb:pe], "hess": hess[pb:pe], "rows": np.nonzero(mine)[0],
+                                       "energy": energy[mine], "state": state[mine]})
+        if dist.get_rank() != 0:
+            return None
+        for q in parts:
+            idepth[q["pb"]:q["pe"]] = q["idepth"]; hess[q["pb"]:q["pe"]] = q["hess"]
+            energy[q["rows"]] = q["energy"]; state[q["rows"]] = q["state"]
+    return {"frames_state": np.asarray(fr["frames"]["state"], np.float64),
+            "frames_world_to_cam": np.asarray(fr["pre_worldToCam"], np.float64),
+            "calib_value": np.asarray(fr["calib_value"], np.float64),
+            "points_idepth": idepth.astype(np.float32),
+            "points_idepth_hessian": hess.astype(np.float32),
+            "residuals_energy": energy.astype(np.float32),
+            "residuals_state": state.astype(np.float32)}
+
+
+def write_outputs(outputs, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    assert sum(a.nbytes for a in outputs.values()) <= 64 << 20
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def measure(args, config, rank, local_rank, world, dist, steps, warmup, min_timed_s=2.0, with_parity=True, full=True, dump_dir=None):
+    """One BASELINE window: time of blocks of EXACTLY `steps` forced GN iterations (one block when min_timed_s is 0, else the median
+    block) and, with `full`, the parity checks and the live roofline of k_linearize.  dump_dir: write the outputs of the first block."""
     from ldso_amd import synth, binding, dist as ldist
     win = synth.make_config(config)
     if not args.no_prior:
@@ -233,22 +278,36 @@ def measure(args, config, rank, local_rank, world, dist, steps, warmup, min_time
                 dist.all_reduce(rbuf)
                 ba.gn_solve_reduced(rbuf.data_ptr(), it0 + i, 1e-1)
 
+    def run_steps(n, it0):
+        # enqueue_gn captures one HIP graph per (first iteration, count, parity of the handle's buffer sets) and replays it afterwards: n iterations go as
+        # chunks of at most GRAPH_CHUNK (even, so every full chunk replays the same graph); the kernels only distinguish iteration < 2, so later chunks start at 2
+        while n > 0:
+            k = min(n, GRAPH_CHUNK)
+            run(k, it0)
+            n, it0 = n - k, max(it0, 2)
+
     def fence():
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
             torch.cuda.synchronize()
 
-    run(warmup, 0)
+    run_steps(warmup, 0)
+    # capture the graphs of the timed block before the clock starts: its chunk shapes once each, then one more iteration if that left the parity flipped
+    shapes = [min(steps, GRAPH_CHUNK)] + ([steps % GRAPH_CHUNK] if steps > GRAPH_CHUNK and steps % GRAPH_CHUNK else [])
+    for k in shapes:
+        run(k, 2)
+    if sum(shapes) % 2:
+        run(1, 2)
     fence()
-    # The contract times EXACTLY `steps` iterations between two fences.  One such block is < 1 ms at the driver's --steps 20, so
-    # the block is repeated until >= min_timed_s (2 s for the headline window: long enough for the driver's GPU-busy sampling to see
-    # it) have been timed and the MEDIAN block is reported (every block bracketed by the fences, maximum over ranks per block).
-    blocks, total = [], 0.0
-    while (total < min_timed_s or len(blocks) < 3) and len(blocks) < 200000:
+    # The contract times EXACTLY `steps` iterations between two fences.  A plain run (min_timed_s 0) times one such block.  With
+    # min_timed_s > 0 (--full: 2 s for the headline window, long enough for GPU-busy sampling to see it) the block is repeated until
+    # that much has been timed and the MEDIAN block is reported (every block bracketed by the fences, maximum over ranks per block).
+    blocks, total, outputs = [], 0.0, None
+    while not blocks or ((total < min_timed_s or len(blocks) < 3) and min_timed_s > 0 and len(blocks) < 200000):
         fence()
         t0 = time.perf_counter()
-        run(steps, 2)
+        run_steps(steps, 2)
         fence()
         d = time.perf_counter() - t0
         if world > 1:
@@ -256,10 +315,30 @@ def measure(args, config, rank, local_rank, world, dist, steps, warmup, min_time
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             d = float(t.item())
         blocks.append(d); total += d
+        if len(blocks) == 1 and dump_dir is not None:
+            # the state after warmup + the first block of `steps` iterations: the same in a plain and a --full run
+            ba.sync(); fence()
+            outputs = collect_outputs(win, ba, world, dist, pb, pe)
     dt = float(np.median(blocks))
     if windows is not None:
         ba.p2p_check()
     ok = bool(np.all(np.isfinite(ba.get_frames()["frames"]["state"])))
+    if outputs is not None:
+        write_outputs(outputs, dump_dir)
+    headline = {
+        "win": win,
+        "value": round(steps / dt, 2),                       # median of the timed blocks of exactly `steps` iterations
+        "mresiduals_per_s": round(steps * R / dt / 1e6, 3),
+        "ms_per_step": round(dt / steps * 1e3, 5),
+        "workload": f"{config}: {F} KF x {P} pt x 8 px, {win.w}x{win.h}, R={R}, forced GN iterations, "
+                    + ("no prior" if args.no_prior else "synthetic rank-6 marginalisation prior H_M/b_M"),
+        "timed_blocks": len(blocks), "timed_total_ms": round(total * 1e3, 2),
+        "ms_per_step_min_max": [round(min(blocks) / steps * 1e3, 5), round(max(blocks) / steps * 1e3, 5)],
+        "state_finite": ok,
+    }
+    if not full:
+        ba.close()
+        return headline
     parity = parity_check(win, ba, stream) if (with_parity and world == 1 and not dist_path) else None
 
     # ---- roofline of the dominant kernel: separate profiled pass (HIP events around every launch) -------------
@@ -318,12 +397,7 @@ def measure(args, config, rank, local_rank, world, dist, steps, warmup, min_time
                            "share_of_step": round(live / (dt / steps * 1e6), 3),
                            "frac_of_8TBps": round(kb / (max(live, cm.get("rocprofv3_us") or 0.0) * 1e-6) / 8e12, 5) if live > 0 else None})
     return {
-        "win": win,
-        "value": round(steps / dt, 2),                       # median of the timed blocks of exactly `steps` iterations
-        "mresiduals_per_s": round(steps * R / dt / 1e6, 3),
-        "ms_per_step": round(dt / steps * 1e3, 5),
-        "workload": f"{config}: {F} KF x {P} pt x 8 px, {win.w}x{win.h}, R={R}, forced GN iterations, "
-                    + ("no prior" if args.no_prior else "synthetic rank-6 marginalisation prior H_M/b_M"),
+        **headline,
         "roofline": {"bound": "hbm", "kernel": "k_linearize", "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
                      "frac": round(achieved / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_src,
                      "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": round(lin_us, 3),
@@ -333,9 +407,7 @@ def measure(args, config, rank, local_rank, world, dist, steps, warmup, min_time
                      "rocprofv3_avg_us_committed_profile": rocprof_us, "rocprofv3_profile": rocprof_src,
                      "step_algorithmic_bytes": step_bytes, "step_achieved_GBps": round(step_GBps, 2), "step_frac": round(step_GBps / 8000.0, 5),
                      "per_kernel": per_kernel},
-        "timed_blocks": len(blocks), "timed_total_ms": round(total * 1e3, 2),
-        "ms_per_step_min_max": [round(min(blocks) / steps * 1e3, 5), round(max(blocks) / steps * 1e3, 5)],
-        "kernels": ktimes, "state_finite": ok, "parity_vs_oracle": parity,
+        "kernels": ktimes, "parity_vs_oracle": parity,
     }
 
 
@@ -345,13 +417,18 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational C4 / C5 / tracker / tracer / initialiser lines")
+    ap.add_argument("--full", action="store_true", help="also the parity checks, kernel timings, roofline, CPU baseline and the other windows / components (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the state the timed iterations left behind as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the informational C4 / C5 / tracker / tracer / initialiser lines")
     ap.add_argument("--no-prior", action="store_true", help="window without the (synthetic) marginalisation prior H_M / b_M")
-    ap.add_argument("--min-timed-s", type=float, default=2.0, help="repeat the timed block of exactly --steps iterations until this much time has been measured (profiling runs pass a small value)")
+    ap.add_argument("--min-timed-s", type=float, default=None, help="repeat the timed block of exactly --steps iterations until this much time has been measured and report the median block "
+                                                                   "(default: 2 with --full, profiling runs pass a small value; 0 without it: one block)")
     ap.add_argument("--allreduce", choices=["rccl", "p2p"], default="rccl", help="N > 1 (or --force-dist-path): RCCL all-reduce through torch.distributed, or the library's one-shot peer-write exchange (ldso_ba_enqueue_gn_p2p, windows shared as IPC handles)")
     ap.add_argument("--force-dist-path", action="store_true", help="1 GPU only: run the multi-GPU step (reduce_local / solve_reduced) with a no-op all-reduce")
     args = ap.parse_args()
+    if args.min_timed_s is None:
+        args.min_timed_s = 2.0 if args.full else 0.0
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -379,7 +456,7 @@ def main():
             except TypeError:          # older torch without device_id
                 dist.init_process_group("nccl", rank=rank, world_size=world)
 
-    m = measure(args, args.config, rank, local_rank, world, dist, args.steps, args.warmup, min_timed_s=args.min_timed_s)
+    m = measure(args, args.config, rank, local_rank, world, dist, args.steps, args.warmup, min_timed_s=args.min_timed_s, full=args.full, dump_dir=args.dump_outputs)
     win = m.pop("win")
     if rank == 0:
         out = {
@@ -400,15 +477,15 @@ def main():
             "config": {"workload": m["workload"],
                        "arithmetic": "f32 residuals / Jacobians / accumulators as the reference, f64 stitch and solve",
                        "parallelism": "1 GPU" if world == 1 else f"points sharded over {world} GPUs, " + ("RCCL all-reduce" if args.allreduce == "rccl" else "one-shot peer-write all-reduce (ldso_ba_enqueue_gn_p2p)") + " of the stitched system per iteration"},
-            "roofline": m["roofline"],
+            **({"roofline": m["roofline"]} if args.full else {}),
             "timed_blocks": m["timed_blocks"], "timed_total_ms": m["timed_total_ms"], "ms_per_step_min_max": m["ms_per_step_min_max"],
-            "kernels": m["kernels"],
+            **({"kernels": m["kernels"]} if args.full else {}),
             "state_finite": m["state_finite"],
-            "parity_vs_oracle": m["parity_vs_oracle"],
+            **({"parity_vs_oracle": m["parity_vs_oracle"]} if args.full else {}),
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(win)
-        if not args.no_extras and world == 1 and not args.force_dist_path:
+        if args.full and not args.no_extras and world == 1 and not args.force_dist_path:
             # the other BASELINE windows (configs[3], configs[4]) on one GPU, each with its own live roofline and parity check
             for key, cfg in (("c4", "C4"), ("c5", "C5")):
                 if cfg == args.config:

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof
 mkdir -p "$OUT"
 ROOT=$PWD
-B="python $ROOT/bench.py --no-cpu-baseline --min-timed-s 0.05"
+B="python $ROOT/bench.py --full --no-cpu-baseline --min-timed-s 0.05"
 BB="python $ROOT/scripts/bench_batched.py --B 32 --min-timed-s 0.05"
 SQA="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"
 SQB="SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS"

@@ -51,7 +51,7 @@ if kt:
 
 # calibration of the gfx950 FETCH_SIZE unit: scripts/micro/pmc_calib.hip (see profiles/r01_pmc_traffic.json "calibration")
 for cfg in ("C3", "C4", "C5", "B32"):
-    res = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, with --kernel-trace only) around `python bench.py --steps 40 --warmup 5 "
+    res = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, with --kernel-trace only) around `python bench.py --full --steps 40 --warmup 5 "
                    f"--no-cpu-baseline --no-extras --config {cfg}`; KB per launch as reported; corrected = 2 x FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE "
                    "tallies 128-B requests at 64 B; calibrated with scripts/micro/pmc_calib.hip: 256 MB of 4-byte coalesced loads report 0.5000x, stores 1.000x)",
            "config": cfg, "kernels": {}}
