@@ -94,7 +94,7 @@ int ldso_ba_get_image(ldso_ba_t *h, int slot, float *out_w_h_3);
 
 /* K-splits (workgroups) per 16 x 16 tile of the Schur complement in the GN fast path (the device counterpart of AccumulatedSCHessianSSE's per-thread accumulators,
  * AccumulatedSCHessian.cc:53-119: each split owns a range of points and adds its fp32 partial tile into the fp64 system).  8 for a lone window (latency), 4 for the
- * windows of a batch of four or more (throughput; LDSO_BATCH_KS overrides).  Two runs agree bit for bit only under the same number. */
+ * windows of a batch of four or more (throughput).  Two runs agree bit for bit only under the same number. */
 int ldso_ba_set_reduce_splits(ldso_ba_t *h, int splits);
 /* Describe the window: EnergyFunctional::frames / allPoints / p->residuals after makeIDX
  * (EnergyFunctional.cc:380-401).  image_slot[f] = slot holding frame f's image.  linJ / lin_res_toZeroF

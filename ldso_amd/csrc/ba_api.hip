@@ -403,7 +403,6 @@ static int create_body(ldso_ba *H, int device, int w, int h, int max_frames, int
     CHK(hipHostGetDevicePointer((void **) &H->d_stop, H->h_stop, 0));
     memset(&H->B, 0, sizeof(H->B));
     memset(&H->D, 0, sizeof(H->D));
-    if (const char *e = getenv("LDSO_REDUCE_KS")) { const int v = atoi(e); if (v >= 1 && v <= 16) H->reduceSplits = v; }          // tuning knob: ldso_ba_set_reduce_splits for every handle of the process
     BaPtrs &B = H->B;
     const size_t F = max_frames, P = max_points, FS = H->FSmax, nmax = 8 * F + 4;
     DA(B.frames, F); DA(B.calib, 1); DA(B.pairs, F * F); DA(B.pairRt, F * F * 12);
@@ -1661,7 +1660,7 @@ struct ldso_ba_batch {
     int chunkPoints = 0;               // the chunking ldso_ba_batch_create gave its windows
     int totalChunks = 0, totalReduce = 0, FS = 0, cur = 0;
     int n0 = 0;                        // windows in the first half (= all of them for batches under 4 windows)
-    int ks = LD_SCT_KS;                // K-splits per Schur tile of the batched reduction (ldso_ba_batch_create: 4 from 4 windows on, LDSO_BATCH_KS)
+    int ks = LD_SCT_KS;                // K-splits per Schur tile of the batched reduction (ldso_ba_batch_create: 4 from 4 windows on)
     int halfChunks[2] = {0, 0}, halfReduce[2] = {0, 0};
     // Balanced launches (round 6): workgroup w of a batched k_linearize works through the blocks [wgStart[w], wgStart[w + 1]) of its launch's table, cut by
     // ldso_ba_batch_create so that every workgroup carries the same load.  wg[0] = the whole batch, wg[1] / wg[2] = the halves; empty: one block per workgroup
@@ -1828,21 +1827,18 @@ int ldso_ba_batch_create(ldso_ba_t *const *handles, int n, ldso_ba_batch_t **out
         long total = 0;
         for (int i = 0; i < n; i++) total += handles[i]->D.P;
         int ppw = (int) (total / ((long) H0->numCU * LD_WAVES));               // points per wavefront slot of the chip
-        const char *e = getenv("LDSO_BATCH_PPW");                              // kernel experiments: the regular chunks of rounds 3-5 with this many points per wavefront
         bool every = true;
         for (int i = 0; i < n; i++) every = every && handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty();
-        if (ppw > 1 && every && !(e && *e)) {
+        if (ppw > 1 && every) {
             // Round 6: every workgroup of a launch gets the SAME load.  With regular chunks the batched launch ran as ceil(chunks / CUs) rounds of equal
             // workgroups - 1344 on 256 CUs: the last round a quarter full - and every chunk paid its fixed costs (staging, pipeline fill, block reduction:
             // about two points per wavefront) for six points per wavefront.  Now one workgroup per CU and launch works through a run of chunks cut to measure.
-            int c0 = 2 * LD_WAVES;          // fixed cost of a chunk in points (two rounds of the workgroup's wavefronts)
-            if (const char *ec = getenv("LDSO_BATCH_C0")) { if (*ec) c0 = std::max(0, atoi(ec)); }          // kernel experiments
+            const int c0 = 2 * LD_WAVES;          // fixed cost of a chunk in points (two rounds of the workgroup's wavefronts)
             const int n0 = (n >= 4) ? n / 2 : n;
             // A half-batch launch does not take every CU: the other half's k_reduce_batch_dense / k_gn_solve_batch run beside it (two streams), and a workgroup that
             // owns its CU for the whole launch leaves them nothing to start on.  Measured (32 windows, MI355X): 128 / 192 / 208 / 224 / 240 / 256 workgroups per half
             // -> 141.6 / 159.2 / 162.2 / 168.3 / 167.7 / 149.5 k window-iterations/s (profiles/r06_batch_sweeps.log).
-            int nWG = (n >= 4) ? std::max(1, H0->numCU * 7 / 8) : H0->numCU;
-            if (const char *ew = getenv("LDSO_BATCH_NWG")) { if (*ew) nWG = std::max(1, atoi(ew)); }          // kernel experiments
+            const int nWG = (n >= 4) ? std::max(1, H0->numCU * 7 / 8) : H0->numCU;
             std::vector<std::vector<int32_t>> cuts((size_t) n);
             balance_batch(handles, 0, n0, nWG, c0, cuts, wgTab[1]);
             if (n0 < n) balance_batch(handles, n0, n, nWG, c0, cuts, wgTab[2]);
@@ -1859,9 +1855,8 @@ int ldso_ba_batch_create(ldso_ba_t *const *handles, int n, ldso_ba_batch_t **out
             Bt_chunk = (int) std::max<long>(1, (total + chunks / 2) / chunks);
             balanced = true;
         } else {
-            if (e && *e) ppw = atoi(e);
-            ppw = ppw < 1 ? 1 : ppw > 8 ? 8 : ppw;
-            if (!(e && *e) && ppw > 6) ppw = 6;
+            // regular chunks of up to 6 points per wavefront (round 4, B = 32: 122.0 / 139.3 / 128.6 k window-iterations/s at 4 / 6 / 8)
+            ppw = ppw < 1 ? 1 : ppw > 6 ? 6 : ppw;
             const int CH = ppw * LD_WAVES;
             Bt_chunk = ppw > 1 ? CH : 0;
             for (int i = 0; i < n; i++) if (handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty() && ppw > 1) {      // ppw == 1: the single-window chunking already is the right one
@@ -1882,7 +1877,6 @@ int ldso_ba_batch_create(ldso_ba_t *const *handles, int n, ldso_ba_batch_t **out
     // K-splits per Schur tile of the batched reduction: a lone window spreads every 16 x 16 tile of its Schur complement over LD_SCT_KS = 8 workgroups (latency); the
     // windows of a batch fill the chip anyway and halve the workgroups and the fp64 atomics (round 6, A/B on one box: 4 -> +3.3 % window-iterations/s at B = 32, 2 -> -11 %)
     Bt->ks = (n >= 4) ? 4 : LD_SCT_KS;
-    if (const char *e = getenv("LDSO_BATCH_KS")) { const int v = atoi(e); if (v >= 1 && v <= 16) Bt->ks = v; }
     Bt->FS = H0->D.FS;
     Bt->Dmax = H0->D;
     for (int i = 0; i < n; i++) if (handles[i]->D.F > Bt->Dmax.F) Bt->Dmax = handles[i]->D;

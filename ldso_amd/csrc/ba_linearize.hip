@@ -21,30 +21,6 @@
 #include <type_traits>
 #include "ba_dev.h"
 
-#ifndef LD_PAIR
-#define LD_PAIR 1          // windows of 9..12 key frames: two points share the pass of the second slot group (k_linearize_one<2, true>)
-#endif
-#ifndef LD_MFMA_SUMS
-#define LD_MFMA_SUMS 0
-#endif
-#ifndef LD_OPAQUE_K
-#define LD_OPAQUE_K 0          // experiment (round 6): masks derived from the lane index recomputed per point instead of kept in (spilled) SGPR pairs - 37 fewer vector instructions in the kernel and SLOWER (B = 32: 173 against 160 us, C5 44.2 against 43.1, one box): not used
-#endif
-#ifndef LD_LDG_PLAIN
-#define LD_LDG_PLAIN 0
-#endif
-#ifndef LD_STASH
-#define LD_STASH 1          // the records of the point in work wait in LDS (see STASH in linearize_body)
-#endif
-#ifndef LD_STASH_LM
-#define LD_STASH_LM 1          // ... and its uniform fields are read from there (ds_read_b32) instead of by v_readlane / DPP broadcasts
-#endif
-#ifndef LD_PEEL
-#define LD_PEEL 1
-#endif
-#ifndef LD_PIPE_ARGS
-#define LD_PIPE_ARGS 1          // the argument-based kernels (fix / linearised / marginalisation / dump passes) up to 8 key frames run the software pipeline too
-#endif
 #define RES_IN 0
 #define RES_OOB 1
 #define RES_OUTLIER 2
@@ -133,15 +109,6 @@ __device__ __forceinline__ float seq8(float x, int k, int lane) {
 // butterflies were measured against this in rounds 3 and 4: bit-identical, 2 % slower in every configuration - removed.
 __device__ __forceinline__ float sum_slots(float x, int a16, int a32) {
     x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xF, 0xF, true));
-#if LD_MFMA_SUMS
-    // experiment (round 6): the sum over the four 16-lane rows on the fp32 matrix core instead of two ds_bpermute butterflies - v_mfma_f32_16x16x4_f32 with A = 1:
-    // D[i][j] = sum_k B[k][j], B[k][j] = the value of lane 16 k + j, every lane l reads column j = l & 15 back (all four result registers hold the same sum)
-    (void) a16; (void) a32;
-    typedef float v4f_ __attribute__((ext_vector_type(4)));
-    const v4f_ z = {0.0f, 0.0f, 0.0f, 0.0f};
-    const v4f_ d = __builtin_amdgcn_mfma_f32_16x16x4f32(1.0f, x, z, 0, 0, 0);
-    return d[0];
-#endif
     x += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(a16, __builtin_bit_cast(int, x)));
     x += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(a32, __builtin_bit_cast(int, x)));
     return x;
@@ -162,9 +129,6 @@ __device__ __forceinline__ float sum_half(float x, int a16) {
 typedef int v16i_t __attribute__((ext_vector_type(16)));
 template <bool DESC, int OFF> static __device__ __forceinline__ v16i_t ldg16(const void *base) {
     v16i_t t;
-#if LD_LDG_PLAIN
-    if (DESC) return *(const __attribute__((address_space(4))) v16i_t *) ((unsigned long long) base + OFF);          // experiment: the compiler's own scalar load, free to be hoisted / merged
-#endif
     if (DESC) asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "s"(base), "n"(OFF) : "memory");
     else __builtin_memcpy(&t, (const char *) base + OFF, 64);          // kernel arguments: the compiler's own scalar loads
     return t;
@@ -351,8 +315,7 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
     // out of that loop it stays live through the point loop - 24 VGPRs, measured: 184 -> 208, and with them the CU sharing with the other half-batch's reduce kernel)
     int tid_ = (int) threadIdx.x;
     asm volatile("" : "+v"(tid_));
-    const int tid = tid_, wave = tid >> 6, lane = tid & 63, s = lane >> 3, k = lane & 7, k_ = k, lane_ = lane;
-    (void) k_; (void) lane_;
+    const int tid = tid_, wave = tid >> 6, lane = tid & 63, s = lane >> 3, k = lane & 7;
     const long long t0_ = wall_clock64();
 #define LSTAMP(i) do { if (LD_STAMP_ON && chunk == 0 && tid == 0) B.energyLog[8 + (i)] = (double) (wall_clock64() - t0_); } while (0)
 
@@ -525,9 +488,6 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
     // 8..11 of point A, lanes 32..63 the targets 8..11 of point B - pu / pv / idp are per-lane values then
     auto front_xT = [&](auto lc, auto gc, auto mc, const PtIn<NSG> &q, const float pu, const float pv, const float idp, TapsG &T) {
         constexpr int g = decltype(gc)::value, MODE = decltype(mc)::value;
-#if LD_OPAQUE_K
-        int k = k_; asm volatile("" : "+v"(k));
-#endif
         const float h1 = qmlane(lc, J5{}, q, g);          // the state of the slot record: m of lane 5 of the group
         const int qState = __builtin_bit_cast(int, h1);
         const int t = (MODE == 3) ? 8 + (s & 3) : g * 8 + s;
@@ -624,9 +584,6 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
             else if constexpr (MODE == 3) X += sum_half(v, a16);
             else { const float s_ = sum_slots(v, a16, a32); X += (half == MODE - 1) ? s_ : 0.0f; }
         };
-#if LD_OPAQUE_K
-        int k = k_; asm volatile("" : "+v"(k));
-#endif
         // the uniform scalars of the slot record sit in the m of lanes 3 (energy), 5 (state), 6 (activity) of its 8-lane group
         int qState[NSG], qActive[NSG];
         float qEnergy[NSG];
@@ -950,9 +907,6 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
 
     auto back_end = [&](const unsigned p, const PtIn<NSG> &q) {
         (void) q;
-#if LD_OPAQUE_K
-        int lane = lane_, k = k_; asm volatile("" : "+v"(lane), "+v"(k));
-#endif
         // ================= per-point Schur quantities (AccumulatedSCHessian.cc:9-31) =====================
         float HdiF = 0, bdSumF = 0, idH = 0;
         float Hc0 = HcdA0 + HcdL0, Hc1 = HcdA1 + HcdL1, Hc2 = HcdA2 + HcdL2, Hc3 = HcdA3 + HcdL3;
@@ -1127,13 +1081,13 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
         // The records of point i + 2 are in flight in both cases.
         using G0 = std::integral_constant<int, 0>;
         using G1 = std::integral_constant<int, NSG - 1>;
-        constexpr bool PIPE = DESC || (NSG == 1 && LD_PIPE_ARGS);
+        constexpr bool PIPE = DESC || NSG == 1;
         // One slot group per point, the batched kernel (round 6, second half): the records of the point in work are parked in the wavefront's own LDS by the
         // iteration in front (two ds_write_b128) and read back where the back half starts (two ds_read_b128) instead of being rotated through a third register set
         // (qa = qb, qb = qc: 16 vector moves per point of an issue-bound loop; LDS instructions have their own issue port)
         // (the batched kernel only: in k_linearize_one a wavefront has one to three points - nothing to amortise the LDS round trips and the peeled copy of the loop
         // body against; measured at C4, 12 points per chunk: 16.36 us with the stash, 15.85 without, profiles/r06_linearize_peel_stash_ab.log)
-        constexpr bool STASH = DESC && !ONE && NSG == 1 && !HAS_L && !FIX && LD_STASH;
+        constexpr bool STASH = DESC && !ONE && NSG == 1 && !HAS_L && !FIX;
         int par = 0;
         float *const wRec = sRec + wave * 1024;                      // [parity][half][lane][4 dwords]
         float *const myRec = wRec + lane * 4;
@@ -1202,7 +1156,7 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
                     // (pinned: the sample is plain arithmetic, which the compiler sinks to its first use - behind the next point's tap loads, with the old taps alive across
                     // them in a second register set and 14 moves per point)
                     asm volatile("" : "+v"(ha.h0), "+v"(ha.h1), "+v"(ha.h2), "+v"(ha.Ku), "+v"(ha.Kv));
-                    using LMS = std::bool_constant<STASH && LD_STASH_LM>;
+                    using LMS = std::bool_constant<STASH>;
                     if constexpr (STASH) { stash(par ^ 1, qb); qb.ls = wRec + (par ^ 1) * 512; }
                     if (n1) sb = pstepT(LMS{}, p1, qb);          // (the fused point step stores: only for a real next point)
                     front_gT(LMS{}, G0{}, qb, sb, ta);
@@ -1243,7 +1197,7 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
                 }
                 pi += LD_WAVES;
             };
-            if constexpr (STASH && LD_PEEL) {
+            if constexpr (STASH) {
                 // The first point peeled off the loop: the wait for the next point's records (the top of the body) counts the stores issued behind their loads, and at
                 // the loop header the compiler takes the minimum over the ways into it - entered straight from the prologue (no store yet) that is vmcnt(0) for every
                 // iteration, i.e. a wait for the stores of the point just finished; entered from a copy of the body it is vmcnt(<stores per point>)
@@ -1416,7 +1370,7 @@ hipError_t ba_launch_linearize_one(const BaPtrs &B, const BaDims &D, const ResSe
     if (D.nsg == 1) {
         if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_one<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         hipLaunchKernelGGL(k_linearize_one<1>, dim3(D.nChunks), dim3(64 * LD_WAVES), lds, st, a);
-    } else if (D.F <= 12 && LD_PAIR) {
+    } else if (D.F <= 12) {
         // 9..12 key frames: the second slot group uses 4 of its 8 slots - two points share its pass (pair mode, round 6)
         if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_one<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         hipLaunchKernelGGL((k_linearize_one<2, true>), dim3(D.nChunks), dim3(64 * LD_WAVES), lds, st, a);

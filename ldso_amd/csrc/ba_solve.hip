@@ -495,18 +495,11 @@ static __device__ __forceinline__ void st2(double *p, double a, double b) { *(do
 //   NB  > 4: packed columns (column c holds rows c..M-1).
 #define LIX(i, c) ((NB == 4) ? ((c) * (M + 2) + (i)) : ((c) * M - (((c) * ((c) -1)) >> 1) + ((i) - (c))))
 
-// LD_MF7 = 1: the trailing update of the 112 x 112 system (9..13 key frames, C5) on the fp64 matrix cores like the 64 x 64 one (28 tiles, seven per wavefront, two
-// matrix rows per lane in phase 1).  Built, correct (24 GPU tests), and NOT faster: k_gn_solve 61.2 us with it, 61.2 without (round 6, one box) - a round of the
-// factorisation is 1.43 us of phase-1 issue, LDS round trips and the barrier either way (25 rounds = 36 us), the matrix cores only replace the cheapest part.
-#ifndef LD_MF7
-#define LD_MF7 0
-#endif
 static __host__ __device__ inline size_t solve_core_lds_doubles(int NB, int n) {
     size_t M = 16 * NB;
     size_t L = (NB == 4) ? M * (M + 2) : M * (M + 1) / 2;
     // NB == 4 (MFMA variant): two panel buffers [M][6] + per-wave private copies of F and G (4 waves x 2 x [64][4]) = 44 M
-    // (matrix-core variants, NB == 4 and NB == 7: two panel buffers [M][6] + per-wave private copies of F and G, 4 waves x 2 x [M][4], = 44 M)
-    return L + 2 * (M + 8) /*D,Y*/ + ((NB == 4 || (NB == 7 && LD_MF7)) ? 46 : 30) * M /*F,G,panel (up to 8 columns, pitch 10)*/ + 2 * M /*scale,x*/ + 7 * (size_t) n + 16;
+    return L + 2 * (M + 8) /*D,Y*/ + ((NB == 4) ? 46 : 30) * M /*F,G,panel (up to 8 columns, pitch 10)*/ + 2 * M /*scale,x*/ + 7 * (size_t) n + 16;
 }
 
 // GN = true (k_gn_solve): the prologue also mirrors the frames / calibration (and, when they fit, the float
@@ -534,12 +527,7 @@ struct SolveIO {
 };
 
 typedef double __attribute__((ext_vector_type(4))) ld_d4;
-#ifndef LD_SKIP_DONE
-#define LD_SKIP_DONE 0          // experiment (round 6): finished tile columns of the 112 x 112 trailing update skipped (uniform branches): k_gn_solve 60.8 -> 63.5 us at C5 - not used
-#endif
-#ifndef LD_C7
 #define LD_C7 4          // columns per round of the 112 x 112 factorisation (VALU variant)
-#endif
 
 template <int NB, int C, bool GN, bool WAIT = false, bool MF = false>
 static __device__ __forceinline__ void solve_core(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, int iteration, double *sm, SolveIO &io) {
@@ -567,25 +555,13 @@ static __device__ __forceinline__ void solve_core(const BaPtrs &B, const BaDims 
     // MF (n + 1 <= 64): the trailing update runs on the fp64 matrix cores (v_mfma_f64_16x16x4_f64).  The ten 16x16 tiles of the lower
     // triangle live in MFMA accumulator layout, three slots per wavefront: lane l, register r of a slot <-> element
     // (16 ta + (l >> 4) + 4 r, 16 tb + (l & 15)) of tile (ta, tb); wave w holds (w,0) | (w+1,w... see the packed tables) - 15 = no tile.
-    static_assert(!MF || ((NB == 4 || NB == 7) && C == 4), "the MFMA variant is written for the 64x64 and the 112x112 system, 4 columns per round");
+    static_assert(!MF || (NB == 4 && C == 4), "the MFMA variant is written for the 64x64 system, 4 columns per round");
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // NS tile slots per wavefront.  NB == 4: the hand-placed ten tiles (three slots; 15 = no tile).  NB == 7 (round 6, windows of 9..13 key frames - C5): the 28
-    // tiles of the lower triangle numbered column by column, wave w holds the tiles w, w + 4, w + 8, ... - as tile columns finish from the left every wave loses
-    // tiles at the same rate; RPL = 2 rows of the matrix per lane in phase 1 (112 rows on 64 lanes).
-    constexpr int NS = !MF ? 1 : (NB == 4 ? 3 : (NTILE + 3) / 4), RPL = (M + 63) / 64;
+    constexpr int NS = MF ? 3 : 1;          // tile slots per wavefront
     int mta[NS], mtb[NS];
-    if constexpr (MF && NB == 4) {
+    if constexpr (MF) {
         mta[0] = (0x3210 >> (4 * wv)) & 15; mta[1] = (0xF321 >> (4 * wv)) & 15; mta[2] = (0xF332 >> (4 * wv)) & 15;
         mtb[0] = 0; mtb[1] = (0xF111 >> (4 * wv)) & 15; mtb[2] = (0xF322 >> (4 * wv)) & 15;
-    } else if constexpr (MF) {
-#pragma unroll
-        for (int s_ = 0; s_ < NS; s_++) {
-            const int t = wv + 4 * s_;          // tile number, column-major over the lower triangle: column b starts at b NB - b (b - 1) / 2
-            int b = 0;
-#pragma unroll
-            for (int q = 1; q < NB; q++) b += (t >= q * NB - (q * (q - 1)) / 2) ? 1 : 0;
-            mtb[s_] = b; mta[s_] = (t < NTILE) ? b + (t - (b * NB - (b * (b - 1)) / 2)) : 15;
-        }
     } else { mta[0] = 15; mtb[0] = 0; }
     ld_d4 Dv[NS];
     if (GN) { HF = B.acc; bF = HF + (size_t) n * n; }
@@ -694,7 +670,7 @@ _Pragma("unroll") \
                 Dv[s_][r] = si * Dv[s_][r] * sj;
             }
         }
-        // first panel (columns 0..3): the tiles of tile column 0 (NB == 4: slot 0 of every wave)
+        // first panel (columns 0..3): the tiles of tile column 0 (slot 0 of every wave)
 #pragma unroll
         for (int s_ = 0; s_ < NS; s_++) {
             if (mta[s_] >= NB || mtb[s_] != 0) continue;          // uniform per wave
@@ -748,12 +724,13 @@ _Pragma("unroll") \
                     const double2 w = ld2(&sPr[(k + r) * CP + q2]);
                     c[r][q2] = w.x; if (q2 + 1 < C) c[r][q2 + 1] = w.y;
                 }
-            // this lane's row(s) of the panel: one (the row of the thread / of the lane), or - matrix-core variant above 64 rows - the rows lane and lane + 64
-            constexpr int NR = MF ? RPL : 1;
+            // this lane's row of the panel (the row of the thread / of the lane).  The single-pass loops over rr stay: written without them, the compiler
+            // allocates k_solve and k_gn_solve differently (272 / 275 instead of 280 VGPRs, different code)
+            constexpr int NR = 1;
             double g[NR][C], f[NR][C];
 #pragma unroll
             for (int rr = 0; rr < NR; rr++) {
-                const int i = MF ? min(lane + 64 * rr, M - 1) : tid;
+                const int i = MF ? lane + 64 * rr : tid;
 #pragma unroll
                 for (int q2 = 0; q2 < C; q2 += 2) { const double2 w = ld2(&sPr[i * CP + q2]); g[rr][q2] = w.x; g[rr][q2 + 1] = w.y; }
             }
@@ -787,7 +764,6 @@ _Pragma("unroll") \
 #pragma unroll
             for (int rr = 0; rr < NR; rr++) {
                 const int i = MF ? lane + 64 * rr : tid;
-                if (MF && i >= M) continue;
                 const bool below = (i >= k + C);
                 const bool rowOn = below && (i <= n), colOn = below && (i < n);
                 if constexpr (MF) {
@@ -852,21 +828,15 @@ _Pragma("unroll") \
         double fi[NB][C], gj[NB][C];
 #pragma unroll
         for (int a = 0; a < NB; a++) {
-            if (NB > 4 && LD_SKIP_DONE && a < a0) {          // uniform: no live tile in this tile row / column any more
-#pragma unroll
-                for (int q = 0; q < C; q++) { fi[a][q] = 0.0; gj[a][q] = 0.0; }
-                continue;
-            }
 #pragma unroll
             for (int q2 = 0; q2 < C; q2 += 2) {
                 const double2 f0 = ld2(&sFp[(ty + 16 * a) * CP + q2]), g0 = ld2(&sGp[(tx + 16 * a) * CP + q2]);
                 fi[a][q2] = f0.x; fi[a][q2 + 1] = f0.y; gj[a][q2] = g0.x; gj[a][q2 + 1] = g0.y;
             }
         }
-        // (tile columns left of the next panel are finished, their G is zero; skipping them - LD_SKIP_DONE - is slower: the round is a latency chain, not fma issue)
+        // (tile columns left of the next panel are finished, their G is zero; skipping them is slower: the round is a latency chain, not fma issue)
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            if (NB > 4 && LD_SKIP_DONE && b < a0) continue;          // uniform
 #pragma unroll
             for (int a = b; a < NB; a++) {
                 double w = v[a * (a + 1) / 2 + b];
@@ -993,7 +963,7 @@ _Pragma("unroll") \
 template <bool GN, bool WAIT = false>
 static __device__ __forceinline__ void solve_core_dispatch(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, int iteration, double *sm, SolveIO &io) {
     if (D.n + 1 <= 64) solve_core<4, 4, GN, WAIT, true>(B, D, S, St, iteration, sm, io);
-    else if (D.n + 1 <= 112) solve_core<7, (LD_MF7 != 0) ? 4 : LD_C7, GN, WAIT, LD_MF7 != 0>(B, D, S, St, iteration, sm, io);
+    else if (D.n + 1 <= 112) solve_core<7, LD_C7, GN, WAIT>(B, D, S, St, iteration, sm, io);
     else solve_core<9, 4, GN, WAIT>(B, D, S, St, iteration, sm, io);
 }
 
@@ -1375,14 +1345,10 @@ __global__ __launch_bounds__(NT) void k_reduce_solve(BaPtrs B, BaDims D, ResSet 
 // window-iterations/s, 5 (96 VGPRs, 30 spilled; also fits beside the two resident k_linearize_batch wavefronts of a SIMD, 2 x 205 + 96 <= 512, so
 // the reduce of one half-batch overlaps the linearisation of the other) 104.8 k, 6 (80 VGPRs, 48 spilled) 83.0 k; B = 8 (520 workgroups per
 // launch, 2 per CU): 82 k unconstrained, 75.7 k with the 96-register allocation (different boxes, same day).
-#ifndef LD_REDB_BLOCKS
 #define LD_REDB_BLOCKS 4             // the dense variant: workgroups per CU its register allocation leaves room for (round 4, against the record-layout
                                      // k_linearize_batch of 187 VGPRs, B = 32 different windows: 3 -> 122.4 k, 4 -> 122.4 k, 5 -> 96.8 k, 6 -> 87.5 k window-iterations/s,
                                      // unconstrained 107.8 k; with round 3's 205-VGPR kernel 5 had been the best: 104.8 k)
-#endif
-#ifndef LD_REDB_DENSE_PER_CU
 #define LD_REDB_DENSE_PER_CU 6       // launches with at least this many workgroups per CU take the dense variant
-#endif
 static __device__ __forceinline__ void reduce_batch_body(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il) {
     int w = 0;
     for (int i = 1; i < nWin; i++) if ((int) blockIdx.x >= items[i].redBlock0) w = i;

@@ -470,16 +470,11 @@ __device__ __forceinline__ void ini_sw2_point(const SwRec &r) {
 }
 // Wavefront 0 sweeps, with the inputs of INI_SW_DEPTH passes in flight.  remote: the records were written by other compute units (k_ini_prep) and lie in
 // memory, not in this XCD's L2 - the other wavefronts of the block pull them in, in sweep order, ahead of wavefront 0 (one dword per 128-byte line).
-#ifndef INI_SW_DEPTH
 #define INI_SW_DEPTH 8
-#endif
-#ifndef INI_SW_TOUCH
-#define INI_SW_TOUCH 1
-#endif
 __device__ void ini_sweep_reg(const IniLevel &L, int *sIR, bool remote) {
     if (L.nPass2 == 0) return;
     if (threadIdx.x >= 64) {
-        if (!(INI_SW_TOUCH && remote)) return;
+        if (!remote) return;
         const int *rec = (const int *) L.swRec;
         const int nLines = (L.nPass2 + INI_SWPAD) * 16;                  // 64 lanes x 32 bytes per pass
         int acc = 0;

@@ -10,9 +10,7 @@
 #define LD_HD inline
 #endif
 
-#ifndef LD_EXP_SERIES_TH2
 #define LD_EXP_SERIES_TH2 0.25      // se3_exp: |omega|^2 below which the coefficient series replace the closed forms (0: always the closed forms)
-#endif
 
 namespace ld {
 

@@ -571,12 +571,8 @@ __device__ __attribute__((noinline)) void tr_solve_fixed_affine(const double *sH
 // nhyp * G by the CU count); sequence numbers grow over the launches of a handle, so nothing has to be cleared in between.
 // ---------------------------------------------------------------------------------------------------------
 #define TR_GMAX 16
-#ifndef TR_COOP_MIN
 #define TR_COOP_MIN 512        // smaller levels stay on the leader: less than the ~1.4 us of a hand-over to win
-#endif
-#ifndef TR_COOP_PER
 #define TR_COOP_PER 64         // finest share: one wavefront with one point per lane
-#endif
 #define TR_COOP_SLOTS 128       // = the maximum number of hypotheses of ldso_tr_track_batch: coop[] is indexed by hypothesis
 #define TR_SPIN_LIMIT 500000000ll   // bail-out of the hand-over polls: 5 s of the 100 MHz wall clock (a track takes < 1 ms)
 struct TrCoop {
