@@ -101,6 +101,8 @@ int adp_set_write_back_jacobians(void *b, int on) { ((GpuBackend *) b)->writeBac
 // the window resident across optimize() calls (ldso_ba_update_window) or flattened and uploaded every time; how many uploads of each kind so far
 int adp_set_resident_window(void *b, int on) { ((GpuBackend *) b)->residentWindow = on != 0; return 0; }
 int adp_upload_counts(void *b, int *delta, int *fresh) { *delta = ((GpuBackend *) b)->uploadsDelta; *fresh = ((GpuBackend *) b)->uploadsFresh; return 0; }
+// GpuBackend::marginalizeFrame: how often the Schur complement ran on the device (ldso_ba_marginalize_frame) and how often the call fell back to the reference's host member
+int adp_marg_frame_counts(void *b, int *device, int *hostFallback) { *device = ((GpuBackend *) b)->margFrameDevice; *hostFallback = ((GpuBackend *) b)->margFrameHostFallback; return 0; }
 // wall-clock split of the last GpuBackend::optimize (seconds): flatten + upload, device (ldso_ba_optimize incl. its read-back of the energies), fetch, write-back into the objects
 int adp_last_optimize_times(void *b, double *out4) { for (int i = 0; i < 4; i++) out4[i] = ((GpuBackend *) b)->lastOptimizeSeconds[i]; return 0; }
 int adp_last_upload_times(void *b, double *out6) { for (int i = 0; i < 6; i++) out6[i] = ((GpuBackend *) b)->lastUploadSeconds[i]; return 0; }

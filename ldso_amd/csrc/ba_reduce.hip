@@ -181,7 +181,7 @@ hipError_t ba_launch_marg_update(const BaPtrs &B, const BaDims &D, double w, hip
 // ---------------------------------------------------------------------------------------------------------
 // EnergyFunctional::marginalizeFrame (EnergyFunctional.cc:72-151) on the device prior H_M / b_M: move the frame's 8 rows /
 // columns to the end, add its prior, scale by (|diag|+10)^-1/2, eliminate the 8x8 block (inverse by partial-pivot LU like Eigen's
-// fixed-size inverse()), unscale, symmetrise.  One workgroup; the matrices live in global memory (n <= 132), W = n*n + n doubles
+// fixed-size inverse()), unscale, symmetrise the result (the result only: see the 8x8 block below).  One workgroup; the matrices live in global memory (n <= 132), W = n*n + n doubles
 // of scratch.  Output: (n-8)^2 row-major + (n-8).  Per key frame, not per iteration: written for clarity, not speed.
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_marg_frame(BaPtrs B, BaDims D, int idx, double *W, double *outH, double *outb) {
@@ -205,8 +205,10 @@ __global__ __launch_bounds__(256) void k_marg_frame(BaPtrs B, BaDims D, int idx,
     for (int e = tid; e < n * n; e += 256) { const int i = e / n, j = e % n; Hs[e] = (1.0 / sSV[i]) * Hs[e] * (1.0 / sSV[j]); }
     for (int i = tid; i < n; i += 256) bs[i] = (1.0 / sSV[i]) * bs[i];
     __syncthreads();
-    // hpi = inverse(0.5 (hpi + hpi^T)) by LU with partial pivoting (thread 0, LDS), then symmetrised again
-    if (tid < 64) { const int r = tid >> 3, c = tid & 7; sLU[tid] = 0.5 * (Hs[(size_t) (nd + r) * n + nd + c] + Hs[(size_t) (nd + c) * n + nd + r]); }
+    // hpi = inverse(0.5 (hpi + hpi)) by LU with partial pivoting (thread 0, LDS), then 0.5 (hpi + hpi) again: the reference averages the block and its
+    // inverse with THEMSELVES (EnergyFunctional.cc:116,118 - sic, a no-op), not with their transposes.  On a prior that is not exactly symmetric the transposed
+    // average is another function: b_M moves in first order of the asymmetry (1e-6 in, 1e-5 out), H_M in second order (tests/test_marg_frame_gpu.py)
+    if (tid < 64) { const int r = tid >> 3, c = tid & 7; const double v = Hs[(size_t) (nd + r) * n + nd + c]; sLU[tid] = 0.5 * (v + v); }
     __syncthreads();
     if (tid == 0) {
         for (int k = 0; k < 8; k++) {
@@ -230,10 +232,7 @@ __global__ __launch_bounds__(256) void k_marg_frame(BaPtrs B, BaDims D, int idx,
         for (int i = 0; i < 8; i++) sHpi[i * 8 + tid] = x[i];
     }
     __syncthreads();
-    double hsym = 0.0;
-    if (tid < 64) { const int r = tid >> 3, c = tid & 7; hsym = 0.5 * (sHpi[r * 8 + c] + sHpi[c * 8 + r]); }
-    __syncthreads();
-    if (tid < 64) sHpi[tid] = hsym;
+    if (tid < 64) sHpi[tid] = 0.5 * (sHpi[tid] + sHpi[tid]);
     __syncthreads();
     // Schur complement of the trailing block: row i of the result needs bli[i][:] = sum_k Hs[nd+k][i] hpi[k][:]
     // (the trailing rows nd.. are only read: all rows of bli first, then every entry of the result on its own thread - the same sums in

@@ -414,6 +414,12 @@ class GpuAdapter:
         self.A.adp_upload_counts(self.h, C.byref(d), C.byref(f))
         return d.value, f.value
 
+    def marg_frame_counts(self):
+        """GpuBackend::marginalizeFrame calls so far -> (on the device, fallen back to the reference's host member)"""
+        d, f = C.c_int(), C.c_int()
+        self.A.adp_marg_frame_counts(self.h, C.byref(d), C.byref(f))
+        return d.value, f.value
+
     def set_write_back_jacobians(self, on: bool):
         self.A.adp_set_write_back_jacobians(self.h, C.c_int(1 if on else 0))
 

@@ -54,3 +54,61 @@ def test_reference_against_itself_is_the_yardstick_of_the_sequence_test():
         assert d["counts"] <= 8 and d["unmatched_points"] <= 40, (name, d)          # two runs of the reference stay the same system
     assert per["O3_build"]["pose"] > 0 and per["O3_build"]["HM"] > 0, "the -O3 build rounds differently from the pin build"
     assert max(per[k]["bM"] for k in per if k.startswith("six_threads")) > 0, "six workers sum in another order than one"
+
+
+@pytest.mark.parametrize("policy", ["middle", "rotate", "two"])
+def test_reference_leg_slides_a_window_by_middle_frames(policy):
+    """FullSystem::flagFramesForMarginalization (FullSystem.cc:647-720) removes MIDDLE frames as its normal case and can flag several in one key frame: the
+    reference leg under the three policies of adapter_sequence_common.frames_to_marginalize beyond `oldest`, and the reference-against-itself yardstick of each
+    (measured on that policy, never borrowed from another one)."""
+    from adapter_sequence_common import run_sequence, reference_yardstick, frames_to_marginalize, QUANTITIES
+    K, max_frames = 8, 6
+    win = synth.make_config("small", extra_frames=K)
+    r, log = run_sequence(win, K, adapter=None, max_frames=max_frames, marg_policy=policy)
+    assert len(log) == K and not any(rec["lost"] for rec in log), "K records, none lost"
+    F0 = win.F
+    first_new = int(win.frames["frameID"].max()) + 1
+    # F as the policy implies, from the policy alone
+    nF, expect_F, removed = F0, [], 0
+    for k in range(K):
+        nF = nF + 1 - len(frames_to_marginalize(policy, k, nF, max_frames))
+        expect_F.append(nF)
+    assert [rec["summary"]["F"] for rec in log] == expect_F
+    if policy == "two":
+        assert expect_F == [6, 6, 5, 6, 5, 6, 5, 6]
+    else:
+        assert expect_F == [6] * K
+    not_contiguous = 0
+    for k, rec in enumerate(log):
+        s = rec["summary"]
+        ids = [int(i) for i in s["ids"]]
+        assert ids == sorted(ids) and ids[-1] == first_new + k, "the others keep their order, the new key frame is the newest"
+        assert np.isfinite(rec["rmse"]) and 0 < rec["rmse"] < 10
+        removed += rec["marginalised"]
+        assert s["F"] == F0 + k + 1 - removed
+        if removed:
+            HM = s["HM"]
+            assert np.abs(HM).max() > 0 and np.allclose(HM, HM.T, rtol=1e-9, atol=1e-6 * np.abs(HM).max()), "the prior is present and symmetric"
+        not_contiguous += ids != list(range(ids[0], ids[0] + len(ids)))
+    assert removed == F0 + K - expect_F[-1] == 7
+    # the window keeps a frame OLDER than one it removed: the ids are not a contiguous run - what `oldest` can never produce
+    assert not_contiguous > 0 and log[-1]["summary"]["ids"][-1] - log[-1]["summary"]["ids"][0] >= log[-1]["summary"]["F"], (policy, [list(rec["summary"]["ids"]) for rec in log])
+    r.close()
+    yard, per = reference_yardstick("small", K, log_ref=log, mt_runs=2, marg_policy=policy)          # asserts same == True for every reference-to-reference pair
+    print("reference vs reference over 8 key frames, policy", policy, {k: {q: float("%.3g" % v) for q, v in d.items()} for k, d in per.items()})
+    assert set(yard) == set(QUANTITIES) and "O3_build" in per and len(per) == 3
+    for name, d in per.items():
+        assert all(np.isfinite(v) for v in d.values()), name
+
+
+def test_oldest_policy_keeps_a_contiguous_run_of_key_frames():
+    """the default policy is the behaviour before policies existed: position 0 once the window is full"""
+    from adapter_sequence_common import run_sequence, frames_to_marginalize
+    assert [frames_to_marginalize("oldest", k, nF, 6) for k, nF in enumerate([5, 6, 6, 6])] == [[], [0], [0], [0]]
+    K = 4
+    win = synth.make_config("small", extra_frames=K)
+    r, log = run_sequence(win, K)
+    for rec in log:
+        ids = [int(i) for i in rec["summary"]["ids"]]
+        assert ids == list(range(ids[0], ids[0] + len(ids)))
+    r.close()

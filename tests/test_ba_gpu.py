@@ -254,9 +254,23 @@ def test_optimize_12_frames():
 
 @pytest.mark.parametrize("with_prior", [False, True])
 def test_marginalize_points(small, with_prior):
+    _marginalize_points(small, with_prior, 0)
+
+
+@pytest.mark.parametrize("marg", [2, -2], ids=["2", "F-2"])
+@pytest.mark.parametrize("with_prior", [False, True])
+def test_marginalize_points_of_a_middle_frame(small, with_prior, marg):
+    _marginalize_points(small, with_prior, marg)
+
+
+def _marginalize_points(small, with_prior, marg):
     """a11: marginalizePointsF on the device (mode-2 accumulate of the flagged points incl. the re-linearise + fixLinearizationF
-    pass of flagPointsForRemoval) against the oracle's flagPointsForRemoval + marginalizePointsF: the new H_M / b_M."""
+    pass of flagPointsForRemoval) against the oracle's flagPointsForRemoval + marginalizePointsF: the new H_M / b_M.  Then marginalizeFrame of
+    the flagged frame `marg` (negative: counted from the newest) - the oldest, a middle one, the last but one (FullSystem::flagFramesForMarginalization,
+    FullSystem.cc:647-720, picks middle frames as its normal case)."""
     win = synth.add_synthetic_prior(copy.deepcopy(small)) if with_prior else small
+    idx = marg if marg >= 0 else win.F + marg
+    assert 0 <= idx < win.F
     o = po.OracleWindow(win); o.set_force_all_iterations(True)
     o.optimize(3)
     # the device handle starts from the oracle's post-optimize state (identical applied state on both sides)
@@ -267,7 +281,7 @@ def test_marginalize_points(small, with_prior):
     w2.frames = fo["frames"]
     w2.calib = w2.calib.copy(); w2.calib["value"] = fo["calib_value"]
     g = binding.BA.from_window(w2)
-    o.flag_frame(0)
+    o.flag_frame(idx)
     o.flag_points_for_removal()
     _, status = o.get_points()
     flags = (status == 3).astype(np.int32)                  # PS_MARGINALIZED
@@ -283,18 +297,18 @@ def test_marginalize_points(small, with_prior):
     # the applied window state is untouched by the call
     rg = g.get_residuals()
     assert np.array_equal(rg["state_state"], ex["residuals"]["state_state"])
-    # marginalizeFrame on the resulting prior (frame 0 = the flagged one)
-    o.marginalize_frame(0)
+    # marginalizeFrame on the resulting prior (the flagged frame)
+    o.marginalize_frame(idx)
     HM2o, bM2o = o.get_prior()
-    HM2g, bM2g = g.marginalize_frame(0)
+    HM2g, bM2g = g.marginalize_frame(idx)
     assert HM2g.shape == HM2o.shape == (8 * (win.F - 1) + 4,) * 2
     # marginalizeFrame is fp64 on both sides: what separates HM2g from HM2o is the fp32 difference of their inputs (HMg vs HMo, within TOL above) pushed through the
     # inverse of the frame's 8 x 8 block - measured apart (tests/test_fullsize_gpu.py::test_c5_end_to_end has the same three steps at C5):
     g.set_prior(HMo, bMo)                                   # (i) the device on the oracle's prior = the oracle's result
-    HM2i, bM2i = g.marginalize_frame(0)
+    HM2i, bM2i = g.marginalize_frame(idx)
     observe("marginalize_frame_same_input", max(blockrel(HM2i, HM2o, 4), rel(bM2i, bM2o)), 1e-9)
     w2b = copy.deepcopy(w2); w2b.HM, w2b.bM = HMg, bMg      # (ii) the oracle on the device's prior = the device's result
-    ob = po.OracleWindow(w2b); ob.marginalize_frame(0)
+    ob = po.OracleWindow(w2b); ob.marginalize_frame(idx)
     HM2b, bM2b = ob.get_prior(); ob.close()
     observe("marginalize_frame_device_input", max(blockrel(HM2g, HM2b, 4), rel(bM2g, bM2b)), 1e-9)
     sens_H, sens_b = blockrel(HM2b, HM2o, 4), rel(bM2b, bM2o)          # (iii) the chained difference = the oracle's own sensitivity to the input difference

@@ -1,6 +1,6 @@
 """Full-size GPU parity of exactly what bench.py times (BASELINE configs C3 / C4 with the marginalisation prior, the fused fast
 path `k_reduce_solve -> k_linearize`, 10 forced iterations) and the C5 stress flow (12 KF x 8000 pt: stage-wise pass, fast-path
-iterations, marginalizePointsF + marginalizeFrame of the oldest frame, 10 more iterations at F = 11), all against the oracle.
+iterations, marginalizePointsF + marginalizeFrame of the oldest frame or of a middle one, 10 more iterations at F = 11), all against the oracle.
 
 Reference loop being reproduced: src/frontend/FullSystem.cc:777-831 (optimize), :1208-1270 (flagPointsForRemoval),
 src/internal/OptimizationBackend/EnergyFunctional.cc:72-151 (marginalizeFrame), :165-222 (marginalizePointsF).
@@ -155,7 +155,15 @@ def test_timed_configuration_parity(name):
 
 
 def test_c5_end_to_end():
-    """BASELINE configs[4]: 12 KF x 8000 pt (R = 88000): stage-wise pass, 4 fast-path iterations, marginalise the oldest frame
+    _c5_end_to_end(0)
+
+
+def test_c5_end_to_end_middle_frame():
+    _c5_end_to_end(6)
+
+
+def _c5_end_to_end(idx):
+    """BASELINE configs[4]: 12 KF x 8000 pt (R = 88000): stage-wise pass, 4 fast-path iterations, marginalise frame `idx` - the oldest or a middle one -
     (points, then the frame), rebuild at F = 11 with the device's own prior, 10 more iterations."""
     torch, st = _one_stream()
     win = get_window("C5")
@@ -182,7 +190,7 @@ def test_c5_end_to_end():
     assert done == 4 and np.all(np.abs(eg - eo) <= TOL * np.abs(eo)), (eo, eg)
     assert abs(rmo - rmg) <= TOL * rmo
 
-    # marginalise the oldest frame; the device starts from the oracle's post-optimize state (identical applied state on both sides)
+    # marginalise frame idx; the device starts from the oracle's post-optimize state (identical applied state on both sides)
     ex, fo = o.export_window(), o.get_frames()
     assert ex["F"] == 12 and len(ex["points"]) == win.P
     w2 = copy.deepcopy(win)
@@ -190,7 +198,7 @@ def test_c5_end_to_end():
     w2.frames = fo["frames"]
     w2.calib = w2.calib.copy(); w2.calib["value"] = fo["calib_value"]
     g = binding.BA.from_window(w2, stream=st)
-    o.flag_frame(0); o.flag_points_for_removal()
+    o.flag_frame(idx); o.flag_points_for_removal()
     _, status = o.get_points()
     flags = (status == 3).astype(np.int32)
     assert 300 < flags.sum() < win.P
@@ -198,19 +206,19 @@ def test_c5_end_to_end():
     HMo, bMo = o.get_prior()
     HMg, bMg = g.marginalize_points(flags)
     assert blockrel(HMg, HMo, 4) < TOL and rel(bMg, bMo) < TOL
-    o.marginalize_frame(0)
+    o.marginalize_frame(idx)
     HM2o, bM2o = o.get_prior()
-    HM2g, bM2g = g.marginalize_frame(0)
+    HM2g, bM2g = g.marginalize_frame(idx)
     assert HM2g.shape == (92, 92)
     # marginalizeFrame is fp64 on both sides; what separates HM2g from HM2o is the fp32 difference of their INPUTS (HMg vs HMo, within TOL above) pushed through
     # the inverse of the frame's 8 x 8 block.  Measured apart (round 6; until round 5 this was one comparison at 5 x TOL):
     #  (i) the device on the ORACLE's prior is the oracle's result to fp64 rounding,
     g.set_prior(HMo, bMo)
-    HM2i, bM2i = g.marginalize_frame(0)
+    HM2i, bM2i = g.marginalize_frame(idx)
     observe("c5_marginalize_frame_same_input_HM", blockrel(HM2i, HM2o, 4), 1e-9); observe("c5_marginalize_frame_same_input_bM", rel(bM2i, bM2o), 1e-9)
     #  (ii) the oracle's own arithmetic on the DEVICE's prior is the device's result (same bound),
     w2b = copy.deepcopy(w2); w2b.HM, w2b.bM = HMg, bMg
-    ob = po.OracleWindow(w2b); ob.marginalize_frame(0)
+    ob = po.OracleWindow(w2b); ob.marginalize_frame(idx)
     HM2b, bM2b = ob.get_prior(); ob.close()
     observe("c5_marginalize_frame_device_input_HM", blockrel(HM2g, HM2b, 4), 1e-9); observe("c5_marginalize_frame_device_input_bM", rel(bM2g, bM2b), 1e-9)
     #  (iii) and the chained difference is the oracle's own sensitivity to that input difference (blockrel(HM2b, HM2o)): no tolerance of its own
@@ -218,14 +226,14 @@ def test_c5_end_to_end():
     assert blockrel(HM2g, HM2o, 4) <= 1.01 * sens_H + 1e-8 and rel(bM2g, bM2o) <= 1.01 * sens_b + 1e-8, (blockrel(HM2g, HM2o, 4), sens_H, rel(bM2g, bM2o), sens_b)
     print("C5 marginalizeFrame: chained difference to the oracle", blockrel(HM2g, HM2o, 4), rel(bM2g, bM2o), "= the oracle's sensitivity to the prior's fp32 difference", sens_H, sens_b)
 
-    # F = 11: window rebuilt without frame 0, carrying the DEVICE's prior; 10 more iterations on both sides
+    # F = 11: window rebuilt without frame idx, carrying the DEVICE's prior; 10 more iterations on both sides
     ex = o.export_window(); fo = o.get_frames()
     assert ex["F"] == 11
     w3 = copy.deepcopy(win)
     w3.points, w3.residuals, w3.lin_J, w3.lin_res_toZeroF = ex["points"], ex["residuals"], ex["lin_J"], ex["lin_res_toZeroF"]
     w3.frames = fo["frames"]
     w3.calib = w3.calib.copy(); w3.calib["value"] = fo["calib_value"]
-    w3.images = win.images[1:]
+    w3.images = win.images[:idx] + win.images[idx + 1:]
     w3.HM, w3.bM = HM2g, bM2g
     assert w3.F == 11 and win.P - flags.sum() - 200 < w3.P <= win.P - flags.sum()      # marginalised points gone, a few more dropped as OOB / outliers
     o3 = po.OracleWindow(w3); o3.set_force_all_iterations(True)

@@ -119,11 +119,29 @@ def test_full_size_c4_bit_exact():
     _stage(synth.add_synthetic_prior(copy.deepcopy(get_window("C4"))))
 
 
+# the flagged frame: 0, 1, 2, F-2, F-1 (negative = counted from the newest).  FullSystem::flagFramesForMarginalization (FullSystem.cc:647-720) removes MIDDLE
+# frames as its normal case: marginalizeFrame's move of the frame's rows / columns to the end (EF.cc:81-100) is the identity at F-1 only
+# (index 0 stays the test it always was; the other four are the parametrised test below it)
+MARG_FRAMES = [1, 2, -2, -1]
+MARG_IDS = ["1", "2", "F-2", "F-1"]
+
+
 def test_marginalization_bit_exact(small):
+    _marginalization_bit_exact(small, 0)
+
+
+@pytest.mark.parametrize("marg", MARG_FRAMES, ids=MARG_IDS)
+def test_marginalization_bit_exact_at_frame(small, marg):
+    _marginalization_bit_exact(small, marg)
+
+
+def _marginalization_bit_exact(small, marg):
     """flagPointsForRemoval's relinearise + fixLinearizationF (Residuals.cc:216-242), marginalizePointsF (EF.cc:165-222, addPoint<2>)
     and marginalizeFrame (EF.cc:72-151) after three GN iterations of the oracle; the reference graph is rebuilt from the oracle's
     post-optimize state, the host policy (which points go) is taken from the oracle."""
     win = synth.add_synthetic_prior(copy.deepcopy(small))
+    idx = marg if marg >= 0 else win.F + marg
+    assert 0 <= idx < win.F
     o = po.OracleWindow(win); o.set_force_all_iterations(True)
     o.optimize(3)
     ex, fo = o.export_window(), o.get_frames()
@@ -133,7 +151,7 @@ def test_marginalization_bit_exact(small):
     w2.calib = w2.calib.copy(); w2.calib["value"] = fo["calib_value"]
     assert np.array_equal(ex["orig_point"], np.arange(win.P))
     o2, r = o, pr.RefWindow(w2)                       # the oracle keeps going; the reference graph holds the same state
-    o2.flag_frame(0); o2.flag_points_for_removal()
+    o2.flag_frame(idx); o2.flag_points_for_removal()
     _, status = o2.get_points()
     assert (status % 100 == 3).sum() > 10
     r.flag_points(status)
@@ -150,7 +168,7 @@ def test_marginalization_bit_exact(small):
     # whose association of the scalar factor differs by one rounding
     for a, b, n in zip(o2.get_prior(), r.get_prior(), ("HM after marginalizePointsF", "bM after marginalizePointsF")):
         _close(a, b, 1e-15, n)
-    o2.marginalize_frame(0); r.marginalize_frame(0)
+    o2.marginalize_frame(idx); r.marginalize_frame(idx)
     (HMo, bMo), (HMr, bMr) = o2.get_prior(), r.get_prior()
     assert HMo.shape == HMr.shape == (8 * (win.F - 1) + 4,) * 2
     _close(HMo, HMr, 1e-12, "HM after marginalizeFrame"); _close(bMo, bMr, 1e-12, "bM after marginalizeFrame")
@@ -354,13 +372,24 @@ def test_fullsystem_canbreak_rule(small):
 
 
 def test_fullsystem_marginalization_members_pinned(small):
+    _fullsystem_marginalization_members_pinned(small, 0)
+
+
+@pytest.mark.parametrize("marg", MARG_FRAMES, ids=MARG_IDS)
+def test_fullsystem_marginalization_members_pinned_at_frame(small, marg):
+    _fullsystem_marginalization_members_pinned(small, marg)
+
+
+def _fullsystem_marginalization_members_pinned(small, marg):
     """FullSystem::flagPointsForRemoval (FullSystem.cc:1208-1270: OOB / inlier policy, re-linearise + fixLinearizationF) and
     FullSystem::marginalizeFrame (:602-640) - the members themselves - against the oracle's restatement of both."""
     win = synth.add_synthetic_prior(copy.deepcopy(small))
+    idx = marg if marg >= 0 else win.F + marg
+    assert 0 <= idx < win.F
     o, r = po.OracleWindow(win), pr.RefWindow(win)
     r.fs_attach()
     o.optimize(3); r.fs_optimize(3)
-    o.flag_frame(0); r.fs_flag_frame(0)
+    o.flag_frame(idx); r.fs_flag_frame(idx)
     o.flag_points_for_removal(); r.fs_flag_points_for_removal()
     (_, so), (_, sr) = o.get_points(), r.get_points()
     _same(so % 100, sr % 100, "point status after flagPointsForRemoval")
@@ -375,7 +404,7 @@ def test_fullsystem_marginalization_members_pinned(small):
     o.marginalize_points(); r.marginalize_points()
     for a, b, n in zip(o.get_prior(), r.get_prior(), ("HM after marginalizePointsF", "bM after marginalizePointsF")):
         _close(a, b, 1e-9, n)
-    o.marginalize_frame(0); r.fs_marginalize_frame(0)
+    o.marginalize_frame(idx); r.fs_marginalize_frame(idx)
     (HMo, bMo), (HMr, bMr) = o.get_prior(), r.get_prior()
     assert HMo.shape == HMr.shape == (8 * (win.F - 1) + 4,) * 2
     _close(HMo, HMr, 1e-9, "HM after marginalizeFrame"); _close(bMo, bMr, 1e-9, "bM after marginalizeFrame")
