@@ -8,7 +8,7 @@
 // Hdd / bd as ONE running sum over (residual, pattern pixel) including the partial contributions of a residual that goes out of
 // bounds half-way through its pattern - so idepth, energies and residual states are bit-identical to the CPU path.
 #include <hip/hip_runtime.h>
-#include "ba_dev.h"
+#include "ba_host.h"
 
 struct ActArgs {
     const ldso_immature_t *pts;

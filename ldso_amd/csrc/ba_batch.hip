@@ -1,0 +1,309 @@
+// ---- batched windows: B independent windows per launch ---------------------------------------------------------------------------
+// One 7-keyframe window is tiny for an MI355X (SURVEY 7 hard part 1, 8e): a batch runs the Gauss-Newton iteration of several
+// independent windows (several agents / sequences / hypotheses) with three launches per iteration for ALL of them: k_reduce_batch
+// (every window's reduce workgroups) -> k_gn_solve_batch (two control workgroups per window) -> k_linearize_batch (every window's
+// chunks).  Per-window arithmetic is exactly that of ldso_ba_enqueue_gn's split schedule; the windows only share the launches.
+#include "ba_host.h"
+
+static int batch_refresh(ldso_ba_batch *Bt) {
+    ldso_ba *H0 = Bt->h[0];
+    const size_t n = Bt->h.size();
+    for (int pass = 0; pass < 2; pass++) {          // pass 0: blocks numbered over the whole batch; pass 1: per half
+        int lin = 0, red = 0;
+        for (size_t i = 0; i < n; i++) {
+            ldso_ba *H = Bt->h[i];
+            BatchItem &it = Bt->items[pass * n + i];
+            if (pass == 1 && (int) i == Bt->n0) { Bt->halfChunks[0] = lin; Bt->halfReduce[0] = red; lin = 0; red = 0; }
+            if (H->B.acc != H->ownAcc) H->B.acc = H->ownAcc;
+            it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[0]; it.set[1] = H->sets[1]; it.cs = H->chunkStarts;
+            it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.linBlock0 = lin; it.redBlock0 = red;
+            const int nT = H->GSP / 16;
+            lin += H->D.nChunks;
+            red += H->D.F * H->D.F + Bt->ks * nT * (nT + 1) / 2 + 1;
+        }
+        if (pass == 0) { Bt->totalChunks = lin; Bt->totalReduce = red; }
+        else if (Bt->n0 == (int) n) { Bt->halfChunks[0] = lin; Bt->halfReduce[0] = red; Bt->halfChunks[1] = 0; Bt->halfReduce[1] = 0; }
+        else { Bt->halfChunks[1] = lin; Bt->halfReduce[1] = red; }
+    }
+    CHK(hipMemcpyAsync(Bt->d_items, Bt->items.data(), Bt->items.size() * sizeof(BatchItem), hipMemcpyHostToDevice, H0->stream));
+    // the workgroup table: whole batch (window index into items[0..n)), then half A (index into items[n..n+n0)) and half B (items[n+n0..))
+    Bt->blocks.clear();
+    for (size_t i = 0; i < n; i++) for (const BatchBlock &b : Bt->h[i]->h_blocks) Bt->blocks.push_back(BatchBlock{(int32_t) i, b.p0, b.np, b.host_chunk});
+    for (size_t i = 0; i < n; i++) { const int32_t w = (int) i < Bt->n0 ? (int32_t) i : (int32_t) i - Bt->n0; for (const BatchBlock &b : Bt->h[i]->h_blocks) Bt->blocks.push_back(BatchBlock{w, b.p0, b.np, b.host_chunk}); }
+    if (Bt->blocks.size() > Bt->blocksCap) {
+        CHK(hipStreamSynchronize(H0->stream));
+        if (Bt->aux) CHK(hipStreamSynchronize(Bt->aux));
+        if (Bt->d_blocks) hipFree(Bt->d_blocks);
+    if (Bt->d_wg) hipFree(Bt->d_wg);
+        Bt->d_blocks = nullptr; Bt->blocksCap = 0;
+        void *q = nullptr;
+        CHK(hipMalloc(&q, Bt->blocks.size() * sizeof(BatchBlock)));
+        Bt->d_blocks = (BatchBlock *) q; Bt->blocksCap = Bt->blocks.size();
+    }
+    CHK(hipMemcpyAsync(Bt->d_blocks, Bt->blocks.data(), Bt->blocks.size() * sizeof(BatchBlock), hipMemcpyHostToDevice, H0->stream));
+    if (Bt->balanced) {
+        // the per-workgroup block ranges of the three launches (whole batch | half A | half B), valid while the windows keep the chunks ldso_ba_batch_create cut
+        bool ok = (int) Bt->wg[0].size() >= 2 && Bt->wg[0].back() == Bt->totalChunks && Bt->wg[1].back() == Bt->halfChunks[0] && (Bt->halfChunks[1] == 0 || Bt->wg[2].back() == Bt->halfChunks[1]);
+        REQ(ok, "ldso_ba_batch: the windows of the batch were re-chunked behind its back (ldso_ba_set_window / ldso_ba_set_chunk_points on a member): destroy and re-create the batch");
+        std::vector<int32_t> all;
+        for (int u = 0; u < 3; u++) { Bt->wgOff[u] = all.size(); Bt->nWG[u] = Bt->wg[u].empty() ? 0 : (int) Bt->wg[u].size() - 1; all.insert(all.end(), Bt->wg[u].begin(), Bt->wg[u].end()); }
+        if (all.size() > Bt->wgCap) {
+            CHK(hipStreamSynchronize(H0->stream));
+            if (Bt->aux) CHK(hipStreamSynchronize(Bt->aux));
+            if (Bt->d_wg) hipFree(Bt->d_wg);
+            Bt->d_wg = nullptr; Bt->wgCap = 0;
+            void *q = nullptr;
+            CHK(hipMalloc(&q, all.size() * sizeof(int32_t)));
+            Bt->d_wg = (int32_t *) q; Bt->wgCap = all.size();
+        }
+        Bt->wgHost.swap(all);
+        CHK(hipMemcpyAsync(Bt->d_wg, Bt->wgHost.data(), Bt->wgHost.size() * sizeof(int32_t), hipMemcpyHostToDevice, H0->stream));
+    }
+    return LDSO_OK;
+}
+
+// Cut the windows [i0, i1) of a batch into chunks so that `nWG` workgroups, each working through a run of consecutive chunks, carry the same load.  A chunk
+// (= one pass of linearize_body: operand staging, software-pipeline fill, block reduction) costs `c0` point-equivalents on top of its points, and never
+// straddles a host frame.  The smallest per-workgroup budget that fits all points into nWG workgroups is found by bisection; cuts[i] receives the chunk ends
+// of window i, wg the first chunk of every workgroup (nWG + 1 entries, counted over the windows [i0, i1) in order).
+// The balancer proper, host logic without a device (C-ABI: ldso_ba_balance_chunks, tests/test_batch_balance_cpu.py): segments (runs of points that may share a chunk: one
+// window's points of one host frame) in launch order -> chunk ends per segment (relative to the segment) and the first chunk of every workgroup.
+struct BalSeg { int owner, p0, n; };
+static long balance_segments(const std::vector<BalSeg> &segs, int nWG, int c0, std::vector<std::vector<int32_t>> *cutsByOwner, std::vector<int32_t> *wg, std::vector<int32_t> *flatEnds) {
+    long total = 0;
+    for (const BalSeg &sg : segs) total += sg.n;
+    auto run = [&](long budget, bool emit) -> bool {
+        size_t si = 0; int used = 0;          // points of segs[si] already handed out
+        int blocks = 0;
+        if (emit) { if (wg) wg->assign(1, 0); if (flatEnds) flatEnds->clear(); }
+        for (int w = 0; w < nWG && si < segs.size(); w++) {
+            long left = budget;
+            while (si < segs.size()) {
+                const int rem = segs[si].n - used;
+                long can = left - c0;
+                if (can < LD_WAVES && left != budget) break;          // not worth a chunk of its own here: the next workgroup takes it
+                if (can < 1) can = 1;
+                int take = (int) std::min<long>(rem, can);
+                if (take < rem) { take = std::max(take / LD_WAVES * LD_WAVES, 1); if (rem - take < LD_WAVES) take = rem; }          // whole rounds of the workgroup's wavefronts, no crumbs left behind
+                if (emit) {
+                    if (cutsByOwner) (*cutsByOwner)[(size_t) segs[si].owner].push_back(segs[si].p0 + used + take);
+                    if (flatEnds) flatEnds->push_back(segs[si].p0 + used + take);
+                }
+                blocks++; left -= c0 + take; used += take;
+                if (used == segs[si].n) { si++; used = 0; }
+                if (left <= 0) break;
+            }
+            if (emit && wg) wg->push_back(blocks);
+        }
+        if (emit && wg) while ((int) wg->size() < nWG + 1) wg->push_back(blocks);
+        return si == segs.size();
+    };
+    long lo = std::max<long>(1, total / std::max(nWG, 1)), hi = total + (long) c0 * (long) segs.size() + 1;
+    while (lo < hi) { const long mid = (lo + hi) / 2; if (run(mid, false)) hi = mid; else lo = mid + 1; }
+    run(lo, true);
+    return lo;
+}
+static void balance_batch(ldso_ba *const *handles, int i0, int i1, int nWG, int c0, std::vector<std::vector<int32_t>> &cuts, std::vector<int32_t> &wg) {
+    std::vector<BalSeg> segs;
+    for (int i = i0; i < i1; i++) {
+        const ldso_ba *H = handles[i];
+        cuts[i].clear();
+        int p = 0;
+        while (p < H->D.P) { int e = p; while (e < H->D.P && H->h_phost[e] == H->h_phost[p]) e++; segs.push_back(BalSeg{i, p, e - p}); p = e; }
+    }
+    balance_segments(segs, nWG, c0, &cuts, &wg, nullptr);
+}
+extern "C" {
+
+// host logic, no device: `n_seg` segments of seg_points[i] points each (in launch order; a chunk never spans two segments), `n_wg` workgroups, `chunk_cost` points of fixed
+// cost per chunk -> chunk_end[] (cumulative over ALL points, ascending, the last one = the total), wg_first_chunk[n_wg + 1]; returns the number of chunks (< 0: error / cap too small)
+int ldso_ba_balance_chunks(int n_seg, const int32_t *seg_points, int n_wg, int chunk_cost, int32_t *chunk_end, int cap, int32_t *wg_first_chunk, int64_t *budget_out) {
+    REQ(n_seg >= 1 && seg_points && n_wg >= 1 && chunk_cost >= 0 && chunk_end && wg_first_chunk, "ldso_ba_balance_chunks: bad arguments");
+    std::vector<BalSeg> segs;
+    int p = 0;
+    for (int i = 0; i < n_seg; i++) { REQ(seg_points[i] >= 1, "ldso_ba_balance_chunks: empty segment"); segs.push_back(BalSeg{0, p, seg_points[i]}); p += seg_points[i]; }
+    std::vector<int32_t> wg, ends;
+    const long budget = balance_segments(segs, n_wg, chunk_cost, nullptr, &wg, &ends);
+    if ((int) ends.size() > cap) { ldso_set_error("ldso_ba_balance_chunks: chunk_end[] too small"); return LDSO_E_INVALID; }
+    for (size_t i = 0; i < ends.size(); i++) chunk_end[i] = ends[i];
+    for (int w = 0; w <= n_wg; w++) wg_first_chunk[w] = wg[(size_t) w];
+    if (budget_out) *budget_out = budget;
+    return (int) ends.size();
+}
+
+int ldso_ba_batch_create(ldso_ba_t *const *handles, int n, ldso_ba_batch_t **out) {
+    REQ(handles && n >= 1 && out, "ldso_ba_batch_create: bad arguments");
+    ldso_ba *H0 = handles[0];
+    REQ(H0 && H0->D.P > 0, "ldso_ba_batch_create: window 0 is not set");
+    for (int i = 0; i < n; i++) {
+        ldso_ba *H = handles[i];
+        REQ(H && H->D.P > 0, "ldso_ba_batch_create: every handle needs a resident window");
+        REQ(H->device == H0->device && H->stream == H0->stream, "ldso_ba_batch_create: the handles of a batch share one device and one stream (ldso_ba_set_stream)");
+        REQ(H->D.FS == H0->D.FS, "ldso_ba_batch_create: the windows of a batch use the same slot-table width (all F <= 8 or all 9 <= F <= 16)");
+        REQ(H->inBatch == nullptr, "ldso_ba_batch_create: a handle belongs to at most one batch at a time");
+        for (int k = 0; k < i; k++) REQ(handles[k] != H, "ldso_ba_batch_create: the same handle twice");
+        REQ(!H->hasL, "ldso_ba_batch_create: windows with linearised residuals run on their own handle");
+        REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, "ldso_ba_batch_create: sharded handles cannot be batched");
+        REQ(H->settings.forceAcceptStep && !H->pendingApply, "ldso_ba_batch_create: forced-accept schedule, no pending linearisation");
+        REQ(memcmp(&H->settings, &H0->settings, sizeof(H0->settings)) == 0, "ldso_ba_batch_create: the batched kernels run with ONE ldso_settings_t: every handle of a batch must have been created with identical settings");
+        // re-chunking re-forms a window's partial sums into its OTHER ping-pong set: the windows stay at one parity only if all of them are re-cut or none
+        REQ(H->chunkPoints == H0->chunkPoints, "ldso_ba_batch_create: the handles of a batch share one chunking policy (ldso_ba_set_chunk_points: all automatic or all the same value)");
+    }
+    CHK(hipSetDevice(H0->device));
+    // Chunking of a batch: the launch is filled by all windows together, so a workgroup takes several points per wavefront (its fixed
+    // costs - operand staging, block reduction, ~4.5 us - are then a fraction of its life) while the grid still holds a few workgroups
+    // per CU for balance.  Handles with an explicit ldso_ba_set_chunk_points keep theirs.
+    int Bt_chunk = 0;
+    bool balanced = false;
+    std::vector<int32_t> wgTab[3];
+    {
+        long total = 0;
+        for (int i = 0; i < n; i++) total += handles[i]->D.P;
+        int ppw = (int) (total / ((long) H0->numCU * LD_WAVES));               // points per wavefront slot of the chip
+        bool every = true;
+        for (int i = 0; i < n; i++) every = every && handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty();
+        if (ppw > 1 && every) {
+            // Round 6: every workgroup of a launch gets the SAME load.  With regular chunks the batched launch ran as ceil(chunks / CUs) rounds of equal
+            // workgroups - 1344 on 256 CUs: the last round a quarter full - and every chunk paid its fixed costs (staging, pipeline fill, block reduction:
+            // about two points per wavefront) for six points per wavefront.  Now one workgroup per CU and launch works through a run of chunks cut to measure.
+            const int c0 = 2 * LD_WAVES;          // fixed cost of a chunk in points (two rounds of the workgroup's wavefronts)
+            const int n0 = (n >= 4) ? n / 2 : n;
+            // A half-batch launch does not take every CU: the other half's k_reduce_batch_dense / k_gn_solve_batch run beside it (two streams), and a workgroup that
+            // owns its CU for the whole launch leaves them nothing to start on.  Measured (32 windows, MI355X): 128 / 192 / 208 / 224 / 240 / 256 workgroups per half
+            // -> 141.6 / 159.2 / 162.2 / 168.3 / 167.7 / 149.5 k window-iterations/s (profiles/r06_batch_sweeps.log).
+            const int nWG = (n >= 4) ? std::max(1, H0->numCU * 7 / 8) : H0->numCU;
+            std::vector<std::vector<int32_t>> cuts((size_t) n);
+            balance_batch(handles, 0, n0, nWG, c0, cuts, wgTab[1]);
+            if (n0 < n) balance_batch(handles, n0, n, nWG, c0, cuts, wgTab[2]);
+            // the whole-batch launch (ldso_ba_batch_time_linearize) runs the two halves' workgroups one after the other
+            wgTab[0] = wgTab[1];
+            if (n0 < n) for (size_t u = 1; u < wgTab[2].size(); u++) wgTab[0].push_back(wgTab[1].back() + wgTab[2][u]);
+            for (int i = 0; i < n; i++) {
+                handles[i]->chunkCuts = cuts[i];
+                const int r_ = rechunk(handles[i]);
+                if (r_ != LDSO_OK) { for (int k = 0; k <= i; k++) { handles[k]->chunkCuts.clear(); rechunk(handles[k]); } return r_; }      // leave nobody with the batch's chunks
+            }
+            long chunks = 0;
+            for (int i = 0; i < n; i++) chunks += handles[i]->D.nChunks;
+            Bt_chunk = (int) std::max<long>(1, (total + chunks / 2) / chunks);
+            balanced = true;
+        } else {
+            // regular chunks of up to 6 points per wavefront (round 4, B = 32: 122.0 / 139.3 / 128.6 k window-iterations/s at 4 / 6 / 8)
+            ppw = ppw < 1 ? 1 : ppw > 6 ? 6 : ppw;
+            const int CH = ppw * LD_WAVES;
+            Bt_chunk = ppw > 1 ? CH : 0;
+            for (int i = 0; i < n; i++) if (handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty() && ppw > 1) {      // ppw == 1: the single-window chunking already is the right one
+                handles[i]->chunkPoints = CH;
+                const int r_ = rechunk(handles[i]);
+                handles[i]->chunkPoints = 0;                                         // the policy stays "automatic": the next ldso_ba_set_window re-chunks for a single window
+                if (r_ != LDSO_OK) { for (int k = 0; k <= i; k++) rechunk(handles[k]); return r_; }      // leave nobody with the batch's chunks
+            }
+        }
+    }
+    ldso_ba_batch *Bt = new ldso_ba_batch();
+    Bt->chunkPoints = Bt_chunk;
+    Bt->balanced = balanced;
+    for (int u = 0; u < 3; u++) Bt->wg[u] = wgTab[u];
+    Bt->h.assign(handles, handles + n);
+    Bt->items.resize(2 * (size_t) n);
+    Bt->n0 = (n >= 4) ? n / 2 : n;
+    // K-splits per Schur tile of the batched reduction: a lone window spreads every 16 x 16 tile of its Schur complement over LD_SCT_KS = 8 workgroups (latency); the
+    // windows of a batch fill the chip anyway and halve the workgroups and the fp64 atomics (round 6, A/B on one box: 4 -> +3.3 % window-iterations/s at B = 32, 2 -> -11 %)
+    Bt->ks = (n >= 4) ? 4 : LD_SCT_KS;
+    Bt->FS = H0->D.FS;
+    Bt->Dmax = H0->D;
+    for (int i = 0; i < n; i++) if (handles[i]->D.F > Bt->Dmax.F) Bt->Dmax = handles[i]->D;
+    void *q = nullptr;
+    for (int i = 0; i < n; i++) handles[i]->inBatch = Bt;
+    // every failure from here on goes through ldso_ba_batch_destroy: it restores the single-window chunking and releases the handles
+    if (hipMalloc(&q, 2 * (size_t) n * sizeof(BatchItem)) != hipSuccess) { (void) hipGetLastError(); ldso_ba_batch_destroy(Bt); ldso_set_error("ldso_ba_batch_create: hipMalloc failed"); return LDSO_E_HIP; }
+    Bt->d_items = (BatchItem *) q;
+    if (Bt->n0 < n) {
+        if (hipStreamCreateWithFlags(&Bt->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&Bt->ev0, hipEventDisableTiming) != hipSuccess
+            || hipEventCreateWithFlags(&Bt->ev1, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&Bt->evEnd, hipEventDisableTiming) != hipSuccess) {
+            ldso_ba_batch_destroy(Bt); ldso_set_error("ldso_ba_batch_create: stream / event creation failed"); return LDSO_E_HIP;
+        }
+    }
+    *out = Bt;
+    return LDSO_OK;
+}
+
+// points per workgroup ldso_ba_batch_create chose for the windows of this batch (0: it left their single-window chunking alone)
+// K-splits per Schur tile the batch reduces its windows with (see ldso_ba_set_reduce_splits)
+int ldso_ba_batch_reduce_splits(ldso_ba_batch_t *Bt, int *splits) {
+    REQ(Bt && splits, "ldso_ba_batch_reduce_splits: bad arguments");
+    *splits = Bt->ks;
+    return LDSO_OK;
+}
+
+int ldso_ba_batch_chunk_points(ldso_ba_batch_t *Bt, int *points_per_workgroup) {
+    REQ(Bt && points_per_workgroup, "ldso_ba_batch_chunk_points: null argument");
+    *points_per_workgroup = Bt->chunkPoints;
+    return LDSO_OK;
+}
+
+int ldso_ba_batch_destroy(ldso_ba_batch_t *Bt) {
+    if (!Bt) return LDSO_OK;
+    hipSetDevice(Bt->h[0]->device);
+    hipStreamSynchronize(Bt->h[0]->stream);
+    if (Bt->aux) { hipStreamSynchronize(Bt->aux); hipStreamDestroy(Bt->aux); }
+    if (Bt->ev0) hipEventDestroy(Bt->ev0);
+    if (Bt->ev1) hipEventDestroy(Bt->ev1);
+    if (Bt->evEnd) hipEventDestroy(Bt->evEnd);
+    if (Bt->d_items) hipFree(Bt->d_items);
+    if (Bt->d_blocks) hipFree(Bt->d_blocks);
+    if (Bt->d_wg) hipFree(Bt->d_wg);
+    // back to the single-window chunking (handles that were re-chunked by ldso_ba_batch_create)
+    if (Bt->balanced) { for (ldso_ba *H : Bt->h) { H->chunkCuts.clear(); if (H->D.P > 0) rechunk(H); } }
+    else if (Bt->chunkPoints > 0) for (ldso_ba *H : Bt->h) if (H->chunkPoints == 0 && H->D.P > 0) rechunk(H);
+    for (ldso_ba *H : Bt->h) if (H->inBatch == Bt) H->inBatch = nullptr;
+    delete Bt;
+    return LDSO_OK;
+}
+
+// `iters` forced Gauss-Newton iterations of every window of the batch: 3 launches per iteration for the whole batch, no host
+// synchronisation.  Every window must hold an applied linearisation (ldso_ba_linearize_all + ldso_ba_apply_res, or a previous
+// optimize / enqueue) and all of them must be at the same ping-pong parity (true after identical call sequences).
+int ldso_ba_batch_enqueue_gn(ldso_ba_batch_t *Bt, int first_iteration, int iters) {
+    REQ(Bt && iters >= 0, "ldso_ba_batch_enqueue_gn: bad arguments");
+    ldso_ba *H0 = Bt->h[0];
+    CHK(hipSetDevice(H0->device));
+    for (ldso_ba *H : Bt->h) REQ(H->cur == H0->cur && !H->pendingApply, "ldso_ba_batch_enqueue_gn: the windows of a batch must be at the same stage");
+    RUN(batch_refresh(Bt));
+    const Damping d = damping(H0->settings, 1e-1);
+    int cur = H0->cur;
+    // The control step of a batch occupies two workgroups per window for ~30 us: the batch runs as two halves on two streams, the second
+    // half an iteration behind the first, so that one half's reduce + control step overlap the other half's (chip-filling) linearisation.
+    const int n = (int) Bt->h.size(), n0 = Bt->n0, n1 = n - n0;
+    const BatchItem *itA = Bt->d_items + n, *itB = Bt->d_items + n + n0;
+    if (n1 > 0 && iters > 0) { CHK(hipEventRecord(Bt->ev0, H0->stream)); CHK(hipStreamWaitEvent(Bt->aux, Bt->ev0, 0)); }
+    for (int i = 0; i < iters; i++) {
+        CHK(ba_launch_reduce_batch(itA, n0, Bt->halfReduce[0], cur, H0->settings.initialCalibHessian, d.l1, d.il, H0->stream));
+        CHK(ba_launch_gn_solve_batch(itA, n0, Bt->Dmax, cur, H0->settings, first_iteration + i, 1e-1, H0->stream));
+        if (n1 > 0 && i == 0) { CHK(hipEventRecord(Bt->ev1, H0->stream)); CHK(hipStreamWaitEvent(Bt->aux, Bt->ev1, 0)); }
+        CHK(ba_launch_linearize_batch(itA, Bt->d_blocks + Bt->totalChunks, Bt->halfChunks[0], Bt->balanced ? Bt->d_wg + Bt->wgOff[1] : nullptr, Bt->nWG[1], Bt->FS, cur, H0->settings, 1, H0->settings.initialCalibHessian, H0->stream));
+        if (n1 > 0) {
+            CHK(ba_launch_reduce_batch(itB, n1, Bt->halfReduce[1], cur, H0->settings.initialCalibHessian, d.l1, d.il, Bt->aux));
+            CHK(ba_launch_gn_solve_batch(itB, n1, Bt->Dmax, cur, H0->settings, first_iteration + i, 1e-1, Bt->aux));
+            CHK(ba_launch_linearize_batch(itB, Bt->d_blocks + Bt->totalChunks + Bt->halfChunks[0], Bt->halfChunks[1], Bt->balanced ? Bt->d_wg + Bt->wgOff[2] : nullptr, Bt->nWG[2], Bt->FS, cur, H0->settings, 1, H0->settings.initialCalibHessian, Bt->aux));
+        }
+        cur ^= 1;
+    }
+    if (n1 > 0 && iters > 0) { CHK(hipEventRecord(Bt->evEnd, Bt->aux)); CHK(hipStreamWaitEvent(H0->stream, Bt->evEnd, 0)); }      // ldso_ba_sync(handle) covers both halves
+    for (ldso_ba *H : Bt->h) H->cur = cur;
+    return LDSO_OK;
+}
+
+// average duration of the batched k_linearize for bench.py's roofline: `reps` back-to-back launches on the applied state (read set ->
+// scratch set, no point step: idempotent) between one pair of HIP events on the batch's stream
+int ldso_ba_batch_time_linearize(ldso_ba_batch_t *Bt, int reps, double *avg_us) {
+    REQ(Bt && reps > 0 && avg_us, "ldso_ba_batch_time_linearize: bad arguments");
+    ldso_ba *H0 = Bt->h[0];
+    CHK(hipSetDevice(H0->device));
+    RUN(batch_refresh(Bt));
+    return time_launches(H0->stream, reps, avg_us, [Bt, H0]() -> int {
+        CHK(ba_launch_linearize_batch(Bt->d_items, Bt->d_blocks, Bt->totalChunks, Bt->balanced ? Bt->d_wg + Bt->wgOff[0] : nullptr, Bt->nWG[0], Bt->FS, H0->cur, H0->settings, 0, H0->settings.initialCalibHessian, H0->stream));
+        return LDSO_OK;
+    });
+}
+}  // extern "C"

@@ -1,0 +1,185 @@
+// ba_host.h — what the host-side translation units of the library share: the error channel, the launcher prototypes of the kernel files, the
+// handle structs, and the host helpers that cross files (hidden: none of them is part of the library's interface).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <vector>
+#include <string>
+#include <cstring>
+#include <cstdio>
+#include <cmath>
+#include <algorithm>
+#include "../../include/ldso_hip.h"
+#include "ba_dev.h"
+#include "pyramid.h"
+#include "ba_solve.h"
+
+void ldso_set_error(const std::string &s);          // ba_api.hip (thread-local, read by ldso_last_error)
+#define CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ldso_set_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LDSO_E_HIP; } } while (0)
+#define REQ(cond, msg) do { if (!(cond)) { ldso_set_error(msg); return LDSO_E_INVALID; } } while (0)
+#define RUN(x) do { int r_ = (x); if (r_ != LDSO_OK) return r_; } while (0)
+
+// the launchers, defined beside their kernels (ba_linearize / ba_reduce / ba_solve / ba_activate .hip)
+hipError_t ba_launch_linearize(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, bool hasL, bool fix, int stepMode, const GnInit &gi, hipStream_t st);
+hipError_t ba_launch_reduce(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, bool hasL, int GSP, int atomicMode, bool hasPrior, float calibPrior, double l1, double il, int itCheck, hipStream_t st);
+hipError_t ba_launch_gather(const BaPtrs &B, const BaDims &D, const ResSet &S, bool hasL, bool hasPrior, int GSP, double lambda, const ldso_settings_t &St, int mode, double *rbuf, hipStream_t st);
+hipError_t ba_launch_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, hipStream_t st);
+hipError_t ba_launch_point_step(const BaPtrs &B, const BaDims &D, const ResSet &S, int mode, hipStream_t st);
+hipError_t ba_launch_linearize_one(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, int stepMode, const GnInit &gi, const LinHead &hd, hipStream_t st);
+hipError_t ba_launch_linearize_marg(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, const int32_t *margFlags, hipStream_t st);
+hipError_t ba_launch_marg_frame(const BaPtrs &B, const BaDims &D, int idx, double *work, double *outH, double *outb, hipStream_t st);
+hipError_t ba_launch_acc_init(const BaPtrs &B, const BaDims &D, const GnInit &gi, hipStream_t st);
+hipError_t ba_launch_gn_export(const BaPtrs &B, const BaDims &D, const ResSet &S, double *tail, hipStream_t st);
+hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
+hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, int FS, int cur, const ldso_settings_t &S, int stepMode, float calibPrior, hipStream_t st, int itCheck = -1);
+hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st);
+hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, int cur, const ldso_settings_t &St, int iteration, double lambda, hipStream_t st);
+hipError_t ba_launch_lm_energies(const BaPtrs &B, const BaDims &D, const ResSet &S, float calibPrior, bool hasPrior, hipStream_t st);
+hipError_t ba_launch_marg_update(const BaPtrs &B, const BaDims &D, double w, hipStream_t st);
+hipError_t ba_launch_gn_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, hipStream_t st);
+hipError_t ba_launch_reduce_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, const ChunkStarts &chunkStart, int atomicMode, float calibPrior, double l1, double il, hipStream_t st);
+
+struct Timer { hipEvent_t a, b; int which; };
+struct ldso_ba {
+    int device = 0, w = 0, h = 0, maxF = 0, maxP = 0, FSmax = 0, maxChunks = 0, numCU = 256;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    ldso_settings_t settings;
+    BaDims D;
+    BaPtrs B;
+    ResSet sets[2];
+    int cur = 0;
+    bool pendingApply = false;
+    bool hasL = false;
+    bool hasPrior = false;
+    int GSP = 0;
+    int R = 0;
+    float *imgSlots[LD_MAXF] = {nullptr};
+    bool imgOwned[LD_MAXF] = {false};
+    int32_t *d_chunkStart = nullptr;
+    int *d_waitCtr = nullptr;          // k_reduce_solve: producer counter (zero between launches)
+    int32_t *d_margFlags = nullptr;
+    float *d_color = nullptr;          // irradiance staging of ldso_ba_set_image_raw
+    void *d_act = nullptr;             // staging of ldso_ba_activate_points: n immature records + n results
+    int actCap = 0;
+    double *ownAcc = nullptr;          // the handle's own HFinal/bFinal accumulator (B.acc may point at a caller's all-reduce buffer)
+    ChunkStarts chunkStarts;
+    ldso_rawjac_t *d_dumpJ = nullptr;
+    std::vector<int32_t> flat2slot;
+    std::vector<int32_t> imageSlot;
+    std::vector<void *> allocs;
+    // host staging of the window (for shard rebuilds)
+    std::vector<int32_t> h_phost;
+    // window upload: ONE pinned staging arena -> ONE device arena -> one scatter kernel (k_win_scatter) instead of ~25 copies + ~20 fills
+    // the window's descriptors in device memory (one BatchItem): the plain linearisation of the GN iteration reads them from there - passed
+    // as kernel arguments, the ~150 pointers outgrow the scalar registers (400 SGPR spill moves in the kernel)
+    BatchItem *d_item = nullptr, *h_item = nullptr;
+    BatchBlock *d_blocks = nullptr;    // [maxChunks] the window's chunks as k_linearize_batch reads them (window index 0)
+    std::vector<BatchBlock> h_blocks;
+    bool appliedValid = false;         // the applied residual set holds a linearisation of the resident window (its per-chunk partials feed the next reduce)
+    LinHead linHead;                   // chunk geometry of the current window by value (k_linearize_one)
+    int reduceSplits = LD_SCT_KS;      // K-splits per 16 x 16 Schur tile (BaDims::ks; ldso_ba_set_reduce_splits)
+    bool linHeadOk = false;            // the chunks are regular (every host cut into CH-point pieces): true for everything build_chunks produces
+    const void *inBatch = nullptr;     // the ldso_ba_batch this handle belongs to (at most one; it must outlive the batch: ldso_ba_destroy refuses while set)
+    int chunkPoints = 0;               // points per workgroup of k_linearize: 0 = as few as keep the grid within one wave of workgroups (one window alone on the chip)
+    std::vector<int32_t> chunkCuts;    // explicit chunk ends (ldso_ba_set_chunk_cuts / ldso_ba_batch_create: uneven chunks, one workload per workgroup); empty: regular chunks of chunkPoints
+    BatchItem itemShadow;
+    bool itemValid = false;
+    int *h_stop = nullptr, *d_stop = nullptr;      // host-mapped word (and its device address): which iteration ended an un-forced optimize() loop
+    char *h_down = nullptr;             // pinned arena of the fetch functions (ldso_ba_get_residuals / _points / _frames): device -> pinned host at link speed, one wait
+    size_t downCap = 0;
+    bool stageBusy = false;            // an asynchronous copy out of h_stage may still be in flight (ldso_ba_set_prior): the next user of the arena waits first
+    // an edit of the resident window being recorded (ldso_ba_window_begin .. ldso_ba_window_commit): frames and residual targets are named by their index in the
+    // RESIDENT window (inserted frames: oF, oF + 1, ...), points by their resident row
+    struct NewPoint { ldso_point_t p; int before; std::vector<ldso_residual_t> res; float mrb; int32_t ngr; };
+    struct WindowEdit {
+        bool active = false;
+        int oF = 0, oP = 0;
+        std::vector<char> frameGone, rowGone;
+        std::vector<int32_t> insertedSlots;
+        std::vector<uint32_t> mask;          // per resident row, bit = edit-time frame id
+        std::vector<NewPoint> fresh;
+    } edit;
+    char *h_stage = nullptr, *d_stage = nullptr;
+    size_t stageCap = 0;
+    // profiling
+    bool profile = false;
+    std::vector<Timer> timers;
+    double tsum[5] = {0, 0, 0, 0, 0};
+    int tcnt[5] = {0, 0, 0, 0, 0};
+    int lastIterations = 0;
+    bool noFusedLaunch = false;        // debug: k_reduce and k_gn_solve as two launches even where the fused k_reduce_solve applies
+    // ldso_ba_enqueue_gn replays a cached HIP graph when the same launch sequence was enqueued before: the key is EVERYTHING the launches take as
+    // arguments (pointer tables, dimensions, both residual sets, settings, chunk geometry, flags, stream, first iteration, count, parity of the sets),
+    // byte for byte (round 6: the 64-bit hash of those bytes only pre-selects - a collision must not replay another window's launches)
+    struct GnGraph { unsigned long long sig; std::vector<unsigned char> key; hipGraphExec_t exec; hipGraph_t graph; };
+    std::vector<GnGraph> gnGraphs;
+    std::vector<unsigned char> gnKeyScratch;      // the key of the current call (kept to avoid an allocation per enqueue)
+    bool gnUseGraphs = true;
+    double *distBuf = nullptr;         // ldso_ba_enqueue_gn_rccl / _p2p: all-reduce buffer [HFinal | bFinal | scalars | candidates]
+    unsigned p2pSeq = 0;               // ldso_ba_enqueue_gn_p2p: exchanges done (the tag of the hand-over words)
+    int *d_p2pErr = nullptr;           // set by k_p2p_sum when a peer's words did not arrive in time
+    double neverStop = 1e300;          // source of the LD_SC_STOP reset (outlives the asynchronous copy)
+};
+
+#define REQ_UNSHARDED(name) REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, name ": not available on a sharded handle (ldso_ba_set_shard): " \
+                                    "use ldso_ba_gn_reduce_local / ldso_ba_gn_solve_reduced or ldso_ba_reduce_local / ldso_ba_solve_reduced around the all-reduce")
+
+// a batch of windows (ba_batch.hip)
+struct ldso_ba_batch {
+    std::vector<ldso_ba *> h;
+    BatchItem *d_items = nullptr;      // [n] numbered over the whole batch, then [n] numbered per half (see ldso_ba_batch_enqueue_gn)
+    std::vector<BatchItem> items;
+    BatchBlock *d_blocks = nullptr;    // [totalChunks] workgroups of the whole batch, then [halfChunks[0]] + [halfChunks[1]] per half
+    std::vector<BatchBlock> blocks;
+    size_t blocksCap = 0;
+    int chunkPoints = 0;               // the chunking ldso_ba_batch_create gave its windows
+    int totalChunks = 0, totalReduce = 0, FS = 0, cur = 0;
+    int n0 = 0;                        // windows in the first half (= all of them for batches under 4 windows)
+    int ks = LD_SCT_KS;                // K-splits per Schur tile of the batched reduction (ldso_ba_batch_create: 4 from 4 windows on)
+    int halfChunks[2] = {0, 0}, halfReduce[2] = {0, 0};
+    // Balanced launches (round 6): workgroup w of a batched k_linearize works through the blocks [wgStart[w], wgStart[w + 1]) of its launch's table, cut by
+    // ldso_ba_batch_create so that every workgroup carries the same load.  wg[0] = the whole batch, wg[1] / wg[2] = the halves; empty: one block per workgroup
+    std::vector<int32_t> wg[3];
+    int32_t *d_wg = nullptr; size_t wgCap = 0;
+    std::vector<int32_t> wgHost;       // what d_wg holds (kept: the copy is asynchronous)
+    int nWG[3] = {0, 0, 0}; size_t wgOff[3] = {0, 0, 0};
+    bool balanced = false;
+    hipStream_t aux = nullptr;         // second stream: the two halves run half an iteration apart
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, evEnd = nullptr;
+    BaDims Dmax;
+};
+
+#pragma GCC visibility push(hidden)
+int build_chunks(ldso_ba *H);          // ba_window.hip
+int rechunk(ldso_ba *H);
+// ba_optimize.hip: the launch helpers (with optional HIP-event timing) and what every caller of a launcher fills in the same way
+void t_begin(ldso_ba *H, int which);
+void t_end(ldso_ba *H);
+int launch_linearize(ldso_ba *H, bool fix, int stepMode = 0, int itCheck = -1);
+int launch_reduce(ldso_ba *H, const ResSet &S, bool atomicMode = false, double lambda = 0.0, int itCheck = -1);
+int launch_gather(ldso_ba *H, const ResSet &S, double lambda, int mode, double *rbuf);
+int launch_solve(ldso_ba *H, const ResSet &S, unsigned flags, int iteration = 0, double lambda = 0, int logIdx = -1, double *rout = nullptr, const double *rin = nullptr);
+int launch_pstep(ldso_ba *H, const ResSet &S, int mode);
+int refresh_item(ldso_ba *H);
+int read_scalars(ldso_ba *H, double *sc);
+SolveArgs solve_args(const ldso_ba *H, unsigned flags);
+struct Damping { double lam, l1, il; };
+Damping damping(const ldso_settings_t &St, double lambda);
+GnInit gn_init(const ldso_ba *H, int itCheck);
+int lend_acc(ldso_ba *H, double *buf);
+// one warm launch, then `reps` launches between ONE pair of HIP events on `st` (the event overhead is amortised over them): microseconds per launch
+template <class Launch> int time_launches(hipStream_t st, int reps, double *avg_us, Launch launch) {
+    hipEvent_t a, b;
+    CHK(hipEventCreate(&a)); CHK(hipEventCreate(&b));
+    RUN(launch());          // warm
+    CHK(hipEventRecord(a, st));
+    for (int i = 0; i < reps; i++) RUN(launch());
+    CHK(hipEventRecord(b, st));
+    CHK(hipEventSynchronize(b));
+    float ms = 0;
+    CHK(hipEventElapsedTime(&ms, a, b));
+    (void) hipEventDestroy(a); (void) hipEventDestroy(b);
+    *avg_us = (double) ms * 1e3 / reps;
+    return LDSO_OK;
+}
+#pragma GCC visibility pop

@@ -19,7 +19,7 @@
 // CPU path; fused multiply-adds are used only (explicitly) in the accumulators.
 #include <hip/hip_runtime.h>
 #include <type_traits>
-#include "ba_dev.h"
+#include "ba_host.h"
 
 #define RES_IN 0
 #define RES_OOB 1
@@ -696,7 +696,7 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
                 newEnergy = energyLeft;
                 ret = (double) energyLeft;
                 c0 = cKu; c1 = cKv; c2 = new_idepth;
-                // stepMode bit 2 (re-chunking, ba_api.hip rechunk()): the applied state is linearised again only to re-form the per-chunk
+                // stepMode bit 2 (re-chunking, ba_window.hip rechunk()): the applied state is linearised again only to re-form the per-chunk
                 // partial sums - the decisions of the pass that produced it stand (its energy thresholds have moved on since)
                 if (stepMode & 4) { newState = st; newEnergy = qEnergy[g]; ret = (double) newEnergy; }
             }

@@ -13,7 +13,7 @@
 // Also here: k_gather (assembly of H_A,b_A,H_L,b_L,H_sc,b_sc,HFinal,bFinal for the step-wise path and the old all-reduce layout),
 // k_marg_update / k_marg_frame (EnergyFunctional::marginalizePointsF tail, marginalizeFrame), k_acc_init.
 #include <hip/hip_runtime.h>
-#include "ba_dev.h"
+#include "ba_host.h"
 
 #include "ba_reduce_body.h"
 

@@ -21,9 +21,8 @@
 // All dense math is fp64 like the reference.  The factorisation is an unpivoted LDL^T of the (diag+10)^-1/2-scaled system (SPD
 // after the scaling; Eigen's LDLT pivots on the diagonal and gives the same solution up to rounding), see solve_core.
 #include <hip/hip_runtime.h>
-#include "ba_dev.h"
+#include "ba_host.h"
 #include "lie_dev.h"
-#include "ba_solve.h"
 
 #include "ba_reduce_body.h"
 #define NT 256

@@ -21,19 +21,8 @@
 // depth of that order (a diagonal front through the raster: 200-590 passes per level at 640 x 480, 20-40 points wide) is what
 // a sweep costs, so a pass is made as short as it can be: optReg with two lanes per point and a fixed selection instead of a
 // count-dependent one (ini_sw2_point: 28 instructions, 0.11 us per pass; round 4: one lane, a 10-key sorting network, 0.38 us).
-#include <hip/hip_runtime.h>
-#include <vector>
-#include <string>
-#include <cstring>
-#include <cmath>
-#include <algorithm>
-#include "../../include/ldso_hip.h"
+#include "ba_host.h"
 #include "lie_dev.h"
-
-void ldso_set_error(const std::string &s);
-extern "C" hipError_t img_launch_make_images(const float *d_color, int w, int h, int levels, float *const *d_levels, hipStream_t st);
-#define CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ldso_set_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LDSO_E_HIP; } } while (0)
-#define REQ(cond, msg) do { if (!(cond)) { ldso_set_error(msg); return LDSO_E_INVALID; } } while (0)
 
 #define INI_MAXL 5            // maxIterations[] has five entries (CoarseInitializer.cc:43)
 #define INI_NT 256            // threads of an eval block: 32 points x 8 pattern pixels

@@ -8,15 +8,7 @@
 // to the CPU path; the best step (first minimum) and the second-best outside the +-radius window are wave reductions.  The
 // short Gauss-Newton refinement (<= 3 iterations of 8 samples) and the scalar bookkeeping run uniformly in all lanes.
 // Memory: per point 128 B record in / out + 4-byte taps of the level-0 image along the epipolar line (L2 resident).
-#include <hip/hip_runtime.h>
-#include <vector>
-#include <string>
-#include <cstring>
-#include <cmath>
-#include "../../include/ldso_hip.h"
-
-void ldso_set_error(const std::string &s);
-#include "pyramid.h"
+#include "ba_host.h"
 
 struct TraceArgs {
     ldso_immature_t *pts;
@@ -253,9 +245,6 @@ struct ldso_tracer {
     bool haveFrame = false;
 };
 
-#define TCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ldso_set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return LDSO_E_HIP; } } while (0)
-#define TREQ(c, msg) do { if (!(c)) { ldso_set_error(msg); return LDSO_E_INVALID; } } while (0)
-
 extern "C" {
 
 int ldso_trace_settings_default(ldso_trace_settings_t *s) {
@@ -267,20 +256,20 @@ int ldso_trace_settings_default(ldso_trace_settings_t *s) {
 }
 
 int ldso_trace_create(int device, int w, int h, int max_points, ldso_tracer_t **out) {
-    TREQ(out && w > 16 && h > 16 && max_points > 0, "ldso_trace_create: bad arguments");
+    REQ(out && w > 16 && h > 16 && max_points > 0, "ldso_trace_create: bad arguments");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    TREQ(device >= 0 && device < ndev, "ldso_trace_create: device index out of range");
-    TCHK(hipSetDevice(device));
+    REQ(device >= 0 && device < ndev, "ldso_trace_create: device index out of range");
+    CHK(hipSetDevice(device));
     ldso_tracer *T = new ldso_tracer();
     T->device = device; T->w = w; T->h = h; T->maxPoints = max_points;
     ldso_trace_settings_default(&T->settings);
-    TCHK(hipStreamCreateWithFlags(&T->stream, hipStreamNonBlocking));
-    TCHK(hipMalloc(&T->d_pts, (size_t) max_points * sizeof(ldso_immature_t)));
-    TCHK(hipMalloc(&T->d_img, (size_t) w * h * 12));
-    TCHK(hipMalloc(&T->d_color, (size_t) w * h * 4));
-    TCHK(hipMalloc(&T->d_pose, (size_t) LDSO_MAX_FRAMES * 14 * 4));
-    TCHK(hipMalloc(&T->d_counts, 8 * 4));
+    CHK(hipStreamCreateWithFlags(&T->stream, hipStreamNonBlocking));
+    CHK(hipMalloc(&T->d_pts, (size_t) max_points * sizeof(ldso_immature_t)));
+    CHK(hipMalloc(&T->d_img, (size_t) w * h * 12));
+    CHK(hipMalloc(&T->d_color, (size_t) w * h * 4));
+    CHK(hipMalloc(&T->d_pose, (size_t) LDSO_MAX_FRAMES * 14 * 4));
+    CHK(hipMalloc(&T->d_counts, 8 * 4));
     *out = T;
     return LDSO_OK;
 }
@@ -296,69 +285,69 @@ int ldso_trace_destroy(ldso_tracer_t *T) {
 }
 
 int ldso_trace_set_settings(ldso_tracer_t *T, const ldso_trace_settings_t *s) {
-    TREQ(T && s, "null argument");
-    TREQ(s->trace_GNIterations >= 0 && s->trace_stepsize > 0 && s->minTraceTestRadius >= 0, "ldso_trace_set_settings: bad values");
+    REQ(T && s, "null argument");
+    REQ(s->trace_GNIterations >= 0 && s->trace_stepsize > 0 && s->minTraceTestRadius >= 0, "ldso_trace_set_settings: bad values");
     T->settings = *s;
     return LDSO_OK;
 }
 
 int ldso_trace_set_points(ldso_tracer_t *T, int n, const ldso_immature_t *pts) {
-    TREQ(T && n >= 0 && n <= T->maxPoints && (n == 0 || pts), "ldso_trace_set_points: bad arguments");
-    TCHK(hipSetDevice(T->device));
-    if (n) TCHK(hipMemcpyAsync(T->d_pts, pts, (size_t) n * sizeof(ldso_immature_t), hipMemcpyHostToDevice, T->stream));
-    TCHK(hipStreamSynchronize(T->stream));
+    REQ(T && n >= 0 && n <= T->maxPoints && (n == 0 || pts), "ldso_trace_set_points: bad arguments");
+    CHK(hipSetDevice(T->device));
+    if (n) CHK(hipMemcpyAsync(T->d_pts, pts, (size_t) n * sizeof(ldso_immature_t), hipMemcpyHostToDevice, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
     T->n = n;
     return LDSO_OK;
 }
 
 int ldso_trace_get_points(ldso_tracer_t *T, ldso_immature_t *out) {
-    TREQ(T && (T->n == 0 || out), "ldso_trace_get_points: bad arguments");
-    TCHK(hipSetDevice(T->device));
-    if (T->n) TCHK(hipMemcpyAsync(out, T->d_pts, (size_t) T->n * sizeof(ldso_immature_t), hipMemcpyDeviceToHost, T->stream));
-    TCHK(hipStreamSynchronize(T->stream));
+    REQ(T && (T->n == 0 || out), "ldso_trace_get_points: bad arguments");
+    CHK(hipSetDevice(T->device));
+    if (T->n) CHK(hipMemcpyAsync(out, T->d_pts, (size_t) T->n * sizeof(ldso_immature_t), hipMemcpyDeviceToHost, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
     return LDSO_OK;
 }
 
 int ldso_trace_set_frame(ldso_tracer_t *T, const float *dI) {
-    TREQ(T && dI, "ldso_trace_set_frame: bad arguments");
-    TCHK(hipSetDevice(T->device));
-    TCHK(hipMemcpyAsync(T->d_img, dI, (size_t) T->w * T->h * 12, hipMemcpyHostToDevice, T->stream));
-    TCHK(hipStreamSynchronize(T->stream));
+    REQ(T && dI, "ldso_trace_set_frame: bad arguments");
+    CHK(hipSetDevice(T->device));
+    CHK(hipMemcpyAsync(T->d_img, dI, (size_t) T->w * T->h * 12, hipMemcpyHostToDevice, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
     T->haveFrame = true; T->img = T->d_img;
     return LDSO_OK;
 }
 
 int ldso_trace_set_frame_raw(ldso_tracer_t *T, const float *irradiance) {
-    TREQ(T && irradiance, "ldso_trace_set_frame_raw: bad arguments");
-    TCHK(hipSetDevice(T->device));
-    TCHK(hipMemcpyAsync(T->d_color, irradiance, (size_t) T->w * T->h * 4, hipMemcpyHostToDevice, T->stream));
+    REQ(T && irradiance, "ldso_trace_set_frame_raw: bad arguments");
+    CHK(hipSetDevice(T->device));
+    CHK(hipMemcpyAsync(T->d_color, irradiance, (size_t) T->w * T->h * 4, hipMemcpyHostToDevice, T->stream));
     float *lv[1] = {T->d_img};
-    TCHK(img_launch_make_images(T->d_color, T->w, T->h, 1, lv, T->stream));
-    TCHK(hipStreamSynchronize(T->stream));
+    CHK(img_launch_make_images(T->d_color, T->w, T->h, 1, lv, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
     T->haveFrame = true; T->img = T->d_img;
     return LDSO_OK;
 }
 
 // the new frame as a resident ldso_pyramid_t (zero-copy: ImmaturePoint::traceOn samples frame->dI = level 0)
 int ldso_trace_set_frame_pyramid(ldso_tracer_t *T, ldso_pyramid_t *pyr) {
-    TREQ(T && pyr, "ldso_trace_set_frame_pyramid: bad arguments");
-    TREQ(pyr->built && pyr->device == T->device && pyr->w == T->w && pyr->h == T->h, "ldso_trace_set_frame_pyramid: pyramid does not match the tracer (device, size) or holds no image");
-    TCHK(hipSetDevice(T->device));
-    TCHK(hipStreamWaitEvent(T->stream, pyr->ready, 0));
+    REQ(T && pyr, "ldso_trace_set_frame_pyramid: bad arguments");
+    REQ(pyr->built && pyr->device == T->device && pyr->w == T->w && pyr->h == T->h, "ldso_trace_set_frame_pyramid: pyramid does not match the tracer (device, size) or holds no image");
+    CHK(hipSetDevice(T->device));
+    CHK(hipStreamWaitEvent(T->stream, pyr->ready, 0));
     T->haveFrame = true; T->img = pyr->lv[0];
     return LDSO_OK;
 }
 
 int ldso_trace_on(ldso_tracer_t *T, int n_hosts, const float *KRKi, const float *Kt, const float *aff, int *counts_out) {
-    TREQ(T && n_hosts > 0 && n_hosts <= LDSO_MAX_FRAMES && KRKi && Kt && aff, "ldso_trace_on: bad arguments");
-    TREQ(T->haveFrame, "ldso_trace_on: set the new frame first");
-    TCHK(hipSetDevice(T->device));
+    REQ(T && n_hosts > 0 && n_hosts <= LDSO_MAX_FRAMES && KRKi && Kt && aff, "ldso_trace_on: bad arguments");
+    REQ(T->haveFrame, "ldso_trace_on: set the new frame first");
+    CHK(hipSetDevice(T->device));
     std::vector<float> pose((size_t) n_hosts * 14);
     memcpy(pose.data(), KRKi, (size_t) n_hosts * 9 * 4);
     memcpy(pose.data() + n_hosts * 9, Kt, (size_t) n_hosts * 3 * 4);
     memcpy(pose.data() + n_hosts * 12, aff, (size_t) n_hosts * 2 * 4);
-    TCHK(hipMemcpyAsync(T->d_pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, T->stream));
-    TCHK(hipMemsetAsync(T->d_counts, 0, 8 * 4, T->stream));
+    CHK(hipMemcpyAsync(T->d_pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, T->stream));
+    CHK(hipMemsetAsync(T->d_counts, 0, 8 * 4, T->stream));
     if (T->n > 0) {
         TraceArgs A;
         A.pts = T->d_pts; A.n = T->n; A.img = T->img; A.w = T->w; A.h = T->h;
@@ -366,11 +355,11 @@ int ldso_trace_on(ldso_tracer_t *T, int n_hosts, const float *KRKi, const float 
         A.s = T->settings; A.counts = T->d_counts;
         const int waves = T->n, blocks = (waves + 3) / 4;
         hipLaunchKernelGGL(k_trace_on, dim3(blocks), dim3(256), 0, T->stream, A);
-        TCHK(hipGetLastError());
+        CHK(hipGetLastError());
     }
     int c[8] = {0};
-    TCHK(hipMemcpyAsync(c, T->d_counts, 8 * 4, hipMemcpyDeviceToHost, T->stream));
-    TCHK(hipStreamSynchronize(T->stream));
+    CHK(hipMemcpyAsync(c, T->d_counts, 8 * 4, hipMemcpyDeviceToHost, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
     if (counts_out) for (int i = 0; i < 6; i++) counts_out[i] = c[i];
     return LDSO_OK;
 }

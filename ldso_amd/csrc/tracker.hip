@@ -11,21 +11,10 @@
 //                                                    accept/reject logic run on the device in fp64.
 // The per-level point clouds are tiny (10^3..10^4 points): the path is latency bound, so the design minimises
 // dependent launches, and batches hypotheses across workgroups (FullSystem::trackNewCoarse tries up to 83).
-#include <hip/hip_runtime.h>
-#include <vector>
 #include <mutex>
-#include <string>
-#include <cstring>
-#include <cmath>
-#include "../../include/ldso_hip.h"
-#include "lie_dev.h"
-#include "pyramid.h"
 #include <cstdlib>
-
-void ldso_set_error(const std::string &s);
-#define CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ldso_set_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LDSO_E_HIP; } } while (0)
-#define REQ(cond, msg) do { if (!(cond)) { ldso_set_error(msg); return LDSO_E_INVALID; } } while (0)
-#define RUN(x) do { int r_ = (x); if (r_ != LDSO_OK) return r_; } while (0)
+#include "ba_host.h"
+#include "lie_dev.h"
 
 #define TR_NT 256          // 4 wavefronts, one per SIMD: 512 registers (VGPR + AGPR) per lane - tr_eval keeps 4 points per lane in flight without scratch spills
 #define TR_MAXL LDSO_PYR_LEVELS
@@ -1087,8 +1076,6 @@ int ldso_tr_set_new_frame(ldso_tracker_t *H, const float *const *new_dIp, float 
     CHK(hipStreamSynchronize(H->stream));
     return LDSO_OK;
 }
-
-hipError_t img_launch_make_images(const float *d_color, int w, int h, int levels, float *const *d_levels, hipStream_t st);
 
 // CoarseTracker's new frame from the raw level-0 irradiance: FrameHessian::makeImages runs on the device (images.hip), one
 // w*h float upload instead of the 12-byte AoS pyramid
