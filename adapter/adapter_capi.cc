@@ -119,6 +119,19 @@ int adp_last_upload_times(void *b, double *out6) { for (int i = 0; i < 6; i++) o
 // newfh = shared_ptr<FrameHessian>* of ref_fs_new_frame.  stats: [candidates, activated, residuals added for old points, points after, lost]
 static bool deviceMarginalisation = false;
 int adp_set_device_marginalisation(int on) { deviceMarginalisation = on != 0; return 0; }
+// FullSystem::activatePointsMT WITH the distance map and the density controller: GpuBackend::activatePointsMT with a backend, the reference's own member without
+// one, in place of the restated candidate rule below.  Then stats[0] = immature points that left that state (selected or deleted), stats[1] = new active points.
+static bool distanceMap = false;
+static std::vector<float> minActDistTrace;          // fs.currentMinActDist after every activatePointsMT of adp_make_keyframe since the switch was last set
+int adp_set_distance_map(int on) { distanceMap = on != 0; minActDistTrace.clear(); return 0; }
+int adp_min_act_dist_trace(int cap, float *out) { for (int i = 0; i < cap && i < (int) minActDistTrace.size(); i++) out[i] = minActDistTrace[i]; return (int) minActDistTrace.size(); }
+static void count_points(FullSystem &fs, int &active, int &immature) {
+    active = immature = 0;
+    for (auto &fr : fs.frames) for (auto &feat : fr->features) {
+        if (feat->status == Feature::FeatureStatus::VALID && feat->point && feat->point->status == Point::PointStatus::ACTIVE) active++;
+        else if (feat->status == Feature::FeatureStatus::IMMATURE && feat->ip) immature++;
+    }
+}
 int adp_make_keyframe(void *b, void *fs_, void *newfh, int margIdx, int kfId, int iterations, float *rmse, int *stats) {
     GUARD(
         GpuBackend *B = (GpuBackend *) b; FullSystem &fs = *(FullSystem *) fs_;
@@ -152,7 +165,14 @@ int adp_make_keyframe(void *b, void *fs_, void *newfh, int margIdx, int kfId, in
             }
         }
         // :473 activatePointsMT: candidate rule of :1090-1150 (no distance map), the optimizeImmaturePoint loop, the object hand-over of :1168-1190
-        {
+        if (distanceMap) {
+            int a0, i0, a1, i1;
+            count_points(fs, a0, i0);
+            if (B) B->activatePointsMT(fs); else fs.activatePointsMT();
+            count_points(fs, a1, i1);
+            stats[0] = i0 - i1; stats[1] = a1 - a0;
+            minActDistTrace.push_back(fs.currentMinActDist);
+        } else {
             auto newestFr = fs.frames.back();
             fs.coarseDistanceMap->makeK(fs.Hcalib->mpCH);
             std::vector<shared_ptr<ImmaturePoint>> toOptimize;
@@ -268,6 +288,163 @@ int adp_graph_idepths(void *fs_, int cap, float *idepth, int *host, float *uv) {
                 n++;
             }
     return n;
+}
+
+// ---- candidate selection (FullSystem::activatePointsMT, FullSystem.cc:1052-1189) ------------------------------------------------------------
+// setting_desiredPointDensity (Settings.h:69); returns the value it replaces
+float adp_set_desired_point_density(float v) { const float old = setting_desiredPointDensity; setting_desiredPointDensity = v; return old; }
+float adp_get_min_act_dist(void *fs) { return ((FullSystem *) fs)->currentMinActDist; }
+void adp_set_min_act_dist(void *fs, float v) { ((FullSystem *) fs)->currentMinActDist = v; }
+int adp_ef_npoints(void *fs) { return ((FullSystem *) fs)->ef->nPoints; }
+void adp_set_ef_npoints(void *fs, int n) { ((FullSystem *) fs)->ef->nPoints = n; }
+// coarseDistanceMap->fwdWarpedIDDistFinal, wG[1] * hG[1] floats; returns that count
+int adp_get_ref_distance_map(void *fs_, float *out) {
+    FullSystem &fs = *(FullSystem *) fs_;
+    const int n = wG[1] * hG[1];
+    if (out) memcpy(out, fs.coarseDistanceMap->fwdWarpedIDDistFinal, (size_t) n * sizeof(float));
+    return n;
+}
+// the reference's own member
+int adp_ref_activate_points_mt(void *fs) { GUARD(((FullSystem *) fs)->activatePointsMT()) }
+int adp_activate_points_mt(void *b, void *fs, int *counts3) { GUARD(((GpuBackend *) b)->activatePointsMT(*(FullSystem *) fs); for (int i = 0; i < 3; i++) counts3[i] = ((GpuBackend *) b)->lastSelection[i]) }
+// ImmaturePoint::my_type of the immature points of the graph in traversal order (all frames, then their features: the order of ref_fs_get_immature)
+int adp_set_immature_types(void *fs_, int n, const float *types) {
+    FullSystem &fs = *(FullSystem *) fs_;
+    int k = 0;
+    for (auto &fr : fs.frames) for (auto &feat : fr->features) if (feat->status == Feature::FeatureStatus::IMMATURE && feat->ip) { if (k < n) feat->ip->my_type = types[k]; k++; }
+    return k;
+}
+// Point::status of every point of the graph (a graph without ACTIVE points has no seeds for the distance map); returns how many were set
+int adp_set_all_point_status(void *fs_, int status) {
+    FullSystem &fs = *(FullSystem *) fs_;
+    int k = 0;
+    for (auto &fr : fs.frames) for (auto &feat : fr->features) if (feat->point) { feat->point->status = (Point::PointStatus) status; k++; }
+    return k;
+}
+// Feature::status of every feature of the graph in traversal order (up to cap); returns the count
+int adp_feature_statuses(void *fs_, int cap, int *status) {
+    FullSystem &fs = *(FullSystem *) fs_;
+    int k = 0;
+    for (auto &fr : fs.frames) for (auto &feat : fr->features) { if (k < cap) status[k] = (int) feat->status; k++; }
+    return k;
+}
+// What the selection reads from the graph (GpuBackend::gatherSelection), as flat arrays: the common state handed to the device leg of a comparison.
+// counts: [seeds, candidates, hosts]; any output may be NULL (first call: sizes only)
+int adp_gather_selection(void *fs_, int *counts, ldso_act_seed_t *seeds, ldso_immature_t *cand, float *myType, float *KRKi, float *Kt, int *flagged) {
+    GUARD(
+        GpuBackend::SelectionInputs in;
+        GpuBackend::gatherSelection(*(FullSystem *) fs_, in);
+        counts[0] = (int) in.seeds.size(); counts[1] = (int) in.cand.size(); counts[2] = (int) in.flagged.size();
+        if (seeds && !in.seeds.empty()) memcpy(seeds, in.seeds.data(), in.seeds.size() * sizeof(ldso_act_seed_t));
+        if (cand && !in.cand.empty()) memcpy(cand, in.cand.data(), in.cand.size() * sizeof(ldso_immature_t));
+        if (myType && !in.myType.empty()) memcpy(myType, in.myType.data(), in.myType.size() * sizeof(float));
+        if (KRKi) memcpy(KRKi, in.KRKi.data(), in.KRKi.size() * sizeof(float));
+        if (Kt) memcpy(Kt, in.Kt.data(), in.Kt.size() * sizeof(float));
+        if (flagged) memcpy(flagged, in.flagged.data(), in.flagged.size() * sizeof(int)))
+}
+// the immature points the selection loop visits, in its order (:1088-1098)
+static std::vector<shared_ptr<ImmaturePoint>> selection_candidates(FullSystem &fs) {
+    std::vector<shared_ptr<ImmaturePoint>> v;
+    shared_ptr<FrameHessian> newest = fs.frames.back()->frameHessian;
+    for (auto fr : fs.frames) {
+        if (fr->frameHessian == newest) continue;
+        for (size_t i = 0; i < fr->features.size(); i++) {
+            shared_ptr<Feature> &feat = fr->features[i];
+            if (feat->status == Feature::FeatureStatus::IMMATURE && feat->ip) { feat->ip->idxInImmaturePoints = i; v.push_back(feat->ip); }
+        }
+    }
+    return v;
+}
+// The selection of FullSystem::activatePointsMT (:1075-1152) at `currentMinActDist`, driven through the reference's COMPILED CoarseDistanceMap members (makeK,
+// makeDistanceMap, addIntoDistFinal) on fs.coarseDistanceMap.  Nothing of the graph changes (no status is written, nothing is activated): decision [n] =
+// 0 keep / 1 drop / 2 selected per candidate in the loop's order, selected [n] = the selected indices in toOptimize's order, mapBefore / mapAfter [wG[1] * hG[1]].
+// Returns the number of candidates (call with NULL outputs for the size), -1 on error.
+int adp_ref_select_candidates(void *fs_, float currentMinActDist, int cap, int *decision, int *selected, int *nSelected, float *mapBefore, float *mapAfter) {
+    try {
+        FullSystem &fs = *(FullSystem *) fs_;
+        std::vector<shared_ptr<ImmaturePoint>> cand = selection_candidates(fs);
+        if (!decision) return (int) cand.size();
+        if ((int) cand.size() > cap) throw std::runtime_error("adp_ref_select_candidates: output too small");
+        auto newestFr = fs.frames.back();
+        vector<shared_ptr<FrameHessian>> frameHessians;
+        for (auto fr : fs.frames) frameHessians.push_back(fr->frameHessian);
+        fs.coarseDistanceMap->makeK(fs.Hcalib->mpCH);
+        fs.coarseDistanceMap->makeDistanceMap(frameHessians, newestFr->frameHessian);
+        const size_t cells = (size_t) wG[1] * hG[1];
+        if (mapBefore) memcpy(mapBefore, fs.coarseDistanceMap->fwdWarpedIDDistFinal, cells * sizeof(float));
+        int k = 0, ns = 0;
+        for (auto host : frameHessians) {
+            if (host == newestFr->frameHessian) continue;
+            SE3 fhToNew = newestFr->frameHessian->PRE_worldToCam * host->PRE_camToWorld;
+            Mat33f KRKi = (fs.coarseDistanceMap->K[1] * fhToNew.rotationMatrix().cast<float>() * fs.coarseDistanceMap->Ki[0]);
+            Vec3f Kt = (fs.coarseDistanceMap->K[1] * fhToNew.translation().cast<float>());
+            for (size_t i = 0; i < host->frame->features.size(); i++) {
+                shared_ptr<Feature> &feat = host->frame->features[i];
+                if (!(feat->status == Feature::FeatureStatus::IMMATURE && feat->ip)) continue;
+                shared_ptr<ImmaturePoint> &ph = feat->ip;
+                int &dec = decision[k++];
+                dec = 0;
+                if (!std::isfinite(ph->idepth_max) || ph->lastTraceStatus == IPS_OUTLIER) { dec = 1; continue; }
+                bool canActivate = (ph->lastTraceStatus == IPS_GOOD || ph->lastTraceStatus == IPS_SKIPPED || ph->lastTraceStatus == IPS_BADCONDITION || ph->lastTraceStatus == IPS_OOB)
+                                   && ph->lastTracePixelInterval < 8 && ph->quality > setting_minTraceQuality && (ph->idepth_max + ph->idepth_min) > 0;
+                if (!canActivate) {
+                    if (ph->feature->host.lock()->frameHessian->flaggedForMarginalization || ph->lastTraceStatus == IPS_OOB) dec = 1;
+                    continue;
+                }
+                Vec3f ptp = KRKi * Vec3f(feat->uv[0], feat->uv[1], 1) + Kt * (0.5f * (ph->idepth_max + ph->idepth_min));
+                int u = ptp[0] / ptp[2] + 0.5f;
+                int v = ptp[1] / ptp[2] + 0.5f;
+                if ((u > 0 && v > 0 && u < wG[1] && v < hG[1])) {
+                    float dist = fs.coarseDistanceMap->fwdWarpedIDDistFinal[u + wG[1] * v] + (ptp[0] - floorf((float) (ptp[0])));
+                    if (dist >= currentMinActDist * ph->my_type) {
+                        fs.coarseDistanceMap->addIntoDistFinal(u, v);
+                        dec = 2; selected[ns++] = k - 1;
+                    }
+                } else dec = 1;
+            }
+        }
+        *nSelected = ns;
+        if (mapAfter) memcpy(mapAfter, fs.coarseDistanceMap->fwdWarpedIDDistFinal, cells * sizeof(float));
+        return k;
+    } catch (const std::exception &e) { std::snprintf(g_err, sizeof(g_err), "%s", e.what()); return -1; }
+}
+// what follows the selection in the member, on the host, for a selection made by adp_ref_select_candidates on this graph: the statuses of the deleted candidates
+// (:1105-1108, :1121-1125, :1145-1148), the reference's activatePointsMT_Reductor on the selected ones (:1154-1164) and the hand-over of :1166-1188
+int adp_ref_apply_selection(void *fs_, int n, const int *decision, int nSelected, const int *selected) {
+    GUARD(
+        FullSystem &fs = *(FullSystem *) fs_;
+        std::vector<shared_ptr<ImmaturePoint>> cand = selection_candidates(fs);
+        if ((int) cand.size() != n) throw std::runtime_error("adp_ref_apply_selection: the graph changed since the selection");
+        std::vector<shared_ptr<ImmaturePoint>> toOptimize;
+        for (int k = 0; k < nSelected; k++) toOptimize.push_back(cand[selected[k]]);
+        for (int i = 0; i < n; i++) if (decision[i] == 1) { shared_ptr<Feature> feat = cand[i]->feature; feat->status = Feature::FeatureStatus::OUTLIER; feat->ReleaseImmature(); }
+        std::vector<shared_ptr<PointHessian>> optimized(toOptimize.size());
+        fs.activatePointsMT_Reductor(&optimized, &toOptimize, 0, (int) toOptimize.size(), 0, 0);
+        for (size_t k = 0; k < toOptimize.size(); k++) {
+            shared_ptr<PointHessian> newpoint = optimized[k];
+            shared_ptr<ImmaturePoint> ph = toOptimize[k];
+            shared_ptr<Feature> feat = ph->feature;
+            if (newpoint != nullptr) {
+                feat->status = Feature::FeatureStatus::VALID;
+                feat->point->mpPH = newpoint;
+                feat->ReleaseImmature();
+                newpoint->takeData();
+                for (auto r : newpoint->residuals) fs.ef->insertResidual(r);
+            } else { feat->status = Feature::FeatureStatus::OUTLIER; feat->ReleaseImmature(); }
+        })
+}
+// wall time of `reps` adp_ref_select_candidates-style selections (seconds each into out[reps]): scripts/time_activate_select.py's reference leg
+int adp_time_ref_select_candidates(void *fs_, float currentMinActDist, int reps, double *out) {
+    FullSystem &fs = *(FullSystem *) fs_;
+    const int n = adp_ref_select_candidates(fs_, currentMinActDist, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    std::vector<int> dec(n + 1), sel(n + 1); int ns = 0;
+    for (int r = 0; r < reps; r++) {
+        auto t0 = std::chrono::steady_clock::now();
+        if (adp_ref_select_candidates(fs_, currentMinActDist, n + 1, dec.data(), sel.data(), &ns, nullptr, nullptr) < 0) return -1;
+        out[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    (void) fs;
+    return ns;
 }
 
 }  // extern "C"

@@ -662,7 +662,6 @@ void GpuBackend::activatePoints(FullSystem &fs, std::vector<shared_ptr<ImmatureP
     if (toOptimize.empty()) return;
     std::vector<shared_ptr<PointHessian>> allPoints;
     if (uploadWindow(fs, allPoints) == 0) throw std::runtime_error("GpuBackend::activatePoints: the window holds no active point yet (activate on the host)");
-    const int F = (int) fs.frames.size();
     std::vector<ldso_immature_t> in(toOptimize.size());
     for (size_t k = 0; k < toOptimize.size(); k++) {
         ImmaturePoint &ip = *toOptimize[k];
@@ -678,25 +677,124 @@ void GpuBackend::activatePoints(FullSystem &fs, std::vector<shared_ptr<ImmatureP
     }
     std::vector<ldso_activation_t> out(toOptimize.size());
     throwOn(ldso_ba_activate_points(ba_, (int) in.size(), in.data(), /*minObs*/ 1, setting_minIdepthH_act, setting_GNItsOnPointActivation, out.data()), "ldso_ba_activate_points");
-    for (size_t k = 0; k < toOptimize.size(); k++) {
-        if (!out[k].ok) continue;                                                                // return 0 / nullptr (:924-926, :945-947, :968-975)
-        shared_ptr<ImmaturePoint> point = toOptimize[k];
-        point->feature->CreateFromImmature();                                                    // :977
-        shared_ptr<PointHessian> p = point->feature->point->mpPH;
-        p->lastResiduals[0].first = nullptr; p->lastResiduals[0].second = ResState::OOB;
-        p->lastResiduals[1].first = nullptr; p->lastResiduals[1].second = ResState::OOB;
-        p->setIdepthZero(out[k].idepth); p->setIdepth(out[k].idepth);
-        shared_ptr<FrameHessian> host = point->feature->host.lock()->frameHessian;
-        for (int t = 0; t < F; t++) {
-            if (out[k].res_state[t] != 0) continue;                                              // ResState::IN only (:989)
-            shared_ptr<FrameHessian> target = fs.frames[t]->frameHessian;
-            shared_ptr<PointFrameResidual> r(new PointFrameResidual(p, host, target));
-            r->state_NewEnergy = r->state_energy = 0; r->state_NewState = ResState::OUTLIER; r->setState(ResState::IN);
-            p->residuals.push_back(r);
-            if (target == fs.frames.back()->frameHessian) { p->lastResiduals[0].first = r; p->lastResiduals[0].second = ResState::IN; }
-            else if (target == (fs.frames.size() < 2 ? nullptr : fs.frames[fs.frames.size() - 2]->frameHessian)) { p->lastResiduals[1].first = r; p->lastResiduals[1].second = ResState::IN; }
+    for (size_t k = 0; k < toOptimize.size(); k++) optimized[k] = makePoint(fs, toOptimize[k], out[k]);
+}
+
+// the tail of FullSystem::optimizeImmaturePoint (:977-1008) from the device's record: the new PointHessian with its residuals, or nullptr
+shared_ptr<PointHessian> GpuBackend::makePoint(FullSystem &fs, const shared_ptr<ImmaturePoint> &point, const ldso_activation_t &out) {
+    if (!out.ok) return nullptr;                                                                 // return 0 / nullptr (:924-926, :945-947, :968-975)
+    const int F = (int) fs.frames.size();
+    point->feature->CreateFromImmature();                                                        // :977
+    shared_ptr<PointHessian> p = point->feature->point->mpPH;
+    p->lastResiduals[0].first = nullptr; p->lastResiduals[0].second = ResState::OOB;
+    p->lastResiduals[1].first = nullptr; p->lastResiduals[1].second = ResState::OOB;
+    p->setIdepthZero(out.idepth); p->setIdepth(out.idepth);
+    shared_ptr<FrameHessian> host = point->feature->host.lock()->frameHessian;
+    for (int t = 0; t < F; t++) {
+        if (out.res_state[t] != 0) continue;                                                     // ResState::IN only (:989)
+        shared_ptr<FrameHessian> target = fs.frames[t]->frameHessian;
+        shared_ptr<PointFrameResidual> r(new PointFrameResidual(p, host, target));
+        r->state_NewEnergy = r->state_energy = 0; r->state_NewState = ResState::OUTLIER; r->setState(ResState::IN);
+        p->residuals.push_back(r);
+        if (target == fs.frames.back()->frameHessian) { p->lastResiduals[0].first = r; p->lastResiduals[0].second = ResState::IN; }
+        else if (target == (fs.frames.size() < 2 ? nullptr : fs.frames[fs.frames.size() - 2]->frameHessian)) { p->lastResiduals[1].first = r; p->lastResiduals[1].second = ResState::IN; }
+    }
+    return p;
+}
+
+static void fillRecord(ldso_immature_t &q, const Feature &feat, const ImmaturePoint &ip, int host) {
+    memset(&q, 0, sizeof(q));
+    q.u = feat.uv[0]; q.v = feat.uv[1];
+    memcpy(q.color, ip.color, sizeof(q.color)); memcpy(q.weights, ip.weights, sizeof(q.weights));
+    q.gradH[0] = ip.gradH(0, 0); q.gradH[1] = ip.gradH(0, 1); q.gradH[2] = ip.gradH(1, 0); q.gradH[3] = ip.gradH(1, 1);
+    q.energyTH = ip.energyTH; q.idepth_min = ip.idepth_min; q.idepth_max = ip.idepth_max; q.quality = ip.quality;
+    q.lastTraceStatus = (int32_t) ip.lastTraceStatus; q.lastTraceUV[0] = ip.lastTraceUV[0]; q.lastTraceUV[1] = ip.lastTraceUV[1];
+    q.lastTracePixelInterval = ip.lastTracePixelInterval; q.host = host;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// void FullSystem::activatePointsMT()                                                                            FullSystem.cc:1052-1189
+// gatherSelection: what the member reads from the object graph, flattened in its own iteration order - the seeds of makeDistanceMap (CoarseTracker.cc:699-717),
+// the immature points of :1088-1102 (idxInImmaturePoints set as there), the per-host K[1] R Ki[0] / K[1] t of :1092-1094 by the reference's own expressions
+// (after coarseDistanceMap->makeK, :1081) and the hosts' flaggedForMarginalization.
+// ------------------------------------------------------------------------------------------------------------------------------------
+void GpuBackend::gatherSelection(FullSystem &fs, SelectionInputs &in) {
+    in.seeds.clear(); in.cand.clear(); in.myType.clear(); in.who.clear();
+    const int F = (int) fs.frames.size();
+    in.KRKi.assign((size_t) F * 9, 0.0f); in.Kt.assign((size_t) F * 3, 0.0f); in.flagged.assign(F, 0);
+    fs.coarseDistanceMap->makeK(fs.Hcalib->mpCH);
+    shared_ptr<FrameHessian> newest = fs.frames.back()->frameHessian;
+    for (int f = 0; f < F; f++) {
+        shared_ptr<FrameHessian> host = fs.frames[f]->frameHessian;
+        in.flagged[f] = host->flaggedForMarginalization ? 1 : 0;
+        if (host == newest) continue;
+        SE3 fhToNew = newest->PRE_worldToCam * host->PRE_camToWorld;
+        Mat33f KRKi = (fs.coarseDistanceMap->K[1] * fhToNew.rotationMatrix().cast<float>() * fs.coarseDistanceMap->Ki[0]);
+        Vec3f Kt = (fs.coarseDistanceMap->K[1] * fhToNew.translation().cast<float>());
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) in.KRKi[(size_t) f * 9 + r * 3 + c] = KRKi(r, c); in.Kt[(size_t) f * 3 + r] = Kt[r]; }
+        for (auto &feat : host->frame->features)
+            if (feat->point && feat->point->status == Point::PointStatus::ACTIVE) {
+                auto ph = feat->point->mpPH;
+                ldso_act_seed_t s; s.u = ph->u; s.v = ph->v; s.idepth_scaled = ph->idepth_scaled; s.host = f;
+                in.seeds.push_back(s);
+            }
+    }
+    for (int f = 0; f < F; f++) {
+        shared_ptr<FrameHessian> host = fs.frames[f]->frameHessian;
+        if (host == newest) continue;
+        for (size_t i = 0; i < host->frame->features.size(); i++) {
+            shared_ptr<Feature> &feat = host->frame->features[i];
+            if (!(feat->status == Feature::FeatureStatus::IMMATURE && feat->ip)) continue;
+            feat->ip->idxInImmaturePoints = i;                                                   // :1102
+            ldso_immature_t q;
+            fillRecord(q, *feat, *feat->ip, f);
+            in.cand.push_back(q); in.myType.push_back(feat->ip->my_type); in.who.push_back(feat->ip);
         }
-        optimized[k] = p;
+    }
+}
+
+void GpuBackend::activatePointsMT(FullSystem &fs) {
+    // :1054-1073 the density controller
+    throwOn(ldso_act_update_min_dist(fs.currentMinActDist, fs.ef->nPoints, setting_desiredPointDensity, &fs.currentMinActDist), "ldso_act_update_min_dist");
+    // :1075-1102 what the selection reads
+    SelectionInputs in;
+    gatherSelection(fs, in);
+    lastSelection[0] = (int) in.cand.size(); lastSelection[1] = lastSelection[2] = 0;
+    if (in.cand.empty()) return;
+    std::vector<shared_ptr<PointHessian>> allPoints;
+    if (uploadWindow(fs, allPoints) == 0) throw std::runtime_error("GpuBackend::activatePointsMT: the window holds no active point yet (activate on the host)");
+    // :1080-1164 distance map, selection and optimizeImmaturePoint of the selected points: one enqueue, one wait
+    const int n = (int) in.cand.size();
+    std::vector<int32_t> decision(n), selected(n);
+    std::vector<ldso_activation_t> out(n);
+    int nSel = 0;
+    throwOn(ldso_ba_select_activate_points(ba_, (int) in.seeds.size(), in.seeds.data(), n, in.cand.data(), in.myType.data(), (int) fs.frames.size(), in.KRKi.data(), in.Kt.data(),
+                                           in.flagged.data(), fs.currentMinActDist, setting_minTraceQuality, /*minObs*/ 1, setting_minIdepthH_act, setting_GNItsOnPointActivation,
+                                           decision.data(), selected.data(), &nSel, out.data()), "ldso_ba_select_activate_points");
+    lastSelection[1] = nSel;
+    // :1105-1108, :1121-1125, :1145-1148 the candidates the loop deletes
+    for (int i = 0; i < n; i++)
+        if (decision[i] == LDSO_ACT_DROP) {
+            shared_ptr<Feature> feat = in.who[i]->feature;
+            feat->status = Feature::FeatureStatus::OUTLIER;
+            feat->ReleaseImmature();
+        }
+    // :1166-1188 the selected ones
+    for (int k = 0; k < nSel; k++) {
+        shared_ptr<ImmaturePoint> ph = in.who[selected[k]];
+        shared_ptr<PointHessian> newpoint = makePoint(fs, ph, out[k]);
+        shared_ptr<Feature> feat = ph->feature;
+        if (newpoint != nullptr) {
+            feat->status = Feature::FeatureStatus::VALID;
+            feat->point->mpPH = newpoint;
+            feat->ReleaseImmature();
+            newpoint->takeData();
+            for (auto r : newpoint->residuals) fs.ef->insertResidual(r);
+            lastSelection[2]++;
+        } else {
+            feat->status = Feature::FeatureStatus::OUTLIER;
+            feat->ReleaseImmature();
+        }
     }
 }
 

@@ -10,6 +10,7 @@
 //   GpuBackend::trackNewestCoarse                   bool CoarseTracker::trackNewestCoarse(...)                      CoarseTracker.cc:61-217
 //   GpuBackend::trackNewCoarse(fs, fh)              Vec4 FullSystem::trackNewCoarse(shared_ptr<FrameHessian>)       FullSystem.cc:179-386
 //   GpuBackend::activatePoints(fs, ...)             the optimizeImmaturePoint loop of activatePointsMT              FullSystem.cc:892-1010,1196-1206
+//   GpuBackend::activatePointsMT(fs)                void FullSystem::activatePointsMT() with CoarseDistanceMap      FullSystem.cc:1052-1189, CoarseTracker.cc:686-818
 //   GpuBackend::traceNewCoarse(fs, fh)              void FullSystem::traceNewCoarse(shared_ptr<FrameHessian>)       FullSystem.cc:1012-1050
 //   GpuBackend::flagPointsForRemoval(fs)            the policy of void FullSystem::flagPointsForRemoval()           FullSystem.cc:1208-1270
 //   GpuBackend::marginalizePoints(fs)               void EnergyFunctional::marginalizePointsF() + FullSystem.cc:1241-1250   EnergyFunctional.cc:165-222
@@ -96,6 +97,22 @@ public:
     // optimized[k] = the new PointHessian of toOptimize[k] or nullptr, exactly what FullSystem::optimizeImmaturePoint returns
     void activatePoints(FullSystem &fs, std::vector<shared_ptr<internal::ImmaturePoint>> &toOptimize, std::vector<shared_ptr<PointHessian>> &optimized);
 
+    // ---- void FullSystem::activatePointsMT()                                                                    FullSystem.cc:1052-1189
+    // The whole member: the density controller on fs.currentMinActDist (:1054-1073), then distance map, candidate selection and optimizeImmaturePoint of the
+    // selected points as ONE device call (ldso_ba_select_activate_points: makeDistanceMap / the loop of :1088-1152 / addIntoDistFinal / :1154-1164), the
+    // status hand-over of the deleted candidates (:1105-1149) and the object hand-over of the new points (:1166-1188) on the host.
+    void activatePointsMT(FullSystem &fs);
+    int lastSelection[3] = {0, 0, 0};                   // of the last activatePointsMT: candidates, selected, activated
+    // what the selection reads from the object graph, in the member's own iteration order (also the test harness's way to hand one state to both sides)
+    struct SelectionInputs {
+        std::vector<ldso_act_seed_t> seeds;
+        std::vector<ldso_immature_t> cand;
+        std::vector<float> myType, KRKi, Kt;
+        std::vector<int32_t> flagged;
+        std::vector<shared_ptr<internal::ImmaturePoint>> who;
+    };
+    static void gatherSelection(FullSystem &fs, SelectionInputs &in);
+
     // ---- immature-point tracing: void FullSystem::traceNewCoarse(shared_ptr<FrameHessian> fh)                   FullSystem.cc:1012-1050
     void traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh);
     int lastTraceCounts[6] = {0, 0, 0, 0, 0, 0};        // good, oob, outlier, skipped, bad condition, uninitialised (the function's trace_* counters)
@@ -111,6 +128,7 @@ public:
 
 private:
     ldso_ba_t *ba_ = nullptr;
+    static shared_ptr<PointHessian> makePoint(FullSystem &fs, const shared_ptr<internal::ImmaturePoint> &point, const ldso_activation_t &out);
     ldso_tracer_t *tracer_ = nullptr;
     int tracerCap_ = 0;
     std::map<CoarseTracker *, ldso_tracker_t *> trackers_;          // the reference double-buffers two CoarseTrackers (FullSystem.h:296-297)

@@ -215,6 +215,28 @@ int ldso_ba_marginalize_frame(ldso_ba_t *h, int frame_idx, double *HM_out, doubl
  * out[i].res_state[t] == 0 lists the target frames that get a PointFrameResidual. */
 int ldso_ba_activate_points(ldso_ba_t *h, int n, const ldso_immature_t *points, int min_obs, float min_idepth_hessian, int gn_iterations,
                             ldso_activation_t *out);
+/* The density controller at the head of FullSystem::activatePointsMT (FullSystem.cc:1054-1073): currentMinActDist moved by how far ef->nPoints is from
+ * setting_desiredPointDensity - the reference's mixed if / else-if ladder as written - and clamped to [0, 4].  Host only. */
+int ldso_act_update_min_dist(float current, int nPoints, float desiredDensity, float *out);
+/* Which immature points get activated: CoarseDistanceMap::makeDistanceMap (CoarseTracker.cc:686-721, growDistBFS :723-811) from the seeds, then the greedy,
+ * order-dependent loop of FullSystem::activatePointsMT (FullSystem.cc:1088-1152) with addIntoDistFinal (CoarseTracker.cc:813-818) for every accepted candidate.
+ * The map is level 1 of the handle's image size.  points / my_type (ImmaturePoint::my_type, ImmaturePoint.h:114): the candidates in the reference's iteration
+ * order (host frames in window order, features in vector order); points[i].host and seeds[i].host index KRKi [n_hosts][9] / Kt [n_hosts][3] - K[1] * R * Ki[0]
+ * and K[1] * t of host -> newest frame (FullSystem.cc:1093-1094, the convention of ldso_trace_on at pyramid level 1) - and host_flagged [n_hosts]
+ * (FrameHessian::flaggedForMarginalization).  decision_out [n]: LDSO_ACT_*; selected_out [n]: the first *n_selected_out entries are the indices of the
+ * SELECTED candidates in the order the reference pushes them into toOptimize. */
+int ldso_ba_select_candidates(ldso_ba_t *h, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts,
+                              const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality,
+                              int32_t *decision_out, int32_t *selected_out, int *n_selected_out);
+/* The same selection followed by ldso_ba_activate_points on the selected list (FullSystem.cc:1080-1164) in one enqueue: the list stays on the device, the host
+ * waits once.  Preconditions of ldso_ba_activate_points (resident window, its images and current poses; n_hosts = its frame count).  out [n]: out[k] is the
+ * record of candidate selected_out[k] for k < *n_selected_out, identical to what ldso_ba_activate_points returns for that list. */
+int ldso_ba_select_activate_points(ldso_ba_t *h, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts,
+                                   const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, int min_obs,
+                                   float min_idepth_hessian, int gn_iterations, int32_t *decision_out, int32_t *selected_out, int *n_selected_out,
+                                   ldso_activation_t *out);
+/* Debug: CoarseDistanceMap::fwdWarpedIDDistFinal as the last selection on this handle left it, (w >> 1) * (h >> 1) floats: 0..39 and 1000. */
+int ldso_ba_get_distance_map(ldso_ba_t *h, float *out_w1_h1);
 /* Asynchronous variant used by bench.py: enqueue `iters` Gauss-Newton iterations (solveSystem +
  * doStepFromBackup + linearizeAll + applyRes) on the handle's stream and return immediately.  The launch sequence of a call is captured into a HIP graph the
  * first time and replayed when the same call comes again (same window, settings, stream, first iteration and count: the key is a hash of every launch

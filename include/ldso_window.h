@@ -187,6 +187,19 @@ typedef struct ldso_activation {
     int32_t res_state[LDSO_MAX_FRAMES];   /* per target frame idx: final state_state (0 IN, 1 OOB, 2 OUTLIER), -1 for the host */
 } ldso_activation_t;                  /* 96 bytes */
 
+/* Candidate selection of FullSystem::activatePointsMT (FullSystem.cc:1052-1152).  A seed of the distance map = one ACTIVE point of the window that is
+ * not hosted by the newest frame, as CoarseDistanceMap::makeDistanceMap reads it (CoarseTracker.cc:706-709): ph->u, ph->v, ph->idepth_scaled and the index
+ * of its host key frame in the per-host pose arrays. */
+typedef struct ldso_act_seed {
+    float u, v;
+    float idepth_scaled;
+    int32_t host;
+} ldso_act_seed_t;                    /* 16 bytes */
+
+/* What the selection loop does with a candidate: KEEP it immature (:1126, or :1141 failed), DROP it (the reference sets Feature::OUTLIER and releases the
+ * immature point: :1105-1108, :1121-1125, :1145-1148), or hand it to optimizeImmaturePoint (:1142-1143). */
+enum { LDSO_ACT_KEEP = 0, LDSO_ACT_DROP = 1, LDSO_ACT_SELECTED = 2 };
+
 /* One candidate of the monocular initialiser: struct Pnt (include/frontend/CoarseInitializer.h:19-57), bools widened to int32. */
 typedef struct ldso_init_point {
     float u, v;                       /* pixel position on its pyramid level (x + 0.1, y + 0.1; CoarseInitializer.cc:578-579) */

@@ -61,6 +61,13 @@ def default_settings() -> np.ndarray:
     return s
 
 
+def act_update_min_dist(current, n_points, desired_density) -> float:
+    """the density controller of FullSystem::activatePointsMT (FullSystem.cc:1054-1073) on currentMinActDist"""
+    out = C.c_float()
+    _chk(lib().ldso_act_update_min_dist(C.c_float(current), C.c_int(n_points), C.c_float(desired_density), C.byref(out)))
+    return out.value
+
+
 class Pyramid:
     """FrameHessian::dIp of one frame resident in HBM (ldso_pyramid_t), shared zero-copy by Tracker / Tracer / BA."""
 
@@ -360,6 +367,37 @@ class BA:
         assert a.dtype == synth.IMMATURE_DTYPE
         out = np.zeros(len(a), synth.ACTIVATION_DTYPE)
         _chk(self.L.ldso_ba_activate_points(self.h, C.c_int(len(a)), _p(a), C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations), _p(out)))
+        return out
+
+    def _select_args(self, seeds, pts, my_type, KRKi, Kt, host_flagged, min_act_dist, min_trace_quality):
+        sd = np.ascontiguousarray(seeds); a = np.ascontiguousarray(pts)
+        assert sd.dtype == synth.ACT_SEED_DTYPE and a.dtype == synth.IMMATURE_DTYPE
+        mt = np.ascontiguousarray(my_type, np.float32); K1 = np.ascontiguousarray(KRKi, np.float32).reshape(-1, 9); K2 = np.ascontiguousarray(Kt, np.float32).reshape(-1, 3)
+        fl = np.ascontiguousarray(host_flagged, np.int32)
+        assert len(mt) == len(a) and len(K1) == len(K2) == len(fl)
+        keep = (sd, a, mt, K1, K2, fl)
+        return keep, (C.c_int(len(sd)), _p(sd), C.c_int(len(a)), _p(a), _p(mt), C.c_int(len(fl)), _p(K1), _p(K2), _p(fl), C.c_float(min_act_dist), C.c_float(min_trace_quality))
+
+    def select_candidates(self, seeds, pts, my_type, KRKi, Kt, host_flagged, min_act_dist, min_trace_quality=3.0):
+        """distance map + candidate selection of FullSystem::activatePointsMT -> (decision [n] LDSO_ACT_*, selected indices in order)"""
+        keep, args = self._select_args(seeds, pts, my_type, KRKi, Kt, host_flagged, min_act_dist, min_trace_quality)
+        n = len(keep[1])
+        dec = np.zeros(n, np.int32); sel = np.zeros(n, np.int32); ns = C.c_int()
+        _chk(self.L.ldso_ba_select_candidates(self.h, *args, _p(dec), _p(sel), C.byref(ns)))
+        return dec, sel[:ns.value].copy()
+
+    def select_activate_points(self, seeds, pts, my_type, KRKi, Kt, host_flagged, min_act_dist, min_trace_quality=3.0, min_obs=1, min_idepth_hessian=100.0, gn_iterations=3):
+        """the selection and ldso_ba_activate_points on the selected list in one enqueue -> (decision, selected, activation records of the selected)"""
+        keep, args = self._select_args(seeds, pts, my_type, KRKi, Kt, host_flagged, min_act_dist, min_trace_quality)
+        n = len(keep[1])
+        dec = np.zeros(n, np.int32); sel = np.zeros(n, np.int32); ns = C.c_int(); out = np.zeros(n, synth.ACTIVATION_DTYPE)
+        _chk(self.L.ldso_ba_select_activate_points(self.h, *args, C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations), _p(dec), _p(sel), C.byref(ns), _p(out)))
+        return dec, sel[:ns.value].copy(), out[:ns.value].copy()
+
+    def get_distance_map(self):
+        """CoarseDistanceMap::fwdWarpedIDDistFinal as the last selection left it: [h >> 1, w >> 1] floats, 0..39 and 1000"""
+        out = np.zeros((self.hh >> 1, self.w >> 1), np.float32)
+        _chk(self.L.ldso_ba_get_distance_map(self.h, _p(out)))
         return out
 
     def enqueue_gn(self, first_iteration, iters):

@@ -1,0 +1,340 @@
+// act_select.hip — which immature points get activated, on the device (gfx950): the first half of FullSystem::activatePointsMT (reference
+// src/frontend/FullSystem.cc:1052-1152) with CoarseDistanceMap::makeDistanceMap / growDistBFS / addIntoDistFinal (src/frontend/CoarseTracker.cc:686-818).
+//
+// One persistent workgroup.  The level-1 distance map is one byte per cell (0..39, 255 = the reference's 1000) in LDS where it fits (320 x 240 = 76 800 B of the
+// CU's 160 KiB) and in global memory otherwise - the same code either way.
+//   phase A (all waves)  fill, project the seeds, grow 39 rounds in parallel (a round writes k into every far cell next to a cell of value k - 1 that is not on
+//                        the border: exactly the reference's frontier, whose order within a round does not matter), then every candidate's canActivate / delete
+//                        rules, projection and bounds test, and the distance test against the INITIAL map: map values only ever decrease, so a candidate that
+//                        fails it here fails it at its turn too - only the others stay pending.
+//   phase B (wave 0)     the pending candidates in order; an accepted one is inserted as addIntoDistFinal does: cell = 0, then the pruned BFS from that single
+//                        seed over a frontier list (a cell joins the next frontier only when the round lowered it), until the frontier is empty.
+// Float projections in the reference's operation order, no contraction, IEEE division, int conversion by truncation after + 0.5f (as trace.hip, ba_activate.hip).
+#include <hip/hip_runtime.h>
+#include "ba_host.h"
+
+namespace {
+
+constexpr int SEL_THREADS = 1024;
+constexpr int SEL_FRONTIER = 512;                 // a round's frontier lies on the octagon of radius k <= 39 around the seed: at most 8 k = 312 cells
+constexpr int SEL_LIST_BYTES = 2 * SEL_FRONTIER * 4;
+constexpr int SEL_LDS_MAX = 160 * 1024;
+constexpr int SEL_PENDING = 3;                    // internal: passed every rule and the test against the initial map
+constexpr unsigned char SEL_FAR = 255;
+
+struct SelArgs {
+    const ldso_act_seed_t *seeds;
+    const ldso_immature_t *pts;
+    const float *myType, *KRKi, *Kt;
+    const int32_t *flagged;
+    int nSeeds, n, nHosts, w1, h1;
+    float minDist, minQuality;
+    unsigned char *gmap;                          // [w1 * h1] the map in global memory: the working copy of the large path, the final map of both
+    int32_t *decision, *selected, *nSelected, *cell;
+    float *frac, *thr;
+};
+
+static __device__ __forceinline__ float map_value(unsigned char m) { return m == SEL_FAR ? 1000.0f : (float) m; }
+
+// Vec3f ptp = KRKi * Vec3f(u, v, 1) + Kt * idepth; int u = ptp[0] / ptp[2] + 0.5f (CoarseTracker.cc:709-712, FullSystem.cc:1130-1135)
+static __device__ __forceinline__ bool project(const float *KRKi, const float *Kt, float pu, float pv, float idepth, int w1, int h1, int &u, int &v, float &p0) {
+    p0 = ((KRKi[0] * pu + KRKi[1] * pv) + KRKi[2] * 1.0f) + Kt[0] * idepth;
+    const float p1 = ((KRKi[3] * pu + KRKi[4] * pv) + KRKi[5] * 1.0f) + Kt[1] * idepth;
+    const float p2 = ((KRKi[6] * pu + KRKi[7] * pv) + KRKi[8] * 1.0f) + Kt[2] * idepth;
+    u = (int) (p0 / p2 + 0.5f);
+    v = (int) (p1 / p2 + 0.5f);
+    return u > 0 && v > 0 && u < w1 && v < h1;
+}
+
+// addIntoDistFinal(u, v) by one wavefront: growDistBFS(1) from the single seed.  Lanes take the frontier's cells 64 at a time and step through the neighbour
+// directions together: within one direction two different cells never share a neighbour, so a cell is lowered (and listed) once per round.
+static __device__ void insert_seed(unsigned char *map, uint32_t *listA, uint32_t *listB, int cellIdx, int w1, int h1, int lane) {
+    uint32_t *cur = listA, *nxt = listB;
+    if (lane == 0) { map[cellIdx] = 0; cur[0] = (uint32_t) (cellIdx % w1) | ((uint32_t) (cellIdx / w1) << 16); }
+    __threadfence_block();
+    int cnt = 1;
+    for (int k = 1; k < 40 && cnt > 0; k++) {
+        const int ndir = (k & 1) ? 8 : 4;
+        int ncnt = 0;
+        for (int p = 0; p < cnt; p += 64) {
+            const int e = p + lane;
+            int x = 0, y = 0;
+            bool act = e < cnt;
+            if (act) {
+                const uint32_t c = cur[e];
+                x = (int) (c & 0xffffu); y = (int) (c >> 16);
+                act = !(x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1);          // a border cell holds a value but never spreads (CoarseTracker.cc:736, :764)
+            }
+            for (int d = 0; d < ndir; d++) {
+                // the reference's order: +x, -x, +y, -y, then (+,+), (-,+), (-,-), (+,-)
+                const int dx = (d == 0 || d == 4 || d == 7) ? 1 : (d == 1 || d == 5 || d == 6) ? -1 : 0;
+                const int dy = (d == 2 || d == 4 || d == 5) ? 1 : (d == 3 || d == 6 || d == 7) ? -1 : 0;
+                const int nx = x + dx, ny = y + dy;
+                bool set = false;
+                if (act) {
+                    const int j = nx + ny * w1;
+                    if (map[j] > k) { map[j] = (unsigned char) k; set = true; }
+                }
+                const unsigned long long bm = __ballot(set);
+                if (set) {
+                    const int pos = ncnt + __popcll(bm & ((1ull << lane) - 1ull));
+                    if (pos < SEL_FRONTIER) nxt[pos] = (uint32_t) nx | ((uint32_t) ny << 16);
+                }
+                ncnt += __popcll(bm);
+                __threadfence_block();
+            }
+        }
+        uint32_t *t = cur; cur = nxt; nxt = t;
+        cnt = ncnt < SEL_FRONTIER ? ncnt : SEL_FRONTIER;
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(SEL_THREADS) void k_act_select(SelArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sel_lds[];
+    uint32_t *listA = (uint32_t *) sel_lds, *listB = listA + SEL_FRONTIER;
+    unsigned char *map = LDS ? sel_lds + SEL_LIST_BYTES : A.gmap;
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+    const int w1 = A.w1, h1 = A.h1, wh = w1 * h1;
+
+    // ---- makeDistanceMap (CoarseTracker.cc:686-721) ----
+    for (int i = tid; i < wh; i += nt) map[i] = SEL_FAR;
+    __syncthreads();
+    for (int i = tid; i < A.nSeeds; i += nt) {
+        const ldso_act_seed_t s = A.seeds[i];
+        if (s.host < 0 || s.host >= A.nHosts) continue;
+        int u, v; float p0;
+        if (project(A.KRKi + 9 * s.host, A.Kt + 3 * s.host, s.u, s.v, s.idepth_scaled, w1, h1, u, v, p0)) map[u + w1 * v] = 0;
+    }
+    __syncthreads();
+    // ---- growDistBFS (CoarseTracker.cc:723-811): every cell is far or final here, so the frontier of round k is the set of cells holding k - 1 ----
+    for (int k = 1; k < 40; k++) {
+        int spread = 0;
+        for (int i = tid; i < wh; i += nt) {
+            if (map[i] != k - 1) continue;
+            const int x = i % w1, y = i / w1;
+            if (x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1) continue;
+            spread = 1;
+            if (map[i + 1] > k) map[i + 1] = (unsigned char) k;
+            if (map[i - 1] > k) map[i - 1] = (unsigned char) k;
+            if (map[i + w1] > k) map[i + w1] = (unsigned char) k;
+            if (map[i - w1] > k) map[i - w1] = (unsigned char) k;
+            if (k & 1) {
+                if (map[i + 1 + w1] > k) map[i + 1 + w1] = (unsigned char) k;
+                if (map[i - 1 + w1] > k) map[i - 1 + w1] = (unsigned char) k;
+                if (map[i - 1 - w1] > k) map[i - 1 - w1] = (unsigned char) k;
+                if (map[i + 1 - w1] > k) map[i + 1 - w1] = (unsigned char) k;
+            }
+        }
+        if (!__syncthreads_or(spread)) break;
+    }
+
+    // ---- the candidate rules of FullSystem.cc:1096-1149, in parallel; the distance test against the initial map ----
+    for (int i = tid; i < A.n; i += nt) {
+        const ldso_immature_t &P = A.pts[i];
+        const int host = P.host, st = P.lastTraceStatus;
+        const float idmin = P.idepth_min, idmax = P.idepth_max;
+        int dec = LDSO_ACT_KEEP;
+        if (host < 0 || host >= A.nHosts || !isfinite(idmax) || st == LDSO_IPS_OUTLIER) dec = LDSO_ACT_DROP;                               // :1105
+        else {
+            const bool canActivate = (st == LDSO_IPS_GOOD || st == LDSO_IPS_SKIPPED || st == LDSO_IPS_BADCONDITION || st == LDSO_IPS_OOB)
+                                     && P.lastTracePixelInterval < 8 && P.quality > A.minQuality && (idmax + idmin) > 0;                   // :1111-1117
+            if (!canActivate) { if (A.flagged[host] != 0 || st == LDSO_IPS_OOB) dec = LDSO_ACT_DROP; }                                     // :1121-1124
+            else {
+                int u, v; float p0;
+                if (!project(A.KRKi + 9 * host, A.Kt + 3 * host, P.u, P.v, 0.5f * (idmax + idmin), w1, h1, u, v, p0)) dec = LDSO_ACT_DROP; // :1145-1148
+                else {
+                    const int c = u + w1 * v;
+                    const float fr = p0 - floorf(p0), th = A.minDist * A.myType[i];                                                        // :1137-1141
+                    if (map_value(map[c]) + fr >= th) { dec = SEL_PENDING; A.cell[i] = c; A.frac[i] = fr; A.thr[i] = th; }
+                }
+            }
+        }
+        A.decision[i] = dec;
+    }
+    __syncthreads();
+
+    // ---- the greedy pass of FullSystem.cc:1137-1144 over the pending candidates, in order ----
+    if (tid < 64) {
+        int nsel = 0;
+        for (int base = 0; base < A.n; base += 64) {
+            const int i = base + lane;
+            int dec = i < A.n ? A.decision[i] : LDSO_ACT_KEEP;
+            int c = 0; float fr = 0, th = 0;
+            if (dec == SEL_PENDING) { c = A.cell[i]; fr = A.frac[i]; th = A.thr[i]; }
+            unsigned long long m = __ballot(dec == SEL_PENDING);
+            while (m) {
+                const int b = __ffsll((long long) m) - 1;
+                m &= m - 1;
+                const int cc = __shfl(c, b, 64);
+                const float f = __shfl(fr, b, 64), t = __shfl(th, b, 64);
+                const bool accept = map_value(map[cc]) + f >= t;
+                if (lane == b) dec = accept ? LDSO_ACT_SELECTED : LDSO_ACT_KEEP;
+                if (accept) {
+                    if (lane == 0) A.selected[nsel] = base + b;
+                    nsel++;
+                    insert_seed(map, listA, listB, cc, w1, h1, lane);
+                }
+            }
+            if (i < A.n) A.decision[i] = dec;
+        }
+        if (lane == 0) *A.nSelected = nsel;
+    }
+    __syncthreads();
+    if (LDS) for (int i = tid; i < wh; i += nt) A.gmap[i] = map[i];
+}
+
+struct SelBuffers {                // the carve-up of ldso_ba::d_sel for one call
+    char *in = nullptr; size_t inBytes = 0;                       // [points | seeds | my_type | KRKi | Kt | flagged]: one upload
+    char *out = nullptr; size_t outBytes = 0;                     // [n_selected (16 B) | decision | selected | activation records]: one download
+    ldso_immature_t *pts = nullptr; ldso_act_seed_t *seeds = nullptr; float *myType = nullptr, *KRKi = nullptr, *Kt = nullptr; int32_t *flagged = nullptr;
+    int32_t *nSelected = nullptr, *decision = nullptr, *selected = nullptr; ldso_activation_t *act = nullptr;
+    int32_t *cell = nullptr; float *frac = nullptr, *thr = nullptr; unsigned char *gmap = nullptr;
+};
+
+static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+
+}  // namespace
+
+static int sel_enqueue(ldso_ba *H, const char *who, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts, const float *KRKi,
+                       const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, SelBuffers &S) {
+    REQ(H && n_seeds >= 0 && n >= 0 && n_hosts >= 1 && n_hosts <= LDSO_MAX_FRAMES && KRKi && Kt && host_flagged && (n_seeds == 0 || seeds) && (n == 0 || (points && my_type)),
+        std::string(who) + ": bad arguments");
+    const int w1 = H->w >> 1, h1 = H->h >> 1;
+    REQ(w1 >= 3 && h1 >= 3 && w1 < 65536 && h1 < 65536, std::string(who) + ": image size out of range");
+    for (int i = 0; i < n; i++) REQ(points[i].host >= 0 && points[i].host < n_hosts, std::string(who) + ": a candidate's host is not a frame of the window");
+    for (int i = 0; i < n_seeds; i++) REQ(seeds[i].host >= 0 && seeds[i].host < n_hosts, std::string(who) + ": a seed's host is not a frame of the window");
+    CHK(hipSetDevice(H->device));
+    const size_t wh = (size_t) w1 * h1, nn = (size_t) n;
+    const size_t oPts = 0, oSeeds = oPts + nn * sizeof(ldso_immature_t), oType = oSeeds + up16((size_t) n_seeds * sizeof(ldso_act_seed_t)), oKRKi = oType + up16(nn * 4),
+                 oKt = oKRKi + up16((size_t) n_hosts * 36), oFlag = oKt + up16((size_t) n_hosts * 12), inBytes = oFlag + up16((size_t) n_hosts * 4);
+    const size_t oDec = 16, oSel = oDec + up16(nn * 4), oAct = oSel + up16(nn * 4), outBytes = oAct + nn * sizeof(ldso_activation_t);
+    const size_t oCell = inBytes + outBytes, oFrac = oCell + up16(nn * 4), oThr = oFrac + up16(nn * 4), oMap = oThr + up16(nn * 4), total = oMap + up16(wh);
+    if (total > H->selCap) {
+        if (H->d_sel) hipFree(H->d_sel);
+        H->d_sel = nullptr; H->selCap = 0;
+        CHK(hipMalloc(&H->d_sel, total + total / 2));
+        H->selCap = total + total / 2;
+    }
+    char *d = (char *) H->d_sel;
+    S.in = d; S.inBytes = inBytes; S.out = d + inBytes; S.outBytes = outBytes;
+    S.pts = (ldso_immature_t *) (d + oPts); S.seeds = (ldso_act_seed_t *) (d + oSeeds); S.myType = (float *) (d + oType); S.KRKi = (float *) (d + oKRKi); S.Kt = (float *) (d + oKt);
+    S.flagged = (int32_t *) (d + oFlag);
+    S.nSelected = (int32_t *) S.out; S.decision = (int32_t *) (S.out + oDec); S.selected = (int32_t *) (S.out + oSel); S.act = (ldso_activation_t *) (S.out + oAct);
+    S.cell = (int32_t *) (d + oCell); S.frac = (float *) (d + oFrac); S.thr = (float *) (d + oThr); S.gmap = (unsigned char *) (d + oMap);
+    H->selHost.resize(std::max(inBytes, outBytes));
+    char *hs = H->selHost.data();
+    memset(hs, 0, inBytes);
+    if (n) { memcpy(hs + oPts, points, nn * sizeof(ldso_immature_t)); memcpy(hs + oType, my_type, nn * 4); }
+    if (n_seeds) memcpy(hs + oSeeds, seeds, (size_t) n_seeds * sizeof(ldso_act_seed_t));
+    memcpy(hs + oKRKi, KRKi, (size_t) n_hosts * 36); memcpy(hs + oKt, Kt, (size_t) n_hosts * 12); memcpy(hs + oFlag, host_flagged, (size_t) n_hosts * 4);
+    CHK(hipMemcpyAsync(S.in, hs, inBytes, hipMemcpyHostToDevice, H->stream));
+    SelArgs A;
+    A.seeds = S.seeds; A.pts = S.pts; A.myType = S.myType; A.KRKi = S.KRKi; A.Kt = S.Kt; A.flagged = S.flagged;
+    A.nSeeds = n_seeds; A.n = n; A.nHosts = n_hosts; A.w1 = w1; A.h1 = h1; A.minDist = currentMinActDist; A.minQuality = minTraceQuality;
+    A.gmap = S.gmap; A.decision = S.decision; A.selected = S.selected; A.nSelected = S.nSelected; A.cell = S.cell; A.frac = S.frac; A.thr = S.thr;
+    // the map in LDS where the workgroup can have that much (beside the kernel's own static bytes), in global memory otherwise
+    const size_t ldsBytes = SEL_LIST_BYTES + up16(wh);
+    if (H->selLdsLimit < 0) {
+        hipFuncAttributes fa; int perBlock = 0;
+        CHK(hipFuncGetAttributes(&fa, (const void *) k_act_select<true>));
+        CHK(hipDeviceGetAttribute(&perBlock, hipDeviceAttributeMaxSharedMemoryPerBlock, H->device));
+        H->selLdsLimit = std::max(0, std::min(perBlock, SEL_LDS_MAX) - (int) fa.sharedSizeBytes);
+    }
+    if (ldsBytes <= (size_t) H->selLdsLimit) {
+        if ((int) ldsBytes > H->selLdsSet) { CHK(hipFuncSetAttribute((const void *) k_act_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes)); H->selLdsSet = (int) ldsBytes; }
+        hipLaunchKernelGGL(k_act_select<true>, dim3(1), dim3(SEL_THREADS), ldsBytes, H->stream, A);
+    } else hipLaunchKernelGGL(k_act_select<false>, dim3(1), dim3(SEL_THREADS), SEL_LIST_BYTES, H->stream, A);
+    CHK(hipGetLastError());
+    H->selW1 = w1; H->selH1 = h1; H->selMapOffset = oMap;
+    return LDSO_OK;
+}
+
+static void sel_unpack(const ldso_ba *H, int n, int32_t *decision_out, int32_t *selected_out, int *n_selected_out) {
+    const char *hs = H->selHost.data();
+    const int ns = *(const int32_t *) hs;
+    const size_t oDec = 16, oSel = oDec + up16((size_t) n * 4);
+    if (n) memcpy(decision_out, hs + oDec, (size_t) n * 4);
+    if (selected_out && ns > 0) memcpy(selected_out, hs + oSel, (size_t) ns * 4);
+    if (n_selected_out) *n_selected_out = ns;
+}
+
+extern "C" {
+
+// The density controller of FullSystem::activatePointsMT (FullSystem.cc:1054-1073), its mixed if / else-if ladder as written: currentMinActDist is a float,
+// the constants are doubles, ef->nPoints an int against float * double.
+int ldso_act_update_min_dist(float current, int nPoints, float desiredDensity, float *out) {
+    REQ(out, "ldso_act_update_min_dist: null argument");
+    float currentMinActDist = current;
+    if (nPoints < desiredDensity * 0.66)
+        currentMinActDist -= 0.8;
+    if (nPoints < desiredDensity * 0.8)
+        currentMinActDist -= 0.5;
+    else if (nPoints < desiredDensity * 0.9)
+        currentMinActDist -= 0.2;
+    else if (nPoints < desiredDensity)
+        currentMinActDist -= 0.1;
+
+    if (nPoints > desiredDensity * 1.5)
+        currentMinActDist += 0.8;
+    if (nPoints > desiredDensity * 1.3)
+        currentMinActDist += 0.5;
+    if (nPoints > desiredDensity * 1.15)
+        currentMinActDist += 0.2;
+    if (nPoints > desiredDensity)
+        currentMinActDist += 0.1;
+
+    if (currentMinActDist < 0) currentMinActDist = 0;
+    if (currentMinActDist > 4) currentMinActDist = 4;
+    *out = currentMinActDist;
+    return LDSO_OK;
+}
+
+// makeDistanceMap + the selection loop of FullSystem::activatePointsMT (FullSystem.cc:1080-1152, CoarseTracker.cc:686-818)
+int ldso_ba_select_candidates(ldso_ba_t *H, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts, const float *KRKi,
+                              const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, int32_t *decision_out, int32_t *selected_out,
+                              int *n_selected_out) {
+    REQ(H && (n <= 0 || decision_out), "ldso_ba_select_candidates: bad arguments");
+    SelBuffers S;
+    RUN(sel_enqueue(H, "ldso_ba_select_candidates", n_seeds, seeds, n, points, my_type, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
+    const size_t bytes = 16 + 2 * up16((size_t) n * 4);
+    CHK(hipMemcpyAsync(H->selHost.data(), S.out, bytes, hipMemcpyDeviceToHost, H->stream));
+    CHK(hipStreamSynchronize(H->stream));
+    sel_unpack(H, n, decision_out, selected_out, n_selected_out);
+    return LDSO_OK;
+}
+
+// ... followed by the optimizeImmaturePoint loop (FullSystem.cc:1154-1164, 892-1010) on the selected list, which never leaves the device: k_activate reads the
+// list and its length where the selection kernel left them.  One synchronisation.  out[k] belongs to candidate selected_out[k], k < *n_selected_out.
+int ldso_ba_select_activate_points(ldso_ba_t *H, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts,
+                                   const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, int min_obs,
+                                   float min_idepth_hessian, int gn_iterations, int32_t *decision_out, int32_t *selected_out, int *n_selected_out, ldso_activation_t *out) {
+    REQ(H && gn_iterations >= 0 && n_selected_out && (n <= 0 || (decision_out && selected_out && out)), "ldso_ba_select_activate_points: bad arguments");
+    REQ(H->D.F >= 2, "ldso_ba_select_activate_points: set the window and the frames first");
+    REQ(n_hosts == H->D.F, "ldso_ba_select_activate_points: one KRKi / Kt / flag per frame of the resident window");
+    for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, "ldso_ba_select_activate_points: a key-frame image is missing");
+    SelBuffers S;
+    RUN(sel_enqueue(H, "ldso_ba_select_activate_points", n_seeds, seeds, n, points, my_type, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
+    CHK(ba_launch_activate_selected(H->B, H->D, H->settings, S.pts, S.selected, S.nSelected, S.act, n, min_obs, min_idepth_hessian, gn_iterations, H->stream));
+    CHK(hipMemcpyAsync(H->selHost.data(), S.out, S.outBytes, hipMemcpyDeviceToHost, H->stream));
+    CHK(hipStreamSynchronize(H->stream));
+    sel_unpack(H, n, decision_out, selected_out, n_selected_out);
+    const size_t oAct = 16 + 2 * up16((size_t) n * 4);
+    if (*n_selected_out > 0) memcpy(out, H->selHost.data() + oAct, (size_t) *n_selected_out * sizeof(ldso_activation_t));
+    return LDSO_OK;
+}
+
+// debug: CoarseDistanceMap::fwdWarpedIDDistFinal as the last selection left it, (w >> 1) * (h >> 1) floats, 0..39 and 1000
+int ldso_ba_get_distance_map(ldso_ba_t *H, float *out) {
+    REQ(H && out, "ldso_ba_get_distance_map: null argument");
+    REQ(H->d_sel && H->selW1 > 0, "ldso_ba_get_distance_map: no selection has run on this handle");
+    CHK(hipSetDevice(H->device));
+    const size_t wh = (size_t) H->selW1 * H->selH1;
+    std::vector<unsigned char> m(wh);
+    CHK(hipMemcpyAsync(m.data(), (const char *) H->d_sel + H->selMapOffset, wh, hipMemcpyDeviceToHost, H->stream));
+    CHK(hipStreamSynchronize(H->stream));
+    for (size_t i = 0; i < wh; i++) out[i] = m[i] == SEL_FAR ? 1000.0f : (float) m[i];
+    return LDSO_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,8 @@ struct ActArgs {
     ldso_activation_t *out;
     int n, minObs, GNIts;
     float minIdepthH_act;
+    const int32_t *sel;      // non-null: wavefront i works on pts[sel[i]] for i < *nSel (the list act_select.hip left on the device), out[i] is its record
+    const int32_t *nSel;
 };
 
 template <int CTRL> static __device__ __forceinline__ int act_dpp(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
@@ -30,7 +32,8 @@ __global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_setti
     const int lane = threadIdx.x & 63, s = lane >> 3, k = lane & 7;
     const int i = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     if (i >= A.n) return;
-    const ldso_immature_t &P = A.pts[i];
+    if (A.sel && i >= *A.nSel) return;
+    const ldso_immature_t &P = A.pts[A.sel ? A.sel[i] : i];
     const int F = D.F, host = P.host;
     ldso_activation_t &O = A.out[i];
     if (host < 0 || host >= F) { if (lane == 0) { O.ok = 0; O.idepth = 0; O.numGoodRes = 0; O.iterations = 0; O.energy = 0; O.Hdd = 0; O.bd = 0; } if (lane < LDSO_MAX_FRAMES) O.res_state[lane] = -1; return; }
@@ -175,8 +178,19 @@ __global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_setti
 hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs,
                               float minIdepthH_act, int GNIts, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    ActArgs A; A.pts = d_pts; A.out = d_out; A.n = n; A.minObs = minObs; A.GNIts = GNIts; A.minIdepthH_act = minIdepthH_act;
+    ActArgs A; A.pts = d_pts; A.out = d_out; A.n = n; A.minObs = minObs; A.GNIts = GNIts; A.minIdepthH_act = minIdepthH_act; A.sel = nullptr; A.nSel = nullptr;
     const int blocks = (n + 3) / 4;
+    if (D.nsg == 1) hipLaunchKernelGGL(k_activate<1>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
+    else hipLaunchKernelGGL(k_activate<2>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
+    return hipGetLastError();
+}
+
+// the same kernel over a selection that lives on the device: at most nMax wavefronts start, those beyond *d_nSel leave at once
+hipError_t ba_launch_activate_selected(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, const int32_t *d_sel, const int32_t *d_nSel,
+                                       ldso_activation_t *d_out, int nMax, int minObs, float minIdepthH_act, int GNIts, hipStream_t st) {
+    if (nMax <= 0) return hipSuccess;
+    ActArgs A; A.pts = d_pts; A.out = d_out; A.n = nMax; A.minObs = minObs; A.GNIts = GNIts; A.minIdepthH_act = minIdepthH_act; A.sel = d_sel; A.nSel = d_nSel;
+    const int blocks = (nMax + 3) / 4;
     if (D.nsg == 1) hipLaunchKernelGGL(k_activate<1>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
     else hipLaunchKernelGGL(k_activate<2>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
     return hipGetLastError();

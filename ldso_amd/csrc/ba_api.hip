@@ -181,6 +181,7 @@ int ldso_ba_destroy(ldso_ba_t *H) {
     if (H->h_stage) hipHostFree(H->h_stage);
     if (H->d_stage) hipFree(H->d_stage);
     if (H->d_act) hipFree(H->d_act);
+    if (H->d_sel) hipFree(H->d_sel);
     if (H->distBuf) hipFree(H->distBuf);
     if (H->d_p2pErr) hipFree(H->d_p2pErr);
     for (auto &t : H->timers) { hipEventDestroy(t.a); hipEventDestroy(t.b); }

@@ -30,6 +30,7 @@ hipError_t ba_launch_marg_frame(const BaPtrs &B, const BaDims &D, int idx, doubl
 hipError_t ba_launch_acc_init(const BaPtrs &B, const BaDims &D, const GnInit &gi, hipStream_t st);
 hipError_t ba_launch_gn_export(const BaPtrs &B, const BaDims &D, const ResSet &S, double *tail, hipStream_t st);
 hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
+hipError_t ba_launch_activate_selected(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, const int32_t *d_sel, const int32_t *d_nSel, ldso_activation_t *d_out, int nMax, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
 hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, int FS, int cur, const ldso_settings_t &S, int stepMode, float calibPrior, hipStream_t st, int itCheck = -1);
 hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st);
 hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, int cur, const ldso_settings_t &St, int iteration, double lambda, hipStream_t st);
@@ -61,6 +62,11 @@ struct ldso_ba {
     float *d_color = nullptr;          // irradiance staging of ldso_ba_set_image_raw
     void *d_act = nullptr;             // staging of ldso_ba_activate_points: n immature records + n results
     int actCap = 0;
+    void *d_sel = nullptr;             // device arena of ldso_ba_select_candidates / ldso_ba_select_activate_points (act_select.hip: inputs, results, scratch, the distance map)
+    size_t selCap = 0, selMapOffset = 0;
+    int selW1 = 0, selH1 = 0;          // size of the distance map the last selection left in d_sel (0: none yet)
+    int selLdsLimit = -1, selLdsSet = 0; // dynamic LDS the selection kernel may have on this device (-1: not asked yet), and what its attribute was last raised to
+    std::vector<char> selHost;         // host staging of the same calls (one upload, one download)
     double *ownAcc = nullptr;          // the handle's own HFinal/bFinal accumulator (B.acc may point at a caller's all-reduce buffer)
     ChunkStarts chunkStarts;
     ldso_rawjac_t *d_dumpJ = nullptr;

@@ -508,6 +508,10 @@ ACTIVATION_DTYPE = np.dtype([
 ], align=True)
 assert ACTIVATION_DTYPE.itemsize == 96
 
+ACT_SEED_DTYPE = np.dtype([("u", "f4"), ("v", "f4"), ("idepth_scaled", "f4"), ("host", "i4")], align=True)      # ldso_act_seed_t
+assert ACT_SEED_DTYPE.itemsize == 16
+ACT_KEEP, ACT_DROP, ACT_SELECTED = 0, 1, 2
+
 
 def default_trace_settings():
     s = np.zeros((), TRACE_SETTINGS_DTYPE)

@@ -1,0 +1,265 @@
+"""Candidate selection of FullSystem::activatePointsMT on the device (ldso_amd/csrc/act_select.hip: distance map, density control, the greedy loop) against the
+reference's compiled CoarseDistanceMap and its own member, always at a transplanted common state: the seeds, candidates and poses the reference leg reads from
+its object graph are handed to the device as flat arrays (activation_select_common.gather).  Exact means np.array_equal."""
+import numpy as np
+import pytest
+
+from conftest import observe
+from ldso_amd import binding, synth
+from oracle import pyref as pr
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not (pr.available() and pr.adapter_available()), reason="oracle/_ref/libldso_ref.so / adapter/_build/libldso_adapter_test.so not built")]
+
+MIN_DISTS = (0.0, 0.5, 1.0, 2.0, 4.0)
+# the states of the selection tests: several thousand candidates on the map, fewer seeds than a full window so that currentMinActDist = 4 still selects
+SELECT_STATES = {"C3": dict(name="C3", per_frame=3000, P=1000), "small": dict(name="small", per_frame=1000, P=150)}
+_STATES = {}
+
+
+def _state(key):
+    import activation_select_common as asc
+    if key not in _STATES:
+        win, (r,), pts = asc.make_state(**SELECT_STATES[key])
+        _STATES[key] = (win, r, asc.gather(r))
+    return _STATES[key]
+
+
+def _device_map(win, g):
+    """the map after makeDistanceMap alone: a selection without candidates"""
+    ba = binding.BA(win.w, win.h, 2, 16)
+    dec, sel = ba.select_candidates(g["seeds"], g["cand"][:0], g["my_type"][:0], g["KRKi"], g["Kt"], g["flagged"], 1.0)
+    assert len(dec) == 0 and len(sel) == 0
+    m = ba.get_distance_map()
+    ba.close()
+    return m
+
+
+# 1280 x 512: 640 x 256 cells = 163 840 B, beyond what the workgroup can hold in LDS beside its frontier lists - the global-memory map; everything else: LDS
+@pytest.mark.parametrize("name,over", [("tiny", {}), ("small", {}), ("C3", {}), ("C4", {}), ("tiny", dict(w=1280, h=512, fx=500.0))], ids=["tiny", "small", "C3", "C4", "1280x512-global"])
+def test_initial_distance_map_equals_make_distance_map(name, over):
+    """CoarseDistanceMap::makeDistanceMap (CoarseTracker.cc:686-721) over all cells, at every image size the synthetic configurations offer"""
+    import activation_select_common as asc
+    win, (r,), _ = asc.make_state(name, per_frame=0, **over)
+    g = asc.gather(r)
+    ref = asc.ref_select(r, 1.0)["map_before"]
+    assert len(g["seeds"]) > 20 and (ref == 0).sum() > 20 and ref.shape == (win.h >> 1, win.w >> 1)
+    assert np.array_equal(_device_map(win, g), ref)
+    # zero seeds: no ACTIVE point in the graph - every cell stays far
+    assert asc.set_all_point_status(r, 1) >= len(g["seeds"])
+    g0 = asc.gather(r)
+    ref0 = asc.ref_select(r, 1.0)["map_before"]
+    assert len(g0["seeds"]) == 0 and (ref0 == 1000).all()
+    assert np.array_equal(_device_map(win, g0), ref0)
+    r.close()
+
+
+def test_initial_distance_map_border_and_skipped_seeds():
+    """seeds that land on the last column / row of the map (u == w1 - 1, v == h1 - 1: border cells hold 0 and must not spread, CoarseTracker.cc:736), seeds that
+    project outside, seeds behind the camera (negative inverse depth: ptp[2] < 0 - the reference has no such test, only the bounds decide)"""
+    import activation_select_common as asc
+    win = synth.make_config("small")
+    rng = np.random.default_rng(5)
+    P = win.P
+    h1, w1 = win.h >> 1, win.w >> 1
+    # the poses of the window, from a first graph: the host pixel that lands on a chosen cell is the back-projection through KRKi / Kt at the point's depth
+    r0 = pr.RefWindow(win)
+    r0.fs_attach()
+    g0 = asc.gather(r0)
+    r0.close()
+    old_hosts = np.nonzero(win.points["host"] != win.F - 1)[0]
+    order = old_hosts[np.argsort(win.points["host"][old_hosts], kind="stable")]               # seed i of the gather = point order[i]
+    assert len(order) == len(g0["seeds"]) and np.array_equal(g0["seeds"]["host"], win.points["host"][order])
+    for i in range(60):
+        k = order[i * 3]
+        sd = g0["seeds"][i * 3]
+        X = np.array([w1 - 1, rng.integers(4, h1 - 4), 1.0]) if i % 2 == 0 else np.array([rng.integers(4, w1 - 4), h1 - 1, 1.0])
+        Q = np.linalg.inv(g0["KRKi"][sd["host"]].reshape(3, 3).astype(np.float64)); t = g0["Kt"][sd["host"]].astype(np.float64) * float(sd["idepth_scaled"])
+        sc = (1.0 + Q[2] @ t) / (Q[2] @ X)
+        uv = Q @ (sc * X - t)
+        win.points["u"][k] = uv[0]; win.points["v"][k] = uv[1]
+    far = order[200:240]
+    win.points["idepth"][far[:20]] = 1000.0                                                   # absurd inverse depths of both signs: the translation dominates,
+    win.points["idepth"][far[20:]] = -1000.0                                                  # the projection leaves the map or falls behind the camera (ptp[2] < 0)
+    win.points["idepth_zero"] = win.points["idepth"]
+    r = pr.RefWindow(win)
+    r.fs_attach()
+    g = asc.gather(r)
+    ref = asc.ref_select(r, 1.0)["map_before"]
+    assert ref.shape == (h1, w1)
+    # the cases are there, on the reference leg
+    sd = g["seeds"]; K = g["KRKi"][sd["host"]]; T = g["Kt"][sd["host"]]
+    p = [((K[:, 3 * i] * sd["u"] + K[:, 3 * i + 1] * sd["v"]) + K[:, 3 * i + 2]) + T[:, i] * sd["idepth_scaled"] for i in range(3)]
+    with np.errstate(all="ignore"):
+        u = p[0] / p[2] + np.float32(0.5); v = p[1] / p[2] + np.float32(0.5)
+    outside = ~((u >= 1) & (v >= 1) & (u < w1) & (v < h1))
+    assert (ref[:, w1 - 1] == 0).sum() >= 20 and (ref[h1 - 1, :] == 0).sum() >= 20, "seeds on the last column and on the last row"
+    print("border test: seeds outside", int(outside.sum()), "behind the camera", int((p[2] < 0).sum()))
+    assert outside.sum() >= 10 and (p[2] < 0).sum() >= 5
+    # a border seed did not spread: beside a 0 on the last column there is a cell that another seed did not reach within one round
+    ys = np.nonzero(ref[1:-1, w1 - 1] == 0)[0] + 1
+    assert any(ref[y, w1 - 2] > 1 for y in ys) or any(ref[h1 - 2, x] > 1 for x in np.nonzero(ref[h1 - 1, 1:-1] == 0)[0] + 1)
+    assert np.array_equal(_device_map(win, g), ref)
+    r.close()
+
+
+def _order_dependent(g, s, min_dist):
+    """candidates that pass the distance test against the map BEFORE the loop and are still kept: rejected at their turn by a candidate accepted before them"""
+    c = g["cand"]
+    keep = np.nonzero(s["decision"] == 0)[0]
+    K = g["KRKi"][c["host"][keep]]; T = g["Kt"][c["host"][keep]]
+    with np.errstate(all="ignore"):
+        d = np.float32(0.5) * (c["idepth_max"][keep] + c["idepth_min"][keep])
+        p = [((K[:, 3 * i] * c["u"][keep] + K[:, 3 * i + 1] * c["v"][keep]) + K[:, 3 * i + 2]) + T[:, i] * d for i in range(3)]
+        u = (p[0] / p[2] + np.float32(0.5)); v = (p[1] / p[2] + np.float32(0.5))
+        h1, w1 = s["map_before"].shape
+        el = np.isfinite(u) & np.isfinite(v) & (u >= 1) & (v >= 1) & (u < w1) & (v < h1)
+    import activation_select_common as asc
+    el &= asc.eligible_in_bounds(g, (h1, w1))[keep]
+    ui, vi = u[el].astype(np.int64), v[el].astype(np.int64)
+    dist = s["map_before"][vi, ui] + (p[0][el] - np.floor(p[0][el]))
+    return int((dist >= np.float32(min_dist) * g["my_type"][keep][el]).sum())
+
+
+@pytest.mark.parametrize("min_dist", MIN_DISTS)
+@pytest.mark.parametrize("key", sorted(SELECT_STATES))
+def test_selection_equals_reference_loop(key, min_dist):
+    """decision codes, the order of the selected candidates and the final map against the loop of FullSystem.cc:1088-1152 driven through the reference's compiled
+    CoarseDistanceMap (adp_ref_select_candidates), with my_type 1 / 2 / 4 mixed and every branch of the candidate rule present"""
+    import activation_select_common as asc
+    win, r, g = _state(key)
+    c = g["cand"]
+    # every branch is there: never traced, OUTLIER, OOB, interval >= 8, low quality, idepth sum <= 0, host flagged, projection out of bounds
+    assert (~np.isfinite(c["idepth_max"])).sum() > 5 and (c["lastTraceStatus"] == 2).sum() > 5 and (c["lastTraceStatus"] == 1).sum() > 5
+    assert (c["lastTracePixelInterval"] >= 8).sum() > 5 and (c["quality"] <= asc.MIN_TRACE_QUALITY).sum() > 5
+    with np.errstate(invalid="ignore"):
+        assert ((c["idepth_max"] + c["idepth_min"]) <= 0).sum() > 5
+    assert g["flagged"].sum() == 1 and (g["flagged"][c["host"]] == 1).sum() > 5 and set(np.unique(g["my_type"])) == {1.0, 2.0, 4.0}
+    s = asc.ref_select(r, min_dist)
+    el = asc.eligible_in_bounds(g, s["map_before"].shape)
+    frac = len(s["selected"]) / el.sum()
+    od = _order_dependent(g, s, min_dist)
+    print("selection", key, min_dist, "candidates", len(c), "eligible in bounds", int(el.sum()), "selected", len(s["selected"]), "fraction", round(frac, 3), "order-dependent", od)
+    assert len(c) >= 3000 and (s["decision"] == asc.DROP).sum() > 40
+    if min_dist > 0:
+        assert 0.10 <= frac <= 0.90, "the reference leg selects neither nearly all nor nearly none of the candidates that reach the distance test"
+        assert od > 0, "a candidate that passes against the initial map is rejected at its turn: the order matters in this set"
+    ba = binding.BA(win.w, win.h, 2, 16)
+    dec, sel = ba.select_candidates(g["seeds"], c, g["my_type"], g["KRKi"], g["Kt"], g["flagged"], min_dist)
+    final = ba.get_distance_map()
+    ba.close()
+    assert np.array_equal(dec, s["decision"]), (int((dec != s["decision"]).sum()), np.nonzero(dec != s["decision"])[0][:10])
+    assert np.array_equal(sel, s["selected"])
+    assert np.array_equal(final, s["map_after"]), int((final != s["map_after"]).sum())
+
+
+@pytest.mark.parametrize("min_dist", (1.0, 4.0))
+def test_fused_selection_and_activation(min_dist):
+    """ldso_ba_select_activate_points: the selection of the test above, and for the selected candidates the records ldso_ba_activate_points returns for that list"""
+    import activation_select_common as asc
+    win, r, g = _state("small")
+    s = asc.ref_select(r, min_dist)
+    ba = binding.BA.from_window(win)
+    dec, sel, out = ba.select_activate_points(g["seeds"], g["cand"], g["my_type"], g["KRKi"], g["Kt"], g["flagged"], min_dist)
+    assert np.array_equal(dec, s["decision"]) and np.array_equal(sel, s["selected"]) and len(sel) > 100
+    assert np.array_equal(ba.get_distance_map(), s["map_after"])
+    want = ba.activate_points(g["cand"][sel])
+    assert out.tobytes() == want.tobytes()
+    assert 0.2 < out["ok"].mean() < 1.0
+    ba.close()
+
+
+def test_adapter_activate_points_mt_equals_reference_member():
+    """GpuBackend::activatePointsMT(fs) against the reference's fs.activatePointsMT() on two identical object graphs, one step: every Feature::status and
+    currentMinActDist exact, the new points as close as tests/test_adapter_gpu.py asks of activatePoints (verdicts exact, inverse depth to 1e-5)."""
+    import activation_select_common as asc
+    win, (r_ref, r_adp), pts = asc.make_state("small", per_frame=400, P=150, n_graphs=2)
+    old = asc.set_desired_point_density(100.0)                      # 150 points against 100 wanted: the controller moves (+ 0.8)
+    try:
+        before = asc.feature_statuses(r_ref)
+        asc.ref_activate_points_mt(r_ref)
+        A = pr.GpuAdapter(max_frames=win.F + 1, max_points=win.P + 16)
+        n_cand, n_sel, n_act = asc.adapter_activate_points_mt(A, r_adp)
+    finally:
+        asc.set_desired_point_density(old)
+    assert np.float32(asc.min_act_dist(r_adp)) == np.float32(asc.min_act_dist(r_ref)) and abs(asc.min_act_dist(r_ref) - 2.8) < 1e-5
+    st_ref, st_adp = asc.feature_statuses(r_ref), asc.feature_statuses(r_adp)
+    assert np.array_equal(st_adp, st_ref)
+    assert n_sel > 100 and 0.2 * n_sel < n_act < n_sel and (st_ref != before).sum() > n_sel
+    ga, gb = pr.graph_summary(r_ref), pr.graph_summary(r_adp)
+    for k in ("points", "immature", "residuals", "host"):
+        assert np.array_equal(ga[k], gb[k]), k
+    assert np.array_equal(ga["uv"], gb["uv"]) and ga["points"].sum() == win.P + n_act
+    assert np.abs(gb["idepth"] - ga["idepth"]).max() <= 1e-5 * np.abs(ga["idepth"]).max()
+    assert asc.ef_npoints(r_adp) == asc.ef_npoints(r_ref)
+    A.close(); r_ref.close(); r_adp.close()
+
+
+SEQ_K, SEQ_PER_FRAME, SEQ_DENSITY = 8, 300, 250.0
+
+
+def _switch_on_yardstick(log_ref, mt_runs=2):
+    """adapter_sequence_common.reference_yardstick with the distance map on: the single-threaded pin build against runs with the reference's 6-worker
+    IndexThreadReduce and against the -O3 build of the same translation units (in a process of its own) -> the largest distance per quantity"""
+    import os, pickle, subprocess, sys, tempfile
+    from adapter_sequence_common import run_sequence, sequence_distance, QUANTITIES
+    win = synth.make_config("small", extra_frames=SEQ_K)
+    runs = {}
+    for i in range(mt_runs):
+        r, log = run_sequence(win, SEQ_K, multithreading=True, per_frame=SEQ_PER_FRAME); r.close()
+        runs["six_threads_run_%d" % i] = log
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ref = os.path.join(root, "oracle", "_ref", "fast", "libldso_ref.so"); adp = os.path.join(root, "adapter", "_build_fast", "libldso_adapter_test.so")
+    try:
+        flags = open("/proc/cpuinfo").read()
+    except OSError:
+        flags = ""
+    if os.path.exists(ref) and os.path.exists(adp) and " avx2" in flags and " fma" in flags:
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "log.pkl")
+            env = dict(os.environ, LDSO_REF_LIB=ref, LDSO_ADAPTER_LIB=adp)
+            p = subprocess.run([sys.executable, os.path.join(root, "tests", "activate_select_sequence_worker.py"), "small", str(SEQ_K), "0", out, str(SEQ_PER_FRAME), str(SEQ_DENSITY)],
+                               env=env, capture_output=True, timeout=900)
+            if p.returncode == 0 and os.path.exists(out):
+                with open(out, "rb") as f:
+                    runs["O3_build"] = pickle.load(f)["log"]
+    per = {}
+    for name, log in runs.items():
+        d, same = sequence_distance(log_ref, log)
+        assert same, ("two runs of the reference disagree on the key-frame set", name)
+        per[name] = d
+    return {q: max(d[q] for d in per.values()) for q in QUANTITIES}, per
+
+
+def test_eight_key_frames_with_the_distance_map_follow_the_reference():
+    """The key-frame sequence of tests/test_adapter_sequence_gpu.py with activatePointsMT WHOLE: GpuBackend::activatePointsMT on one graph, the reference's member on
+    the other, 300 fresh immature points per key frame and a desired density the window crosses, so that currentMinActDist rises to its clamp and falls to 0.
+    Limit: 3 x the reference's own spread per quantity, measured with the switch on, and the same key frames kept.
+    Observed on MI355X (worst over the eight key frames | the reference against itself, before x 3): rmse 1.2e-3 | 2.0e-3, pose 1.2e-4 | 2.9e-4, aff 1.6e-2 | 2.0e-2,
+    HM 2.6e-3 | 5.3e-3, bM 7.8e-2 | 1.7e-1, idepth_med 2.2e-4 | 4.0e-4, idepth_max 1.1e-2 | 1.3e-2, counts 7 | 6, residual_counts 20 | 20, unmatched_points 11 | 20."""
+    import activation_select_common as asc
+    from adapter_sequence_common import run_sequence, sequence_distance, QUANTITIES
+    win = synth.make_config("small", extra_frames=SEQ_K)
+    old = asc.set_desired_point_density(SEQ_DENSITY)
+    try:
+        asc.set_distance_map(True)
+        r_ref, log_ref = run_sequence(win, SEQ_K, per_frame=SEQ_PER_FRAME)
+        trace_ref = asc.min_act_dist_trace()
+        assert len(trace_ref) == SEQ_K and (np.diff(np.concatenate([[2.0], trace_ref])) > 0).any() and (np.diff(trace_ref) < 0).any(), trace_ref
+        A = pr.GpuAdapter(max_frames=8, max_points=8000)
+        asc.set_distance_map(True)                                  # restarts the trace
+        r_adp, log_adp = run_sequence(win, SEQ_K, adapter=A, per_frame=SEQ_PER_FRAME)
+        trace_adp = asc.min_act_dist_trace()
+        yard, per = _switch_on_yardstick(log_ref)
+    finally:
+        asc.set_distance_map(False)
+        asc.set_desired_point_density(old)
+    assert len(log_ref) == len(log_adp) == SEQ_K and not any(rec["lost"] for rec in log_ref + log_adp)
+    assert sum(rec["activated"] for rec in log_adp) > 1000
+    worst, same = sequence_distance(log_ref, log_adp)
+    print("distance-map sequence: currentMinActDist reference", trace_ref, "drop-in", trace_adp)
+    print("distance-map sequence, worst over", SEQ_K, "key frames:", {k: float("%.3g" % v) for k, v in worst.items()}, "| reference vs reference:", {k: float("%.3g" % v) for k, v in yard.items()},
+          "| runs:", sorted(per))
+    assert same, "same key frames in the window after every key frame, >= 97 % of the points held by both graphs"
+    for q in QUANTITIES:
+        observe("sequence_distance_map_" + q, worst[q], 3.0 * yard[q])
+    A.close(); r_ref.close(); r_adp.close()
