@@ -268,7 +268,18 @@ int ldso_ba_batch_reduce_splits(ldso_ba_batch_t *b, int *splits);          /* K-
  * a chunk never spans two segments) and wg_first_chunk[n_wg + 1] (workgroup w works through the chunks [wg_first_chunk[w], wg_first_chunk[w + 1])), chosen so that the
  * largest workgroup load (points + chunk_cost per chunk) is minimal for this greedy cut (bisection on the budget, *budget_out).  Returns the number of chunks. */
 int ldso_ba_balance_chunks(int n_seg, const int32_t *seg_points, int n_wg, int chunk_cost, int32_t *chunk_end, int cap, int32_t *wg_first_chunk, int64_t *budget_out);
+/* ldso_ba_batch_enqueue_gn needs every window at the same ping-pong parity ("the same stage") and refuses otherwise - also after a ldso_ba_batch_optimize
+ * whose windows stopped at iterations of different parity. */
 int ldso_ba_batch_enqueue_gn(ldso_ba_batch_t *b, int first_iteration, int iters);
+/* FullSystem::optimize(mnumOptIts) for every window of the batch: per window exactly what ldso_ba_optimize(handle, mnumOptIts, force_all_iterations, ...) gives on
+ * that handle alone (resetOOB preamble, lambda = 1e-1 * 0.25^it, the window's own iteration cap - 15 below four key frames unless forced - and device-side
+ * canbreak exit, the tail with linearizeAll(true), energy log, rmse), with a number of launches that does not depend on n and one host synchronisation at the end.
+ * The windows need not be at the same parity, and stop at iterations of their own.  rmse_out / iterations_out / status_out: n entries each, any of them may
+ * be NULL; status_out[i] is LDSO_OK or LDSO_E_NONFINITE by the test of ldso_ba_optimize.  Returns LDSO_OK when every window is, LDSO_E_NONFINITE when at least
+ * one is not (the others' results are unaffected), other codes as usual.  Afterwards every handle is where ldso_ba_optimize would have left it: the per-handle
+ * getters, ldso_ba_get_energy_log, ldso_ba_marginalize_points / _frame and a second ldso_ba_batch_optimize work on it.
+ * Beyond ldso_ba_batch_create's conditions: every window has at least 2 key frames and at most 8 (the 8-slot table). */
+int ldso_ba_batch_optimize(ldso_ba_batch_t *b, int mnumOptIts, int force_all_iterations, float *rmse_out /*n*/, int *iterations_out /*n*/, int *status_out /*n*/);
 int ldso_ba_batch_destroy(ldso_ba_batch_t *b);
 /* points per workgroup ldso_ba_batch_create gave the windows of the batch - since round 6 the AVERAGE, rounded: the cuts are uneven, ldso_ba_get_chunk_cuts has
  * them - (0: their single-window chunking was kept; ldso_ba_batch_destroy restores it) */

@@ -14,6 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 
+E_NONFINITE = -3          # LDSO_E_NONFINITE (ldso_hip.h)
+
+
 class LdsoError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"ldso_hip error {code}: {msg}")
@@ -512,6 +515,16 @@ class BABatch:
 
     def enqueue_gn(self, first_iteration, iters):
         _chk(self.L.ldso_ba_batch_enqueue_gn(self.h, C.c_int(first_iteration), C.c_int(iters)))
+
+    def optimize(self, niters, force_all=False):
+        """FullSystem::optimize(niters) on every window of the batch (ldso_ba_batch_optimize) -> (rmse[n], iterations[n], status[n]).
+        A non-finite window is reported in status (LDSO_E_NONFINITE = -3), not raised: the other windows' results stay readable."""
+        n = len(self.handles)
+        rm, it, st = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        code = self.L.ldso_ba_batch_optimize(self.h, C.c_int(niters), C.c_int(1 if force_all else 0), _p(rm), _p(it), _p(st))
+        if code != E_NONFINITE:
+            _chk(code)
+        return rm, it, st
 
     def sync(self):
         self.handles[0].sync()

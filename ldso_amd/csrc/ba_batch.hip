@@ -15,8 +15,9 @@ static int batch_refresh(ldso_ba_batch *Bt) {
             BatchItem &it = Bt->items[pass * n + i];
             if (pass == 1 && (int) i == Bt->n0) { Bt->halfChunks[0] = lin; Bt->halfReduce[0] = red; lin = 0; red = 0; }
             if (H->B.acc != H->ownAcc) H->B.acc = H->ownAcc;
-            it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[0]; it.set[1] = H->sets[1]; it.cs = H->chunkStarts;
-            it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.linBlock0 = lin; it.redBlock0 = red;
+            // the per-window parity: set[0] = the window's applied set, so the launches name the sets relative to it and windows at different parities share them
+            it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[H->cur]; it.set[1] = H->sets[H->cur ^ 1]; it.cs = H->chunkStarts;
+            it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.linBlock0 = lin; it.redBlock0 = red; it.outSlot = (int32_t) i;
             const int nT = H->GSP / 16;
             lin += H->D.nChunks;
             red += H->D.F * H->D.F + Bt->ks * nT * (nT + 1) / 2 + 1;
@@ -218,6 +219,11 @@ int ldso_ba_batch_create(ldso_ba_t *const *handles, int n, ldso_ba_batch_t **out
     // every failure from here on goes through ldso_ba_batch_destroy: it restores the single-window chunking and releases the handles
     if (hipMalloc(&q, 2 * (size_t) n * sizeof(BatchItem)) != hipSuccess) { (void) hipGetLastError(); ldso_ba_batch_destroy(Bt); ldso_set_error("ldso_ba_batch_create: hipMalloc failed"); return LDSO_E_HIP; }
     Bt->d_items = (BatchItem *) q;
+    const size_t scBytes = (size_t) n * 16 * sizeof(double);          // ldso_ba_batch_optimize reads every window's scalars back in one copy
+    if (hipMalloc(&q, scBytes) != hipSuccess) { (void) hipGetLastError(); ldso_ba_batch_destroy(Bt); ldso_set_error("ldso_ba_batch_create: hipMalloc failed"); return LDSO_E_HIP; }
+    Bt->d_scalars = (double *) q;
+    if (hipHostMalloc(&q, scBytes, hipHostMallocDefault) != hipSuccess) { (void) hipGetLastError(); ldso_ba_batch_destroy(Bt); ldso_set_error("ldso_ba_batch_create: hipHostMalloc failed"); return LDSO_E_HIP; }
+    Bt->h_scalars = (double *) q;
     if (Bt->n0 < n) {
         if (hipStreamCreateWithFlags(&Bt->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&Bt->ev0, hipEventDisableTiming) != hipSuccess
             || hipEventCreateWithFlags(&Bt->ev1, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&Bt->evEnd, hipEventDisableTiming) != hipSuccess) {
@@ -251,6 +257,8 @@ int ldso_ba_batch_destroy(ldso_ba_batch_t *Bt) {
     if (Bt->ev1) hipEventDestroy(Bt->ev1);
     if (Bt->evEnd) hipEventDestroy(Bt->evEnd);
     if (Bt->d_items) hipFree(Bt->d_items);
+    if (Bt->d_scalars) hipFree(Bt->d_scalars);
+    if (Bt->h_scalars) hipHostFree(Bt->h_scalars);
     if (Bt->d_blocks) hipFree(Bt->d_blocks);
     if (Bt->d_wg) hipFree(Bt->d_wg);
     // back to the single-window chunking (handles that were re-chunked by ldso_ba_batch_create)
@@ -263,7 +271,8 @@ int ldso_ba_batch_destroy(ldso_ba_batch_t *Bt) {
 
 // `iters` forced Gauss-Newton iterations of every window of the batch: 3 launches per iteration for the whole batch, no host
 // synchronisation.  Every window must hold an applied linearisation (ldso_ba_linearize_all + ldso_ba_apply_res, or a previous
-// optimize / enqueue) and all of them must be at the same ping-pong parity (true after identical call sequences).
+// optimize / enqueue) and all of them must be at the same ping-pong parity (true after identical call sequences; not, in general, after
+// ldso_ba_batch_optimize, whose windows stop at iterations of their own).
 int ldso_ba_batch_enqueue_gn(ldso_ba_batch_t *Bt, int first_iteration, int iters) {
     REQ(Bt && iters >= 0, "ldso_ba_batch_enqueue_gn: bad arguments");
     ldso_ba *H0 = Bt->h[0];
@@ -271,7 +280,7 @@ int ldso_ba_batch_enqueue_gn(ldso_ba_batch_t *Bt, int first_iteration, int iters
     for (ldso_ba *H : Bt->h) REQ(H->cur == H0->cur && !H->pendingApply, "ldso_ba_batch_enqueue_gn: the windows of a batch must be at the same stage");
     RUN(batch_refresh(Bt));
     const Damping d = damping(H0->settings, 1e-1);
-    int cur = H0->cur;
+    int cur = 0;          // relative to every window's applied set (BatchItem::set[0], batch_refresh)
     // The control step of a batch occupies two workgroups per window for ~30 us: the batch runs as two halves on two streams, the second
     // half an iteration behind the first, so that one half's reduce + control step overlap the other half's (chip-filling) linearisation.
     const int n = (int) Bt->h.size(), n0 = Bt->n0, n1 = n - n0;
@@ -290,8 +299,80 @@ int ldso_ba_batch_enqueue_gn(ldso_ba_batch_t *Bt, int first_iteration, int iters
         cur ^= 1;
     }
     if (n1 > 0 && iters > 0) { CHK(hipEventRecord(Bt->evEnd, Bt->aux)); CHK(hipStreamWaitEvent(H0->stream, Bt->evEnd, 0)); }      // ldso_ba_sync(handle) covers both halves
-    for (ldso_ba *H : Bt->h) H->cur = cur;
+    for (ldso_ba *H : Bt->h) H->cur ^= cur;
     return LDSO_OK;
+}
+
+// FullSystem::optimize(mnumOptIts) (FullSystem.cc:725-884, forced-accept schedule) of every window of the batch: per window what ldso_ba_optimize gives on its
+// handle alone - resetOOB preamble, lambda = 1e-1 * 0.25^it, its own iteration cap and device-side canbreak exit, the tail (statistics, setNewFrameEnergyTH,
+// re-anchoring, adjoints, precalc, linearizeAll(true)), energy log, rmse, non-finite verdict.  Launches per call: one k_batch_begin, then 4 + 3 cap per half (preamble, 3 per iteration, 3 of the tail; cap = the largest iteration cap
+// of the batch), whatever the number of windows; no host synchronisation before the one that reads the n scalar blocks.  The schedule of the iterations is that of ldso_ba_batch_enqueue_gn (two
+// halves on two streams from four windows on); a window that has stopped costs its workgroups one test of its own scalars[LD_SC_STOP] per launch.
+int ldso_ba_batch_optimize(ldso_ba_batch_t *Bt, int mnumOptIts, int force_all_iterations, float *rmse_out, int *iterations_out, int *status_out) {
+    REQ(Bt && mnumOptIts >= 0, "ldso_ba_batch_optimize: bad arguments");
+    ldso_ba *H0 = Bt->h[0];
+    const int n = (int) Bt->h.size(), n0 = Bt->n0, n1 = n - n0;
+    REQ(Bt->FS == 8, "ldso_ba_batch_optimize: windows of more than 8 key frames are not supported in a batched optimize (every window needs F <= 8): run them with ldso_ba_optimize");
+    int caps = 0;
+    for (ldso_ba *H : Bt->h) {
+        REQ(H->D.F >= 2, "ldso_ba_batch_optimize: every window of the batch needs at least 2 key frames (F >= 2)");
+        REQ(!H->pendingApply, "ldso_ba_batch_optimize: a window has a pending linearisation (ldso_ba_apply_res first)");
+        int cap = mnumOptIts;
+        if (!force_all_iterations) { if (H->D.F < 3) cap = 20; if (H->D.F < 4) cap = 15; }          // the rule of ldso_ba_optimize (k_batch_begin applies the same one)
+        caps = std::max(caps, cap);
+    }
+    REQ(caps + 2 < 64, "ldso_ba_batch_optimize: too many iterations");
+    CHK(hipSetDevice(H0->device));
+    RUN(batch_refresh(Bt));
+    const ldso_settings_t &St = H0->settings;
+    const BatchItem *itH[2] = {Bt->d_items + n, Bt->d_items + n + n0};
+    const BatchBlock *blH[2] = {Bt->d_blocks + Bt->totalChunks, Bt->d_blocks + Bt->totalChunks + Bt->halfChunks[0]};
+    const int nH[2] = {n0, n1};
+    hipStream_t stH[2] = {H0->stream, Bt->aux};
+    const int halves = n1 > 0 ? 2 : 1;
+    auto linearize = [&](int u, int cur, int stepMode, int itCheck) -> hipError_t {
+        return ba_launch_linearize_batch(itH[u], blH[u], Bt->halfChunks[u], Bt->balanced ? Bt->d_wg + Bt->wgOff[1 + u] : nullptr, Bt->nWG[1 + u], Bt->FS, cur, St, stepMode, St.initialCalibHessian, stH[u], itCheck);
+    };
+    // energy logs cleared, every window's LD_SC_STOP = its cap - 1 (both halves: one launch in front of the fork)
+    CHK(ba_launch_batch_begin(Bt->d_items, n, mnumOptIts, force_all_iterations ? 1 : 0, H0->stream));
+    if (halves == 2) { CHK(hipEventRecord(Bt->ev0, H0->stream)); CHK(hipStreamWaitEvent(Bt->aux, Bt->ev0, 0)); }
+    // linearizeAll(false) with the resetOOB of the preamble fused in (stepMode bit 1) + applyRes: set[0] -> set[1]
+    for (int u = 0; u < halves; u++) CHK(linearize(u, 0, 2, -1));
+    double lambda = 1e-1;
+    for (int i = 0; i < caps; i++) {
+        const int cur = 1 ^ (i & 1), itCheck = force_all_iterations ? -1 : i;
+        const Damping d = damping(St, lambda);
+        for (int u = 0; u < halves; u++) {
+            CHK(ba_launch_reduce_batch(itH[u], nH[u], Bt->halfReduce[u], cur, St.initialCalibHessian, d.l1, d.il, stH[u], itCheck));
+            CHK(ba_launch_gn_solve_batch(itH[u], nH[u], Bt->Dmax, cur, St, i, lambda, stH[u], i, itCheck));          // POST / THRESH / LOG of the previous linearisation ride along
+            if (halves == 2 && u == 0 && i == 0) { CHK(hipEventRecord(Bt->ev1, H0->stream)); CHK(hipStreamWaitEvent(Bt->aux, Bt->ev1, 0)); }      // the second half runs half an iteration behind
+            CHK(linearize(u, cur, 1, itCheck));
+        }
+        lambda *= 0.25;
+    }
+    // tail: statistics of the last linearisation, re-anchor the newest frame, adjoints, precalc; linearizeAll(true); its statistics
+    for (int u = 0; u < halves; u++) {
+        CHK(ba_launch_solve_batch(itH[u], nH[u], Bt->Dmax, St, SK_POST | SK_THRESH | SK_LOG | SK_REANCHOR | SK_ADJ | SK_NONULLSPACE | SK_PRECALC, 0, nullptr, stH[u]));
+        CHK(ba_launch_linearize_batch_fix(itH[u], blH[u], Bt->halfChunks[u], Bt->balanced ? Bt->d_wg + Bt->wgOff[1 + u] : nullptr, Bt->nWG[1 + u], St, St.initialCalibHessian, stH[u]));
+        CHK(ba_launch_solve_batch(itH[u], nH[u], Bt->Dmax, St, SK_POST | SK_THRESH | SK_LOG, 1, Bt->d_scalars, stH[u]));
+    }
+    if (halves == 2) { CHK(hipEventRecord(Bt->evEnd, Bt->aux)); CHK(hipStreamWaitEvent(H0->stream, Bt->evEnd, 0)); }
+    CHK(hipMemcpyAsync(Bt->h_scalars, Bt->d_scalars, (size_t) n * 16 * sizeof(double), hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipStreamSynchronize(H0->stream));
+    int rc = LDSO_OK;
+    for (int i = 0; i < n; i++) {
+        ldso_ba *H = Bt->h[i];
+        const double *sc = Bt->h_scalars + (size_t) i * 16;
+        const int done = (int) sc[LD_SC_STOP] + 1;          // the scalar names the last iteration the window executed
+        H->cur ^= done & 1;                                 // preamble + done iterations + the fixing pass swapped the sets done + 2 times
+        H->pendingApply = false; H->appliedValid = true; H->lastIterations = done;
+        const bool bad = !std::isfinite(sc[0]) || sc[4] != 0.0;
+        if (bad) rc = LDSO_E_NONFINITE;
+        if (iterations_out) iterations_out[i] = done;
+        if (rmse_out) rmse_out[i] = sqrtf((float) (sc[0] / (8 * sc[9])));
+        if (status_out) status_out[i] = bad ? LDSO_E_NONFINITE : LDSO_OK;
+    }
+    return rc;
 }
 
 // average duration of the batched k_linearize for bench.py's roofline: `reps` back-to-back launches on the applied state (read set ->
@@ -302,7 +383,7 @@ int ldso_ba_batch_time_linearize(ldso_ba_batch_t *Bt, int reps, double *avg_us) 
     CHK(hipSetDevice(H0->device));
     RUN(batch_refresh(Bt));
     return time_launches(H0->stream, reps, avg_us, [Bt, H0]() -> int {
-        CHK(ba_launch_linearize_batch(Bt->d_items, Bt->d_blocks, Bt->totalChunks, Bt->balanced ? Bt->d_wg + Bt->wgOff[0] : nullptr, Bt->nWG[0], Bt->FS, H0->cur, H0->settings, 0, H0->settings.initialCalibHessian, H0->stream));
+        CHK(ba_launch_linearize_batch(Bt->d_items, Bt->d_blocks, Bt->totalChunks, Bt->balanced ? Bt->d_wg + Bt->wgOff[0] : nullptr, Bt->nWG[0], Bt->FS, 0, H0->settings, 0, H0->settings.initialCalibHessian, H0->stream));
         return LDSO_OK;
     });
 }

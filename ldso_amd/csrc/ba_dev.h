@@ -177,6 +177,9 @@ struct BatchItem {
     ResSet set[2];
     ChunkStarts cs;
     int32_t hasPrior, GSP, linBlock0, redBlock0;
+    // In a batch (batch_refresh) set[0] is the window's APPLIED set whichever of the handle's two sets that is (set[k] = the handle's sets[k ^ cur]): the window's parity
+    // lives in this order, the kernels index the sets relative to the launch, and windows at different parities share it.  outSlot = the window's index in the whole batch.
+    int32_t outSlot, pad_;
 };
 
 // GN fast path: what k_linearize needs to initialise B.acc for the solve that follows it

@@ -1286,8 +1286,8 @@ __global__ __launch_bounds__(64 * LD_WAVES) void k_linearize(BaPtrs B, BaDims D,
 }
 
 // Batched windows (one 7-keyframe window is tiny for the chip): the chunks of nWin independent windows in one
-// launch.  Workgroup -> window by the prefix of chunk counts (items[w].linBlock0); `cur` = which residual set is the applied one
-// (all windows of a batch iterate in lockstep).
+// launch.  Workgroup -> window by the block table (BatchBlock::win); `cur` = which residual set is read, RELATIVE to every window's own applied set
+// (BatchItem::set[0], see batch_refresh: the windows of a batch need not be at the same ping-pong parity, and with itCheck >= 0 each stops on its own).
 template <int NSG>
 __global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch(const BatchItem *__restrict__ items, const BatchBlock *__restrict__ blocks, const int32_t *__restrict__ wgStart, int cur,
                                                                    ldso_settings_t S, int stepMode, float calibPrior, int itCheck) {
@@ -1302,6 +1302,23 @@ __global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch(const BatchIt
         GnInit gi; gi.enable = 1; gi.hasPrior = it.hasPrior; gi.calibPrior = calibPrior; gi.itCheck = itCheck;
         linearize_body<NSG, false, false, false, true>(it.B, it.D, it.set[cur], it.set[cur ^ 1], S, stepMode, gi, nullptr, bb.host_chunk >> 8, it.D.nChunks, bb.p0, bb.np, bb.host_chunk & 0xFF);
         __syncthreads();                                            // the next block re-uses the operand / reduction LDS
+    }
+}
+
+// linearizeAll(true) at the end of a batched optimize() (ldso_ba_batch_optimize), one slot group per point: every window reads ITS applied set, which the parity
+// of its own last executed iteration names (scalars[LD_SC_STOP], see k_solve_batch in ba_solve.hip), and writes the other one.
+__global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch_fix(const BatchItem *__restrict__ items, const BatchBlock *__restrict__ blocks, const int32_t *__restrict__ wgStart,
+                                                                       ldso_settings_t S, float calibPrior) {
+    int b0 = (int) blockIdx.x, b1 = b0 + 1;
+    if (wgStart != nullptr) { b0 = wgStart[blockIdx.x]; b1 = wgStart[blockIdx.x + 1]; }
+#pragma clang loop unroll(disable)
+    for (int b = b0; b < b1; b++) {
+        const BatchBlock bb = blocks[b];
+        const BatchItem &it = items[bb.win];
+        const int applied = __builtin_amdgcn_readfirstlane((int) it.B.scalars[LD_SC_STOP]) & 1;          // wave-uniform: the body fetches the sets' pointer groups with scalar loads
+        GnInit gi; gi.enable = 1; gi.hasPrior = it.hasPrior; gi.calibPrior = calibPrior; gi.itCheck = -1;
+        linearize_body<1, false, true, false, true>(it.B, it.D, it.set[applied], it.set[applied ^ 1], S, 0, gi, nullptr, bb.host_chunk >> 8, it.D.nChunks, bb.p0, bb.np, bb.host_chunk & 0xFF);
+        __syncthreads();
     }
 }
 
@@ -1403,5 +1420,15 @@ hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock 
         if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_batch<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         hipLaunchKernelGGL(k_linearize_batch<2>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
     }
+    return hipGetLastError();
+}
+
+hipError_t ba_launch_linearize_batch_fix(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, const ldso_settings_t &S, float calibPrior, hipStream_t st) {
+    if (totalChunks == 0) return hipSuccess;
+    const size_t lds = ba_linearize_lds_bytes(8, false, true);
+    const int grid = d_wgStart != nullptr ? nWG : totalChunks;
+    if (grid <= 0) return hipSuccess;
+    if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_batch_fix, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    hipLaunchKernelGGL(k_linearize_batch_fix, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, S, calibPrior);
     return hipGetLastError();
 }

@@ -984,7 +984,9 @@ static __device__ __forceinline__ void frames_step(const BaPtrs &B, const ldso_s
 }
 
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void k_solve(BaPtrs B, BaDims D, ResSet S, ldso_settings_t St, SolveArgs A) {
+// The control kernel's body, shared by k_solve (one window: everything in the kernel arguments) and k_solve_batch (the tail of a batched optimize(): the
+// descriptors live in device memory).  nRoles == 2: the statistics (role 1) run next to the control part (role 0), one workgroup each.
+static __device__ __forceinline__ void solve_body(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, const int nRoles, const int role) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x, F = D.F, n = D.n;
     const int NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
@@ -995,7 +997,7 @@ __global__ __launch_bounds__(NT) void k_solve(BaPtrs B, BaDims D, ResSet S, ldso
     // two workgroups (ba_launch_solve): the statistics of the last linearizeAll (POST / THRESH / LOG) run next to the control part;
     // they touch disjoint data (frameEnergyTH is only written by the statistics and only read by k_linearize)
     unsigned fl = A.flags;
-    if (gridDim.x == 2) fl &= (blockIdx.x == 1) ? (SK_POST | SK_THRESH | SK_LOG) : ~(unsigned) (SK_POST | SK_THRESH | SK_LOG);
+    if (nRoles == 2) fl &= (role == 1) ? (SK_POST | SK_THRESH | SK_LOG) : ~(unsigned) (SK_POST | SK_THRESH | SK_LOG);
 
     if (fl & SK_COLLECT) {
         // FullSystem::optimize preamble: resetOOB on every non-linearised residual (FullSystem.cc:744-748)
@@ -1082,6 +1084,9 @@ __global__ __launch_bounds__(NT) void k_solve(BaPtrs B, BaDims D, ResSet S, ldso
         __syncthreads();
     }
     if (fl & SK_PRECALC) set_precalc(B, D, B.frames, B.calib, B.adHostF, B.adTargetF);
+}
+__global__ __launch_bounds__(NT) void k_solve(BaPtrs B, BaDims D, ResSet S, ldso_settings_t St, SolveArgs A) {
+    solve_body(B, D, S, St, A, (int) gridDim.x, (int) blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1348,28 +1353,61 @@ __global__ __launch_bounds__(NT) void k_reduce_solve(BaPtrs B, BaDims D, ResSet 
                                      // k_linearize_batch of 187 VGPRs, B = 32 different windows: 3 -> 122.4 k, 4 -> 122.4 k, 5 -> 96.8 k, 6 -> 87.5 k window-iterations/s,
                                      // unconstrained 107.8 k; with round 3's 205-VGPR kernel 5 had been the best: 104.8 k)
 #define LD_REDB_DENSE_PER_CU 6       // launches with at least this many workgroups per CU take the dense variant
-static __device__ __forceinline__ void reduce_batch_body(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il) {
+static __device__ __forceinline__ void reduce_batch_body(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il, int itCheck) {
     int w = 0;
     for (int i = 1; i < nWin; i++) if ((int) blockIdx.x >= items[i].redBlock0) w = i;
     const BatchItem &it = items[w];
-    reduce_body(it.B, it.D, it.set[cur], it.cs, 0, it.GSP, 1, it.hasPrior, calibPrior, l1, il, -1, (int) blockIdx.x - it.redBlock0);
+    reduce_body(it.B, it.D, it.set[cur], it.cs, 0, it.GSP, 1, it.hasPrior, calibPrior, l1, il, itCheck, (int) blockIdx.x - it.redBlock0);
 }
-__global__ __launch_bounds__(NT) void k_reduce_batch(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il) {
-    reduce_batch_body(items, nWin, cur, calibPrior, l1, il);
+__global__ __launch_bounds__(NT) void k_reduce_batch(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il, int itCheck) {
+    reduce_batch_body(items, nWin, cur, calibPrior, l1, il, itCheck);
 }
-__global__ __launch_bounds__(NT, LD_REDB_BLOCKS) void k_reduce_batch_dense(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il) {
-    reduce_batch_body(items, nWin, cur, calibPrior, l1, il);
+__global__ __launch_bounds__(NT, LD_REDB_BLOCKS) void k_reduce_batch_dense(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il, int itCheck) {
+    reduce_batch_body(items, nWin, cur, calibPrior, l1, il, itCheck);
 }
 
-__global__ __launch_bounds__(NT) void k_gn_solve_batch(const BatchItem *__restrict__ items, int cur, ldso_settings_t St, int iteration, double lambda) {
+// logIdx / itCheck >= 0: an iteration of ldso_ba_batch_optimize (energy log entry of the previous linearisation; un-forced: the window's own LD_SC_STOP decides
+// whether its two workgroups still have work)
+__global__ __launch_bounds__(NT) void k_gn_solve_batch(const BatchItem *__restrict__ items, int cur, ldso_settings_t St, int iteration, double lambda, int logIdx, int itCheck) {
     const BatchItem &it = items[blockIdx.x >> 1];
     SolveArgs A;
-    A.flags = 0; A.iteration = iteration; A.lambda = lambda; A.hasL = 0; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = -1;
-    A.reduceOut = nullptr; A.reduceIn = nullptr; A.itCheck = -1; A.waitCtr = nullptr; A.waitTarget = 0; A.hostStop = nullptr; A.lastIt = -1;
+    A.flags = 0; A.iteration = iteration; A.lambda = lambda; A.hasL = 0; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = logIdx;
+    A.reduceOut = nullptr; A.reduceIn = nullptr; A.itCheck = itCheck; A.waitCtr = nullptr; A.waitTarget = 0; A.hostStop = nullptr; A.lastIt = -1;
     gn_solve_body<false>(it.B, it.D, it.set[cur], St, A, (int) (blockIdx.x & 1));
 }
 
-hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st) {
+// ---- ldso_ba_batch_optimize: what surrounds the iterations --------------------------------------------------------------------------------------------
+// A window of a batched optimize() stops on its own: scalars[LD_SC_STOP] starts at (its iteration cap - 1) and canbreak only lowers it (gn_tail), so it always
+// names the LAST iteration the window executes - the per-window cap and the early exit are the same test (LD_ITER_SKIPPED), and the tail derives from it,
+// on the device, how many iterations ran and which of the window's two residual sets is the applied one.  set[0] of a BatchItem is the set that was applied
+// when the call began (batch_refresh): the preamble linearises set[0] -> set[1], iteration i reads set[1 ^ (i & 1)].
+static __device__ __forceinline__ int batch_cap(int F, int mnumOptIts, int forceAll) {
+    int cap = mnumOptIts;
+    if (!forceAll) { if (F < 3) cap = 20; if (F < 4) cap = 15; }          // FullSystem.cc:735-736, as ldso_ba_optimize restates it
+    return cap;
+}
+__global__ __launch_bounds__(64) void k_batch_begin(const BatchItem *__restrict__ items, int mnumOptIts, int forceAll) {
+    const BatchItem &it = items[blockIdx.x];
+    it.B.energyLog[threadIdx.x] = 0.0;
+    if (threadIdx.x == 0) it.B.scalars[LD_SC_STOP] = (double) (batch_cap(it.D.F, mnumOptIts, forceAll) - 1);
+}
+// The tail of optimize() for every window of a (half-)batch.  phase 0 (two workgroups per window): flags on the applied set, log entry `done`; phase 1 (one
+// workgroup per window): flags on the set the fixing linearisation wrote, log entry `done + 1`, then the window's 16 scalars into the batch's read-back block.
+__global__ __launch_bounds__(NT) void k_solve_batch(const BatchItem *__restrict__ items, ldso_settings_t St, unsigned flags, int phase, int nRoles, double *__restrict__ scalarsOut) {
+    const int w = (int) blockIdx.x / nRoles, role = (int) blockIdx.x % nRoles;
+    const BatchItem &it = items[w];
+    const int stop = (int) it.B.scalars[LD_SC_STOP], applied = stop & 1;          // = 1 ^ (done & 1), done = stop + 1
+    SolveArgs A;
+    A.flags = flags; A.iteration = 0; A.lambda = 0; A.hasL = 0; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = stop + 1 + phase;
+    A.reduceOut = nullptr; A.reduceIn = nullptr; A.itCheck = -1; A.waitCtr = nullptr; A.waitTarget = 0; A.hostStop = nullptr; A.lastIt = -1;
+    solve_body(it.B, it.D, it.set[applied ^ phase], St, A, nRoles, role);
+    if (scalarsOut != nullptr) {
+        __syncthreads();
+        if (threadIdx.x < 16) scalarsOut[(size_t) it.outSlot * 16 + threadIdx.x] = it.B.scalars[threadIdx.x];
+    }
+}
+
+hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st, int itCheck) {
     const size_t lds = (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB) * sizeof(float);
     static int numCU[64] = {0};
     int dev = 0;
@@ -1379,19 +1417,36 @@ hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalB
         (void) hipFuncSetAttribute((const void *) k_reduce_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         (void) hipFuncSetAttribute((const void *) k_reduce_batch_dense, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
     }
-    if (totalBlocks >= LD_REDB_DENSE_PER_CU * numCU[dev]) hipLaunchKernelGGL(k_reduce_batch_dense, dim3(totalBlocks), dim3(NT), lds, st, d_items, nWin, cur, calibPrior, l1, il);
-    else hipLaunchKernelGGL(k_reduce_batch, dim3(totalBlocks), dim3(NT), lds, st, d_items, nWin, cur, calibPrior, l1, il);
+    if (totalBlocks >= LD_REDB_DENSE_PER_CU * numCU[dev]) hipLaunchKernelGGL(k_reduce_batch_dense, dim3(totalBlocks), dim3(NT), lds, st, d_items, nWin, cur, calibPrior, l1, il, itCheck);
+    else hipLaunchKernelGGL(k_reduce_batch, dim3(totalBlocks), dim3(NT), lds, st, d_items, nWin, cur, calibPrior, l1, il, itCheck);
     return hipGetLastError();
 }
 
 // Dmax: the window of the batch with the most frames (LDS of the control step)
-hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, int cur, const ldso_settings_t &St, int iteration, double lambda, hipStream_t st) {
+hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, int cur, const ldso_settings_t &St, int iteration, double lambda, hipStream_t st, int logIdx, int itCheck) {
     size_t mirror = (size_t) Dmax.F * sizeof(DevFrame) + sizeof(DevCalib) + (Dmax.F <= 8 ? (size_t) Dmax.F * Dmax.F * 2 * LD_AD_LDS_PITCH * sizeof(float) : 0), stats = 64 * sizeof(double) + (256 + 8) * sizeof(int) + TH_CAP * sizeof(float);
     const int n = Dmax.n, NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
     size_t lds0 = solve_core_lds_doubles(NBsel, n) * sizeof(double) + 64 * sizeof(double) + mirror + 64;
     size_t lds = lds0 > stats + 64 ? lds0 : stats + 64;
     if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_gn_solve_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    hipLaunchKernelGGL(k_gn_solve_batch, dim3(2 * nWin), dim3(NT), lds, st, d_items, cur, St, iteration, lambda);
+    hipLaunchKernelGGL(k_gn_solve_batch, dim3(2 * nWin), dim3(NT), lds, st, d_items, cur, St, iteration, lambda, logIdx, itCheck);
+    return hipGetLastError();
+}
+
+hipError_t ba_launch_batch_begin(const BatchItem *d_items, int nWin, int mnumOptIts, int forceAll, hipStream_t st) {
+    hipLaunchKernelGGL(k_batch_begin, dim3(nWin), dim3(64), 0, st, d_items, mnumOptIts, forceAll);
+    return hipGetLastError();
+}
+
+// Dmax as above; the LDS is that of ba_launch_solve (further down) for the largest window
+hipError_t ba_launch_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, const ldso_settings_t &St, unsigned flags, int phase, double *d_scalarsOut, hipStream_t st) {
+    const int n = Dmax.n, NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
+    const size_t stats = (256 + 8) * sizeof(int) + TH_CAP * sizeof(float), core = solve_core_lds_doubles(NBsel, n) * sizeof(double);
+    const size_t lds = (core > stats ? core : stats) + (7 * (size_t) n + 64) * sizeof(double) + 64;
+    if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_solve_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    const unsigned fstats = SK_POST | SK_THRESH | SK_LOG, fctl = SK_REANCHOR | SK_ADJ | SK_NONULLSPACE | SK_PRECALC;
+    const int nRoles = ((flags & fstats) && (flags & fctl) && !(flags & ~(fstats | fctl))) ? 2 : 1;          // as ba_launch_solve splits one window's tail
+    hipLaunchKernelGGL(k_solve_batch, dim3(nRoles * nWin), dim3(NT), lds, st, d_items, St, flags, phase, nRoles, d_scalarsOut);
     return hipGetLastError();
 }
 
