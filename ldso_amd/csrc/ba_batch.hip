@@ -18,9 +18,8 @@ static int batch_refresh(ldso_ba_batch *Bt) {
             // the per-window parity: set[0] = the window's applied set, so the launches name the sets relative to it and windows at different parities share them
             it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[H->cur]; it.set[1] = H->sets[H->cur ^ 1]; it.cs = H->chunkStarts;
             it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.linBlock0 = lin; it.redBlock0 = red; it.outSlot = (int32_t) i;
-            const int nT = H->GSP / 16;
             lin += H->D.nChunks;
-            red += H->D.F * H->D.F + Bt->ks * nT * (nT + 1) / 2 + 1;
+            red += reduce_grid(H->D.F, 0, Bt->ks, H->GSP).total;
         }
         if (pass == 0) { Bt->totalChunks = lin; Bt->totalReduce = red; }
         else if (Bt->n0 == (int) n) { Bt->halfChunks[0] = lin; Bt->halfReduce[0] = red; Bt->halfChunks[1] = 0; Bt->halfReduce[1] = 0; }
@@ -35,7 +34,6 @@ static int batch_refresh(ldso_ba_batch *Bt) {
         CHK(hipStreamSynchronize(H0->stream));
         if (Bt->aux) CHK(hipStreamSynchronize(Bt->aux));
         if (Bt->d_blocks) hipFree(Bt->d_blocks);
-    if (Bt->d_wg) hipFree(Bt->d_wg);
         Bt->d_blocks = nullptr; Bt->blocksCap = 0;
         void *q = nullptr;
         CHK(hipMalloc(&q, Bt->blocks.size() * sizeof(BatchBlock)));
@@ -317,9 +315,7 @@ int ldso_ba_batch_optimize(ldso_ba_batch_t *Bt, int mnumOptIts, int force_all_it
     for (ldso_ba *H : Bt->h) {
         REQ(H->D.F >= 2, "ldso_ba_batch_optimize: every window of the batch needs at least 2 key frames (F >= 2)");
         REQ(!H->pendingApply, "ldso_ba_batch_optimize: a window has a pending linearisation (ldso_ba_apply_res first)");
-        int cap = mnumOptIts;
-        if (!force_all_iterations) { if (H->D.F < 3) cap = 20; if (H->D.F < 4) cap = 15; }          // the rule of ldso_ba_optimize (k_batch_begin applies the same one)
-        caps = std::max(caps, cap);
+        caps = std::max(caps, optimize_iteration_cap(H->D.F, mnumOptIts, force_all_iterations));          // k_batch_begin gives every window its own
     }
     REQ(caps + 2 < 64, "ldso_ba_batch_optimize: too many iterations");
     CHK(hipSetDevice(H0->device));

@@ -209,6 +209,21 @@ struct GnInit {
 #define LD_SYS_MATS 4       // HA, HL, Hsc, HFinal
 
 #ifdef __HIPCC__
+// The workgroups of a reduction in atomic mode (GN fast path), numbered pairs | tiles | extras: one per (host, target) pair and pass (A, L), `ks` per 16 x 16 tile of the upper
+// triangle of the Schur complement, one for the prior / lambda terms.  Read by everything that sizes, splits or waits for such a launch (k_reduce_solve waits for `total` signals).
+struct ReduceGrid { int nPair, nTile, nExtra, total; };
+__host__ __device__ inline int reduce_pairs(int F, int hasL) { return F * F * (hasL ? 2 : 1); }
+__host__ __device__ inline int reduce_tiles(int ks, int GSP) { const int nT = GSP / 16; return ks * nT * (nT + 1) / 2; }
+__host__ __device__ inline ReduceGrid reduce_grid(int F, int hasL, int ks, int GSP) {
+    const int nTile = reduce_tiles(ks, GSP), nPair = reduce_pairs(F, hasL);
+    return ReduceGrid{nPair, nTile, 1, nPair + nTile + 1};
+}
+#define LD_FUSED_CTL 2      // k_reduce_solve: workgroups 0 and 1 are the control step and the statistics, the reduce workgroups follow them
+// iteration cap of optimize() (FullSystem.cc:735-736; both tests apply, as there: a window under 3 key frames ends at 15)
+__host__ __device__ inline int optimize_iteration_cap(int F, int mnumOptIts, int forceAll) {
+    if (!forceAll) { if (F < 3) mnumOptIts = 20; if (F < 4) mnumOptIts = 15; }
+    return mnumOptIts;
+}
 // The kernels of a GN iteration are chains of dependent memory levels (a 5 MB window on a chip that moves that in 0.7 us), and the first link of
 // every chain is the kernel-argument block: 0.6 - 1.1 KB that the compiler fetches lazily, a few words at a time, each fetch a fresh scalar-cache
 // line nobody on this CU has touched yet.  ld_touch_kernarg<LINES>() requests one dword of each of the first LINES 64-byte lines back to back and

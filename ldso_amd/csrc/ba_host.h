@@ -18,6 +18,14 @@ void ldso_set_error(const std::string &s);          // ba_api.hip (thread-local,
 #define REQ(cond, msg) do { if (!(cond)) { ldso_set_error(msg); return LDSO_E_INVALID; } } while (0)
 #define RUN(x) do { int r_ = (x); if (r_ != LDSO_OK) return r_; } while (0)
 
+// A launch with dynamic LDS: above 48 KB the kernel's limit is raised first; the status of that call is no reason to skip the launch, whose own error the caller sees
+template <class Kernel, class... Args>
+hipError_t launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t ldsBytes, hipStream_t st, const Args &... args) {
+    if (ldsBytes > 48 * 1024) (void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes);
+    hipLaunchKernelGGL(kernel, grid, block, ldsBytes, st, args...);
+    return hipGetLastError();
+}
+
 // the launchers, defined beside their kernels (ba_linearize / ba_reduce / ba_solve / ba_activate .hip)
 hipError_t ba_launch_linearize(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, bool hasL, bool fix, int stepMode, const GnInit &gi, hipStream_t st);
 hipError_t ba_launch_reduce(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, bool hasL, int GSP, int atomicMode, bool hasPrior, float calibPrior, double l1, double il, int itCheck, hipStream_t st);

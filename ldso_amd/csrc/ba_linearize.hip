@@ -1359,11 +1359,7 @@ size_t ba_linearize_lds_bytes(int FS, bool hasL, bool stash = false) {
 template <int NSG, bool HAS_L, bool FIX, bool MARG = false>
 static hipError_t launch_one(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, int stepMode, const GnInit &gi, hipStream_t st,
                             const int32_t *margFlags = nullptr) {
-    size_t lds = ba_linearize_lds_bytes(D.FS, HAS_L);
-    auto kfn = k_linearize<NSG, HAS_L, FIX, MARG>;
-    if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    hipLaunchKernelGGL(kfn, dim3(D.nChunks), dim3(64 * LD_WAVES), lds, st, B, D, cur, nxt, S, stepMode, gi, margFlags);
-    return hipGetLastError();
+    return launch_lds(k_linearize<NSG, HAS_L, FIX, MARG>, dim3(D.nChunks), dim3(64 * LD_WAVES), ba_linearize_lds_bytes(D.FS, HAS_L), st, B, D, cur, nxt, S, stepMode, gi, margFlags);
 }
 
 hipError_t ba_launch_linearize(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S,
@@ -1384,18 +1380,11 @@ hipError_t ba_launch_linearize_one(const BaPtrs &B, const BaDims &D, const ResSe
     const size_t lds = ba_linearize_lds_bytes(D.FS, false);
     OneArgs a;
     a.B = B; a.D = D; a.cur = cur; a.nxt = nxt; a.S = S; a.stepMode = stepMode; a.gi = gi; a.hd = hd;
-    if (D.nsg == 1) {
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_one<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-        hipLaunchKernelGGL(k_linearize_one<1>, dim3(D.nChunks), dim3(64 * LD_WAVES), lds, st, a);
-    } else if (D.F <= 12) {
-        // 9..12 key frames: the second slot group uses 4 of its 8 slots - two points share its pass (pair mode, round 6)
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_one<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-        hipLaunchKernelGGL((k_linearize_one<2, true>), dim3(D.nChunks), dim3(64 * LD_WAVES), lds, st, a);
-    } else {
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_one<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-        hipLaunchKernelGGL(k_linearize_one<2>, dim3(D.nChunks), dim3(64 * LD_WAVES), lds, st, a);
-    }
-    return hipGetLastError();
+    const dim3 grid(D.nChunks), block(64 * LD_WAVES);
+    if (D.nsg == 1) return launch_lds(k_linearize_one<1>, grid, block, lds, st, a);
+    // 9..12 key frames: the second slot group uses 4 of its 8 slots - two points share its pass (pair mode, round 6)
+    if (D.F <= 12) return launch_lds(k_linearize_one<2, true>, grid, block, lds, st, a);
+    return launch_lds(k_linearize_one<2>, grid, block, lds, st, a);
 }
 
 // marginalizePointsF accumulate for the flagged points (see the MARG note at k_linearize); `nxt` is scratch
@@ -1413,14 +1402,8 @@ hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock 
     const size_t lds = ba_linearize_lds_bytes(FS, false, true);
     const int grid = d_wgStart != nullptr ? nWG : totalChunks;
     if (grid <= 0) return hipSuccess;
-    if (FS == 8) {
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_batch<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-        hipLaunchKernelGGL(k_linearize_batch<1>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
-    } else {
-        if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_batch<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-        hipLaunchKernelGGL(k_linearize_batch<2>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
-    }
-    return hipGetLastError();
+    if (FS == 8) return launch_lds(k_linearize_batch<1>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
+    return launch_lds(k_linearize_batch<2>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
 }
 
 hipError_t ba_launch_linearize_batch_fix(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, const ldso_settings_t &S, float calibPrior, hipStream_t st) {
@@ -1428,7 +1411,5 @@ hipError_t ba_launch_linearize_batch_fix(const BatchItem *d_items, const BatchBl
     const size_t lds = ba_linearize_lds_bytes(8, false, true);
     const int grid = d_wgStart != nullptr ? nWG : totalChunks;
     if (grid <= 0) return hipSuccess;
-    if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_linearize_batch_fix, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    hipLaunchKernelGGL(k_linearize_batch_fix, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, S, calibPrior);
-    return hipGetLastError();
+    return launch_lds(k_linearize_batch_fix, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, S, calibPrior);
 }

@@ -78,10 +78,9 @@ int read_scalars(ldso_ba *H, double *sc) {
     CHK(hipStreamSynchronize(H->stream));
     return LDSO_OK;
 }
-SolveArgs solve_args(const ldso_ba *H, unsigned flags) {          // every optional field neutral: the callers set what differs
+SolveArgs solve_args(const ldso_ba *H, unsigned flags) {          // what every launch of this handle passes; the rest stays neutral (ba_solve.h) until a caller sets it
     SolveArgs A;
-    A.flags = flags; A.iteration = 0; A.lambda = 0; A.hasL = H->hasL ? 1 : 0; A.hasPrior = H->hasPrior ? 1 : 0; A.GSP = H->GSP; A.logIdx = -1;
-    A.reduceOut = nullptr; A.reduceIn = nullptr; A.itCheck = -1; A.waitCtr = nullptr; A.waitTarget = 0; A.hostStop = nullptr; A.lastIt = -1;
+    A.flags = flags; A.hasL = H->hasL ? 1 : 0; A.hasPrior = H->hasPrior ? 1 : 0; A.GSP = H->GSP;
     return A;
 }
 // the damping of a reduction from the settings and the nominal lambda; `il` is rounded through float (the results are bit-reproducible only with this expression)
@@ -200,9 +199,7 @@ static int enqueue_iteration(ldso_ba *H, int iteration, double lambda, int logId
     RUN(lend_acc(H, H->ownAcc));      // the accumulator was lent to an all-reduce buffer: take it back (and re-initialise)
     SolveArgs A = solve_args(H, 0);
     A.iteration = iteration; A.lambda = lambda; A.logIdx = logIdx; A.itCheck = itCheck; A.hostStop = (itCheck >= 0) ? H->d_stop : nullptr; A.lastIt = lastIt;
-    const int nT = H->GSP / 16;
-    const int nReduce = H->D.F * H->D.F * (H->hasL ? 2 : 1) + H->D.ks * nT * (nT + 1) / 2 + 1;      // grid of ba_launch_reduce in atomic mode
-    if (nReduce + 2 <= H->numCU && !H->noFusedLaunch) {
+    if (reduce_grid(H->D.F, H->hasL, H->D.ks, H->GSP).total + LD_FUSED_CTL <= H->numCU && !H->noFusedLaunch) {
         // k_reduce (fp64 atomics straight into B.acc, no k_gather on this path) and the control step in ONE launch: the control
         // workgroup waits on a device counter for the reduce workgroups (k_reduce_solve, ba_solve.hip).  Only while every workgroup
         // of the launch gets its own CU (F <= 8; from F = 9 the Schur part alone has 180 workgroups): the fused kernel's LDS footprint allows one workgroup per CU.
@@ -303,8 +300,7 @@ int ldso_ba_calc_lm_energies(ldso_ba_t *H, double *energy_M, double *energy_L) {
 // E_P + E_L + E_M; a rejected step restores the backup (loadSateBackup), re-linearises and multiplies lambda by 100.  One host
 // round trip per stage - this is not the default schedule of the reference (Setting.cc:73) and not the timed path.
 static int optimize_lm(ldso_ba *H, int mnumOptIts, int force_all, float *rmse_out, int *iters_out) {
-    const int F = H->D.F;
-    if (!force_all) { if (F < 3) mnumOptIts = 20; if (F < 4) mnumOptIts = 15; }
+    mnumOptIts = optimize_iteration_cap(H->D.F, mnumOptIts, force_all);
     REQ(mnumOptIts + 2 < 64, "too many iterations");
     std::vector<double> elog;
     RUN(ldso_ba_collect_active(H));
@@ -361,7 +357,7 @@ int ldso_ba_optimize(ldso_ba_t *H, int mnumOptIts, int force_all, float *rmse_ou
     if (!H->settings.forceAcceptStep) return optimize_lm(H, mnumOptIts, force_all, rmse_out, iters_out);
     const int F = H->D.F;
     if (F < 2) { if (rmse_out) *rmse_out = 0; return LDSO_OK; }
-    if (!force_all) { if (F < 3) mnumOptIts = 20; if (F < 4) mnumOptIts = 15; }
+    mnumOptIts = optimize_iteration_cap(F, mnumOptIts, force_all);
     REQ(mnumOptIts + 2 < 64, "too many iterations");
     CHK(hipMemsetAsync(H->B.energyLog, 0, 64 * 8, H->stream));
     H->pendingApply = false;

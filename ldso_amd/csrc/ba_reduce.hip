@@ -155,12 +155,9 @@ hipError_t ba_launch_gather(const BaPtrs &B, const BaDims &D, const ResSet &S, b
 
 hipError_t ba_launch_reduce(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, bool hasL, int GSP, int atomicMode, bool hasPrior,
                             float calibPrior, double l1, double il, int itCheck, hipStream_t st) {
-    const int nT = GSP / 16;
-    int nb = D.F * D.F * (hasL ? 2 : 1) + (atomicMode ? D.ks * nT * (nT + 1) / 2 + 1 : LD_SC_SPLITS);
-    size_t lds = atomicMode ? (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB) * sizeof(float) : (size_t) (SC_SLAB * GSP) * sizeof(float);
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void *) k_reduce, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    hipLaunchKernelGGL(k_reduce, dim3(nb), dim3(256), lds, st, B, D, S, chunkStart, hasL ? 1 : 0, GSP, atomicMode, hasPrior ? 1 : 0, calibPrior, l1, il, itCheck);
-    return hipGetLastError();
+    const int nb = atomicMode ? reduce_grid(D.F, hasL, D.ks, GSP).total : reduce_pairs(D.F, hasL) + LD_SC_SPLITS;
+    const size_t lds = atomicMode ? reduce_atomic_lds_bytes() : (size_t) (SC_SLAB * GSP) * sizeof(float);
+    return launch_lds(k_reduce, dim3(nb), dim3(256), lds, st, B, D, S, chunkStart, hasL ? 1 : 0, GSP, atomicMode, hasPrior ? 1 : 0, calibPrior, l1, il, itCheck);
 }
 
 // EnergyFunctional::marginalizePointsF tail (EnergyFunctional.cc:203-216): HM += margWeightFac (M - Msc), bM += margWeightFac (Mb - Mbsc),

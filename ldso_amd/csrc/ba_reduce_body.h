@@ -13,6 +13,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define SC_MAXT 12      // tiles per wave: GSP=144 (FS=16) -> 45 upper tiles / 4 waves
 
 __host__ __device__ constexpr int tri13r(int r, int c) { return r * 13 - (r * (r - 1)) / 2 + (c - r); }
+// dynamic LDS of a workgroup in atomic mode: the slab of a tile workgroup, two 16-column blocks of SCT_SLAB G rows and their weights (reduce_body: sAc, sBc, sWc)
+__host__ __device__ constexpr size_t reduce_atomic_lds_bytes() { return (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB) * sizeof(float); }
 
 // chunkStart[h]..chunkStart[h+1]: chunks of host h (chunks are host-major)
 // atomicMode (GN fast path): instead of pairC / scPart the results are added (fp64 atomics) straight into the lower triangle of
@@ -27,7 +29,7 @@ static __device__ __forceinline__ void reduce_body(const BaPtrs &B, const BaDims
                                    int hasPrior, float calibPrior, double l1, double il, int itCheck, const int bid) {
     if (LD_ITER_SKIPPED(B, itCheck)) return;
     const int F = D.F, FS = D.FS;
-    const int nPairBlocks = F * F * (hasL ? 2 : 1);
+    const int nPairBlocks = reduce_pairs(F, hasL);          // the ranges below: pairs | tiles | extras (atomic mode; otherwise pairs | LD_SC_SPLITS K-ranges)
     const int tid = threadIdx.x;
     __shared__ double sA[13 * 13];
     __shared__ double sT[2][64];
@@ -130,7 +132,7 @@ static __device__ __forceinline__ void reduce_body(const BaPtrs &B, const BaDims
 
     const int nSplitBase = nPairBlocks;
     const int KS = D.ks;          // K-splits per Schur tile: a field of the window's dimensions since round 6 (a batch runs its windows with fewer)
-    if (atomicMode && bid < nSplitBase + KS * (GSP / 16) * (GSP / 16 + 1) / 2) {
+    if (atomicMode && bid < nSplitBase + reduce_tiles(KS, GSP)) {
         // ------------------------------- Part B, atomic mode: one block per (16x16 tile, K-split) ---------------------
         // The block stages the two 16-column blocks of its G rows (and the weights HdiF) in LDS with 16-byte loads, its four
         // waves interleave the k-steps of v_mfma_f32_16x16x4_f32, the four partial tiles are summed through LDS and each

@@ -10,19 +10,22 @@ enum {
 };
 enum { PS_RESUB = 1, PS_BACKUP = 2, PS_STEP = 4, PS_LOAD = 8 };
 
-struct SolveArgs {
-    unsigned flags;
-    int iteration;
-    double lambda;
-    int hasL;
-    int hasPrior;               // HM/bM non-zero
-    int GSP;
-    int logIdx;
-    double *reduceOut;          // multi-GPU: rank-local sums are exported here (SK_GATHER)
-    const double *reduceIn;     // multi-GPU: all-reduced sums are read from here (SK_FROMREDUCED)
-    int itCheck;                // k_gn_solve: >= 0 = un-forced optimize(): iteration index for the device-side `canbreak` early exit
-    int *waitCtr;               // k_reduce_solve: counter the reduce workgroups of the same launch increment when their sums are in B.acc
-    int waitTarget;             //                 ... and its value when all of them are done (0 / nullptr: no wait)
-    int *hostStop;              // un-forced optimize(): host-mapped word that receives the index of the iteration that ended the loop (canbreak, or the
-    int lastIt;                 //                       last enqueued iteration lastIt) as soon as the device knows it - no stream synchronisation
+// the tail of optimize(): flags of both groups and of nothing else = two workgroups (roles), the statistics (role 1) next to the independent control part (role 0)
+enum { SK_STATS = SK_POST | SK_THRESH | SK_LOG, SK_CTL = SK_REANCHOR | SK_ADJ | SK_NONULLSPACE | SK_PRECALC };
+static inline int solve_roles(unsigned flags) { return ((flags & SK_STATS) && (flags & SK_CTL) && !(flags & ~(unsigned) (SK_STATS | SK_CTL))) ? 2 : 1; }
+struct SolveArgs {          // every field starts neutral: the callers set what differs
+    unsigned flags = 0;
+    int iteration = 0;
+    double lambda = 0;
+    int hasL = 0;
+    int hasPrior = 0;           // HM/bM non-zero
+    int GSP = 0;
+    int logIdx = -1;
+    double *reduceOut = nullptr;          // multi-GPU: rank-local sums are exported here (SK_GATHER)
+    const double *reduceIn = nullptr;     // multi-GPU: all-reduced sums are read from here (SK_FROMREDUCED)
+    int itCheck = -1;           // k_gn_solve: >= 0 = un-forced optimize(): iteration index for the device-side `canbreak` early exit
+    int *waitCtr = nullptr;     // k_reduce_solve: counter the reduce workgroups of the same launch increment when their sums are in B.acc
+    int waitTarget = 0;         //                 ... and its value when all of them are done (0 / nullptr: no wait)
+    int *hostStop = nullptr;    // un-forced optimize(): host-mapped word that receives the index of the iteration that ended the loop (canbreak, or the
+    int lastIt = -1;            //                       last enqueued iteration lastIt) as soon as the device knows it - no stream synchronisation
 };

@@ -27,6 +27,7 @@
 #include "ba_reduce_body.h"
 #define NT 256
 #define TH_CAP 8192      // candidate energies staged in LDS up to this many points
+#define LD_THRESH_DOUBLES ((256 + 8 + TH_CAP) / 2)      // LDS of the threshold pass (post_thresh), in doubles
 
 static __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -97,7 +98,9 @@ static __device__ __forceinline__ void res_counts(const BaPtrs &B, const BaDims 
 // written compactly by the linearize kernel (S.candE[p], -1 = no candidate).
 // extE (multi-GPU): all-reduced array of P doubles holding value+1 for candidates and 0 otherwise.
 static __device__ __forceinline__ void post_thresh(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St,
-                                   const double *extE, float *sVal /*LDS, TH_CAP floats*/, int *sHist /*256 ints*/, int *sI /*8 ints*/) {
+                                   const double *extE, int *sTh /*LDS, LD_THRESH_DOUBLES*/) {
+    int *sHist = sTh, *sI = sHist + 256;          // histogram [256] | counters [8] | staged candidates [TH_CAP] float
+    float *sVal = (float *) (sI + 8);
     const int tid = threadIdx.x;
     const int F = D.F;
     const int tN = F - 1;
@@ -473,13 +476,6 @@ static __device__ __forceinline__ double fast_rcp(double d) {
     return __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
 }
 
-static __device__ __forceinline__ double readlane_f64(double v, int lane) {
-    unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    unsigned lo = (unsigned) __builtin_amdgcn_readlane((int) (u & 0xFFFFFFFFu), lane);
-    unsigned hi = (unsigned) __builtin_amdgcn_readlane((int) (u >> 32), lane);
-    return __builtin_bit_cast(double, ((unsigned long long) hi << 32) | lo);
-}
-
 // reciprocal square root: hardware estimate (v_rsq_f64) + one Newton step (relative error <= 4.2e-15; only used as a scaling)
 static __device__ __forceinline__ double fast_rsqrt(double d) {
     double r = __builtin_amdgcn_rsq(d);
@@ -493,13 +489,6 @@ static __device__ __forceinline__ void st2(double *p, double a, double b) { *(do
 //   NB == 4: zero-initialised square [c][i] with row pitch M+2, so that lane c reads its whole column with 16-byte loads;
 //   NB  > 4: packed columns (column c holds rows c..M-1).
 #define LIX(i, c) ((NB == 4) ? ((c) * (M + 2) + (i)) : ((c) * M - (((c) * ((c) -1)) >> 1) + ((i) - (c))))
-
-static __host__ __device__ inline size_t solve_core_lds_doubles(int NB, int n) {
-    size_t M = 16 * NB;
-    size_t L = (NB == 4) ? M * (M + 2) : M * (M + 1) / 2;
-    // NB == 4 (MFMA variant): two panel buffers [M][6] + per-wave private copies of F and G (4 waves x 2 x [64][4]) = 44 M
-    return L + 2 * (M + 8) /*D,Y*/ + ((NB == 4) ? 46 : 30) * M /*F,G,panel (up to 8 columns, pitch 10)*/ + 2 * M /*scale,x*/ + 7 * (size_t) n + 16;
-}
 
 // GN = true (k_gn_solve): the prologue also mirrors the frames / calibration (and, when they fit, the float
 // adjoints) into LDS and reduces sumNID, so that the whole control step has ONE global-load latency level; the
@@ -525,33 +514,134 @@ struct SolveIO {
     int waitTarget;
 };
 
-typedef double __attribute__((ext_vector_type(4))) ld_d4;
+// ---------------------------------------------------------------------------------------------------------
+// The dynamic LDS of the solve kernels, described once per body - core_lds (solve_core), solve_lds (solve_body), gn_lds (gn_solve_body): the kernels take their region
+// pointers from these descriptions, the launchers the byte count.  The byte counts are what the residency of these kernels was tuned at (k_reduce_solve: one workgroup
+// per CU): room that no region explains stays, as named slack.
+// Which factorisation for n unknowns (row n of the augmented system is the right-hand side): n + 1 <= 64 -> NB = 4 blocks of 16 rows (on the matrix cores),
+// n + 1 <= 112 -> 7, else 9 (the VALU variants)
+#define LD_SOLVE_BY_N(n, for4, for7, for9) (((n) + 1 <= 64) ? for4 : ((n) + 1 <= 112) ? for7 : for9)
+#define LD_SOLVE_NB(n) LD_SOLVE_BY_N(n, 4, 7, 9)
 #define LD_C7 4          // columns per round of the 112 x 112 factorisation (VALU variant)
+static __host__ __device__ constexpr int solve_cols(int NB) { return (NB == 7) ? LD_C7 : 4; }          // columns per round of solve_core<NB>
+#define LD_XFP (8 * LD_MAXF + 8)          // gn_tail: floats of one copy of x (or of the new deltas)
+// solve_core, offsets in doubles from the base.  sTail aliases the panel buffers (free after the factorisation): gn_tail's float copies of x and of the deltas,
+// 3 x 2 x LD_XFP floats.  slack: the launchers have always counted 46 M doubles (NB == 4) or 30 M (three panels of up to 8 columns at pitch 10) for sFp .. sPn and
+// 16 more behind sNs; the panels take 44 M and 3 CP M, no region uses the difference
+static __host__ __device__ constexpr size_t core_lds_end(int NB, int n) {          // CoreLds::end by itself, for the bodies: they lay their regions out behind it at run time
+    size_t M = 16 * NB;
+    size_t L = (NB == 4) ? M * (M + 2) : M * (M + 1) / 2;
+    return L + 2 * (M + 8) /*D,Y*/ + ((NB == 4) ? 46 : 30) * M /*F,G,panel + slack*/ + 2 * M /*scale,x*/ + 7 * (size_t) n + 16;
+}
+struct CoreLds { size_t sL, sD, sY, sFp, sGp, sPn, sSc, sx, sNs, sTail, slack, end; };
+static __host__ __device__ constexpr CoreLds core_lds(int NB, int n) {
+    const size_t M = 16 * NB, CP = solve_cols(NB) + 2;          // CP: row pitch of the panel buffers (see solve_core)
+    CoreLds o{};
+    o.sL = 0;                                                       // L (see LIX): NB == 4 the zero-initialised square [M][M + 2], NB > 4 packed columns
+    o.sD = o.sL + ((NB == 4) ? M * (M + 2) : M * (M + 1) / 2);      // [M + 8]
+    o.sY = o.sD + M + 8;                                            // [M + 8]
+    o.sFp = o.sTail = o.sY + M + 8;                                 // [M][CP]        (NB == 4: panel buffer A)
+    o.sGp = o.sFp + CP * M;                                         // [M][CP]        (NB == 4: panel buffer B)
+    o.sPn = o.sGp + CP * M;                                         // [M][CP]        (NB == 4: per-wave copies of F, then of G: 2 x 4 x [M][4])
+    o.sSc = o.sPn + ((NB == 4) ? 2 * 4 * M * 4 : CP * M);           // [M]
+    o.sx = o.sSc + M;                                               // [M]
+    o.sNs = o.sx + M;                                               // [7][n], the last region
+    o.end = core_lds_end(NB, n);
+    o.slack = o.end - (o.sNs + 7 * (size_t) n);
+    return o;
+}
+#define LD_LDS_SLACK 64          // slack: BYTES the launchers have always added behind the last region
+
+// Both bodies lay their own regions out behind the core: their offsets count from core_lds_end, which is all of the layout that depends on n at run time.
+// solve_body, offsets in doubles:  core | sW.  sW, 7 n + 64 doubles: the nullspace basis [7][n] of set_adjoints; the re-anchor's logs [14][6] and, at sEv, the new
+// evalPT [12]; the partial sums of post_sums / res_counts [8] and io.sRed [16].  Aliases from the base, over the core (both are over when solve_core starts): the
+// threshold pass (post_thresh, LD_THRESH_DOUBLES) and set_adjoints' staging of 37 doubles per pair.
+struct SolveLds { size_t sW, sEv, end; };
+static __host__ __device__ constexpr SolveLds solve_lds(int n) {
+    SolveLds o{};
+    o.sW = 0;
+    o.sEv = o.sW + 96;
+    o.end = o.sW + 7 * (size_t) n + 64;
+    return o;
+}
+static __host__ __device__ constexpr size_t solve_lds_bytes(int n) { return (core_lds_end(LD_SOLVE_NB(n), n) + solve_lds(n).end) * sizeof(double) + LD_LDS_SLACK; }
+
+// gn_solve_body, offsets in BYTES (the regions are of unlike type).  Role 0 (control step):  core | sW | sFr | sCal | ldsAd.  sW, LD_SW_DOUBLES doubles: [0, LD_SW_RED)
+// are io.sRed (solve_core's partial sums of sumNID - the only part of it the solve may touch), the floats behind them belong to gn_tail: canbreak sums 0..3, K^-1 from
+// LD_TAIL_KI, the calibration hand-over flag at LD_TAIL_FLAG.  sFr [F] DevFrame and sCal are the mirrors, ldsAd both float adjoint tables, gn_ad_floats each (windows of
+// up to 8 key frames: F * F * 16 <= 1024 float4 per table, solve_core's prologue); gn_lds_end adds them, so that the kernel, which needs no end, does not evaluate it.
+// The kernel reaches ldsAd as sCal + 1 (lds_layouts_ok: the same place): behind a constant step the pointer is known not to be null, which solve_core tests.
+// Role 1 (statistics) never runs solve_core; its offsets (gn_stats_lds) count from the base:  sW [LD_SW_DOUBLES] | sTh, the threshold pass.
+#define LD_SW_DOUBLES 64
+#define LD_SW_RED 8
+#define LD_TAIL_KI 8
+#define LD_TAIL_FLAG 20          // float index behind cbF of the calibration hand-over flag
+static __host__ __device__ constexpr bool gn_mirrors_adjoints(int F) { return F <= 8; }
+static __host__ __device__ constexpr int gn_ad_floats(int F) { return F * F * LD_AD_LDS_PITCH; }          // one adjoint table in LDS
+struct GnLds { size_t sW, sFr, sCal, ldsAd; };
+static __host__ __device__ constexpr GnLds gn_lds(int F) {
+    GnLds o{};
+    o.sW = 0;
+    o.sFr = o.sW + LD_SW_DOUBLES * sizeof(double);
+    o.sCal = o.sFr + F * sizeof(DevFrame);
+    o.ldsAd = o.sCal + sizeof(DevCalib);
+    return o;
+}
+static __host__ __device__ constexpr size_t gn_lds_end(int F) { return gn_lds(F).ldsAd + (gn_mirrors_adjoints(F) ? 2 * gn_ad_floats(F) * sizeof(float) : 0); }
+struct GnStatsLds { size_t sW, sTh, end; };
+static __host__ __device__ constexpr GnStatsLds gn_stats_lds() {
+    GnStatsLds o{};
+    o.sW = 0;
+    o.sTh = o.sW + LD_SW_DOUBLES * sizeof(double);
+    o.end = o.sTh + LD_THRESH_DOUBLES * sizeof(double);
+    return o;
+}
+static __host__ __device__ constexpr size_t gn_lds_bytes(int F, int n) {
+    const size_t role0 = core_lds_end(LD_SOLVE_NB(n), n) * sizeof(double) + gn_lds_end(F), role1 = gn_stats_lds().end;
+    return (role0 > role1 ? role0 : role1) + LD_LDS_SLACK;
+}
+
+// What the code around the layouts relies on, for every window size (n = 8 F + 4): regions of unlike type are cast onto each other and read with 16-byte accesses
+// (ld2 / st2, the float4 of the adjoint copies and of gn_tail), so every offset is a multiple of 16 bytes; the aliases fit what they lie over; and, since a batched
+// launch is sized by the window with the most key frames (Dmax) while each window lays itself out by its own F, the byte count does not decrease with F among the
+// windows one batch can hold - 1..8 or 9..LD_MAXF key frames (one slot-table width, ldso_ba_batch_create).  From F = 8 to 9 gn_lds_bytes does decrease, 132512 to
+// 97312: the adjoint copies (36864 bytes) end there.
+static constexpr bool lds_layouts_ok() {
+    size_t solvePrev = 0, gnPrev = 0;
+    for (int F = 1; F <= LD_MAXF; F++) {
+        const int n = 8 * F + 4;
+        const CoreLds c = core_lds(LD_SOLVE_NB(n), n);
+        const SolveLds s = solve_lds(n);
+        const GnLds g = gn_lds(F);
+        if ((c.sD | c.sY | c.sFp | c.sGp | c.sPn | c.sSc | c.sx | c.sNs | c.end | s.sW | s.sEv) % 2 != 0 || (g.sW | g.sFr | g.sCal | g.ldsAd | gn_stats_lds().sTh) % 16 != 0 || LD_XFP % 4 != 0 || g.ldsAd != g.sCal + sizeof(DevCalib)) return false;
+        if (c.sTail * sizeof(double) + 3 * 2 * LD_XFP * sizeof(float) > c.sSc * sizeof(double)) return false;
+        if (LD_THRESH_DOUBLES > c.end || 37 * (size_t) F * F > c.end || s.sEv + 12 > s.end || s.sW + 14 * 6 > s.sEv) return false;
+        if (solve_lds_bytes(n) < solvePrev || (F != 9 && gn_lds_bytes(F, n) < gnPrev)) return false;
+        solvePrev = solve_lds_bytes(n); gnPrev = gn_lds_bytes(F, n);
+    }
+    return true;
+}
+static_assert(lds_layouts_ok(), "solve kernels: an offset lost its alignment, an alias outgrew what it lies over, or a smaller window needs more LDS than a larger one");
+typedef double __attribute__((ext_vector_type(4))) ld_d4;
 
 template <int NB, int C, bool GN, bool WAIT = false, bool MF = false>
 static __device__ __forceinline__ void solve_core(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, int iteration, double *sm, SolveIO &io) {
     constexpr int M = 16 * NB;
     constexpr int CP = C + 2;      // row pitch of the panel buffers: 16-byte aligned rows, conflict-free 16-byte accesses at stride CP
     constexpr int NTILE = NB * (NB + 1) / 2;
-    constexpr int LSZ = (NB == 4) ? M * (M + 2) : M * (M + 1) / 2;
+    static_assert(MF == (NB == 4) && C == solve_cols(NB), "core_lds lays the panel buffers out for this variant");
+    constexpr CoreLds lds = core_lds(NB, 0);          // n moves the end alone
+    constexpr int LSZ = (int) (lds.sD - lds.sL);
     const double TINY = 2.2250738585072014e-308;
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, F = D.F, n = D.n;
-    double *sL = sm;                       // L (see LIX)
-    double *sD = sL + LSZ;                 // [M + 8]
-    double *sY = sD + M + 8;               // [M + 8]
-    double *sFp = sY + M + 8;              // [M][CP]        (MF: panel buffer A)
-    double *sGp = sFp + CP * M;            // [M][CP]        (MF: panel buffer B)
-    double *sPn = sGp + CP * M;            // [M][CP]        (MF: per-wave copies of F, then of G: 2 x 4 x [64][4])
-    double *sSc = sPn + (MF ? 2 * 4 * M * 4 : CP * M);            // [M]
-    double *sx = sSc + M;                  // [M]
-    double *sNs = sx + M;                  // [7][n]
+    double *sL = sm + lds.sL, *sD = sm + lds.sD, *sY = sm + lds.sY, *sFp = sm + lds.sFp, *sGp = sm + lds.sGp, *sPn = sm + lds.sPn, *sSc = sm + lds.sSc, *sx = sm + lds.sx, *sNs = sm + lds.sNs;
     const double *HF = B.sys + 3 * (n * n + n), *bF = HF + n * n;      // assembled by k_gather (step-wise path)
     const bool ortho = (St.solverMode & LDSO_SOLVER_ORTHOGONALIZE_X) || (iteration >= 2 && (St.solverMode & LDSO_SOLVER_ORTHOGONALIZE_X_LATER));
 
     // ---------------- prologue: every global load of the control step, issued back to back ----------------
     // GN: HFinal / bFinal (lower triangle) come straight from the accumulator k_reduce added into (B.acc)
     double v[NTILE], dI[NB], dJ[NB], dS = 0.0;
-    // MF (n + 1 <= 64): the trailing update runs on the fp64 matrix cores (v_mfma_f64_16x16x4_f64).  The ten 16x16 tiles of the lower
+    // MF (NB == 4): the trailing update runs on the fp64 matrix cores (v_mfma_f64_16x16x4_f64).  The ten 16x16 tiles of the lower
     // triangle live in MFMA accumulator layout, three slots per wavefront: lane l, register r of a slot <-> element
     // (16 ta + (l >> 4) + 4 r, 16 tb + (l & 15)) of tile (ta, tb); wave w holds (w,0) | (w+1,w... see the packed tables) - 15 = no tile.
     static_assert(!MF || (NB == 4 && C == 4), "the MFMA variant is written for the 64x64 system, 4 columns per round");
@@ -630,10 +720,10 @@ _Pragma("unroll") \
         for (int u = 0; u < MW; u++) { const int i = tid + u * NT; if (i < F * FW) lF[i] = mw[u]; }
         if (tid < CW) ((unsigned *) io.cal)[tid] = cw;
         if (io.ldsAd != nullptr) {
-            float4 *lh = (float4 *) io.ldsAd, *lt = (float4 *) (io.ldsAd + F * F * LD_AD_LDS_PITCH);
+            float4 *lh = (float4 *) io.ldsAd, *lt = (float4 *) (io.ldsAd + gn_ad_floats(F));
 #pragma unroll
             for (int u = 0; u < 4; u++) { const int i = tid + u * NT, sl = i >> 4, j = ((sl % F) * F + sl / F) * (LD_AD_LDS_PITCH / 4) + (i & 15); if (i < F * F * 16) { lh[j] = ah[u]; lt[j] = at[u]; } }
-            io.adH = io.ldsAd; io.adT = io.ldsAd + F * F * LD_AD_LDS_PITCH; io.adPitch = LD_AD_LDS_PITCH;
+            io.adH = io.ldsAd; io.adT = io.ldsAd + gn_ad_floats(F); io.adPitch = LD_AD_LDS_PITCH;
         }
         for (int o = 32; o > 0; o >>= 1) { double a_ = __shfl_xor(ns, o, 64), b_ = __shfl_xor(nc, o, 64); ns += a_; nc += b_; }
         if ((tid & 63) == 0) { io.sRed[tid >> 6] = ns; io.sRed[4 + (tid >> 6)] = nc; }
@@ -875,7 +965,7 @@ _Pragma("unroll") \
             // finished values of a block to the lanes below through LDS: bitwise the same x, 2.04 against 1.78 us.  A column is one broadcast + one fp64 fma
             // on the dependent chain either way, ~50 cycles; the DPP moves wait for the fma like the readlanes do, and the LDS hand-overs come on top.)
 #pragma unroll
-            for (int kk = 63; kk >= 1; kk--) { double xk = readlane_f64(xi, kk); xi = __builtin_fma(-row[kk], xk, xi); }
+            for (int kk = 63; kk >= 1; kk--) { double xk = readlane_d(xi, kk); xi = __builtin_fma(-row[kk], xk, xi); }
             if (lane < n) sx[lane] = xi * sSc[lane];
         } else {
             // lane l owns x_i for i = l, l + 64, (l + 128) in registers; x_k is broadcast with v_readlane (no LDS round trip and no
@@ -898,7 +988,7 @@ _Pragma("unroll") \
                 for (int sg = 0; sg < NSEG; sg++) { const int i = lane + 64 * sg; lk[sg] = (i < kk) ? sL[LIX(kk, min(i, kk))] : 0.0; }
                 double xk = 0.0;
 #pragma unroll
-                for (int sg = 0; sg < NSEG; sg++) if ((kk >> 6) == sg) xk = readlane_f64(xr[sg], kk & 63);      // uniform
+                for (int sg = 0; sg < NSEG; sg++) if ((kk >> 6) == sg) xk = readlane_d(xr[sg], kk & 63);      // uniform
 #pragma unroll
                 for (int sg = 0; sg < NSEG; sg++) xr[sg] = __builtin_fma(-lk[sg], xk, xr[sg]);
             }
@@ -914,7 +1004,7 @@ _Pragma("unroll") \
             c += __shfl_xor(c, 1, 64); c += __shfl_xor(c, 2, 64); c += __shfl_xor(c, 4, 64);
             double cc[7];
 #pragma unroll
-            for (int q = 0; q < 7; q++) cc[q] = readlane_f64(c, q * 8);
+            for (int q = 0; q < 7; q++) cc[q] = readlane_d(c, q * 8);
             for (int r = lane; r < n; r += 64) {
                 double s_ = 0;
 #pragma unroll
@@ -942,7 +1032,7 @@ _Pragma("unroll") \
         for (int kk = 0; kk < 8; kk++) s2 += (float) sx[4 + 8 * t + kk] * at[kk];
         B.xAd[i] = s1 + s2;
     };
-    if constexpr (GN) { io.sTail = (float *) sFp; return; }          // the panel buffers are free now; gn_tail does the rest
+    if constexpr (GN) { io.sTail = (float *) (sm + lds.sTail); return; }          // the panel buffers are free now; gn_tail does the rest
     bool bad = false;
     for (int i = tid; i < n; i += NT) { B.x[i] = sx[i]; if (!isfinite(sx[i])) bad = true; }
     if (bad) B.scalars[4] = 1.0;
@@ -961,9 +1051,8 @@ _Pragma("unroll") \
 
 template <bool GN, bool WAIT = false>
 static __device__ __forceinline__ void solve_core_dispatch(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, int iteration, double *sm, SolveIO &io) {
-    if (D.n + 1 <= 64) solve_core<4, 4, GN, WAIT, true>(B, D, S, St, iteration, sm, io);
-    else if (D.n + 1 <= 112) solve_core<7, LD_C7, GN, WAIT>(B, D, S, St, iteration, sm, io);
-    else solve_core<9, 4, GN, WAIT>(B, D, S, St, iteration, sm, io);
+    LD_SOLVE_BY_N(D.n, (solve_core<4, solve_cols(4), GN, WAIT, true>(B, D, S, St, iteration, sm, io)), (solve_core<7, solve_cols(7), GN, WAIT>(B, D, S, St, iteration, sm, io)),
+                  (solve_core<9, solve_cols(9), GN, WAIT>(B, D, S, St, iteration, sm, io)));
 }
 
 // frame / calibration part of backupState, doStepFromBackup (+ canbreak), loadSateBackup on the working copies
@@ -989,15 +1078,12 @@ static __device__ __forceinline__ void frames_step(const BaPtrs &B, const ldso_s
 static __device__ __forceinline__ void solve_body(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, const int nRoles, const int role) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x, F = D.F, n = D.n;
-    const int NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
-    double *sW = sm + solve_core_lds_doubles(NBsel, n);      // scratch: 7n + 64
-    // the threshold pass (histogram + staged candidates) runs before the solve and is over when solve_core starts: it aliases its LDS
-    int *sHist = (int *) sm;                 // 256
-    int *sI = sHist + 256;                   // 8 (+ TH_CAP floats of candidate staging behind it)
-    // two workgroups (ba_launch_solve): the statistics of the last linearizeAll (POST / THRESH / LOG) run next to the control part;
+    const SolveLds lds = solve_lds(n);
+    double *const top = sm + core_lds_end(LD_SOLVE_NB(n), n), *sW = top + lds.sW;
+    // two workgroups (solve_roles): the statistics of the last linearizeAll (POST / THRESH / LOG) run next to the control part;
     // they touch disjoint data (frameEnergyTH is only written by the statistics and only read by k_linearize)
     unsigned fl = A.flags;
-    if (nRoles == 2) fl &= (role == 1) ? (SK_POST | SK_THRESH | SK_LOG) : ~(unsigned) (SK_POST | SK_THRESH | SK_LOG);
+    if (nRoles == 2) fl &= (role == 1) ? (unsigned) SK_STATS : ~(unsigned) SK_STATS;
 
     if (fl & SK_COLLECT) {
         // FullSystem::optimize preamble: resetOOB on every non-linearised residual (FullSystem.cc:744-748)
@@ -1013,7 +1099,7 @@ static __device__ __forceinline__ void solve_body(const BaPtrs &B, const BaDims 
         // (bit-identical), a fourteenth of its latency (it was 30 us of the 39 us tail on one lane)
         DevFrame &f = B.frames[F - 1];
         double *sLp = sW;                  // [14][6] logs
-        double *sEv = sW + 96;             // the new evalPT
+        double *sEv = top + lds.sEv;             // the new evalPT
         if (tid < 12) sEv[tid] = f.PRE_w2c[tid];
         __syncthreads();
         if (tid < 14) {
@@ -1066,7 +1152,7 @@ static __device__ __forceinline__ void solve_body(const BaPtrs &B, const BaDims 
         if (tid == 0) { B.scalars[0] = sc[0]; B.scalars[1] = sc[1]; B.scalars[2] = sc[2]; B.scalars[6] = sc[3]; B.scalars[7] = sc[4]; B.scalars[9] = sc[5]; B.scalars[10] = sc[6]; }
         __syncthreads();
     }
-    if (fl & SK_THRESH) post_thresh(B, D, S, St, (fl & SK_FROMREDUCED) ? (A.reduceIn + 3 * (n * n + n) + 8) : nullptr, (float *) (sI + 8), sHist, sI);
+    if (fl & SK_THRESH) post_thresh(B, D, S, St, (fl & SK_FROMREDUCED) ? (A.reduceIn + 3 * (n * n + n) + 8) : nullptr, (int *) sm);
     if (fl & SK_LOG) { if (tid == 0 && A.logIdx >= 0 && A.logIdx < 64) B.energyLog[A.logIdx] = B.scalars[0]; __syncthreads(); }
 
     if (fl & SK_SOLVE) {
@@ -1110,13 +1196,6 @@ __global__ __launch_bounds__(NT) void k_solve(BaPtrs B, BaDims D, ResSet S, ldso
 // Device stamps, C3, us after the back substitution - before: outputs 1.2, poses 2.0 - 2.8, pair records 1.0, adHTdeltaF 0.85 = 5.6 (the poses stored through
 // LDS between dependent products, canbreak walked four divergent branches with LDS round trips inside, and every wave walked every phase); now: see DESIGN 5.
 // ---------------------------------------------------------------------------------------------------------
-#define LD_XFP (8 * LD_MAXF + 8)
-// LDS scratch of the control workgroup (gn_solve_body: sW, LD_SW_DOUBLES doubles): doubles [0, LD_SW_RED) are io.sRed (solve_core's partial sums of sumNID - the
-// only part of it the solve may touch), the floats behind them belong to gn_tail: canbreak sums 0..3, K^-1 8..16, the calibration hand-over flag LD_TAIL_FLAG
-#define LD_SW_DOUBLES 64
-#define LD_SW_RED 8
-#define LD_TAIL_KI 8
-#define LD_TAIL_FLAG 20          // float index behind cbF of the calibration hand-over flag
 static_assert(NT == 256, "gn_tail is laid out for exactly four wavefronts: wave 0 waits for a flag that wave 3 sets");
 static_assert(LD_TAIL_KI + 9 <= LD_TAIL_FLAG && (LD_TAIL_FLAG + 1) * 4 <= (LD_SW_DOUBLES - LD_SW_RED) * 8, "gn_tail's floats must fit the scratch behind io.sRed");
 static __device__ __forceinline__ void gn_tail(const BaPtrs &B, const BaDims &D, DevFrame *fr, DevCalib *cal, const SolveIO &io, const ldso_settings_t &St, float *cbF,
@@ -1243,38 +1322,39 @@ template <bool WAIT>
 static __device__ __forceinline__ void gn_solve_body(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, const int role) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x, F = D.F, n = D.n;
-    const int NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
-    double *sW = sm + solve_core_lds_doubles(NBsel, n);      // LD_SW_DOUBLES doubles of scratch (layout: above gn_tail)
+    char *const top = (char *) (sm + core_lds_end(LD_SOLVE_NB(n), n));
     if (LD_ITER_SKIPPED(B, A.itCheck)) return;
     const long long t0_ = wall_clock64();
 #define GSTAMP(i) do { if (LD_STAMP_ON && tid == 0) B.energyLog[40 + (i)] = (double) (wall_clock64() - t0_); } while (0)
     if (role == 1) {
-        double *sW1 = sm;                        // block 1 never runs solve_core: its scratch starts at the base
-        int *sHist = (int *) (sW1 + 64);
-        int *sI = sHist + 256;
+        constexpr GnStatsLds lds = gn_stats_lds();
+        double *sW1 = (double *) ((char *) sm + lds.sW);
+        int *sTh = (int *) ((char *) sm + lds.sTh);
         if (A.reduceIn != nullptr) {
             // multi-GPU: the sums over all ranks arrive in the all-reduce buffer (k_gn_export layout), the candidates behind them
             const double *sc = A.reduceIn;
             if (tid == 0) { B.scalars[0] = sc[0]; B.scalars[1] = sc[1]; B.scalars[2] = sc[2]; B.scalars[6] = sc[3]; B.scalars[7] = sc[4]; B.scalars[9] = sc[5]; B.scalars[10] = sc[6]; }
             __syncthreads();
-            post_thresh(B, D, S, St, A.reduceIn + 8, (float *) (sI + 8), sHist, sI);
+            post_thresh(B, D, S, St, A.reduceIn + 8, sTh);
         } else {
             post_sums(B, D, S, sW1);
             GSTAMP(10);
             res_counts(B, D, S, sW1);
             GSTAMP(11);
-            post_thresh(B, D, S, St, nullptr, (float *) (sI + 8), sHist, sI);
+            post_thresh(B, D, S, St, nullptr, sTh);
             GSTAMP(12);
         }
         if (tid == 0 && A.logIdx >= 0 && A.logIdx < 64) B.energyLog[A.logIdx] = B.scalars[0];
         return;
     }
-    DevFrame *sFr = (DevFrame *) (sW + LD_SW_DOUBLES);
-    DevCalib *sCal = (DevCalib *) (sFr + F);
+    const GnLds lds = gn_lds(F);
+    double *sW = (double *) (top + lds.sW);
+    DevFrame *sFr = (DevFrame *) (top + lds.sFr);
+    DevCalib *sCal = (DevCalib *) (top + lds.sCal);
     if (LD_STAMP_ON && tid == 0) B.energyLog[39] = (double) t0_;
     SolveIO io;
     io.fr = sFr; io.cal = sCal; io.adH = B.adHostF; io.adT = B.adTargetF; io.adPitch = 64; io.sRed = sW; io.sumNID = 0; io.lambda = A.lambda; io.hasPrior = A.hasPrior; io.redScalars = A.reduceIn; io.waitCtr = A.waitCtr; io.waitTarget = A.waitTarget;
-    io.ldsAd = (F <= 8) ? (float *) (sCal + 1) : nullptr;
+    io.ldsAd = gn_mirrors_adjoints(F) ? (float *) (sCal + 1) : nullptr;
     if (tid == 0) *(int *) ((float *) (sW + LD_SW_RED) + LD_TAIL_FLAG) = 0;          // gn_tail's hand-over flag (the solve's barriers publish it)
     solve_core_dispatch<true, WAIT>(B, D, S, St, A.iteration, sm, io);      // + mirrors
     GSTAMP(4);
@@ -1299,7 +1379,7 @@ __global__ __launch_bounds__(NT) void k_gn_solve(BaPtrs B, BaDims D, ResSet S, l
     // the 672 bytes of arguments into the scalar cache with one wait (ba_dev.h) - for the systems up to 64 x 64 only: measured (round 4, A/B on one box)
     // 27.2 -> 26.5 us at C3 (n = 60), but 62.1 -> 63.6 us at C5 (n = 100, the generic factorisation)
     static_assert(sizeof(BaPtrs) + sizeof(BaDims) + sizeof(ResSet) + sizeof(ldso_settings_t) + sizeof(SolveArgs) >= 10 * 64 - 60, "k_gn_solve: ld_touch_kernarg<10> must stay inside the arguments");
-    if (D.n + 1 <= 64) ld_touch_kernarg<10>();
+    if (LD_SOLVE_NB(D.n) == 4) ld_touch_kernarg<10>();
     gn_solve_body<false>(B, D, S, St, A, (int) blockIdx.x);
 }
 
@@ -1316,14 +1396,14 @@ __global__ __launch_bounds__(NT) void k_reduce_solve(BaPtrs B, BaDims D, ResSet 
                                                      float calibPrior, double l1, double il) {
     static_assert(sizeof(BaPtrs) + sizeof(BaDims) + sizeof(ResSet) + sizeof(ldso_settings_t) + sizeof(SolveArgs) + sizeof(ChunkStarts) + 24 >= 12 * 64 - 60, "k_reduce_solve: ld_touch_kernarg<12> must stay inside the arguments");
     ld_touch_kernarg<12>();          // 768 bytes of arguments into the scalar cache with one wait (ba_dev.h): 31.8 -> 31.25 us at C3
-    if (blockIdx.x >= 2) {
+    if (blockIdx.x >= LD_FUSED_CTL) {
         const long long tStart_ = LD_STAMP_ON ? wall_clock64() : 0;
         if (LD_ITER_SKIPPED(B, A.itCheck)) return;
         // dispatch order = index order: the Schur tile workgroups (the longest) get the lowest indices, then the pair workgroups,
         // the extras workgroup last; reduce_body numbers them pairs | tiles | extras
-        const int nT_ = A.GSP / 16, nTiles = D.ks * nT_ * (nT_ + 1) / 2, nPair = D.F * D.F * (A.hasL ? 2 : 1);
-        const int q = (int) blockIdx.x - 2;
-        const int bid = (q < nTiles) ? nPair + q : (q < nTiles + nPair) ? q - nTiles : q;
+        const ReduceGrid rg = reduce_grid(D.F, A.hasL, D.ks, A.GSP);
+        const int q = (int) blockIdx.x - LD_FUSED_CTL;
+        const int bid = (q < rg.nTile) ? rg.nPair + q : (q < rg.nTile + rg.nPair) ? q - rg.nTile : q;
         reduce_body(B, D, S, chunkStart, A.hasL, A.GSP, atomicMode, A.hasPrior, calibPrior, l1, il, -1, bid);
         // Everything a reduce workgroup hands to the control workgroup went through device-scope atomics (performed at the memory
         // side): waiting for their acknowledgement is enough - a release FENCE would also write the whole L2 back (the outputs of
@@ -1371,8 +1451,7 @@ __global__ __launch_bounds__(NT, LD_REDB_BLOCKS) void k_reduce_batch_dense(const
 __global__ __launch_bounds__(NT) void k_gn_solve_batch(const BatchItem *__restrict__ items, int cur, ldso_settings_t St, int iteration, double lambda, int logIdx, int itCheck) {
     const BatchItem &it = items[blockIdx.x >> 1];
     SolveArgs A;
-    A.flags = 0; A.iteration = iteration; A.lambda = lambda; A.hasL = 0; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = logIdx;
-    A.reduceOut = nullptr; A.reduceIn = nullptr; A.itCheck = itCheck; A.waitCtr = nullptr; A.waitTarget = 0; A.hostStop = nullptr; A.lastIt = -1;
+    A.iteration = iteration; A.lambda = lambda; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = logIdx; A.itCheck = itCheck;
     gn_solve_body<false>(it.B, it.D, it.set[cur], St, A, (int) (blockIdx.x & 1));
 }
 
@@ -1381,15 +1460,10 @@ __global__ __launch_bounds__(NT) void k_gn_solve_batch(const BatchItem *__restri
 // names the LAST iteration the window executes - the per-window cap and the early exit are the same test (LD_ITER_SKIPPED), and the tail derives from it,
 // on the device, how many iterations ran and which of the window's two residual sets is the applied one.  set[0] of a BatchItem is the set that was applied
 // when the call began (batch_refresh): the preamble linearises set[0] -> set[1], iteration i reads set[1 ^ (i & 1)].
-static __device__ __forceinline__ int batch_cap(int F, int mnumOptIts, int forceAll) {
-    int cap = mnumOptIts;
-    if (!forceAll) { if (F < 3) cap = 20; if (F < 4) cap = 15; }          // FullSystem.cc:735-736, as ldso_ba_optimize restates it
-    return cap;
-}
 __global__ __launch_bounds__(64) void k_batch_begin(const BatchItem *__restrict__ items, int mnumOptIts, int forceAll) {
     const BatchItem &it = items[blockIdx.x];
     it.B.energyLog[threadIdx.x] = 0.0;
-    if (threadIdx.x == 0) it.B.scalars[LD_SC_STOP] = (double) (batch_cap(it.D.F, mnumOptIts, forceAll) - 1);
+    if (threadIdx.x == 0) it.B.scalars[LD_SC_STOP] = (double) (optimize_iteration_cap(it.D.F, mnumOptIts, forceAll) - 1);
 }
 // The tail of optimize() for every window of a (half-)batch.  phase 0 (two workgroups per window): flags on the applied set, log entry `done`; phase 1 (one
 // workgroup per window): flags on the set the fixing linearisation wrote, log entry `done + 1`, then the window's 16 scalars into the batch's read-back block.
@@ -1398,8 +1472,7 @@ __global__ __launch_bounds__(NT) void k_solve_batch(const BatchItem *__restrict_
     const BatchItem &it = items[w];
     const int stop = (int) it.B.scalars[LD_SC_STOP], applied = stop & 1;          // = 1 ^ (done & 1), done = stop + 1
     SolveArgs A;
-    A.flags = flags; A.iteration = 0; A.lambda = 0; A.hasL = 0; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = stop + 1 + phase;
-    A.reduceOut = nullptr; A.reduceIn = nullptr; A.itCheck = -1; A.waitCtr = nullptr; A.waitTarget = 0; A.hostStop = nullptr; A.lastIt = -1;
+    A.flags = flags; A.hasPrior = it.hasPrior; A.GSP = it.GSP; A.logIdx = stop + 1 + phase;
     solve_body(it.B, it.D, it.set[applied ^ phase], St, A, nRoles, role);
     if (scalarsOut != nullptr) {
         __syncthreads();
@@ -1408,29 +1481,17 @@ __global__ __launch_bounds__(NT) void k_solve_batch(const BatchItem *__restrict_
 }
 
 hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st, int itCheck) {
-    const size_t lds = (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB) * sizeof(float);
     static int numCU[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (numCU[dev] == 0) { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256; numCU[dev] = cu; }
-    if (lds > 48 * 1024) {
-        (void) hipFuncSetAttribute((const void *) k_reduce_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-        (void) hipFuncSetAttribute((const void *) k_reduce_batch_dense, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    }
-    if (totalBlocks >= LD_REDB_DENSE_PER_CU * numCU[dev]) hipLaunchKernelGGL(k_reduce_batch_dense, dim3(totalBlocks), dim3(NT), lds, st, d_items, nWin, cur, calibPrior, l1, il, itCheck);
-    else hipLaunchKernelGGL(k_reduce_batch, dim3(totalBlocks), dim3(NT), lds, st, d_items, nWin, cur, calibPrior, l1, il, itCheck);
-    return hipGetLastError();
+    return launch_lds(totalBlocks >= LD_REDB_DENSE_PER_CU * numCU[dev] ? k_reduce_batch_dense : k_reduce_batch, dim3(totalBlocks), dim3(NT), reduce_atomic_lds_bytes(), st,
+                      d_items, nWin, cur, calibPrior, l1, il, itCheck);
 }
 
-// Dmax: the window of the batch with the most frames (LDS of the control step)
+// Dmax: the window of the batch with the most frames.  It sizes the LDS of the launch; every window lays itself out by its own F (lds_layouts_ok: none needs more)
 hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, int cur, const ldso_settings_t &St, int iteration, double lambda, hipStream_t st, int logIdx, int itCheck) {
-    size_t mirror = (size_t) Dmax.F * sizeof(DevFrame) + sizeof(DevCalib) + (Dmax.F <= 8 ? (size_t) Dmax.F * Dmax.F * 2 * LD_AD_LDS_PITCH * sizeof(float) : 0), stats = 64 * sizeof(double) + (256 + 8) * sizeof(int) + TH_CAP * sizeof(float);
-    const int n = Dmax.n, NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
-    size_t lds0 = solve_core_lds_doubles(NBsel, n) * sizeof(double) + 64 * sizeof(double) + mirror + 64;
-    size_t lds = lds0 > stats + 64 ? lds0 : stats + 64;
-    if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_gn_solve_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    hipLaunchKernelGGL(k_gn_solve_batch, dim3(2 * nWin), dim3(NT), lds, st, d_items, cur, St, iteration, lambda, logIdx, itCheck);
-    return hipGetLastError();
+    return launch_lds(k_gn_solve_batch, dim3(2 * nWin), dim3(NT), gn_lds_bytes(Dmax.F, Dmax.n), st, d_items, cur, St, iteration, lambda, logIdx, itCheck);
 }
 
 hipError_t ba_launch_batch_begin(const BatchItem *d_items, int nWin, int mnumOptIts, int forceAll, hipStream_t st) {
@@ -1438,16 +1499,9 @@ hipError_t ba_launch_batch_begin(const BatchItem *d_items, int nWin, int mnumOpt
     return hipGetLastError();
 }
 
-// Dmax as above; the LDS is that of ba_launch_solve (further down) for the largest window
 hipError_t ba_launch_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, const ldso_settings_t &St, unsigned flags, int phase, double *d_scalarsOut, hipStream_t st) {
-    const int n = Dmax.n, NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
-    const size_t stats = (256 + 8) * sizeof(int) + TH_CAP * sizeof(float), core = solve_core_lds_doubles(NBsel, n) * sizeof(double);
-    const size_t lds = (core > stats ? core : stats) + (7 * (size_t) n + 64) * sizeof(double) + 64;
-    if (lds > 48 * 1024) (void) hipFuncSetAttribute((const void *) k_solve_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    const unsigned fstats = SK_POST | SK_THRESH | SK_LOG, fctl = SK_REANCHOR | SK_ADJ | SK_NONULLSPACE | SK_PRECALC;
-    const int nRoles = ((flags & fstats) && (flags & fctl) && !(flags & ~(fstats | fctl))) ? 2 : 1;          // as ba_launch_solve splits one window's tail
-    hipLaunchKernelGGL(k_solve_batch, dim3(nRoles * nWin), dim3(NT), lds, st, d_items, St, flags, phase, nRoles, d_scalarsOut);
-    return hipGetLastError();
+    const int nRoles = solve_roles(flags);
+    return launch_lds(k_solve_batch, dim3(nRoles * nWin), dim3(NT), solve_lds_bytes(Dmax.n), st, d_items, St, flags, phase, nRoles, d_scalarsOut);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1578,46 +1632,22 @@ hipError_t ba_launch_lm_energies(const BaPtrs &B, const BaDims &D, const ResSet 
     return hipGetLastError();
 }
 
-static size_t solve_lds_common(const BaDims &D) {
-    const int n = D.n, NBsel = (n + 1 <= 64) ? 4 : (n + 1 <= 112) ? 7 : 9;
-    return solve_core_lds_doubles(NBsel, n) * sizeof(double);
-}
-
 hipError_t ba_launch_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, hipStream_t st) {
-    size_t stats = (256 + 8) * sizeof(int) + TH_CAP * sizeof(float), core = solve_lds_common(D);
-    size_t lds = (core > stats ? core : stats) + (7 * (size_t) D.n + 64) * sizeof(double) + 64;
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void *) k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    // the tail of optimize(): statistics and the re-anchor / adjoint / precalc part are independent -> two workgroups
-    const unsigned fstats = SK_POST | SK_THRESH | SK_LOG, fctl = SK_REANCHOR | SK_ADJ | SK_NONULLSPACE | SK_PRECALC;
-    const bool split = (A.flags & fstats) && (A.flags & fctl) && !(A.flags & ~(fstats | fctl));
-    hipLaunchKernelGGL(k_solve, dim3(split ? 2 : 1), dim3(NT), lds, st, B, D, S, St, A);
-    return hipGetLastError();
+    return launch_lds(k_solve, dim3(solve_roles(A.flags)), dim3(NT), solve_lds_bytes(D.n), st, B, D, S, St, A);
 }
 
 hipError_t ba_launch_gn_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, hipStream_t st) {
-    size_t mirror = (size_t) D.F * sizeof(DevFrame) + sizeof(DevCalib) + (D.F <= 8 ? (size_t) D.F * D.F * 2 * LD_AD_LDS_PITCH * sizeof(float) : 0), stats = 64 * sizeof(double) + (256 + 8) * sizeof(int) + TH_CAP * sizeof(float);
-    size_t lds0 = solve_lds_common(D) + 64 * sizeof(double) + mirror + 64;      // block 0
-    size_t lds = lds0 > stats + 64 ? lds0 : stats + 64;                         // block 1 aliases the base
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void *) k_gn_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    hipLaunchKernelGGL(k_gn_solve, dim3(2), dim3(NT), lds, st, B, D, S, St, A);
-    return hipGetLastError();
+    return launch_lds(k_gn_solve, dim3(2), dim3(NT), gn_lds_bytes(D.F, D.n), st, B, D, S, St, A);          // control step | statistics
 }
 
-// nReduce = workgroups of ba_launch_reduce in atomic mode (see there)
+// the control workgroup waits until every reduce workgroup of the launch has signalled: the grid and the wait target come from the same reduce_grid
 hipError_t ba_launch_reduce_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, const ChunkStarts &chunkStart,
                                   int atomicMode, float calibPrior, double l1, double il, hipStream_t st) {
-    const int nT = A.GSP / 16;
-    const int nReduce = D.F * D.F * (A.hasL ? 2 : 1) + D.ks * nT * (nT + 1) / 2 + 1;
-    size_t mirror = (size_t) D.F * sizeof(DevFrame) + sizeof(DevCalib) + (D.F <= 8 ? (size_t) D.F * D.F * 2 * LD_AD_LDS_PITCH * sizeof(float) : 0), stats = 64 * sizeof(double) + (256 + 8) * sizeof(int) + TH_CAP * sizeof(float);
-    size_t lds0 = solve_lds_common(D) + 64 * sizeof(double) + mirror + 64;
-    size_t lds = lds0 > stats + 64 ? lds0 : stats + 64;
-    const size_t ldsR = (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB) * sizeof(float);
-    if (ldsR > lds) lds = ldsR;
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void *) k_reduce_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    const ReduceGrid rg = reduce_grid(D.F, A.hasL, D.ks, A.GSP);
     SolveArgs A2 = A;
-    A2.waitTarget = nReduce;
-    hipLaunchKernelGGL(k_reduce_solve, dim3(nReduce + 2), dim3(NT), lds, st, B, D, S, St, A2, chunkStart, atomicMode, calibPrior, l1, il);
-    return hipGetLastError();
+    A2.waitTarget = rg.total;
+    return launch_lds(k_reduce_solve, dim3(rg.total + LD_FUSED_CTL), dim3(NT), std::max(gn_lds_bytes(D.F, D.n), reduce_atomic_lds_bytes()), st,
+                      B, D, S, St, A2, chunkStart, atomicMode, calibPrior, l1, il);
 }
 
 hipError_t ba_launch_point_step(const BaPtrs &B, const BaDims &D, const ResSet &S, int mode, hipStream_t st) {

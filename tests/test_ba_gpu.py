@@ -316,10 +316,11 @@ def _marginalize_points(small, with_prior, marg):
     assert np.abs(HM2g - HM2g.T).max() <= 1e-9 * np.abs(HM2g).max()
 
 
-@pytest.mark.parametrize("F,P", [(2, 37), (3, 50), (8, 130), (9, 131), (16, 97)])
+@pytest.mark.parametrize("F,P", [(2, 37), (3, 50), (7, 113), (8, 130), (9, 131), (13, 101), (14, 103), (16, 97)])
 def test_window_shape_boundaries(F, P):
     """Frame counts at the layout boundaries (F = 2 minimum, F = 8 fills one slot group exactly, F = 9 needs the second one, F = 16
-    = LDSO_MAX_FRAMES with the 144-padded LDL^T) and point counts that are not multiples of the chunk size: one stage-wise pass
+    = LDSO_MAX_FRAMES with the 144-padded LDL^T; F = 7 | 8 and F = 13 | 14 are the two sides of each switch of the factorisation, and with it of the
+    solve kernels' LDS layout: n + 1 = 61 | 69 around 64, 109 | 117 around 112) and point counts that are not multiples of the chunk size: one stage-wise pass
     and two fast-path iterations against the oracle."""
     win = synth.make_window(F=F, P=P, w=256, h=192, fx=160.0, seed=100 + F)
     o = po.OracleWindow(win); g = binding.BA.from_window(win)
@@ -565,14 +566,15 @@ def test_large_batch_is_rechunked_and_equals_solo_runs_under_the_same_chunking()
 
 
 def test_batched_windows_equal_individual_runs():
-    """ldso_ba_batch_*: five independent windows (different scenes, point counts and frame counts <= 8, one with a prior) iterated by
+    """ldso_ba_batch_*: six independent windows (different scenes, point counts and frame counts <= 8, one with a prior; the window of 8 key frames sizes the
+    control step's LDS for the whole batch and lays itself out for the 112 x 112 factorisation, the others for the 64 x 64 one) iterated by
     three launches per iteration for the whole batch; every window must end where its own ldso_ba_enqueue_gn (split schedule) ends."""
     import torch
     ts = torch.cuda.Stream(); torch.cuda.set_stream(ts)
     st = ts.cuda_stream
     wins = [synth.make_window(F=5, P=400, w=320, h=240, fx=200.0, seed=31), synth.make_window(F=5, P=333, w=320, h=240, fx=200.0, seed=32),
             synth.make_window(F=7, P=500, w=320, h=240, fx=200.0, seed=33), synth.make_window(F=4, P=150, w=256, h=192, fx=160.0, seed=34),
-            synth.add_synthetic_prior(synth.make_window(F=6, P=420, w=320, h=240, fx=200.0, seed=35))]
+            synth.add_synthetic_prior(synth.make_window(F=6, P=420, w=320, h=240, fx=200.0, seed=35)), synth.make_window(F=8, P=260, w=320, h=240, fx=200.0, seed=37)]
     solo, batch = [], []
     for w in wins:
         for lst in (solo, batch):
