@@ -95,6 +95,41 @@ int adp_trace_new_coarse(void *b, void *fs, void *fh, int *counts) {
     GUARD(((GpuBackend *) b)->traceNewCoarse(*(FullSystem *) fs, *(std::shared_ptr<FrameHessian> *) fh); for (int i = 0; i < 6; i++) counts[i] = ((GpuBackend *) b)->lastTraceCounts[i])
 }
 
+// fh = ref_fs_new_frame(window, ...): GpuBackend::makeNewTraces in place of FullSystem::makeNewTraces with setting_pointSelection = 1 and
+// setting_desiredImmatureDensity = n_desired; response = CalibHessian::B to use (256 floats) or null (the window's own, identity by default).
+// Returns what the frame's features hold afterwards, at most cap of them: feat [cap][5] = u, v, score, isCorner, angle; desc [cap][32]; imm [cap] = the
+// ImmaturePoint of each (host = index of its frame in the window, -1 when it is not a window frame); counts[4] = features detected, corners, dropped, frame->features.size()
+int adp_make_new_traces(void *b, void *fs_, void *fh_, const int *orb_pattern, int n_desired, const float *response, int cap, float *feat, unsigned char *desc, ldso_immature_t *imm, int *counts) {
+    GUARD(
+        GpuBackend &B = *(GpuBackend *) b; FullSystem &fs = *(FullSystem *) fs_; std::shared_ptr<FrameHessian> fh = *(std::shared_ptr<FrameHessian> *) fh_;
+        setting_pointSelection = 1; setting_desiredImmatureDensity = n_desired; setting_gammaWeightsPixelSelect = 1;
+        if (response) for (int i = 0; i < 256; i++) fs.Hcalib->mpCH->B[i] = response[i];
+        B.orbPattern = orb_pattern;
+        fh->frame->features.clear();
+        B.makeNewTraces(fs, fh);
+        for (int i = 0; i < 3; i++) counts[i] = B.lastNewTraces[i];
+        counts[3] = (int) fh->frame->features.size();
+        int hostIdx = -1;
+        for (size_t f = 0; f < fs.frames.size(); f++) if (fs.frames[f] == fh->frame) hostIdx = (int) f;
+        int k = 0;
+        for (auto &f : fh->frame->features) {
+            if (k >= cap) break;
+            float *o = feat + 5 * k;
+            o[0] = f->uv[0]; o[1] = f->uv[1]; o[2] = f->score; o[3] = f->isCorner ? 1 : 0; o[4] = f->angle;
+            memcpy(desc + 32 * k, f->descriptor, 32);
+            ldso_immature_t &q = imm[k];
+            memset(&q, 0, sizeof(q));
+            ImmaturePoint &ip = *f->ip;
+            q.u = f->uv[0]; q.v = f->uv[1];
+            memcpy(q.color, ip.color, sizeof(q.color)); memcpy(q.weights, ip.weights, sizeof(q.weights));
+            q.gradH[0] = ip.gradH(0, 0); q.gradH[1] = ip.gradH(0, 1); q.gradH[2] = ip.gradH(1, 0); q.gradH[3] = ip.gradH(1, 1);
+            q.energyTH = ip.energyTH; q.idepth_min = ip.idepth_min; q.idepth_max = ip.idepth_max; q.quality = ip.quality;
+            q.lastTraceStatus = (int32_t) ip.lastTraceStatus; q.lastTraceUV[0] = ip.lastTraceUV[0]; q.lastTraceUV[1] = ip.lastTraceUV[1];
+            q.lastTracePixelInterval = ip.lastTracePixelInterval; q.host = hostIdx;
+            k++;
+        })
+}
+
 int adp_set_device_pyramids(void *b, int on) { ((GpuBackend *) b)->useDevicePyramids = on != 0; return 0; }
 int adp_pyramids_built(void *b) { return ((GpuBackend *) b)->pyramidsBuilt; }
 int adp_set_write_back_jacobians(void *b, int on) { ((GpuBackend *) b)->writeBackJacobians = on != 0; return 0; }

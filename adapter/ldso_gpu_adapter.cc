@@ -103,6 +103,7 @@ GpuBackend::GpuBackend(int device, int maxFrames, int maxPoints) : device_(devic
 GpuBackend::~GpuBackend() {
     for (auto &kv : trackers_) ldso_tr_destroy(kv.second);
     if (tracer_) ldso_trace_destroy(tracer_);
+    if (features_) ldso_feat_destroy(features_);
     if (ba_) ldso_ba_destroy(ba_);
     slotPyr_.clear(); tracerPyr_.reset(); trackerPyr_.clear(); pyr_.clear();          // the pyramids, after their consumers
 }
@@ -860,6 +861,57 @@ void GpuBackend::traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh) {
         ip.idepth_min = q.idepth_min; ip.idepth_max = q.idepth_max; ip.quality = q.quality;
         ip.lastTraceStatus = (ImmaturePointStatus) q.lastTraceStatus;
         ip.lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip.lastTracePixelInterval = q.lastTracePixelInterval;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// void FullSystem::makeNewTraces(shared_ptr<FrameHessian> newFrame, float *gtDepth), setting_pointSelection == 1 (FullSystem.cc:1272-1283)
+// ------------------------------------------------------------------------------------------------------------------------------------
+void GpuBackend::makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame) {
+    if (setting_pointSelection != 1) throw std::runtime_error("GpuBackend::makeNewTraces: only setting_pointSelection == 1 (FeatureDetector::DetectCorners) runs on the device");
+    const int w = wG[0], h = hG[0], want = (int) setting_desiredImmatureDensity;
+    int capacity = 0;
+    throwOn(ldso_feat_grid(w, h, want, nullptr, nullptr, nullptr, nullptr, nullptr, &capacity), "ldso_feat_grid");
+    for (int i = 0; i < 3; i++) lastNewTraces[i] = 0;
+    shared_ptr<Frame> frame = newFrame->frame;
+    frame->features.reserve(want);                                                                   // :1276
+    if (capacity == 0) return;
+    if (!features_ || capacity > featuresCap_ || featuresPattern_ != orbPattern) {
+        if (features_) ldso_feat_destroy(features_);
+        features_ = nullptr;
+        featuresCap_ = std::max(capacity, 4096);
+        throwOn(ldso_feat_create(device_, w, h, featuresCap_, orbPattern, &features_), "ldso_feat_create");
+        featuresPattern_ = orbPattern;
+    }
+    shared_ptr<CalibHessian> calib = fs.Hcalib ? fs.Hcalib->mpCH : nullptr;
+    throwOn(ldso_feat_set_response(features_, setting_gammaWeightsPixelSelect == 1 && calib ? calib->B : nullptr), "ldso_feat_set_response");
+    int hostIdx = (int) fs.frames.size();                                                            // the frame's index in the window (the new key frame is its last)
+    for (size_t f = 0; f < fs.frames.size(); f++) if (fs.frames[f] == frame) hostIdx = (int) f;
+    PyrRef pyr = pyramidOf(newFrame);
+    int n = 0, nCorners = 0;
+    throwOn(ldso_feat_detect(features_, pyr->p, want, hostIdx, &n, &nCorners), "ldso_feat_detect");
+    std::vector<ldso_feature_t> feats((size_t) n);
+    std::vector<ldso_immature_t> rec((size_t) n);
+    throwOn(ldso_feat_get(features_, feats.data(), rec.data()), "ldso_feat_get");
+    lastNewTraces[0] = n; lastNewTraces[1] = nCorners;
+    for (int i = 0; i < n; i++) {
+        const ldso_feature_t &g = feats[i]; const ldso_immature_t &q = rec[i];
+        if (!std::isfinite(q.energyTH)) { lastNewTraces[2]++; continue; }
+        shared_ptr<Feature> feat(new Feature(g.u, g.v, frame));
+        feat->score = g.score; feat->isCorner = g.is_corner != 0; feat->angle = g.angle;
+        memcpy(feat->descriptor, g.descriptor, 32);
+        // the constructor samples the host image itself; its sampling stays inside the image and its results are replaced by the device record's
+        const float uc = std::min(std::max(g.u, 8.0f), (float) w - 9), vc = std::min(std::max(g.v, 8.0f), (float) h - 9);
+        feat->uv = Vec2f(uc, vc);
+        shared_ptr<ImmaturePoint> ip(new ImmaturePoint(frame, feat, 1, calib));                       // :1280-1281
+        feat->uv = Vec2f(g.u, g.v);
+        memcpy(ip->color, q.color, sizeof(q.color)); memcpy(ip->weights, q.weights, sizeof(q.weights));
+        ip->gradH(0, 0) = q.gradH[0]; ip->gradH(0, 1) = q.gradH[1]; ip->gradH(1, 0) = q.gradH[2]; ip->gradH(1, 1) = q.gradH[3];
+        ip->energyTH = q.energyTH; ip->idepth_min = q.idepth_min; ip->idepth_max = q.idepth_max; ip->quality = q.quality;
+        ip->lastTraceStatus = (ImmaturePointStatus) q.lastTraceStatus;
+        ip->lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip->lastTracePixelInterval = q.lastTracePixelInterval;
+        feat->ip = ip;
+        frame->features.push_back(feat);
     }
 }
 

@@ -12,6 +12,7 @@
 //   GpuBackend::activatePoints(fs, ...)             the optimizeImmaturePoint loop of activatePointsMT              FullSystem.cc:892-1010,1196-1206
 //   GpuBackend::activatePointsMT(fs)                void FullSystem::activatePointsMT() with CoarseDistanceMap      FullSystem.cc:1052-1189, CoarseTracker.cc:686-818
 //   GpuBackend::traceNewCoarse(fs, fh)              void FullSystem::traceNewCoarse(shared_ptr<FrameHessian>)       FullSystem.cc:1012-1050
+//   GpuBackend::makeNewTraces(fs, fh)               void FullSystem::makeNewTraces(fh, gtDepth), pointSelection == 1 FullSystem.cc:1272-1283
 //   GpuBackend::flagPointsForRemoval(fs)            the policy of void FullSystem::flagPointsForRemoval()           FullSystem.cc:1208-1270
 //   GpuBackend::marginalizePoints(fs)               void EnergyFunctional::marginalizePointsF() + FullSystem.cc:1241-1250   EnergyFunctional.cc:165-222
 //
@@ -117,6 +118,17 @@ public:
     void traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh);
     int lastTraceCounts[6] = {0, 0, 0, 0, 0, 0};        // good, oob, outlier, skipped, bad condition, uninitialised (the function's trace_* counters)
 
+    // ---- new features of a key frame: void FullSystem::makeNewTraces(shared_ptr<FrameHessian> newFrame, float *gtDepth)   FullSystem.cc:1272-1283
+    // for setting_pointSelection == 1 (any other value throws): FeatureDetector::DetectCorners(setting_desiredImmatureDensity, frame) and the ImmaturePoint
+    // constructors as ONE device call (ldso_feat_detect on the frame's device pyramid), then frame->features filled in the reference's order - uv, score,
+    // isCorner, angle, descriptor - each with its ImmaturePoint (constructed, then its fields overwritten from the device record).  A feature whose record
+    // has a non-finite energyTH is dropped, as :1298 does for the other selection modes.  The gamma weight of absSquaredGrad follows
+    // setting_gammaWeightsPixelSelect and Hcalib->mpCH->B (FrameHessian.cc:93-97).
+    // orbPattern: the 1024 ints of ldso::bit_pattern_31_ (src/frontend/FeatureDetector.cc), set by the caller before the first call; null: descriptors stay zero.
+    const int *orbPattern = nullptr;
+    void makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame);
+    int lastNewTraces[3] = {0, 0, 0};                   // of the last makeNewTraces: features detected, corners among them, features dropped
+
     // ---- FrameHessian::dIp on the device: one ldso_pyramid_t per frame (FrameHessian.cc:44-113 on the device from the frame's irradiance, 4 bytes per pixel
     // over PCIe once per frame), shared zero-copy by the BA image slot, the tracer and both roles of the coarse trackers - as the reference shares fh->dIp by
     // pointer.  Off: every consumer uploads the host arrays it needs (12 bytes per pixel and consumer).  Pyramids of frames that left the window and are neither
@@ -131,6 +143,9 @@ private:
     static shared_ptr<PointHessian> makePoint(FullSystem &fs, const shared_ptr<internal::ImmaturePoint> &point, const ldso_activation_t &out);
     ldso_tracer_t *tracer_ = nullptr;
     int tracerCap_ = 0;
+    ldso_features_t *features_ = nullptr;
+    int featuresCap_ = 0;
+    const int *featuresPattern_ = nullptr;
     std::map<CoarseTracker *, ldso_tracker_t *> trackers_;          // the reference double-buffers two CoarseTrackers (FullSystem.h:296-297)
     std::map<unsigned long, int> slotOf_;                            // key frame (Frame::id: addresses get reused) -> image slot of the BA handle
     std::vector<long> slotOwner_;                                    // slot -> Frame::id, -1 = free

@@ -431,6 +431,9 @@ int ldso_trace_destroy(ldso_tracer_t *t);
 int ldso_trace_set_settings(ldso_tracer_t *t, const ldso_trace_settings_t *s);
 int ldso_trace_set_points(ldso_tracer_t *t, int n, const ldso_immature_t *points);
 int ldso_trace_get_points(ldso_tracer_t *t, ldso_immature_t *points_out);
+/* n records that already lie in device memory (ldso_feat_device) are copied device-to-device behind the tracer's current points: the fresh points of
+ * FullSystem::makeNewTraces (FullSystem.cc:1272-1325) never cross to the host and back.  LDSO_E_INVALID when they would exceed max_points. */
+int ldso_trace_append_points_device(ldso_tracer_t *t, int n, const void *immature_dev);
 /* the new frame: level-0 image as FrameHessian::dIp[0] (w*h*3 floats), or the raw irradiance (makeImages on the device) */
 int ldso_trace_set_frame(ldso_tracer_t *t, const float *dI_level0);
 int ldso_trace_set_frame_raw(ldso_tracer_t *t, const float *irradiance);
@@ -438,6 +441,36 @@ int ldso_trace_set_frame_pyramid(ldso_tracer_t *t, ldso_pyramid_t *pyr);
 /* per host key frame h < n_hosts (FullSystem.cc:1025-1032): KRKi[h] = K R K^-1 (row-major 3x3), Kt[h] = K t,
  * aff[h] = AffLight::fromToVecExposure(host, new).  counts_out[6] (optional): points per resulting LDSO_IPS_* status. */
 int ldso_trace_on(ldso_tracer_t *t, int n_hosts, const float *KRKi, const float *Kt, const float *aff, int *counts_out);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * New features of a key frame: FullSystem::makeNewTraces (FullSystem.cc:1272-1325) for setting_pointSelection == 1 (the default, Setting.cc:125) =
+ * FeatureDetector::DetectCorners (src/frontend/FeatureDetector.cc:34-130; ShiTomasiScore and IC_Angle: include/frontend/FeatureDetector.h:49-114;
+ * ComputeDescriptor: FeatureDetector.cc:132-189) and one ImmaturePoint constructor per feature (src/internal/ImmaturePoint.cc:14-38), on level 0 of a
+ * resident pyramid.  Features come in the reference's order (cells gx-major, gy inner, by rank inside a cell); where the reference leaves the order of
+ * equal scores to std::sort, the lower idx = y * gridsize + x comes first.  Two calls on the same input give byte-identical buffers.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct ldso_features ldso_features_t;
+/* Host only, no device: the grid of FeatureDetector.cc:37-42 for n wanted features (0 < n <= w * h).  per_cell = picks per cell (:88-91),
+ * capacity = cells visited (:44-45) * per_cell = the most features a call can return.  Every output pointer is optional. */
+int ldso_feat_grid(int w, int h, int n, int *gridsize, int *gridX, int *gridY, int *skip, int *per_cell, int *capacity);
+/* orb_pattern: the 1024 ints of ldso::bit_pattern_31_ (FeatureDetector.cc:213-471), copied; NULL: descriptors stay zero, angles are still computed */
+int ldso_feat_create(int device, int w, int h, int max_features, const int32_t *orb_pattern_1024_or_null, ldso_features_t **out);
+int ldso_feat_destroy(ldso_features_t *f);
+int ldso_feat_set_stream(ldso_features_t *f, void *hip_stream);
+/* CalibHessian::B (CalibHessian.h:138) for the gamma weight of absSquaredGrad (FrameHessian.cc:93-97, getBGradOnly: CalibHessian.h:102-111);
+ * NULL: no weighting (HCalib == 0 there), which equals the identity table */
+int ldso_feat_set_response(ldso_features_t *f, const float *B_256_or_null);
+/* DetectCorners(n_features, frame) + the ImmaturePoint constructors with host = host_index: one call, one synchronisation at its end.
+ * *n_corners_out = DetectCorners' return value.  LDSO_E_INVALID when the grid's capacity exceeds max_features, LDSO_E_UNSUPPORTED for a gridsize above 64,
+ * LDSO_E_NONFINITE when a pixel read by the selection, a score, an angle or a record's colour is not finite (the results are still there to be fetched; a
+ * NaN score never wins a comparison, a record with a non-finite colour has energyTH = NaN as ImmaturePoint.cc:28-31 leaves it: FullSystem.cc:1298 drops it). */
+int ldso_feat_detect(ldso_features_t *f, ldso_pyramid_t *pyr, int n_features, int host_index, int *n_features_out, int *n_corners_out);
+/* the results of the last ldso_feat_detect on the host (immature_out optional) / as device pointers (valid until the next detect or destroy) */
+int ldso_feat_get(ldso_features_t *f, ldso_feature_t *out, ldso_immature_t *immature_out_or_null);
+int ldso_feat_device(ldso_features_t *f, const void **features_dev, const void **immature_dev, int *n);
+/* enable != 0: ldso_feat_detect brackets its kernels with HIP events; us_out[4] (optional) = microseconds of the last profiled call:
+ * cells + compaction (FeatureDetector.cc:44-95), corners (:98-118), angle + descriptor (:120-128), records (ImmaturePoint.cc:14-38) */
+int ldso_feat_profile(ldso_features_t *f, int enable, float us_out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Monocular initialiser: CoarseInitializer (src/frontend/CoarseInitializer.cc, include/frontend/CoarseInitializer.h).

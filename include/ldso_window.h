@@ -162,6 +162,17 @@ typedef struct ldso_immature {
     int32_t pad_;
 } ldso_immature_t;                    /* 128 bytes */
 
+/* One feature of FeatureDetector::DetectCorners (src/frontend/FeatureDetector.cc:34-130): the members of ldso::Feature it fills (include/Feature.h:81-90). */
+typedef struct ldso_feature {
+    float u, v;                       /* Feature::uv (integer pixel positions)                    FeatureDetector.cc:82-85 */
+    float score;                      /* Feature::score, Shi-Tomasi                               FeatureDetector.h:49-82  */
+    float angle;                      /* Feature::angle = IC_Angle, radians; 0 unless is_corner   FeatureDetector.h:91-114 */
+    int32_t is_corner;                /* Feature::isCorner after the suppression                  FeatureDetector.cc:98-118 */
+    int32_t cell;                     /* gx * gridY + gy of the grid cell that picked it          FeatureDetector.cc:44-45 */
+    uint8_t descriptor[32];           /* Feature::descriptor; zeros unless is_corner              FeatureDetector.cc:132-189 */
+    int32_t pad_[2];
+} ldso_feature_t;                     /* 64 bytes */
+
 typedef struct ldso_trace_settings {
     float maxPixSearch;               /* 0.027   Setting.cc:28 */
     float trace_stepsize;             /* 1.0     Setting.cc:89 */

@@ -108,6 +108,69 @@ class Pyramid:
         return out
 
 
+class Features:
+    """Corner features and immature points of a new key frame (ldso_features_t): FeatureDetector::DetectCorners + the ImmaturePoint constructors."""
+
+    def __init__(self, w, h, max_features, orb_pattern=None, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        pat = None if orb_pattern is None else np.ascontiguousarray(orb_pattern, np.int32)
+        assert pat is None or pat.size == 1024
+        _chk(self.L.ldso_feat_create(C.c_int(device), C.c_int(w), C.c_int(h), C.c_int(max_features), _p(pat), C.byref(self.h)))
+        self.w, self.hh, self.n, self.n_corners = w, h, 0, 0
+
+    def close(self):
+        if self.h:
+            self.L.ldso_feat_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def grid(w, h, n):
+        """the grid rule of FeatureDetector.cc:37-42 (host only)"""
+        v = [C.c_int() for _ in range(6)]
+        _chk(lib().ldso_feat_grid(C.c_int(w), C.c_int(h), C.c_int(n), *[C.byref(x) for x in v]))
+        return dict(zip(("gridsize", "gridX", "gridY", "skip", "per_cell", "capacity"), (x.value for x in v)))
+
+    def set_stream(self, stream_ptr):
+        _chk(self.L.ldso_feat_set_stream(self.h, C.c_void_p(stream_ptr)))
+
+    def set_response(self, B):
+        b = None if B is None else np.ascontiguousarray(B, np.float32)
+        assert b is None or b.size == 256
+        _chk(self.L.ldso_feat_set_response(self.h, _p(b)))
+
+    def detect(self, pyr: "Pyramid", n_features, host_index=0):
+        """(features, corners) found; raises LdsoError (code E_NONFINITE: the results can still be fetched)"""
+        n, nc = C.c_int(), C.c_int()
+        code = self.L.ldso_feat_detect(self.h, pyr.h, C.c_int(n_features), C.c_int(host_index), C.byref(n), C.byref(nc))
+        if code in (0, E_NONFINITE):
+            self.n, self.n_corners = n.value, nc.value
+        _chk(code)
+        return self.n, self.n_corners
+
+    def get(self):
+        f = np.zeros(self.n, synth.FEATURE_DTYPE)
+        q = np.zeros(self.n, synth.IMMATURE_DTYPE)
+        _chk(self.L.ldso_feat_get(self.h, _p(f), _p(q)))
+        return f, q
+
+    def device_ptrs(self):
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_int()
+        _chk(self.L.ldso_feat_device(self.h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def profile(self, enable=True):
+        us = np.zeros(4, np.float32)
+        _chk(self.L.ldso_feat_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
+        return us
+
+
 class BA:
     """Windowed bundle adjustment handle (EnergyFunctional + FullSystem::optimize slice) on one GPU."""
 
@@ -720,6 +783,11 @@ class Tracer:
         out = np.zeros(self.n, synth.IMMATURE_DTYPE)
         _chk(self.L.ldso_trace_get_points(self.h, _p(out)))
         return out
+
+    def append_points_device(self, n, immature_dev_ptr):
+        """n immature records in device memory (Features.device_ptrs) behind the current points, device to device"""
+        _chk(self.L.ldso_trace_append_points_device(self.h, C.c_int(n), C.c_void_p(immature_dev_ptr)))
+        self.n += n
 
     def set_frame(self, dI_level0):
         a = np.ascontiguousarray(dI_level0, np.float32)

@@ -300,6 +300,18 @@ int ldso_trace_set_points(ldso_tracer_t *T, int n, const ldso_immature_t *pts) {
     return LDSO_OK;
 }
 
+// fresh immature points straight from the device (ldso_feat_device): appended behind the resident ones, stream-ordered behind the caller's work on `immature_dev`
+// only through the synchronisation its producer ended with (ldso_feat_detect synchronises before it returns)
+int ldso_trace_append_points_device(ldso_tracer_t *T, int n, const void *immature_dev) {
+    REQ(T && n >= 0 && (n == 0 || immature_dev), "ldso_trace_append_points_device: bad arguments");
+    REQ(n <= T->maxPoints - T->n, "ldso_trace_append_points_device: more points than max_points");
+    CHK(hipSetDevice(T->device));
+    if (n) CHK(hipMemcpyAsync(T->d_pts + T->n, immature_dev, (size_t) n * sizeof(ldso_immature_t), hipMemcpyDeviceToDevice, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
+    T->n += n;
+    return LDSO_OK;
+}
+
 int ldso_trace_get_points(ldso_tracer_t *T, ldso_immature_t *out) {
     REQ(T && (T->n == 0 || out), "ldso_trace_get_points: bad arguments");
     CHK(hipSetDevice(T->device));

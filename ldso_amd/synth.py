@@ -513,6 +513,12 @@ assert ACT_SEED_DTYPE.itemsize == 16
 ACT_KEEP, ACT_DROP, ACT_SELECTED = 0, 1, 2
 
 
+FEATURE_DTYPE = np.dtype([
+    ("u", "f4"), ("v", "f4"), ("score", "f4"), ("angle", "f4"), ("is_corner", "i4"), ("cell", "i4"), ("descriptor", "u1", (32,)), ("pad_", "i4", (2,)),
+], align=True)      # ldso_feature_t
+assert FEATURE_DTYPE.itemsize == 64
+
+
 def default_trace_settings():
     s = np.zeros((), TRACE_SETTINGS_DTYPE)
     s["maxPixSearch"] = 0.027; s["trace_stepsize"] = 1.0; s["trace_GNThreshold"] = 0.1; s["trace_extraSlackOnTH"] = 1.2
