@@ -130,6 +130,21 @@ int adp_make_new_traces(void *b, void *fs_, void *fh_, const int *orb_pattern, i
         })
 }
 
+// ---- raw camera frames (tests/test_undistort_adapter_gpu.py) ---------------------------------------------------------------------------------
+// GpuBackend::setUndistortion under the two settings it reads; the output size is the window's (wG[0] x hG[0])
+int adp_set_undistortion(void *b, int wOrg, int hOrg, const float *remapX, const float *remapY, const float *G, int GDepth, const float *vignetteMapInv, int photometricCalibration, int useExposure) {
+    GUARD(setting_photometricCalibration = photometricCalibration; setting_useExposure = useExposure != 0;
+          ((GpuBackend *) b)->setUndistortion(wOrg, hOrg, remapX, remapY, G, GDepth, vignetteMapInv))
+}
+// fh = ref_fs_new_frame(window, ...): its Frame::id, the key undistortFrame registers the pyramid under
+long adp_frame_id(void *fh) { return (long) (*(std::shared_ptr<FrameHessian> *) fh)->frame->id; }
+int adp_undistort_frame(void *b, long frameId, const void *raw, int bytesPerPixel, float exposure, float factor, float *hostIrradiance, float *exposureOut) {
+    GUARD(*exposureOut = ((GpuBackend *) b)->undistortFrame((unsigned long) frameId, raw, bytesPerPixel, exposure, factor, hostIrradiance))
+}
+int adp_pyr_levels_used() { return pyrLevelsUsed; }
+// level lvl of the device pyramid the backend holds for fh (built from fh->dIp[0] if there is none yet): wG[lvl] * hG[lvl] * 3 floats
+int adp_get_pyramid_level(void *b, void *fh, int lvl, float *out) { GUARD(((GpuBackend *) b)->getPyramidLevel(*(std::shared_ptr<FrameHessian> *) fh, lvl, out)) }
+
 int adp_set_device_pyramids(void *b, int on) { ((GpuBackend *) b)->useDevicePyramids = on != 0; return 0; }
 int adp_pyramids_built(void *b) { return ((GpuBackend *) b)->pyramidsBuilt; }
 int adp_set_write_back_jacobians(void *b, int on) { ((GpuBackend *) b)->writeBackJacobians = on != 0; return 0; }

@@ -104,6 +104,7 @@ GpuBackend::~GpuBackend() {
     for (auto &kv : trackers_) ldso_tr_destroy(kv.second);
     if (tracer_) ldso_trace_destroy(tracer_);
     if (features_) ldso_feat_destroy(features_);
+    if (undist_) ldso_undist_destroy(undist_);
     if (ba_) ldso_ba_destroy(ba_);
     slotPyr_.clear(); tracerPyr_.reset(); trackerPyr_.clear(); pyr_.clear();          // the pyramids, after their consumers
 }
@@ -118,7 +119,10 @@ GpuBackend::PyrRef GpuBackend::pyramidOf(const shared_ptr<FrameHessian> &fh) {
     const unsigned long id = fh->frame->id;
     std::lock_guard<std::mutex> lk(pyrMutex_);
     auto it = pyr_.find(id);
-    if (it != pyr_.end()) return it->second;
+    if (it != pyr_.end()) {
+        pendingPyr_.erase(std::remove(pendingPyr_.begin(), pendingPyr_.end(), id), pendingPyr_.end());          // the caller holds it from here on
+        return it->second;
+    }
     PyrRef e = std::make_shared<PyrHolder>();
     const size_t n = (size_t) wG[0] * hG[0];
     e->irradiance.resize(n);
@@ -132,7 +136,42 @@ GpuBackend::PyrRef GpuBackend::pyramidOf(const shared_ptr<FrameHessian> &fh) {
     return e;
 }
 
-// Frames that left the window AND that no consumer holds any more (use_count 1 = the map alone).  A consumer can only gain a reference through pyramidOf,
+// Undistort::undistort<T> (Undistort.cc:357-457) on the device, straight into the frame's pyramid
+void GpuBackend::setUndistortion(int wOrg, int hOrg, const float *remapX, const float *remapY, const float *G, int GDepth, const float *vignetteMapInv) {
+    if (undist_) { ldso_undist_destroy(undist_); undist_ = nullptr; }
+    throwOn(ldso_undist_create(device_, wOrg, hOrg, wG[0], hG[0], &undist_), "ldso_undist_create");
+    throwOn(ldso_undist_set_remap(undist_, remapX, remapY), "ldso_undist_set_remap");
+    throwOn(ldso_undist_set_photometric(undist_, G, GDepth, vignetteMapInv, setting_photometricCalibration, setting_useExposure ? 1 : 0), "ldso_undist_set_photometric");
+}
+
+float GpuBackend::undistortFrame(unsigned long frameId, const void *raw, int bytesPerPixel, float exposure, float factor, float *hostIrradiance) {
+    if (!undist_) throw std::runtime_error("GpuBackend::undistortFrame: setUndistortion has not been called");
+    PyrRef e = std::make_shared<PyrHolder>();
+    float exposureOut = exposure;
+    int rc = ldso_pyr_create(device_, wG[0], hG[0], pyrLevelsUsed, &e->p);
+    if (rc == LDSO_OK) rc = ldso_undist_frame(undist_, raw, bytesPerPixel, exposure, factor, e->p, &exposureOut);
+    throwOn(rc, "ldso_pyr_create / ldso_undist_frame");
+    if (hostIrradiance) {          // the holder's host copy only when somebody wants the image on the host
+        e->irradiance.resize((size_t) wG[0] * hG[0]);
+        throwOn(ldso_undist_get(undist_, e->irradiance.data()), "ldso_undist_get");
+        memcpy(hostIrradiance, e->irradiance.data(), e->irradiance.size() * sizeof(float));
+    }
+    std::lock_guard<std::mutex> lk(pyrMutex_);
+    pyr_[frameId] = e;
+    pendingPyr_.erase(std::remove(pendingPyr_.begin(), pendingPyr_.end(), frameId), pendingPyr_.end());
+    pendingPyr_.push_back(frameId);
+    if (pendingPyr_.size() > kMaxPending) pendingPyr_.pop_front();
+    pyramidsBuilt++;
+    return exposureOut;
+}
+
+void GpuBackend::getPyramidLevel(const shared_ptr<FrameHessian> &fh, int lvl, float *out) {
+    PyrRef pr = pyramidOf(fh);
+    throwOn(ldso_pyr_get_level(pr->p, lvl, out), "ldso_pyr_get_level");
+}
+
+// Frames that left the window AND that no consumer holds any more (use_count 1 = the map alone) AND that are not waiting for their first consumer
+// (pendingPyr_: registered by undistortFrame).  A consumer can only gain a reference through pyramidOf,
 // i.e. under pyrMutex_: a count of 1 seen here cannot grow behind our back; a consumer letting go concurrently only delays the release by one call.
 void GpuBackend::releasePyramids(FullSystem &fs) {
     std::set<unsigned long> keep;
@@ -141,7 +180,8 @@ void GpuBackend::releasePyramids(FullSystem &fs) {
     {
         std::lock_guard<std::mutex> lk(pyrMutex_);
         for (auto it = pyr_.begin(); it != pyr_.end();) {
-            if (!keep.count(it->first) && it->second.use_count() == 1) { dying.push_back(std::move(it->second)); it = pyr_.erase(it); } else ++it;
+            const bool pending = std::find(pendingPyr_.begin(), pendingPyr_.end(), it->first) != pendingPyr_.end();          // undistorted, not yet asked for
+            if (!keep.count(it->first) && !pending && it->second.use_count() == 1) { dying.push_back(std::move(it->second)); it = pyr_.erase(it); } else ++it;
         }
     }
 }

@@ -15,6 +15,7 @@
 //   GpuBackend::makeNewTraces(fs, fh)               void FullSystem::makeNewTraces(fh, gtDepth), pointSelection == 1 FullSystem.cc:1272-1283
 //   GpuBackend::flagPointsForRemoval(fs)            the policy of void FullSystem::flagPointsForRemoval()           FullSystem.cc:1208-1270
 //   GpuBackend::marginalizePoints(fs)               void EnergyFunctional::marginalizePointsF() + FullSystem.cc:1241-1250   EnergyFunctional.cc:165-222
+//   GpuBackend::undistortFrame(id, raw, ...)        ImageAndExposure *Undistort::undistort<T>(...) + makeImages     Undistort.cc:357-457
 //
 // The functions reach into private members of FullSystem / CoarseTracker (frames, ef, activeResiduals, allFrameHistory, lastCoarseRMSE,
 // shellPoseMutex ...): a maintainer makes them member functions or adds `friend class ldso::GpuBackend;` to the two classes.  The reference tree
@@ -24,6 +25,7 @@
 #include <map>
 #include <memory>
 #include <chrono>
+#include <deque>
 #include <mutex>
 #include <vector>
 
@@ -136,9 +138,26 @@ public:
     bool useDevicePyramids = true;
     int pyramidsBuilt = 0;               // statistics: pyramids built so far (one per frame seen)
 
+    // ---- raw camera frames: ImageAndExposure *Undistort::undistort<T>(image_raw, exposure, timestamp, factor)       Undistort.cc:357-457
+    // setUndistortion: the calibration as the plain arrays the reference's constructors leave (they are protected / private members, Undistort.h:55-61, :97-106:
+    // INTEGRATION.md names the two accessors a maintainer adds).  remapX / remapY: wG[0] * hG[0] floats each, both null for a passthrough undistorter;
+    // G: GDepth entries or null (no valid photometric calibration); vignetteMapInv: wOrg * hOrg floats (needed for setting_photometricCalibration == 2).
+    // setting_photometricCalibration and setting_useExposure are read here, once.
+    void setUndistortion(int wOrg, int hOrg, const float *remapX, const float *remapY, const float *G, int GDepth, const float *vignetteMapInv);
+    // undistortFrame: the raw frame (wOrg * hOrg pixels of 1 or 2 bytes) goes up, the irradiance is written into a new device pyramid and the pyramid is
+    // built behind it on the same stream, registered under frameId = Frame::id: the tracker, the tracer and the BA slot of that frame find it (pyramidOf)
+    // instead of building one from fh->dIp[0]; until the first of them has, releasePyramids() leaves it alone (for the kMaxPending most recent such
+    // frames), whichever thread runs it.  No host synchronisation unless hostIrradiance (wG[0] * hG[0] floats, optional) asks for the image.
+    // Returns ImageAndExposure::exposure_time.  One deliberate difference from the reference: a remap entry whose four taps are not all inside the raw
+    // frame gives 0, where the reference reads one row past the frame for the entry xxi == 0 && yyi == hOrg - 1 (include/ldso_hip.h).
+    float undistortFrame(unsigned long frameId, const void *raw, int bytesPerPixel, float exposure, float factor, float *hostIrradiance = nullptr);
+    // test fetch: level lvl of the frame's device pyramid ((wG[lvl] * hG[lvl] * 3 floats), built from fh->dIp[0] if the frame has none yet
+    void getPyramidLevel(const shared_ptr<FrameHessian> &fh, int lvl, float *out);
+
     const char *lastError() const;
 
 private:
+    ldso_undistorter_t *undist_ = nullptr;
     ldso_ba_t *ba_ = nullptr;
     static shared_ptr<PointHessian> makePoint(FullSystem &fs, const shared_ptr<internal::ImmaturePoint> &point, const ldso_activation_t &out);
     ldso_tracer_t *tracer_ = nullptr;
@@ -162,6 +181,12 @@ private:
     typedef std::shared_ptr<PyrHolder> PyrRef;
     std::map<unsigned long, PyrRef> pyr_;                            // Frame::id -> pyramid
     std::mutex pyrMutex_;                                            // tracking thread (new frame / reference) and mapping thread (window, tracer) share the map
+    // Frames undistortFrame registered that no consumer has asked for yet (guarded by pyrMutex_): such a frame is in no window and no consumer holds its
+    // pyramid, so releasePyramids() - the mapping thread may run it between the tracking thread's undistortFrame(id) and its trackNewCoarse(fh) - would
+    // take the map's reference for the last one.  It spares these ids; pyramidOf() takes an id off the list when it hands the pyramid out.  At most
+    // kMaxPending ids: a frame that never reaches a consumer loses the protection when kMaxPending newer frames have been registered, and is released then.
+    static constexpr size_t kMaxPending = 8;
+    std::deque<unsigned long> pendingPyr_;
     std::vector<PyrRef> slotPyr_;                                    // BA image slot -> the pyramid it aliases (mapping thread only)
     PyrRef tracerPyr_;                                               // the frame the tracer currently reads (mapping thread only)
     struct TrackerPyr { PyrRef ref, newFrame; };

@@ -473,6 +473,43 @@ int ldso_feat_device(ldso_features_t *f, const void **features_dev, const void *
 int ldso_feat_profile(ldso_features_t *f, int enable, float us_out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Raw camera frames: Undistort::undistort<T> (src/frontend/Undistort.cc:357-457) = PhotometricUndistorter::processFrame (:189-227) and the bilinear remap
+ * (:390-443) as one kernel.  The raw 8- or 16-bit frame goes up (1 or 2 bytes per pixel), the irradiance is written into a frame's pyramid and
+ * FrameHessian::makeImages follows on the same stream: the frame never exists on the host as floats.  The calibration arrives as the plain arrays the
+ * reference's constructors leave (Undistort::remapX / remapY, Undistort.h:105-106; PhotometricUndistorter::G, GDepth, vignetteMapInv, Undistort.h:56-59).
+ * The result is bit for bit what the reference returns, with ONE deliberate difference: the validity rule of the tables (:853-864) compares the row with
+ * wOrg - 1 (not hOrg - 1), so a table can hold rows at or beyond hOrg - 1; the reference's range check (:428) zeroes them except for xxi == 0 && yyi == hOrg - 1,
+ * which reads one row past the end of the source image.  Here a pixel whose four taps are not all inside the wOrg x hOrg image is 0 and nothing outside
+ * the raw buffer is read, whatever the tables hold.  benchmark_varNoise / benchmark_varBlurNoise (:376-413, :468-555; both 0 in Setting.cc) are out of scope.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct ldso_undistorter ldso_undistorter_t;
+/* wOrg x hOrg: the raw frame (Undistort::getOriginalSize), w x h: the output (getSize).  Tables are set by the two calls below before the first frame. */
+int ldso_undist_create(int device, int wOrg, int hOrg, int w, int h, ldso_undistorter_t **out);
+int ldso_undist_destroy(ldso_undistorter_t *u);
+int ldso_undist_set_stream(ldso_undistorter_t *u, void *hip_stream);
+/* Undistort::remapX / remapY (w*h floats each, copied).  Both NULL: passthrough (rectification "none", :450-452; needs w == wOrg && h == hOrg).
+ * LDSO_E_INVALID for a non-finite entry. */
+int ldso_undist_set_remap(ldso_undistorter_t *u, const float *remapX, const float *remapY);
+/* PhotometricUndistorter::G (GDepth entries, 256..65536, as the constructor :43-158 leaves them) and vignetteMapInv (wOrg*hOrg, required for mode 2), copied;
+ * G == NULL: no valid calibration (:197 `!valid`), every frame takes factor * raw.  photometricCalibration = setting_photometricCalibration (0, 1, 2),
+ * useExposure = setting_useExposure. */
+int ldso_undist_set_photometric(ldso_undistorter_t *u, const float *G, int GDepth, const float *vignetteMapInv, int photometricCalibration, int useExposure);
+/* undistort<unsigned char / unsigned short>(image_raw, exposure, timestamp, factor): raw = wOrg*hOrg pixels of bytes_per_pixel (1 | 2) bytes, copied to a pinned
+ * staging buffer before the call returns.  Copy, kernel, and - with a pyramid (w x h, same device) - its build and its `ready` event are enqueued on the
+ * undistorter's stream; no host synchronisation.  Without a pyramid the irradiance stays in the undistorter's own buffer.  *exposure_out (optional) =
+ * ImageAndExposure::exposure_time (:203, :220, :224-225).  The writes into the pyramid are ordered on the undistorter's stream only, as those of
+ * ldso_pyr_make_images are on its stream: handing in a pyramid that a consumer on another stream may still be reading is the caller's to avoid.  LDSO_E_INVALID for a 16-bit frame on a calibrated path with fewer than 65536 entries of G
+ * (the reference indexes G unchecked). */
+int ldso_undist_frame(ldso_undistorter_t *u, const void *raw, int bytes_per_pixel, float exposure, float factor, ldso_pyramid_t *pyr_or_null, float *exposure_out);
+/* the last frame's irradiance (w*h floats) on the host (synchronises) / as a device pointer: the pyramid's staging when the frame went into one (valid
+ * while that pyramid lives and holds this frame), else the undistorter's buffer (valid until the next frame) */
+int ldso_undist_get(ldso_undistorter_t *u, float *irradiance_out);
+int ldso_undist_device(ldso_undistorter_t *u, const void **dev_ptr);
+/* enable != 0: ldso_undist_frame brackets its stages with HIP events; us_out[3] (optional) = microseconds of the last profiled frame: copy of the raw
+ * frame, undistortion kernel, pyramid build (this call waits for that frame) */
+int ldso_undist_profile(ldso_undistorter_t *u, int enable, float us_out[3]);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Monocular initialiser: CoarseInitializer (src/frontend/CoarseInitializer.cc, include/frontend/CoarseInitializer.h).
  * Replaces setFirst (:547-619, minus the pixel selection and the kd-tree of makeNN, whose results arrive as the point records),
  * trackFrame (:40-178) and what it calls: calcResAndGS (:181-405), calcEC (:412-428), optReg (:430-459), propagateUp/Down

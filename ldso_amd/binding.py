@@ -171,6 +171,68 @@ class Features:
         return us
 
 
+class Undistorter:
+    """Undistort::undistort<T> on the device (ldso_undistorter_t): raw 8- / 16-bit frame in, irradiance into a Pyramid (or the handle's own buffer)."""
+
+    def __init__(self, w_org, h_org, w, h, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        _chk(self.L.ldso_undist_create(C.c_int(device), C.c_int(w_org), C.c_int(h_org), C.c_int(w), C.c_int(h), C.byref(self.h)))
+        self.w_org, self.h_org, self.w, self.hh = w_org, h_org, w, h
+
+    def close(self):
+        if self.h:
+            self.L.ldso_undist_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr):
+        _chk(self.L.ldso_undist_set_stream(self.h, C.c_void_p(stream_ptr)))
+
+    def set_remap(self, remap_x, remap_y):
+        """both None: passthrough"""
+        x = None if remap_x is None else np.ascontiguousarray(remap_x, np.float32)
+        y = None if remap_y is None else np.ascontiguousarray(remap_y, np.float32)
+        assert all(a is None or a.size == self.w * self.hh for a in (x, y))
+        _chk(self.L.ldso_undist_set_remap(self.h, _p(x), _p(y)))
+
+    def set_photometric(self, G, vignette_inv, photometric_calibration=2, use_exposure=True):
+        """G None: no valid calibration"""
+        g = None if G is None else np.ascontiguousarray(G, np.float32)
+        v = None if vignette_inv is None else np.ascontiguousarray(vignette_inv, np.float32)
+        assert v is None or v.size == self.w_org * self.h_org
+        _chk(self.L.ldso_undist_set_photometric(self.h, _p(g), C.c_int(0 if g is None else g.size), _p(v), C.c_int(photometric_calibration), C.c_int(1 if use_exposure else 0)))
+
+    def frame(self, raw, exposure=1.0, factor=1.0, pyr: "Pyramid" = None):
+        """raw: uint8 or uint16 image of the original size -> the exposure the reference would return"""
+        r = np.ascontiguousarray(raw)
+        assert r.dtype in (np.uint8, np.uint16) and r.size == self.w_org * self.h_org
+        e = C.c_float()
+        _chk(self.L.ldso_undist_frame(self.h, _p(r), C.c_int(r.dtype.itemsize), C.c_float(exposure), C.c_float(factor), pyr.h if pyr is not None else None, C.byref(e)))
+        return e.value
+
+    def get(self):
+        out = np.zeros((self.hh, self.w), np.float32)
+        _chk(self.L.ldso_undist_get(self.h, _p(out)))
+        return out
+
+    def device_ptr(self):
+        p = C.c_void_p()
+        _chk(self.L.ldso_undist_device(self.h, C.byref(p)))
+        return p.value
+
+    def profile(self, enable=True):
+        """microseconds of the last profiled frame: copy, undistortion kernel, pyramid build"""
+        us = np.zeros(3, np.float32)
+        _chk(self.L.ldso_undist_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
+        return us
+
+
 class BA:
     """Windowed bundle adjustment handle (EnergyFunctional + FullSystem::optimize slice) on one GPU."""
 
