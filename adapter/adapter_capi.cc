@@ -157,6 +157,31 @@ int adp_marg_frame_counts(void *b, int *device, int *hostFallback) { *device = (
 int adp_last_optimize_times(void *b, double *out4) { for (int i = 0; i < 4; i++) out4[i] = ((GpuBackend *) b)->lastOptimizeSeconds[i]; return 0; }
 int adp_last_upload_times(void *b, double *out6) { for (int i = 0; i < 6; i++) out6[i] = ((GpuBackend *) b)->lastUploadSeconds[i]; return 0; }
 
+// ---- the immature set resident on the device (GpuBackend::residentImmature; tests/test_immature_resident_*.py) -----------------------------------------------
+// the three entries refuse a missing backend / graph / output with LDSO_E_INVALID and touch nothing
+int adp_set_resident_immature(void *b, int on) { if (!b) return LDSO_E_INVALID; ((GpuBackend *) b)->residentImmature = on != 0; return 0; }
+// GpuBackend::syncImmaturePoints: the device's trace state into the ImmaturePoint objects
+int adp_sync_immature(void *b, void *fs) { if (!b || !fs) return LDSO_E_INVALID; GUARD(((GpuBackend *) b)->syncImmaturePoints(*(FullSystem *) fs)) }
+// how the reconcile steps of this backend went: [rows unchanged, one compaction, full upload]
+int adp_immature_reconcile_counts(void *b, int *out3) { if (!b || !out3) return LDSO_E_INVALID; for (int i = 0; i < 3; i++) out3[i] = ((GpuBackend *) b)->immatureReconcile[i]; return 0; }
+
+// a new tracer of this backend holds at least n records (GpuBackend::tracerMinCapacity): a small value lets a test reach the path on which the tracer has to grow
+int adp_set_tracer_min_capacity(void *b, int n) { if (!b || n < 1) return LDSO_E_INVALID; ((GpuBackend *) b)->tracerMinCapacity = n; return 0; }
+// GpuBackend::makeNewTraces on key frame frameIdx of the window, behind the features it already has (adp_make_new_traces clears them and takes a frame from
+// ref_fs_new_frame): the new immature points are hosted by a frame of the window, so the traces and activations that follow see them.  counts[4] as there.
+int adp_make_new_traces_window(void *b, void *fs_, int frameIdx, const int *orb_pattern, int n_desired, int *counts) {
+    if (!b || !fs_ || !counts) return LDSO_E_INVALID;
+    GUARD(
+        GpuBackend &B = *(GpuBackend *) b; FullSystem &fs = *(FullSystem *) fs_;
+        if (frameIdx < 0 || frameIdx >= (int) fs.frames.size()) throw std::runtime_error("adp_make_new_traces_window: no such key frame");
+        setting_pointSelection = 1; setting_desiredImmatureDensity = n_desired; setting_gammaWeightsPixelSelect = 1;
+        B.orbPattern = orb_pattern;
+        shared_ptr<FrameHessian> fh = fs.frames[frameIdx]->frameHessian;
+        B.makeNewTraces(fs, fh);
+        for (int i = 0; i < 3; i++) counts[i] = B.lastNewTraces[i];
+        counts[3] = (int) fh->frame->features.size())
+}
+
 // ---- one key frame in the order of FullSystem::makeKeyFrame (FullSystem.cc:410-640) on a reference object graph -----------------------------
 // b == nullptr: the reference's own members everywhere.  b != nullptr: GpuBackend::traceNewCoarse / activatePoints / optimize in place of
 // FullSystem::traceNewCoarse (:429), the optimizeImmaturePoint loop of activatePointsMT (:1157-1166) and FullSystem::optimize (:478); everything

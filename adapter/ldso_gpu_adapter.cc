@@ -759,8 +759,7 @@ static void fillRecord(ldso_immature_t &q, const Feature &feat, const ImmaturePo
 // the immature points of :1088-1102 (idxInImmaturePoints set as there), the per-host K[1] R Ki[0] / K[1] t of :1092-1094 by the reference's own expressions
 // (after coarseDistanceMap->makeK, :1081) and the hosts' flaggedForMarginalization.
 // ------------------------------------------------------------------------------------------------------------------------------------
-void GpuBackend::gatherSelection(FullSystem &fs, SelectionInputs &in) {
-    in.seeds.clear(); in.cand.clear(); in.myType.clear(); in.who.clear();
+void GpuBackend::selectionPoses(FullSystem &fs, SelectionInputs &in) {
     const int F = (int) fs.frames.size();
     in.KRKi.assign((size_t) F * 9, 0.0f); in.Kt.assign((size_t) F * 3, 0.0f); in.flagged.assign(F, 0);
     fs.coarseDistanceMap->makeK(fs.Hcalib->mpCH);
@@ -773,6 +772,17 @@ void GpuBackend::gatherSelection(FullSystem &fs, SelectionInputs &in) {
         Mat33f KRKi = (fs.coarseDistanceMap->K[1] * fhToNew.rotationMatrix().cast<float>() * fs.coarseDistanceMap->Ki[0]);
         Vec3f Kt = (fs.coarseDistanceMap->K[1] * fhToNew.translation().cast<float>());
         for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) in.KRKi[(size_t) f * 9 + r * 3 + c] = KRKi(r, c); in.Kt[(size_t) f * 3 + r] = Kt[r]; }
+    }
+}
+
+void GpuBackend::gatherSelection(FullSystem &fs, SelectionInputs &in) {
+    in.seeds.clear(); in.cand.clear(); in.myType.clear(); in.who.clear();
+    const int F = (int) fs.frames.size();
+    selectionPoses(fs, in);
+    shared_ptr<FrameHessian> newest = fs.frames.back()->frameHessian;
+    for (int f = 0; f < F; f++) {
+        shared_ptr<FrameHessian> host = fs.frames[f]->frameHessian;
+        if (host == newest) continue;
         for (auto &feat : host->frame->features)
             if (feat->point && feat->point->status == Point::PointStatus::ACTIVE) {
                 auto ph = feat->point->mpPH;
@@ -799,19 +809,46 @@ void GpuBackend::activatePointsMT(FullSystem &fs) {
     throwOn(ldso_act_update_min_dist(fs.currentMinActDist, fs.ef->nPoints, setting_desiredPointDensity, &fs.currentMinActDist), "ldso_act_update_min_dist");
     // :1075-1102 what the selection reads
     SelectionInputs in;
-    gatherSelection(fs, in);
-    lastSelection[0] = (int) in.cand.size(); lastSelection[1] = lastSelection[2] = 0;
-    if (in.cand.empty()) return;
-    std::vector<shared_ptr<PointHessian>> allPoints;
-    if (uploadWindow(fs, allPoints) == 0) throw std::runtime_error("GpuBackend::activatePointsMT: the window holds no active point yet (activate on the host)");
-    // :1080-1164 distance map, selection and optimizeImmaturePoint of the selected points: one enqueue, one wait
-    const int n = (int) in.cand.size();
-    std::vector<int32_t> decision(n), selected(n);
-    std::vector<ldso_activation_t> out(n);
-    int nSel = 0;
-    throwOn(ldso_ba_select_activate_points(ba_, (int) in.seeds.size(), in.seeds.data(), n, in.cand.data(), in.myType.data(), (int) fs.frames.size(), in.KRKi.data(), in.Kt.data(),
-                                           in.flagged.data(), fs.currentMinActDist, setting_minTraceQuality, /*minObs*/ 1, setting_minIdepthH_act, setting_GNItsOnPointActivation,
-                                           decision.data(), selected.data(), &nSel, out.data()), "ldso_ba_select_activate_points");
+    std::vector<int32_t> decision, selected;
+    std::vector<ldso_activation_t> out;
+    int n = 0, nSel = 0;
+    lastSelection[0] = lastSelection[1] = lastSelection[2] = 0;
+    if (residentImmature) {
+        // the candidates are the tracer's rows, the seeds the resident window's points: only the poses and flags are gathered, nothing of the set goes up
+        reconcileImmature(fs, true);
+        const int F = (int) fs.frames.size();
+        n = (int) who_.size();
+        for (int i = 0; i < n; i++) if (whoHost_[i] != F - 1) lastSelection[0]++;
+        if (lastSelection[0] == 0) return;
+        selectionPoses(fs, in);
+        std::vector<shared_ptr<PointHessian>> allPoints;
+        if (uploadWindow(fs, allPoints) == 0) throw std::runtime_error("GpuBackend::activatePointsMT: the window holds no active point yet (activate on the host)");
+        decision.resize(n); selected.resize(n); out.resize(n);
+        int nLeft = 0;
+        try {
+            throwOn(ldso_ba_select_activate_tracer(ba_, tracer_, F, in.KRKi.data(), in.Kt.data(), in.flagged.data(), fs.currentMinActDist, setting_minTraceQuality, /*minObs*/ 1,
+                                                   setting_minIdepthH_act, setting_GNItsOnPointActivation, /*compact*/ 1, decision.data(), selected.data(), &nSel, out.data(), &nLeft),
+                    "ldso_ba_select_activate_tracer");
+        } catch (...) { who_.clear(); whoHost_.clear(); throw; }          // the tracer may or may not have compacted: forget the rows, the next reconcile uploads the set
+        in.who = who_;
+        // the rows the device kept: the same decisions compact the host's view of them
+        size_t k = 0;
+        for (int i = 0; i < n; i++) if (decision[i] == LDSO_ACT_KEEP) { who_[k] = who_[i]; whoHost_[k] = whoHost_[i]; k++; }
+        who_.resize(k); whoHost_.resize(k);
+        if ((int) k != nLeft) { who_.clear(); whoHost_.clear(); throw std::runtime_error("GpuBackend::activatePointsMT: the tracer's count after the compaction differs from the decisions'"); }
+    } else {
+        gatherSelection(fs, in);
+        lastSelection[0] = (int) in.cand.size();
+        if (in.cand.empty()) return;
+        std::vector<shared_ptr<PointHessian>> allPoints;
+        if (uploadWindow(fs, allPoints) == 0) throw std::runtime_error("GpuBackend::activatePointsMT: the window holds no active point yet (activate on the host)");
+        // :1080-1164 distance map, selection and optimizeImmaturePoint of the selected points: one enqueue, one wait
+        n = (int) in.cand.size();
+        decision.resize(n); selected.resize(n); out.resize(n);
+        throwOn(ldso_ba_select_activate_points(ba_, (int) in.seeds.size(), in.seeds.data(), n, in.cand.data(), in.myType.data(), (int) fs.frames.size(), in.KRKi.data(), in.Kt.data(),
+                                               in.flagged.data(), fs.currentMinActDist, setting_minTraceQuality, /*minObs*/ 1, setting_minIdepthH_act, setting_GNItsOnPointActivation,
+                                               decision.data(), selected.data(), &nSel, out.data()), "ldso_ba_select_activate_points");
+    }
     lastSelection[1] = nSel;
     // :1105-1108, :1121-1125, :1145-1148 the candidates the loop deletes
     for (int i = 0; i < n; i++)
@@ -844,32 +881,116 @@ void GpuBackend::activatePointsMT(FullSystem &fs) {
 // Every immature point of the window's key frames is traced into the new frame by one ldso_trace_on call (one wavefront per point);
 // the per-host KRKi / Kt / affine transfer are formed here exactly as the reference forms them (its own Eigen / Sophus expressions).
 // ------------------------------------------------------------------------------------------------------------------------------------
+static void writeTraceState(ImmaturePoint &ip, const ldso_immature_t &q) {          // what ImmaturePoint::traceOn leaves in the object (ImmaturePoint.cc:47-310)
+    ip.idepth_min = q.idepth_min; ip.idepth_max = q.idepth_max; ip.quality = q.quality;
+    ip.lastTraceStatus = (ImmaturePointStatus) q.lastTraceStatus;
+    ip.lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip.lastTracePixelInterval = q.lastTracePixelInterval;
+}
+
+// a tracer that holds `capacity` records; a new one starts empty, so the rows the backend remembers are forgotten with the old one
+void GpuBackend::ensureTracer(int capacity) {
+    if (tracer_ && capacity <= tracerCap_) return;
+    if (tracer_) ldso_trace_destroy(tracer_);
+    tracer_ = nullptr;
+    who_.clear(); whoHost_.clear();
+    tracerCap_ = std::max(capacity * 2, tracerMinCapacity);
+    throwOn(ldso_trace_create(device_, wG[0], hG[0], tracerCap_, &tracer_), "ldso_trace_create");
+}
+
+// the device's records into the objects of the rows (alive: only rows i with (*alive)[i] != 0)
+void GpuBackend::downloadImmature(const std::vector<char> *alive) {
+    if (!tracer_ || who_.empty()) return;
+    std::vector<ldso_immature_t> rec(who_.size());
+    throwOn(ldso_trace_get_points(tracer_, rec.data()), "ldso_trace_get_points");
+    for (size_t i = 0; i < who_.size(); i++) if (!alive || (*alive)[i]) writeTraceState(*who_[i], rec[i]);
+}
+
+void GpuBackend::syncImmaturePoints(FullSystem &fs) {
+    unique_lock<mutex> lock(fs.mapMutex);
+    downloadImmature(nullptr);
+}
+
+// resident mode: bring the tracer's rows in line with the immature points of the graph (ldso_gpu_adapter.h: the three outcomes)
+void GpuBackend::reconcileImmature(FullSystem &fs, bool setIdxInImmaturePoints) {
+    const int F = (int) fs.frames.size();
+    std::vector<shared_ptr<ImmaturePoint>> cur;
+    std::vector<int> curHost;
+    for (int f = 0; f < F; f++) {
+        auto &features = fs.frames[f]->features;
+        for (size_t i = 0; i < features.size(); i++) {
+            shared_ptr<Feature> &feat = features[i];
+            if (!(feat->status == Feature::FeatureStatus::IMMATURE && feat->ip)) continue;
+            if (setIdxInImmaturePoints && f != F - 1) feat->ip->idxInImmaturePoints = i;           // :1102
+            cur.push_back(feat->ip); curHost.push_back(f);
+        }
+    }
+    if (tracer_ && cur == who_ && curHost == whoHost_) { immatureReconcile[0]++; return; }
+    // an ordered subsequence of the rows, under ONE map of the host indices?
+    const size_t nRows = who_.size();
+    std::vector<uint8_t> keep(nRows, 0);
+    int32_t hostMap[LDSO_MAX_FRAMES];
+    for (int f = 0; f < LDSO_MAX_FRAMES; f++) hostMap[f] = -1;
+    bool subsequence = tracer_ != nullptr && cur.size() <= nRows;
+    size_t row = 0;
+    for (size_t k = 0; subsequence && k < cur.size(); k++) {
+        while (row < nRows && who_[row] != cur[k]) row++;
+        if (row == nRows) { subsequence = false; break; }
+        const int oldHost = whoHost_[row];
+        if (oldHost < 0 || oldHost >= LDSO_MAX_FRAMES || (hostMap[oldHost] >= 0 && hostMap[oldHost] != curHost[k])) { subsequence = false; break; }
+        hostMap[oldHost] = curHost[k];
+        keep[row++] = 1;
+    }
+    if (subsequence) {
+        int nLeft = 0;
+        try {
+            throwOn(ldso_trace_compact(tracer_, keep.data(), LDSO_MAX_FRAMES, hostMap, &nLeft), "ldso_trace_compact");
+            if (nLeft != (int) cur.size()) throw std::runtime_error("GpuBackend: the tracer's count after the compaction differs from the graph's");
+        } catch (...) { who_.clear(); whoHost_.clear(); throw; }
+        who_.swap(cur); whoHost_.swap(curHost);
+        immatureReconcile[1]++;
+        return;
+    }
+    // the host holds points the device has not seen: what the device knows goes into the objects that are still there, then everything goes up
+    if (tracer_ && !who_.empty()) {
+        std::vector<ImmaturePoint *> sorted;
+        for (auto &p : cur) sorted.push_back(p.get());
+        std::sort(sorted.begin(), sorted.end());
+        std::vector<char> alive(nRows);
+        for (size_t i = 0; i < nRows; i++) alive[i] = std::binary_search(sorted.begin(), sorted.end(), who_[i].get()) ? 1 : 0;
+        downloadImmature(&alive);
+    }
+    who_.clear(); whoHost_.clear();
+    immatureReconcile[2]++;
+    if (cur.empty()) { if (tracer_) throwOn(ldso_trace_set_points(tracer_, 0, nullptr), "ldso_trace_set_points"); return; }
+    ensureTracer((int) cur.size());
+    std::vector<ldso_immature_t> rec(cur.size());
+    std::vector<float> types(cur.size());
+    for (size_t k = 0; k < cur.size(); k++) { fillRecord(rec[k], *cur[k]->feature, *cur[k], curHost[k]); types[k] = cur[k]->my_type; }
+    throwOn(ldso_trace_set_points(tracer_, (int) rec.size(), rec.data()), "ldso_trace_set_points");
+    throwOn(ldso_trace_set_point_types(tracer_, types.data()), "ldso_trace_set_point_types");
+    who_.swap(cur); whoHost_.swap(curHost);
+}
+
 void GpuBackend::traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh) {
     unique_lock<mutex> lock(fs.mapMutex);
     for (int i = 0; i < 6; i++) lastTraceCounts[i] = 0;
     const int F = (int) fs.frames.size();
     std::vector<ldso_immature_t> rec;
     std::vector<ImmaturePoint *> who;
-    for (int f = 0; f < F; f++)
-        for (auto &feat : fs.frames[f]->features) {
-            if (!(feat->status == Feature::FeatureStatus::IMMATURE && feat->ip)) continue;
-            ImmaturePoint &ip = *feat->ip;
-            ldso_immature_t q;
-            memset(&q, 0, sizeof(q));
-            q.u = feat->uv[0]; q.v = feat->uv[1];
-            memcpy(q.color, ip.color, sizeof(q.color)); memcpy(q.weights, ip.weights, sizeof(q.weights));
-            q.gradH[0] = ip.gradH(0, 0); q.gradH[1] = ip.gradH(0, 1); q.gradH[2] = ip.gradH(1, 0); q.gradH[3] = ip.gradH(1, 1);
-            q.energyTH = ip.energyTH; q.idepth_min = ip.idepth_min; q.idepth_max = ip.idepth_max; q.quality = ip.quality;
-            q.lastTraceStatus = (int32_t) ip.lastTraceStatus; q.lastTraceUV[0] = ip.lastTraceUV[0]; q.lastTraceUV[1] = ip.lastTraceUV[1];
-            q.lastTracePixelInterval = ip.lastTracePixelInterval; q.host = f;
-            rec.push_back(q); who.push_back(&ip);
-        }
-    if (rec.empty()) return;
-    if (!tracer_ || (int) rec.size() > tracerCap_) {
-        if (tracer_) ldso_trace_destroy(tracer_);
-        tracer_ = nullptr;
-        tracerCap_ = std::max((int) rec.size() * 2, 16384);
-        throwOn(ldso_trace_create(device_, wG[0], hG[0], tracerCap_, &tracer_), "ldso_trace_create");
+    if (residentImmature) {
+        reconcileImmature(fs, false);
+        if (who_.empty()) return;
+    } else {
+        for (int f = 0; f < F; f++)
+            for (auto &feat : fs.frames[f]->features) {
+                if (!(feat->status == Feature::FeatureStatus::IMMATURE && feat->ip)) continue;
+                ldso_immature_t q;
+                fillRecord(q, *feat, *feat->ip, f);
+                rec.push_back(q); who.push_back(feat->ip.get());
+            }
+        if (rec.empty()) return;
+        ensureTracer((int) rec.size());
+        who_.clear(); whoHost_.clear();                  // ldso_trace_set_points below replaces whatever rows a resident phase left
     }
     ldso_trace_settings_t ts;
     ldso_trace_settings_default(&ts);
@@ -891,17 +1012,13 @@ void GpuBackend::traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh) {
         for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) KRKi[(size_t) f * 9 + r * 3 + c] = M(r, c); Kt[(size_t) f * 3 + r] = t[r]; }
         aff[(size_t) f * 2] = a[0]; aff[(size_t) f * 2 + 1] = a[1];
     }
-    throwOn(ldso_trace_set_points(tracer_, (int) rec.size(), rec.data()), "ldso_trace_set_points");
+    if (!residentImmature) throwOn(ldso_trace_set_points(tracer_, (int) rec.size(), rec.data()), "ldso_trace_set_points");
     if (useDevicePyramids && fh->frame) { tracerPyr_ = pyramidOf(fh); throwOn(ldso_trace_set_frame_pyramid(tracer_, tracerPyr_->p), "ldso_trace_set_frame_pyramid"); }
     else throwOn(ldso_trace_set_frame(tracer_, (const float *) fh->dIp[0]), "ldso_trace_set_frame");
     throwOn(ldso_trace_on(tracer_, F, KRKi.data(), Kt.data(), aff.data(), lastTraceCounts), "ldso_trace_on");
+    if (residentImmature) return;                      // the records stay where they are: syncImmaturePoints brings them over on demand
     throwOn(ldso_trace_get_points(tracer_, rec.data()), "ldso_trace_get_points");
-    for (size_t i = 0; i < rec.size(); i++) {          // what ImmaturePoint::traceOn leaves in the object (ImmaturePoint.cc:47-310)
-        ImmaturePoint &ip = *who[i]; const ldso_immature_t &q = rec[i];
-        ip.idepth_min = q.idepth_min; ip.idepth_max = q.idepth_max; ip.quality = q.quality;
-        ip.lastTraceStatus = (ImmaturePointStatus) q.lastTraceStatus;
-        ip.lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip.lastTracePixelInterval = q.lastTracePixelInterval;
-    }
+    for (size_t i = 0; i < rec.size(); i++) writeTraceState(*who[i], rec[i]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -914,6 +1031,7 @@ void GpuBackend::makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame
     throwOn(ldso_feat_grid(w, h, want, nullptr, nullptr, nullptr, nullptr, nullptr, &capacity), "ldso_feat_grid");
     for (int i = 0; i < 3; i++) lastNewTraces[i] = 0;
     shared_ptr<Frame> frame = newFrame->frame;
+    if (residentImmature) reconcileImmature(fs, false);                                              // the rows in line with the graph before the new ones follow them
     frame->features.reserve(want);                                                                   // :1276
     if (capacity == 0) return;
     if (!features_ || capacity > featuresCap_ || featuresPattern_ != orbPattern) {
@@ -934,6 +1052,7 @@ void GpuBackend::makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame
     std::vector<ldso_immature_t> rec((size_t) n);
     throwOn(ldso_feat_get(features_, feats.data(), rec.data()), "ldso_feat_get");
     lastNewTraces[0] = n; lastNewTraces[1] = nCorners;
+    std::vector<shared_ptr<ImmaturePoint>> fresh;
     for (int i = 0; i < n; i++) {
         const ldso_feature_t &g = feats[i]; const ldso_immature_t &q = rec[i];
         if (!std::isfinite(q.energyTH)) { lastNewTraces[2]++; continue; }
@@ -952,7 +1071,34 @@ void GpuBackend::makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame
         ip->lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip->lastTracePixelInterval = q.lastTracePixelInterval;
         feat->ip = ip;
         frame->features.push_back(feat);
+        fresh.push_back(ip);
     }
+    if (!residentImmature || n == 0) return;
+    // the records never leave the device: appended behind the tracer's rows as they lie in the detector's buffer, the dropped ones compacted away
+    const int need = (int) who_.size() + n;
+    if (tracer_ && need > tracerCap_ && !who_.empty()) {
+        // the tracer has to grow: its state goes into the objects, and the next reconcile uploads the whole set (the new objects hold their records already)
+        downloadImmature(nullptr);
+        ensureTracer(need);
+        return;
+    }
+    ensureTracer(need);
+    const void *featDev = nullptr, *immDev = nullptr;
+    int nDev = 0;
+    throwOn(ldso_feat_device(features_, &featDev, &immDev, &nDev), "ldso_feat_device");
+    if (nDev != n) throw std::runtime_error("GpuBackend::makeNewTraces: the detector's device buffer does not hold the features it reported");
+    // from here to the end the tracer's count and the row list move together: a failure in between forgets the rows, and the next reconcile uploads the set anew
+    try {
+        throwOn(ldso_trace_append_points_device(tracer_, n, immDev), "ldso_trace_append_points_device");
+        if (lastNewTraces[2] > 0) {
+            std::vector<uint8_t> keep(who_.size() + (size_t) n, 1);
+            for (int i = 0; i < n; i++) if (!std::isfinite(rec[i].energyTH)) keep[who_.size() + i] = 0;
+            int nLeft = 0;
+            throwOn(ldso_trace_compact(tracer_, keep.data(), LDSO_MAX_FRAMES, nullptr, &nLeft), "ldso_trace_compact");
+            if (nLeft != (int) (who_.size() + fresh.size())) throw std::runtime_error("GpuBackend::makeNewTraces: the tracer's count after the compaction differs from the features kept");
+        }
+    } catch (...) { who_.clear(); whoHost_.clear(); throw; }
+    for (auto &ip : fresh) { who_.push_back(ip); whoHost_.push_back(hostIdx); }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------

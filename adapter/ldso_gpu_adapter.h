@@ -13,6 +13,7 @@
 //   GpuBackend::activatePointsMT(fs)                void FullSystem::activatePointsMT() with CoarseDistanceMap      FullSystem.cc:1052-1189, CoarseTracker.cc:686-818
 //   GpuBackend::traceNewCoarse(fs, fh)              void FullSystem::traceNewCoarse(shared_ptr<FrameHessian>)       FullSystem.cc:1012-1050
 //   GpuBackend::makeNewTraces(fs, fh)               void FullSystem::makeNewTraces(fh, gtDepth), pointSelection == 1 FullSystem.cc:1272-1283
+//   GpuBackend::residentImmature / syncImmaturePoints   the three members above with the immature set resident on the device (no reference counterpart)
 //   GpuBackend::flagPointsForRemoval(fs)            the policy of void FullSystem::flagPointsForRemoval()           FullSystem.cc:1208-1270
 //   GpuBackend::marginalizePoints(fs)               void EnergyFunctional::marginalizePointsF() + FullSystem.cc:1241-1250   EnergyFunctional.cc:165-222
 //   GpuBackend::undistortFrame(id, raw, ...)        ImageAndExposure *Undistort::undistort<T>(...) + makeImages     Undistort.cc:357-457
@@ -115,10 +116,33 @@ public:
         std::vector<shared_ptr<internal::ImmaturePoint>> who;
     };
     static void gatherSelection(FullSystem &fs, SelectionInputs &in);
+    // of that, the per-host part alone: KRKi / Kt of host -> newest frame (:1092-1094) and the hosts' flaggedForMarginalization
+    static void selectionPoses(FullSystem &fs, SelectionInputs &in);
 
     // ---- immature-point tracing: void FullSystem::traceNewCoarse(shared_ptr<FrameHessian> fh)                   FullSystem.cc:1012-1050
     void traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh);
     int lastTraceCounts[6] = {0, 0, 0, 0, 0, 0};        // good, oob, outlier, skipped, bad condition, uninitialised (the function's trace_* counters)
+
+    // ---- the immature set RESIDENT on the device from detection through activation ------------------------------------------------------------------------
+    // Off (default): every member above and below does what it always did - traceNewCoarse and activatePointsMT flatten every ImmaturePoint of the window,
+    // upload the records, and traceNewCoarse downloads them again and writes six fields back into every object.
+    // On: the tracer owns the set.  The backend remembers which ImmaturePoint every tracer row belongs to; a RECONCILE step at the head of traceNewCoarse,
+    // activatePointsMT and makeNewTraces walks the graph (pointers only) and compares:
+    //   - the graph's list equals the rows, host indices unchanged                      nothing is uploaded                          immatureReconcile[0]
+    //   - it is an ordered subsequence of the rows (points released by host code, a frame marginalised, host indices shifted)
+    //                                                                                   one ldso_trace_compact (mask + host map)     immatureReconcile[1]
+    //   - anything else (the host created points the device has not seen, the tracer was re-created, the mode was just switched on)
+    //                                  the device records are written into the surviving objects, then everything goes up anew        immatureReconcile[2]
+    // traceNewCoarse then only sends the poses and traces (no record crosses PCIe, no object is written: lastTraceCounts as before); activatePointsMT runs
+    // ldso_ba_select_activate_tracer with the compaction by its decisions and does the host hand-over.  makePoint uses the constructor's fields of an
+    // ImmaturePoint; CreateFromImmature's PointHessian constructor also reads the STALE idepth_min / idepth_max (PointHessian.cc:14), which is harmless only
+    // because makePoint overwrites the inverse depth with setIdepthZero / setIdepth right after - a makePoint that starts to use trace state needs a sync first; makeNewTraces appends the new records device to device.  Between two syncImmaturePoints calls the six fields traceOn writes (idepth_min,
+    // idepth_max, quality, lastTraceStatus, lastTraceUV, lastTracePixelInterval) are current on the DEVICE only: host code that reads them (a viewer, a switch
+    // back to the host path with the flag off) calls syncImmaturePoints first.
+    bool residentImmature = false;
+    int tracerMinCapacity = 16384;                   // records a new tracer holds at least (it is created with twice what is needed, or this)
+    int immatureReconcile[3] = {0, 0, 0};
+    void syncImmaturePoints(FullSystem &fs);
 
     // ---- new features of a key frame: void FullSystem::makeNewTraces(shared_ptr<FrameHessian> newFrame, float *gtDepth)   FullSystem.cc:1272-1283
     // for setting_pointSelection == 1 (any other value throws): FeatureDetector::DetectCorners(setting_desiredImmatureDensity, frame) and the ImmaturePoint
@@ -162,6 +186,13 @@ private:
     static shared_ptr<PointHessian> makePoint(FullSystem &fs, const shared_ptr<internal::ImmaturePoint> &point, const ldso_activation_t &out);
     ldso_tracer_t *tracer_ = nullptr;
     int tracerCap_ = 0;
+    // resident mode: the ImmaturePoint of every tracer row in order (held: a released point's address must not come back as a new one's), and the host index
+    // the device record carries
+    std::vector<shared_ptr<internal::ImmaturePoint>> who_;
+    std::vector<int> whoHost_;
+    void reconcileImmature(FullSystem &fs, bool setIdxInImmaturePoints);
+    void ensureTracer(int capacity);
+    void downloadImmature(const std::vector<char> *alive);
     ldso_features_t *features_ = nullptr;
     int featuresCap_ = 0;
     const int *featuresPattern_ = nullptr;

@@ -434,6 +434,30 @@ int ldso_trace_get_points(ldso_tracer_t *t, ldso_immature_t *points_out);
 /* n records that already lie in device memory (ldso_feat_device) are copied device-to-device behind the tracer's current points: the fresh points of
  * FullSystem::makeNewTraces (FullSystem.cc:1272-1325) never cross to the host and back.  LDSO_E_INVALID when they would exceed max_points. */
 int ldso_trace_append_points_device(ldso_tracer_t *t, int n, const void *immature_dev);
+/* ImmaturePoint::my_type (ImmaturePoint.h:114; the factor on currentMinActDist, FullSystem.cc:1141) travels with the record, in an array of the tracer's own beside
+ * the records: ldso_trace_set_points resets it to 1 for its n records, ldso_trace_append_points_device sets 1 for the appended ones (FullSystem.cc:1281 constructs
+ * the points of setting_pointSelection == 1 with my_type = 1).  my_type / out: one float per current record. */
+int ldso_trace_set_point_types(ldso_tracer_t *t, const float *my_type);
+int ldso_trace_get_point_types(ldso_tracer_t *t, float *out);
+/* What leaves the immature set leaves it on the device: a STABLE compaction of the records and their types.  Record i stays iff keep[i] != 0 (keep: n bytes of
+ * host memory, NULL: all kept) and host_map[record.host] >= 0 (host_map: n_hosts entries, NULL: the identity); a record whose host is outside [0, n_hosts) is
+ * dropped, not dereferenced.  A surviving record gets host = host_map[host]: one call covers points released by host code (FullSystem.cc:1105-1188), the points
+ * of a marginalised frame (FullSystem.cc:602-645) and the shift of the host indices behind it.  The survivors keep their relative order - the reference's
+ * iteration order (FullSystem.cc:1088-1098), on which the greedy selection depends.  The records move out of place into a second buffer of the tracer's and
+ * the two swap.  One synchronisation, behind which *n_out (optional) = the new count. */
+int ldso_trace_compact(ldso_tracer_t *t, const uint8_t *keep_or_null, int n_hosts, const int32_t *host_map_or_null, int *n_out);
+/* ldso_ba_select_activate_points (FullSystem.cc:1080-1164) with the immature set where it lives: the candidates are the tracer's records and types, in their
+ * order, the seeds every point of the handle's resident window whose host is not the newest frame, at its CURRENT inverse depth (PointHessian::idepth_scaled,
+ * CoarseTracker.cc:706-709).  Only KRKi / Kt / host_flagged go up.  A record hosted by frame n_hosts - 1 is no candidate (the loop skips the newest frame,
+ * :1089): its decision is LDSO_ACT_KEEP and it is not touched.  A candidate or window point whose host is no frame of the window is dropped / skipped by the
+ * kernel.  compact != 0: every record whose decision is not LDSO_ACT_KEEP leaves the tracer's set in the same enqueue - the deleted candidates and every
+ * SELECTED one, whether optimizeImmaturePoint accepts it or not (:1170-1187).  decision_out / selected_out / out: n = the tracer's count before the call, as
+ * ldso_ba_select_activate_points; *n_left_out (optional) = its count afterwards.  ldso_ba_get_distance_map works as after the explicit call.
+ * Preconditions beyond ldso_ba_select_activate_points': an unsharded window, n_hosts = its frame count, tracer and handle on one device, the tracer idle (all of
+ * its entry points synchronise before they return).  A violation gives LDSO_E_INVALID before anything is launched.  Runs on the handle's stream, one wait. */
+int ldso_ba_select_activate_tracer(ldso_ba_t *h, ldso_tracer_t *t, int n_hosts, const float *KRKi, const float *Kt, const int32_t *host_flagged,
+                                   float currentMinActDist, float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations, int compact,
+                                   int32_t *decision_out /*n*/, int32_t *selected_out /*n*/, int *n_selected_out, ldso_activation_t *out /*n*/, int *n_left_out);
 /* the new frame: level-0 image as FrameHessian::dIp[0] (w*h*3 floats), or the raw irradiance (makeImages on the device) */
 int ldso_trace_set_frame(ldso_tracer_t *t, const float *dI_level0);
 int ldso_trace_set_frame_raw(ldso_tracer_t *t, const float *irradiance);

@@ -15,6 +15,8 @@ _LIB = None
 
 
 E_NONFINITE = -3          # LDSO_E_NONFINITE (ldso_hip.h)
+E_INVALID = -1            # LDSO_E_INVALID
+MAX_FRAMES = 16           # LDSO_MAX_FRAMES (ldso_window.h)
 
 
 class LdsoError(RuntimeError):
@@ -522,6 +524,18 @@ class BA:
         _chk(self.L.ldso_ba_select_activate_points(self.h, *args, C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations), _p(dec), _p(sel), C.byref(ns), _p(out)))
         return dec, sel[:ns.value].copy(), out[:ns.value].copy()
 
+    def select_activate_tracer(self, tracer: "Tracer", KRKi, Kt, host_flagged, min_act_dist, min_trace_quality=3.0, min_obs=1, min_idepth_hessian=100.0, gn_iterations=3, compact=True):
+        """select_activate_points with the tracer's resident records and types as candidates and the resident window's points as seeds; compact: whatever the loop
+        did not KEEP leaves the tracer's set -> (decision, selected, activation records of the selected)"""
+        K1 = np.ascontiguousarray(KRKi, np.float32).reshape(-1, 9); K2 = np.ascontiguousarray(Kt, np.float32).reshape(-1, 3); fl = np.ascontiguousarray(host_flagged, np.int32)
+        assert len(K1) == len(K2) == len(fl)
+        n = tracer.n
+        dec = np.zeros(n, np.int32); sel = np.zeros(n, np.int32); ns = C.c_int(); left = C.c_int(n); out = np.zeros(n, synth.ACTIVATION_DTYPE)
+        _chk(self.L.ldso_ba_select_activate_tracer(self.h, tracer.h, C.c_int(len(fl)), _p(K1), _p(K2), _p(fl), C.c_float(min_act_dist), C.c_float(min_trace_quality), C.c_int(min_obs),
+                                                   C.c_float(min_idepth_hessian), C.c_int(gn_iterations), C.c_int(1 if compact else 0), _p(dec), _p(sel), C.byref(ns), _p(out), C.byref(left)))
+        tracer.n = left.value
+        return dec, sel[:ns.value].copy(), out[:ns.value].copy()
+
     def get_distance_map(self):
         """CoarseDistanceMap::fwdWarpedIDDistFinal as the last selection left it: [h >> 1, w >> 1] floats, 0..39 and 1000"""
         out = np.zeros((self.hh >> 1, self.w >> 1), np.float32)
@@ -845,6 +859,29 @@ class Tracer:
         out = np.zeros(self.n, synth.IMMATURE_DTYPE)
         _chk(self.L.ldso_trace_get_points(self.h, _p(out)))
         return out
+
+    def set_point_types(self, my_type):
+        """ImmaturePoint::my_type of the current records (set_points resets them to 1)"""
+        t = np.ascontiguousarray(my_type, np.float32)
+        assert len(t) == self.n
+        _chk(self.L.ldso_trace_set_point_types(self.h, _p(t)))
+
+    def get_point_types(self):
+        out = np.zeros(self.n, np.float32)
+        _chk(self.L.ldso_trace_get_point_types(self.h, _p(out)))
+        return out
+
+    def compact(self, keep=None, host_map=None, n_hosts=None):
+        """stable compaction on the device: record i stays iff keep[i] and host_map[host] >= 0, and gets host = host_map[host] -> the new count.
+        n_hosts: the frames a host may name (default: len(host_map), else the library's capacity)"""
+        k = None if keep is None else np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+        m = None if host_map is None else np.ascontiguousarray(host_map, np.int32)
+        assert k is None or len(k) == self.n
+        nh = n_hosts if n_hosts is not None else (len(m) if m is not None else MAX_FRAMES)
+        left = C.c_int()
+        _chk(self.L.ldso_trace_compact(self.h, _p(k), C.c_int(nh), _p(m), C.byref(left)))
+        self.n = left.value
+        return self.n
 
     def append_points_device(self, n, immature_dev_ptr):
         """n immature records in device memory (Features.device_ptrs) behind the current points, device to device"""

@@ -29,6 +29,12 @@ struct SelArgs {
     const int32_t *flagged;
     int nSeeds, n, nHosts, w1, h1;
     float minDist, minQuality;
+    // the seeds straight from a resident window instead of `seeds` (pgeo != null): every point whose host is not `newestHost`, at its CURRENT inverse depth
+    // (PointHessian::idepth_scaled, CoarseTracker.cc:706-709)
+    const PtGeo *pgeo;
+    const int32_t *phost;
+    int nWin;
+    int newestHost;                               // candidates hosted by this frame are no candidates (FullSystem.cc:1089): KEEP, never touched; < 0: none
     unsigned char *gmap;                          // [w1 * h1] the map in global memory: the working copy of the large path, the final map of both
     int32_t *decision, *selected, *nSelected, *cell;
     float *frac, *thr;
@@ -106,6 +112,13 @@ __global__ __launch_bounds__(SEL_THREADS) void k_act_select(SelArgs A) {
         int u, v; float p0;
         if (project(A.KRKi + 9 * s.host, A.Kt + 3 * s.host, s.u, s.v, s.idepth_scaled, w1, h1, u, v, p0)) map[u + w1 * v] = 0;
     }
+    if (A.pgeo) for (int i = tid; i < A.nWin; i += nt) {
+        const int host = A.phost[i];
+        if (host < 0 || host >= A.nHosts || host == A.newestHost) continue;
+        const PtGeo &g = A.pgeo[i];
+        int u, v; float p0;
+        if (project(A.KRKi + 9 * host, A.Kt + 3 * host, g.u, g.v, g.idepth, w1, h1, u, v, p0)) map[u + w1 * v] = 0;
+    }
     __syncthreads();
     // ---- growDistBFS (CoarseTracker.cc:723-811): every cell is far or final here, so the frontier of round k is the set of cells holding k - 1 ----
     for (int k = 1; k < 40; k++) {
@@ -135,6 +148,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_act_select(SelArgs A) {
         const int host = P.host, st = P.lastTraceStatus;
         const float idmin = P.idepth_min, idmax = P.idepth_max;
         int dec = LDSO_ACT_KEEP;
+        if (A.newestHost >= 0 && host == A.newestHost) { A.decision[i] = dec; continue; }                                                  // :1089
         if (host < 0 || host >= A.nHosts || !isfinite(idmax) || st == LDSO_IPS_OUTLIER) dec = LDSO_ACT_DROP;                               // :1105
         else {
             const bool canActivate = (st == LDSO_IPS_GOOD || st == LDSO_IPS_SKIPPED || st == LDSO_IPS_BADCONDITION || st == LDSO_IPS_OOB)
@@ -196,17 +210,30 @@ static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
 
 }  // namespace
 
-static int sel_enqueue(ldso_ba *H, const char *who, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts, const float *KRKi,
-                       const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, SelBuffers &S) {
-    REQ(H && n_seeds >= 0 && n >= 0 && n_hosts >= 1 && n_hosts <= LDSO_MAX_FRAMES && KRKi && Kt && host_flagged && (n_seeds == 0 || seeds) && (n == 0 || (points && my_type)),
-        std::string(who) + ": bad arguments");
+// Where a selection takes its candidates and seeds from: flat host arrays (uploaded with the poses), or device memory - the records and types of a tracer's
+// resident set and the points of the handle's resident window - of which nothing is uploaded.
+struct SelSource {
+    int nSeeds = 0; const ldso_act_seed_t *seeds = nullptr;                          // host
+    int n = 0; const ldso_immature_t *points = nullptr; const float *myType = nullptr;      // host
+    const ldso_immature_t *d_points = nullptr; const float *d_myType = nullptr;      // device (then points / myType / seeds are null)
+    bool windowSeeds = false;
+    int newestHost = -1;
+};
+
+static int sel_enqueue(ldso_ba *H, const char *who, const SelSource &I, int n_hosts, const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist,
+                       float minTraceQuality, SelBuffers &S) {
+    const int n = I.n, n_seeds = I.nSeeds;
+    const bool onDevice = I.d_points != nullptr || I.windowSeeds;
+    REQ(H && n_seeds >= 0 && n >= 0 && n_hosts >= 1 && n_hosts <= LDSO_MAX_FRAMES && KRKi && Kt && host_flagged && (n_seeds == 0 || I.seeds)
+        && (n == 0 || (I.points && I.myType) || (I.d_points && I.d_myType)), std::string(who) + ": bad arguments");
     const int w1 = H->w >> 1, h1 = H->h >> 1;
     REQ(w1 >= 3 && h1 >= 3 && w1 < 65536 && h1 < 65536, std::string(who) + ": image size out of range");
-    for (int i = 0; i < n; i++) REQ(points[i].host >= 0 && points[i].host < n_hosts, std::string(who) + ": a candidate's host is not a frame of the window");
-    for (int i = 0; i < n_seeds; i++) REQ(seeds[i].host >= 0 && seeds[i].host < n_hosts, std::string(who) + ": a seed's host is not a frame of the window");
+    // device data cannot be range-checked here: the kernel drops a candidate and skips a seed whose host is not a frame of the window
+    for (int i = 0; !onDevice && i < n; i++) REQ(I.points[i].host >= 0 && I.points[i].host < n_hosts, std::string(who) + ": a candidate's host is not a frame of the window");
+    for (int i = 0; i < n_seeds; i++) REQ(I.seeds[i].host >= 0 && I.seeds[i].host < n_hosts, std::string(who) + ": a seed's host is not a frame of the window");
     CHK(hipSetDevice(H->device));
-    const size_t wh = (size_t) w1 * h1, nn = (size_t) n;
-    const size_t oPts = 0, oSeeds = oPts + nn * sizeof(ldso_immature_t), oType = oSeeds + up16((size_t) n_seeds * sizeof(ldso_act_seed_t)), oKRKi = oType + up16(nn * 4),
+    const size_t wh = (size_t) w1 * h1, nn = (size_t) n, nUp = I.points ? nn : 0;
+    const size_t oPts = 0, oSeeds = oPts + nUp * sizeof(ldso_immature_t), oType = oSeeds + up16((size_t) n_seeds * sizeof(ldso_act_seed_t)), oKRKi = oType + up16(nUp * 4),
                  oKt = oKRKi + up16((size_t) n_hosts * 36), oFlag = oKt + up16((size_t) n_hosts * 12), inBytes = oFlag + up16((size_t) n_hosts * 4);
     const size_t oDec = 16, oSel = oDec + up16(nn * 4), oAct = oSel + up16(nn * 4), outBytes = oAct + nn * sizeof(ldso_activation_t);
     const size_t oCell = inBytes + outBytes, oFrac = oCell + up16(nn * 4), oThr = oFrac + up16(nn * 4), oMap = oThr + up16(nn * 4), total = oMap + up16(wh);
@@ -225,13 +252,14 @@ static int sel_enqueue(ldso_ba *H, const char *who, int n_seeds, const ldso_act_
     H->selHost.resize(std::max(inBytes, outBytes));
     char *hs = H->selHost.data();
     memset(hs, 0, inBytes);
-    if (n) { memcpy(hs + oPts, points, nn * sizeof(ldso_immature_t)); memcpy(hs + oType, my_type, nn * 4); }
-    if (n_seeds) memcpy(hs + oSeeds, seeds, (size_t) n_seeds * sizeof(ldso_act_seed_t));
+    if (nUp) { memcpy(hs + oPts, I.points, nn * sizeof(ldso_immature_t)); memcpy(hs + oType, I.myType, nn * 4); }
+    if (n_seeds) memcpy(hs + oSeeds, I.seeds, (size_t) n_seeds * sizeof(ldso_act_seed_t));
     memcpy(hs + oKRKi, KRKi, (size_t) n_hosts * 36); memcpy(hs + oKt, Kt, (size_t) n_hosts * 12); memcpy(hs + oFlag, host_flagged, (size_t) n_hosts * 4);
     CHK(hipMemcpyAsync(S.in, hs, inBytes, hipMemcpyHostToDevice, H->stream));
     SelArgs A;
-    A.seeds = S.seeds; A.pts = S.pts; A.myType = S.myType; A.KRKi = S.KRKi; A.Kt = S.Kt; A.flagged = S.flagged;
+    A.seeds = S.seeds; A.pts = I.d_points ? I.d_points : S.pts; A.myType = I.d_points ? I.d_myType : S.myType; A.KRKi = S.KRKi; A.Kt = S.Kt; A.flagged = S.flagged;
     A.nSeeds = n_seeds; A.n = n; A.nHosts = n_hosts; A.w1 = w1; A.h1 = h1; A.minDist = currentMinActDist; A.minQuality = minTraceQuality;
+    A.pgeo = I.windowSeeds ? H->B.pgeo : nullptr; A.phost = I.windowSeeds ? H->B.phost : nullptr; A.nWin = I.windowSeeds ? H->D.P : 0; A.newestHost = I.newestHost;
     A.gmap = S.gmap; A.decision = S.decision; A.selected = S.selected; A.nSelected = S.nSelected; A.cell = S.cell; A.frac = S.frac; A.thr = S.thr;
     // the map in LDS where the workgroup can have that much (beside the kernel's own static bytes), in global memory otherwise
     const size_t ldsBytes = SEL_LIST_BYTES + up16(wh);
@@ -248,6 +276,34 @@ static int sel_enqueue(ldso_ba *H, const char *who, int n_seeds, const ldso_act_
     CHK(hipGetLastError());
     H->selW1 = w1; H->selH1 = h1; H->selMapOffset = oMap;
     return LDSO_OK;
+}
+
+static SelSource host_source(int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type) {
+    SelSource I;
+    I.nSeeds = n_seeds; I.seeds = seeds; I.n = n; I.points = points; I.myType = my_type;
+    return I;
+}
+
+// the preconditions of point activation on the resident window (ldso_ba_activate_points)
+static int act_preconditions(const ldso_ba *H, const char *who, int n_hosts) {
+    REQ(H->D.F >= 2, std::string(who) + ": set the window and the frames first");
+    REQ(n_hosts == H->D.F, std::string(who) + ": one KRKi / Kt / flag per frame of the resident window");
+    for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, std::string(who) + ": a key-frame image is missing");
+    return LDSO_OK;
+}
+
+// selection, then k_activate on the selected list where the selection kernel left it; the results come down with the caller's one synchronisation
+static int sel_activate_enqueue(ldso_ba *H, const char *who, const SelSource &I, int n_hosts, const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist,
+                                float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations, SelBuffers &S) {
+    RUN(sel_enqueue(H, who, I, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
+    CHK(ba_launch_activate_selected(H->B, H->D, H->settings, I.d_points ? I.d_points : S.pts, S.selected, S.nSelected, S.act, I.n, min_obs, min_idepth_hessian, gn_iterations, H->stream));
+    CHK(hipMemcpyAsync(H->selHost.data(), S.out, S.outBytes, hipMemcpyDeviceToHost, H->stream));
+    return LDSO_OK;
+}
+
+static void sel_unpack_activations(const ldso_ba *H, int n, int n_selected, ldso_activation_t *out) {
+    const size_t oAct = 16 + 2 * up16((size_t) n * 4);
+    if (n_selected > 0) memcpy(out, H->selHost.data() + oAct, (size_t) n_selected * sizeof(ldso_activation_t));
 }
 
 static void sel_unpack(const ldso_ba *H, int n, int32_t *decision_out, int32_t *selected_out, int *n_selected_out) {
@@ -296,7 +352,7 @@ int ldso_ba_select_candidates(ldso_ba_t *H, int n_seeds, const ldso_act_seed_t *
                               int *n_selected_out) {
     REQ(H && (n <= 0 || decision_out), "ldso_ba_select_candidates: bad arguments");
     SelBuffers S;
-    RUN(sel_enqueue(H, "ldso_ba_select_candidates", n_seeds, seeds, n, points, my_type, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
+    RUN(sel_enqueue(H, "ldso_ba_select_candidates", host_source(n_seeds, seeds, n, points, my_type), n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
     const size_t bytes = 16 + 2 * up16((size_t) n * 4);
     CHK(hipMemcpyAsync(H->selHost.data(), S.out, bytes, hipMemcpyDeviceToHost, H->stream));
     CHK(hipStreamSynchronize(H->stream));
@@ -310,17 +366,40 @@ int ldso_ba_select_activate_points(ldso_ba_t *H, int n_seeds, const ldso_act_see
                                    const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, int min_obs,
                                    float min_idepth_hessian, int gn_iterations, int32_t *decision_out, int32_t *selected_out, int *n_selected_out, ldso_activation_t *out) {
     REQ(H && gn_iterations >= 0 && n_selected_out && (n <= 0 || (decision_out && selected_out && out)), "ldso_ba_select_activate_points: bad arguments");
-    REQ(H->D.F >= 2, "ldso_ba_select_activate_points: set the window and the frames first");
-    REQ(n_hosts == H->D.F, "ldso_ba_select_activate_points: one KRKi / Kt / flag per frame of the resident window");
-    for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, "ldso_ba_select_activate_points: a key-frame image is missing");
+    RUN(act_preconditions(H, "ldso_ba_select_activate_points", n_hosts));
     SelBuffers S;
-    RUN(sel_enqueue(H, "ldso_ba_select_activate_points", n_seeds, seeds, n, points, my_type, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
-    CHK(ba_launch_activate_selected(H->B, H->D, H->settings, S.pts, S.selected, S.nSelected, S.act, n, min_obs, min_idepth_hessian, gn_iterations, H->stream));
-    CHK(hipMemcpyAsync(H->selHost.data(), S.out, S.outBytes, hipMemcpyDeviceToHost, H->stream));
+    RUN(sel_activate_enqueue(H, "ldso_ba_select_activate_points", host_source(n_seeds, seeds, n, points, my_type), n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality,
+                             min_obs, min_idepth_hessian, gn_iterations, S));
     CHK(hipStreamSynchronize(H->stream));
     sel_unpack(H, n, decision_out, selected_out, n_selected_out);
-    const size_t oAct = 16 + 2 * up16((size_t) n * 4);
-    if (*n_selected_out > 0) memcpy(out, H->selHost.data() + oAct, (size_t) *n_selected_out * sizeof(ldso_activation_t));
+    sel_unpack_activations(H, n, *n_selected_out, out);
+    return LDSO_OK;
+}
+
+// The same with nothing of the immature set crossing PCIe: the candidates are the tracer's resident records and types where they lie, the seeds the points of
+// the resident window at their current inverse depth, and with compact != 0 everything the loop did not KEEP leaves the tracer's set behind the activation
+// (FullSystem.cc:1105-1108, :1121-1125, :1145-1148 the deleted candidates; :1166-1188 the selected ones, accepted or not).  All on the handle's stream, one wait.
+int ldso_ba_select_activate_tracer(ldso_ba_t *H, ldso_tracer_t *T, int n_hosts, const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist,
+                                   float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations, int compact, int32_t *decision_out, int32_t *selected_out,
+                                   int *n_selected_out, ldso_activation_t *out, int *n_left_out) {
+    REQ(H && T && gn_iterations >= 0 && n_selected_out, "ldso_ba_select_activate_tracer: bad arguments");
+    const int n = T->n;
+    REQ(n <= 0 || (decision_out && selected_out && out), "ldso_ba_select_activate_tracer: bad arguments");
+    REQ(T->device == H->device, "ldso_ba_select_activate_tracer: the tracer and the window live on different devices");
+    REQ_UNSHARDED("ldso_ba_select_activate_tracer");
+    RUN(act_preconditions(H, "ldso_ba_select_activate_tracer", n_hosts));
+    SelSource I;
+    I.n = n; I.d_points = T->d_pts; I.d_myType = T->d_type; I.windowSeeds = true; I.newestHost = n_hosts - 1;
+    SelBuffers S;
+    RUN(sel_activate_enqueue(H, "ldso_ba_select_activate_tracer", I, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, min_obs, min_idepth_hessian,
+                             gn_iterations, S));
+    const int rcCompact = compact ? trace_compact_enqueue(T, nullptr, S.decision, LDSO_ACT_KEEP, n_hosts, false, H->stream) : LDSO_OK;
+    CHK(hipStreamSynchronize(H->stream));          // also where the compaction could not be enqueued: the copy into selHost is in flight
+    if (rcCompact != LDSO_OK) return rcCompact;
+    if (compact) trace_compact_finish(T);
+    sel_unpack(H, n, decision_out, selected_out, n_selected_out);
+    sel_unpack_activations(H, n, *n_selected_out, out);
+    if (n_left_out) *n_left_out = T->n;
     return LDSO_OK;
 }
 

@@ -168,7 +168,28 @@ struct ldso_ba_batch {
     double *d_scalars = nullptr, *h_scalars = nullptr;      // [n][16]: every window's scalars after ldso_ba_batch_optimize (device block, pinned host copy)
 };
 
+// the immature-point tracer (trace.hip)
+struct ldso_tracer {
+    int device = 0, w = 0, h = 0, maxPoints = 0, n = 0;
+    hipStream_t stream = nullptr;
+    ldso_trace_settings_t settings;
+    ldso_immature_t *d_pts = nullptr, *d_alt = nullptr;     // the resident records; the buffer the next compaction writes (the two swap)
+    float *d_type = nullptr, *d_typeAlt = nullptr;          // ImmaturePoint::my_type of every record (ImmaturePoint.h:114), beside d_pts / d_alt
+    unsigned char *d_keep = nullptr, *d_flag = nullptr;     // [maxPoints] compaction: the caller's keep flags, the flags of the count pass
+    int32_t *d_cmp = nullptr;                               // [LDSO_MAX_FRAMES host map | 4: the new count | maxPoints / 256 workgroup counts]
+    int nAfterCompact = 0;                                  // where an enqueued compaction's count lands (trace_compact_finish)
+    float *d_img = nullptr, *d_color = nullptr, *d_pose = nullptr;      // pose: [LDSO_MAX_FRAMES][14]
+    const float *img = nullptr;       // the frame traced on: d_img, or level 0 of a shared ldso_pyramid_t
+    int *d_counts = nullptr;
+    bool haveFrame = false;
+};
+
 #pragma GCC visibility push(hidden)
+// trace.hip: the compaction of the tracer's resident immature set with keep flags that lie in device memory (ldso_ba_select_activate_tracer, act_select.hip):
+// record i stays where d_keep8[i] != 0 / d_keep32[i] == keepValue (both null: everywhere) and its host is a frame of the window.  Enqueued on `st`;
+// trace_compact_finish swaps the buffers and takes the new count once the caller has synchronised `st`.
+int trace_compact_enqueue(ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, bool haveMap, hipStream_t st);
+void trace_compact_finish(ldso_tracer *T);
 int build_chunks(ldso_ba *H);          // ba_window.hip
 int rechunk(ldso_ba *H);
 // ba_optimize.hip: the launch helpers (with optional HIP-event timing) and what every caller of a launcher fills in the same way

@@ -231,19 +231,106 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------
+// Stable compaction of the resident set (what leaves it: points the selection dropped or activated, FullSystem.cc:1105-1188; points of a marginalised host
+// frame, FullSystem.cc:602-645).  Record i survives iff its keep flag is set and its host maps to a frame of the new window; survivors keep their relative order
+// (the reference's iteration order, FullSystem.cc:1088-1098: the greedy selection depends on it) and move OUT OF PLACE into the tracer's second buffer.
+//   k_compact_count  one flag per record, one count per workgroup of 256 records
+//   k_compact_move   every workgroup sums the counts in front of it (<= max_points / 256 words), ranks its own records, then moves them: 8 lanes x 16 B per
+//                    128-byte record, the lane that holds `host` rewrites it
+// ---------------------------------------------------------------------------------------------------------
+constexpr int CMP_THREADS = 256;
+
+struct CompactArgs {
+    const ldso_immature_t *src; ldso_immature_t *dst;
+    const float *srcType; float *dstType;
+    int n, nHosts;
+    const unsigned char *keep8;      // keep flags as bytes, or
+    const int32_t *keep32;           // ... record i is kept where keep32[i] == keepValue, or (both null) every record
+    int keepValue;
+    const int32_t *hostMap;          // [nHosts] new host index, < 0: the frame left; null: identity
+    unsigned char *flag;             // [n]
+    int32_t *blockCount;             // [ceil(n / 256)]
+    int32_t *nOut;
+};
+
+__global__ __launch_bounds__(CMP_THREADS) void k_compact_count(CompactArgs A) {
+    __shared__ int s_cnt[CMP_THREADS / 64];
+    const int i = blockIdx.x * CMP_THREADS + threadIdx.x;
+    bool keep = false;
+    if (i < A.n) {
+        const int host = A.src[i].host;
+        keep = A.keep8 ? A.keep8[i] != 0 : A.keep32 ? A.keep32[i] == A.keepValue : true;
+        keep = keep && host >= 0 && host < A.nHosts && (!A.hostMap || A.hostMap[host] >= 0);       // a host outside the window: dropped, not dereferenced
+        A.flag[i] = keep ? 1 : 0;
+    }
+    const int c = __popcll(__ballot(keep));
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) A.blockCount[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+__global__ __launch_bounds__(CMP_THREADS) void k_compact_move(CompactArgs A) {
+    __shared__ int s_part[2][CMP_THREADS / 64], s_wave[CMP_THREADS / 64], s_dest[CMP_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nBlocks = gridDim.x;
+    // the workgroups in front of this one, and all of them
+    int before = 0, total = 0;
+    for (int j = tid; j < nBlocks; j += CMP_THREADS) { const int c = A.blockCount[j]; total += c; if (j < (int) blockIdx.x) before += c; }
+    for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o, 64); total += __shfl_xor(total, o, 64); }
+    const int i = blockIdx.x * CMP_THREADS + tid;
+    const bool keep = i < A.n && A.flag[i] != 0;
+    const unsigned long long bm = __ballot(keep);
+    if (lane == 0) { s_part[0][wave] = before; s_part[1][wave] = total; s_wave[wave] = __popcll(bm); }
+    __syncthreads();
+    before = s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3];
+    total = s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3];
+    if (blockIdx.x == 0 && tid == 0) *A.nOut = total;
+    int rank = before + __popcll(bm & ((1ull << lane) - 1ull));
+    for (int wv = 0; wv < wave; wv++) rank += s_wave[wv];
+    s_dest[tid] = keep ? rank : -1;
+    if (keep) A.dstType[rank] = A.srcType[i];
+    __syncthreads();
+    const int part = tid & 7;
+    static_assert(sizeof(ldso_immature_t) == 128 && offsetof(ldso_immature_t, host) == 120, "a record is eight 16-byte parts, host is dword 2 of the last");
+    for (int r = tid >> 3; r < CMP_THREADS; r += CMP_THREADS / 8) {
+        const int d = s_dest[r];
+        if (d < 0) continue;                       // covers r beyond n: s_dest is -1 there
+        uint4 q = ((const uint4 *) (A.src + blockIdx.x * CMP_THREADS + r))[part];
+        if (part == 7 && A.hostMap) q.z = (unsigned) A.hostMap[(int) q.z];            // the count pass kept only hosts in [0, nHosts)
+        ((uint4 *) (A.dst + d))[part] = q;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-struct ldso_tracer {
-    int device = 0, w = 0, h = 0, maxPoints = 0, n = 0;
-    hipStream_t stream = nullptr;
-    ldso_trace_settings_t settings;
-    ldso_immature_t *d_pts = nullptr;
-    float *d_img = nullptr, *d_color = nullptr, *d_pose = nullptr;      // pose: [LDSO_MAX_FRAMES][14]
-    const float *img = nullptr;       // the frame traced on: d_img, or level 0 of a shared ldso_pyramid_t
-    int *d_counts = nullptr;
-    bool haveFrame = false;
-};
+
+static constexpr int TYPE_ONE = 0x3f800000;      // 1.0f as the word hipMemsetD32Async writes
+
+// The compaction on stream `st` (the tracer's own, or the stream of the BA handle whose selection produced keep32: the tracer is idle then).  The host map, when
+// there is one, lies in d_cmp already.  Nothing of the tracer's host state changes until trace_compact_finish, which the caller runs behind its synchronisation.
+int trace_compact_enqueue(ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, bool haveMap, hipStream_t st) {
+    T->nAfterCompact = T->n;
+    if (T->n <= 0) return LDSO_OK;
+    CompactArgs A;
+    A.src = T->d_pts; A.dst = T->d_alt; A.srcType = T->d_type; A.dstType = T->d_typeAlt; A.n = T->n; A.nHosts = n_hosts;
+    A.keep8 = d_keep8; A.keep32 = d_keep32; A.keepValue = keepValue; A.hostMap = haveMap ? T->d_cmp : nullptr;
+    A.flag = T->d_flag; A.nOut = T->d_cmp + LDSO_MAX_FRAMES; A.blockCount = T->d_cmp + LDSO_MAX_FRAMES + 4;
+    const int blocks = (T->n + CMP_THREADS - 1) / CMP_THREADS;
+    hipLaunchKernelGGL(k_compact_count, dim3(blocks), dim3(CMP_THREADS), 0, st, A);
+    CHK(hipGetLastError());
+    hipLaunchKernelGGL(k_compact_move, dim3(blocks), dim3(CMP_THREADS), 0, st, A);
+    CHK(hipGetLastError());
+    CHK(hipMemcpyAsync(&T->nAfterCompact, A.nOut, 4, hipMemcpyDeviceToHost, st));
+    return LDSO_OK;
+}
+
+void trace_compact_finish(ldso_tracer *T) {
+    if (T->n <= 0) return;
+    std::swap(T->d_pts, T->d_alt); std::swap(T->d_type, T->d_typeAlt);
+    T->n = std::min(std::max(T->nAfterCompact, 0), T->n);
+}
 
 extern "C" {
 
@@ -266,6 +353,12 @@ int ldso_trace_create(int device, int w, int h, int max_points, ldso_tracer_t **
     ldso_trace_settings_default(&T->settings);
     CHK(hipStreamCreateWithFlags(&T->stream, hipStreamNonBlocking));
     CHK(hipMalloc(&T->d_pts, (size_t) max_points * sizeof(ldso_immature_t)));
+    CHK(hipMalloc(&T->d_alt, (size_t) max_points * sizeof(ldso_immature_t)));
+    CHK(hipMalloc(&T->d_type, (size_t) max_points * 4));
+    CHK(hipMalloc(&T->d_typeAlt, (size_t) max_points * 4));
+    CHK(hipMalloc(&T->d_keep, (size_t) max_points));
+    CHK(hipMalloc(&T->d_flag, (size_t) max_points));
+    CHK(hipMalloc(&T->d_cmp, (size_t) (LDSO_MAX_FRAMES + 4 + (max_points + CMP_THREADS - 1) / CMP_THREADS) * 4));
     CHK(hipMalloc(&T->d_img, (size_t) w * h * 12));
     CHK(hipMalloc(&T->d_color, (size_t) w * h * 4));
     CHK(hipMalloc(&T->d_pose, (size_t) LDSO_MAX_FRAMES * 14 * 4));
@@ -278,7 +371,7 @@ int ldso_trace_destroy(ldso_tracer_t *T) {
     if (!T) return LDSO_OK;
     hipSetDevice(T->device);
     hipDeviceSynchronize();
-    hipFree(T->d_pts); hipFree(T->d_img); hipFree(T->d_color); hipFree(T->d_pose); hipFree(T->d_counts);
+    hipFree(T->d_pts); hipFree(T->d_alt); hipFree(T->d_type); hipFree(T->d_typeAlt); hipFree(T->d_keep); hipFree(T->d_flag); hipFree(T->d_cmp); hipFree(T->d_img); hipFree(T->d_color); hipFree(T->d_pose); hipFree(T->d_counts);
     if (T->stream) hipStreamDestroy(T->stream);
     delete T;
     return LDSO_OK;
@@ -295,8 +388,40 @@ int ldso_trace_set_points(ldso_tracer_t *T, int n, const ldso_immature_t *pts) {
     REQ(T && n >= 0 && n <= T->maxPoints && (n == 0 || pts), "ldso_trace_set_points: bad arguments");
     CHK(hipSetDevice(T->device));
     if (n) CHK(hipMemcpyAsync(T->d_pts, pts, (size_t) n * sizeof(ldso_immature_t), hipMemcpyHostToDevice, T->stream));
+    if (n) CHK(hipMemsetD32Async((hipDeviceptr_t) T->d_type, TYPE_ONE, (size_t) n, T->stream));
     CHK(hipStreamSynchronize(T->stream));
     T->n = n;
+    return LDSO_OK;
+}
+
+int ldso_trace_set_point_types(ldso_tracer_t *T, const float *my_type) {
+    REQ(T && (T->n == 0 || my_type), "ldso_trace_set_point_types: bad arguments");
+    CHK(hipSetDevice(T->device));
+    if (T->n) CHK(hipMemcpyAsync(T->d_type, my_type, (size_t) T->n * 4, hipMemcpyHostToDevice, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
+    return LDSO_OK;
+}
+
+int ldso_trace_get_point_types(ldso_tracer_t *T, float *out) {
+    REQ(T && (T->n == 0 || out), "ldso_trace_get_point_types: bad arguments");
+    CHK(hipSetDevice(T->device));
+    if (T->n) CHK(hipMemcpyAsync(out, T->d_type, (size_t) T->n * 4, hipMemcpyDeviceToHost, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
+    return LDSO_OK;
+}
+
+int ldso_trace_compact(ldso_tracer_t *T, const uint8_t *keep, int n_hosts, const int32_t *host_map, int *n_out) {
+    REQ(T && n_hosts >= 1 && n_hosts <= LDSO_MAX_FRAMES, "ldso_trace_compact: bad arguments");
+    for (int f = 0; host_map && f < n_hosts; f++) REQ(host_map[f] < LDSO_MAX_FRAMES, "ldso_trace_compact: a host maps beyond LDSO_MAX_FRAMES");
+    CHK(hipSetDevice(T->device));
+    if (T->n > 0) {
+        if (keep) CHK(hipMemcpyAsync(T->d_keep, keep, (size_t) T->n, hipMemcpyHostToDevice, T->stream));
+        if (host_map) CHK(hipMemcpyAsync(T->d_cmp, host_map, (size_t) n_hosts * 4, hipMemcpyHostToDevice, T->stream));
+        RUN(trace_compact_enqueue(T, keep ? T->d_keep : nullptr, nullptr, 0, n_hosts, host_map != nullptr, T->stream));
+        CHK(hipStreamSynchronize(T->stream));          // the call's one synchronisation: the count is behind it
+        trace_compact_finish(T);
+    }
+    if (n_out) *n_out = T->n;
     return LDSO_OK;
 }
 
@@ -307,6 +432,7 @@ int ldso_trace_append_points_device(ldso_tracer_t *T, int n, const void *immatur
     REQ(n <= T->maxPoints - T->n, "ldso_trace_append_points_device: more points than max_points");
     CHK(hipSetDevice(T->device));
     if (n) CHK(hipMemcpyAsync(T->d_pts + T->n, immature_dev, (size_t) n * sizeof(ldso_immature_t), hipMemcpyDeviceToDevice, T->stream));
+    if (n) CHK(hipMemsetD32Async((hipDeviceptr_t) (T->d_type + T->n), TYPE_ONE, (size_t) n, T->stream));      // my_type = 1 (FullSystem.cc:1281)
     CHK(hipStreamSynchronize(T->stream));
     T->n += n;
     return LDSO_OK;
