@@ -29,6 +29,11 @@ static __device__ __forceinline__ float interp31(const float *img, float x, floa
     return dxdy * bp[3 + 3 * w] + (dy - dxdy) * bp[3 * w] + (dx - dxdy) * bp[3] + (1 - dx - dy + dxdy) * bp[0];
 }
 
+// A NaN that an invalid operation (0 / 0, Inf / Inf, Inf - Inf) produces is, in the reference's records, the x86 default NaN 0xFFC00000 (sign bit set), and SSE
+// hands it on unchanged; the same operation on the device yields 0x7FC00000.  The three values a point's record can hold such a NaN in - quality and the two ends
+// of the new interval - take the reference's bits through this, so that records compare byte for byte.
+static __device__ __forceinline__ float x86_default_nan(float x) { return x != x ? __builtin_bit_cast(float, 0xFFC00000u) : x; }
+
 static __device__ __forceinline__ void trace_fail(ldso_immature_t *p, int lane, int status, int *counts) {
     if (lane == 0) { p->lastTraceUV[0] = -1; p->lastTraceUV[1] = -1; p->lastTracePixelInterval = 0; p->lastTraceStatus = status; atomicAdd(&counts[status], 1); }
 }
@@ -82,6 +87,12 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
     const float a = (dx * g0 + dy * g2) * dx + (dx * g1 + dy * g3) * dy;
     const float b = (dy * g0 + -dx * g2) * dy + (dy * g1 + -dx * g3) * -dx;
     float errorInPixel = 0.2f + 0.2f * (a + b) / a;
+    // a NaN handed in through gradH reaches errorInPixel with its own bits, quieted (SSE returns the NaN operand; g0, g2, g1, g3 is the order they enter `a`);
+    // any other NaN here is 0 / 0 where gradH is zero along the line
+    if (errorInPixel != errorInPixel) {
+        const float gn = g0 != g0 ? g0 : g2 != g2 ? g2 : g1 != g1 ? g1 : g3;
+        errorInPixel = gn != gn ? __builtin_bit_cast(float, __builtin_bit_cast(unsigned, gn) | 0x00400000u) : x86_default_nan(errorInPixel);
+    }
     if (errorInPixel * S.trace_minImprovementFactor > dist && finiteMax) {
         if (lane == 0) { P->lastTraceUV[0] = (uMax + uMin) * 0.5f; P->lastTraceUV[1] = (vMax + vMin) * 0.5f; P->lastTracePixelInterval = dist;
                          P->lastTraceStatus = LDSO_IPS_BADCONDITION; atomicAdd(&A.counts[LDSO_IPS_BADCONDITION], 1); }
@@ -160,7 +171,7 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
         secondBest = sb;
     }
     float quality = P->quality;
-    const float newQuality = secondBest / bestEnergy;
+    const float newQuality = x86_default_nan(secondBest / bestEnergy);      // neither operand is ever NaN: 0 / 0 where every step matches exactly
     if (newQuality < quality || numSteps > 10) quality = newQuality;
     // ---- Gauss-Newton refinement along the line (:218-268), uniform in all lanes ----
     float uBak = bestU, vBak = bestV, gnstepsize = 1, stepBack = 0;
@@ -168,7 +179,7 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
     float wgt[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) wgt[k] = P->weights[k];
-    for (int it = 0; it < S.trace_GNIterations; it++) {
+    for (int it = 0; it < S.trace_GNIterations && bestIdx >= 0; it++) {
         float H = 1, bb = 0, energy = 0;
         float h0[8], h1[8], h2[8];
 #pragma unroll
@@ -207,7 +218,9 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
     }
     if (lane == 0) P->quality = quality;
     // ---- energy-based outlier (:271-278) ----
-    if (!(bestEnergy < P->energyTH * S.trace_extraSlackOnTH)) {
+    // bestIdx < 0 (no step below 1e10: a non-finite colour or affine value makes every energy NaN): the loop above read nothing, and the point ends here whatever
+    // energyTH is - the reference samples around (0, 0), in front of the image, and ends here too unless that memory happens to match (tracer)
+    if (bestIdx < 0 || !(bestEnergy < P->energyTH * S.trace_extraSlackOnTH)) {
         trace_fail(P, lane, prevStatus == LDSO_IPS_OUTLIER ? LDSO_IPS_OOB : LDSO_IPS_OUTLIER, A.counts);
         return;
     }
@@ -221,6 +234,8 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
         nmax = (pr2 * (bestV + errorInPixel * dy) - pr1) / (Kt[1] - Kt[2] * (bestV + errorInPixel * dy));
     }
     if (nmin > nmax) { const float t = nmin; nmin = nmax; nmax = t; }
+    // a NaN errorInPixel passes through every operation above as it is; any other NaN here was made by an invalid operation
+    if (errorInPixel != errorInPixel) { nmin = errorInPixel; nmax = errorInPixel; } else { nmin = x86_default_nan(nmin); nmax = x86_default_nan(nmax); }
     if (lane == 0) { P->idepth_min = nmin; P->idepth_max = nmax; }
     if (!isfinite(nmin) || !isfinite(nmax) || (nmax < 0)) { trace_fail(P, lane, LDSO_IPS_OUTLIER, A.counts); return; }
     if (lane == 0) {

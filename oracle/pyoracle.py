@@ -411,9 +411,32 @@ def trace_on(points, dI_level0, KRKi, Kt, aff, settings=None):
     return counts
 
 
-def activate_points(points, images_level0, K4, pairs, w, h, huberTH=9.0, min_idepth_hessian=100.0, gn_iterations=3, min_obs=1):
+# columns and mask bits of trace_on_diag (oracle/trace.cc, TD_*)
+TD_NUMSTEPS, TD_BESTIDX, TD_TIES, TD_GNITS, TD_MASK, TD_MARGIN, TD_TIE_LO, TD_TIE_HI = range(8)
+TD_BITS = {name: 1 << i for i, name in enumerate((
+    "clamp_maxpix", "clamp_99", "nonfinite_tap_search", "nonfinite_tap_gn", "step_back", "step_clamped", "step_nonfinite", "y_dominant", "swapped",
+    "interval_nonfinite", "idepth_max_negative", "scale_oob", "error_clamped", "error_nan", "dx_nonfinite"))}
+
+
+def trace_on_diag(points, dI_level0, KRKi, Kt, aff, settings=None):
+    """trace_on plus the per-point diagnostics of the same function body -> counts[6], diag int32 [n, 8] (columns TD_*, mask bits TD_BITS)"""
+    L = lib()
+    s = np.ascontiguousarray(synth.default_trace_settings() if settings is None else settings)
+    img = np.ascontiguousarray(dI_level0, np.float32)
+    h, w = img.shape[:2]
+    K1 = np.ascontiguousarray(KRKi, np.float32); K2 = np.ascontiguousarray(Kt, np.float32); A = np.ascontiguousarray(aff, np.float32)
+    counts = np.zeros(6, np.int32); diag = np.zeros((len(points), 8), np.int32)
+    assert points.flags["C_CONTIGUOUS"] and points.dtype == synth.IMMATURE_DTYPE
+    L.orc_trace_on_diag(C.c_int(len(points)), _p(points), _p(img), C.c_int(w), C.c_int(h), C.c_int(len(K1)), _p(K1), _p(K2), _p(A), _p(s), _p(counts), _p(diag))
+    return counts, diag
+
+
+AD_MID_PATTERN, AD_NONFINITE_FIRST, AD_NONFINITE_LATER, AD_FIRST_PASS_OUTLIER = range(4)      # columns of activate_points(..., diag=True)
+
+
+def activate_points(points, images_level0, K4, pairs, w, h, huberTH=9.0, min_idepth_hessian=100.0, gn_iterations=3, min_obs=1, diag=False):
     """FullSystem::optimizeImmaturePoint over immature-point records.  images_level0: list of F arrays [h,w,3]; K4 = (fx,fy,cx,cy);
-    pairs [F*F,14] = R (9), t (3), aff (2) of the current state at [host*F + target]."""
+    pairs [F*F,14] = R (9), t (3), aff (2) of the current state at [host*F + target].  diag=True: -> (records, int32 [n, 4] per-point counts AD_* of the same run)"""
     L = lib()
     pts = np.ascontiguousarray(points)
     F = len(images_level0)
@@ -421,6 +444,11 @@ def activate_points(points, images_level0, K4, pairs, w, h, huberTH=9.0, min_ide
     arr = (C.c_void_p * F)(*[im.ctypes.data for im in imgs])
     K = np.ascontiguousarray(K4, np.float32); pr = np.ascontiguousarray(pairs, np.float32)
     out = np.zeros(len(pts), synth.ACTIVATION_DTYPE)
+    if diag:
+        dg = np.zeros((len(pts), 4), np.int32)
+        L.orc_activate_points_diag(C.c_int(len(pts)), _p(pts), C.c_int(F), arr, C.c_int(w), C.c_int(h), _p(K), _p(pr), C.c_float(huberTH),
+                                   C.c_float(min_idepth_hessian), C.c_int(gn_iterations), C.c_int(min_obs), _p(out), _p(dg))
+        return out, dg
     L.orc_activate_points(C.c_int(len(pts)), _p(pts), C.c_int(F), arr, C.c_int(w), C.c_int(h), _p(K), _p(pr), C.c_float(huberTH),
                           C.c_float(min_idepth_hessian), C.c_int(gn_iterations), C.c_int(min_obs), _p(out))
     return out

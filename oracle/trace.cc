@@ -29,10 +29,27 @@ inline void interp33(const float *img, float x, float y, int w, float out[3]) {
         out[c] = dxdy * bp[3 + 3 * w + c] + (dy - dxdy) * bp[3 * w + c] + (dx - dxdy) * bp[3 + c] + (1 - dx - dy + dxdy) * bp[c];
 }
 
+// Per-point diagnostics of trace_on (orc_trace_on_diag): which of the function's paths a point took, so that a test can say what its inputs reach.
+// int32 [8] per point: numSteps (0: the point left before the search), bestIdx, number of steps whose energy equals the best, Gauss-Newton iterations run,
+// bit mask TD_*, smallest distance in pixels of any 2x2 tap from the image border (negative: a read outside the image), lowest and highest tied step.
+enum { TD_NUMSTEPS = 0, TD_BESTIDX, TD_TIES, TD_GNITS, TD_MASK, TD_MARGIN, TD_TIE_LO, TD_TIE_HI };
+enum { TD_CLAMP_MAXPIX = 1 << 0, TD_CLAMP_99 = 1 << 1, TD_NF_TAP_SEARCH = 1 << 2, TD_NF_TAP_GN = 1 << 3, TD_STEP_BACK = 1 << 4, TD_STEP_CLAMPED = 1 << 5,
+       TD_STEP_NONFINITE = 1 << 6, TD_Y_DOMINANT = 1 << 7, TD_SWAPPED = 1 << 8, TD_INTERVAL_NONFINITE = 1 << 9, TD_IDEPTH_MAX_NEG = 1 << 10, TD_SCALE_OOB = 1 << 11,
+       TD_ERR_CLAMPED = 1 << 12, TD_ERR_NAN = 1 << 13, TD_DX_NONFINITE = 1 << 14 };
+inline void diag_tap(int *diag, float x, float y, int w, int h) {
+    if (!diag) return;
+    const int ix = (int) x, iy = (int) y;
+    int m = ix < iy ? ix : iy;
+    if (w - 2 - ix < m) m = w - 2 - ix;
+    if (h - 2 - iy < m) m = h - 2 - iy;
+    if (m < diag[TD_MARGIN]) diag[TD_MARGIN] = m;
+}
+
 inline int fail(ldso_immature_t &p, int status) { p.lastTraceUV[0] = -1; p.lastTraceUV[1] = -1; p.lastTracePixelInterval = 0; return p.lastTraceStatus = status; }
 
 // ImmaturePoint.cc:47-310
-int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRKi, const float *Kt, const float *aff, const ldso_trace_settings_t &s) {
+int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRKi, const float *Kt, const float *aff, const ldso_trace_settings_t &s, int *diag) {
+    if (diag) { for (int i = 0; i < 8; i++) diag[i] = 0; diag[TD_MARGIN] = 1 << 30; diag[TD_TIE_LO] = diag[TD_TIE_HI] = -1; }
     if (p.lastTraceStatus == LDSO_IPS_OOB) return p.lastTraceStatus;                                   // :53
     const float maxPixSearch = (w + h) * s.maxPixSearch;                                             // :54
     // ---- project idepth_min / idepth_max (:59-124) ----
@@ -62,7 +79,7 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
         uMax = uMin + dist * dx * d; vMax = vMin + dist * dy * d;
         if (!(uMax > 4 && vMax > 4 && uMax < w - 5 && vMax < h - 5)) return fail(p, LDSO_IPS_OOB);
     }
-    if (!(p.idepth_min < 0 || (ptpMin[2] > 0.75f && ptpMin[2] < 1.5f))) return fail(p, LDSO_IPS_OOB);    // scale change (:127-131)
+    if (!(p.idepth_min < 0 || (ptpMin[2] > 0.75f && ptpMin[2] < 1.5f))) { if (diag) diag[TD_MASK] |= TD_SCALE_OOB; return fail(p, LDSO_IPS_OOB); }    // scale change (:127-131)
     // ---- error bound in pixels (:134-147) ----
     float dx = s.trace_stepsize * (uMax - uMin), dy = s.trace_stepsize * (vMax - vMin);
     const float *g = p.gradH;
@@ -70,30 +87,33 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
     float a = (dx * g[0] + dy * g[2]) * dx + (dx * g[1] + dy * g[3]) * dy;
     float b = (dy * g[0] + -dx * g[2]) * dy + (dy * g[1] + -dx * g[3]) * -dx;
     float errorInPixel = 0.2f + 0.2f * (a + b) / a;
+    if (diag && std::isnan(errorInPixel)) diag[TD_MASK] |= TD_ERR_NAN;
     if (errorInPixel * s.trace_minImprovementFactor > dist && std::isfinite(p.idepth_max)) {
         p.lastTraceUV[0] = (uMax + uMin) * 0.5f; p.lastTraceUV[1] = (vMax + vMin) * 0.5f;
         p.lastTracePixelInterval = dist;
         return p.lastTraceStatus = LDSO_IPS_BADCONDITION;
     }
-    if (errorInPixel > 10) errorInPixel = 10;
+    if (errorInPixel > 10) { errorInPixel = 10; if (diag) diag[TD_MASK] |= TD_ERR_CLAMPED; }
     // ---- discrete search (:150-205) ----
     dx /= dist; dy /= dist;
+    if (diag && dist > maxPixSearch) diag[TD_MASK] |= TD_CLAMP_MAXPIX;
     if (dist > maxPixSearch) { uMax = uMin + maxPixSearch * dx; vMax = vMin + maxPixSearch * dy; dist = maxPixSearch; }
     int numSteps = (int) (1.9999f + dist / s.trace_stepsize);
     float randShift = uMin * 1000 - floorf(uMin * 1000);
     float ptx = uMin - randShift * dx, pty = vMin - randShift * dy;
     float rot[8][2];
     for (int i = 0; i < 8; i++) { rot[i][0] = KRKi[0] * kPat[i][0] + KRKi[1] * kPat[i][1]; rot[i][1] = KRKi[3] * kPat[i][0] + KRKi[4] * kPat[i][1]; }
-    if (!std::isfinite(dx) || !std::isfinite(dy)) return fail(p, LDSO_IPS_OOB);
+    if (!std::isfinite(dx) || !std::isfinite(dy)) { if (diag) diag[TD_MASK] |= TD_DX_NONFINITE; return fail(p, LDSO_IPS_OOB); }
     float errors[100];
     float bestU = 0, bestV = 0, bestEnergy = 1e10f;
     int bestIdx = -1;
-    if (numSteps >= 100) numSteps = 99;
+    if (numSteps >= 100) { numSteps = 99; if (diag) diag[TD_MASK] |= TD_CLAMP_99; }
     for (int i = 0; i < numSteps; i++) {
         float energy = 0;
         for (int k = 0; k < 8; k++) {
+            diag_tap(diag, ptx + rot[k][0], pty + rot[k][1], w, h);
             float hit = interp31(dI, ptx + rot[k][0], pty + rot[k][1], w);
-            if (!std::isfinite(hit)) { energy += 1e5f; continue; }
+            if (!std::isfinite(hit)) { energy += 1e5f; if (diag) diag[TD_MASK] |= TD_NF_TAP_SEARCH; continue; }
             float r = hit - (float) (aff[0] * p.color[k] + aff[1]);
             float hw = fabsf(r) < s.huberTH ? 1 : s.huberTH / fabsf(r);
             energy += hw * r * r * (2 - hw);
@@ -101,6 +121,10 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
         errors[i] = energy;
         if (energy < bestEnergy) { bestU = ptx; bestV = pty; bestEnergy = energy; bestIdx = i; }
         ptx += dx; pty += dy;
+    }
+    if (diag) {
+        diag[TD_NUMSTEPS] = numSteps; diag[TD_BESTIDX] = bestIdx;
+        for (int i = 0; i < numSteps; i++) if (errors[i] == bestEnergy) { diag[TD_TIES]++; if (diag[TD_TIE_LO] < 0) diag[TD_TIE_LO] = i; diag[TD_TIE_HI] = i; }
     }
     float secondBest = 1e10f;                                                                        // best score outside +-radius (:208-215)
     for (int i = 0; i < numSteps; i++)
@@ -110,12 +134,16 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
     // ---- Gauss-Newton refinement along the line (:218-268) ----
     float uBak = bestU, vBak = bestV, gnstepsize = 1, stepBack = 0;
     if (s.trace_GNIterations > 0) bestEnergy = 1e5f;
-    for (int it = 0; it < s.trace_GNIterations; it++) {
+    // bestIdx < 0: no step below 1e10 (a non-finite colour or affine value).  The reference refines around (0, 0) here and reads in front of the image; this loop
+    // reads nothing and the point ends in the outlier branch below (tracer).
+    for (int it = 0; it < s.trace_GNIterations && bestIdx >= 0; it++) {
+        if (diag) diag[TD_GNITS]++;
         float H = 1, bb = 0, energy = 0;
         for (int k = 0; k < 8; k++) {
             float hit[3];
+            diag_tap(diag, bestU + rot[k][0], bestV + rot[k][1], w, h);
             interp33(dI, bestU + rot[k][0], bestV + rot[k][1], w, hit);
-            if (!std::isfinite(hit[0])) { energy += 1e5f; continue; }
+            if (!std::isfinite(hit[0])) { energy += 1e5f; if (diag) diag[TD_MASK] |= TD_NF_TAP_GN; continue; }
             float r = hit[0] - (aff[0] * p.color[k] + aff[1]);
             float dResdDist = dx * hit[1] + dy * hit[2];
             float hw = fabsf(r) < s.huberTH ? 1 : s.huberTH / fabsf(r);
@@ -125,10 +153,13 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
         }
         if (energy > bestEnergy) {
             stepBack *= 0.5f;
+            if (diag) diag[TD_MASK] |= TD_STEP_BACK;
             bestU = uBak + stepBack * dx; bestV = vBak + stepBack * dy;
         } else {
             float step = -gnstepsize * bb / H;
+            if (diag && (step < -0.5f || step > 0.5f)) diag[TD_MASK] |= TD_STEP_CLAMPED;
             if (step < -0.5f) step = -0.5f; else if (step > 0.5f) step = 0.5f;
+            if (diag && !std::isfinite(step)) diag[TD_MASK] |= TD_STEP_NONFINITE;
             if (!std::isfinite(step)) step = 0;
             uBak = bestU; vBak = bestV; stepBack = step;
             bestU += step * dx; bestV += step * dy;
@@ -137,7 +168,7 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
         if (fabsf(stepBack) < s.trace_GNThreshold) break;
     }
     // ---- energy-based outlier (:271-278) ----
-    if (!(bestEnergy < p.energyTH * s.trace_extraSlackOnTH)) {
+    if (bestIdx < 0 || !(bestEnergy < p.energyTH * s.trace_extraSlackOnTH)) {
         int prev = p.lastTraceStatus;
         return fail(p, prev == LDSO_IPS_OUTLIER ? LDSO_IPS_OOB : LDSO_IPS_OUTLIER);
     }
@@ -146,10 +177,14 @@ int trace_on(ldso_immature_t &p, const float *dI, int w, int h, const float *KRK
         p.idepth_min = (pr[2] * (bestU - errorInPixel * dx) - pr[0]) / (Kt[0] - Kt[2] * (bestU - errorInPixel * dx));
         p.idepth_max = (pr[2] * (bestU + errorInPixel * dx) - pr[0]) / (Kt[0] - Kt[2] * (bestU + errorInPixel * dx));
     } else {
+        if (diag) diag[TD_MASK] |= TD_Y_DOMINANT;
         p.idepth_min = (pr[2] * (bestV - errorInPixel * dy) - pr[1]) / (Kt[1] - Kt[2] * (bestV - errorInPixel * dy));
         p.idepth_max = (pr[2] * (bestV + errorInPixel * dy) - pr[1]) / (Kt[1] - Kt[2] * (bestV + errorInPixel * dy));
     }
+    if (diag && p.idepth_min > p.idepth_max) diag[TD_MASK] |= TD_SWAPPED;
     if (p.idepth_min > p.idepth_max) { float t = p.idepth_min; p.idepth_min = p.idepth_max; p.idepth_max = t; }
+    if (diag && (!std::isfinite(p.idepth_min) || !std::isfinite(p.idepth_max))) diag[TD_MASK] |= TD_INTERVAL_NONFINITE;
+    else if (diag && p.idepth_max < 0) diag[TD_MASK] |= TD_IDEPTH_MAX_NEG;
     if (!std::isfinite(p.idepth_min) || !std::isfinite(p.idepth_max) || (p.idepth_max < 0)) return fail(p, LDSO_IPS_OUTLIER);
     p.lastTracePixelInterval = 2 * errorInPixel;
     p.lastTraceUV[0] = bestU; p.lastTraceUV[1] = bestV;
@@ -167,15 +202,22 @@ void orc_trace_settings_default(ldso_trace_settings_t *s) {
 }
 
 // FullSystem::traceNewCoarse (FullSystem.cc:1012-1050): every immature point against the new frame; counts[6] per status
-void orc_trace_on(int n, ldso_immature_t *pts, const float *dI, int w, int h, int n_hosts, const float *KRKi, const float *Kt, const float *aff,
-                  const ldso_trace_settings_t *s, int *counts) {
+// diag: null, or int32 [n][8]; the row of a point whose host is out of range is zero.  Columns in order: 0 numSteps (0: the point left before the search), 1 bestIdx,
+// 2 number of steps whose energy equals the best, 3 Gauss-Newton iterations run, 4 bit mask of the branches taken (TD_* above), 5 smallest distance in pixels of any
+// 2 x 2 tap from the image border (negative: a read outside the image), 6 lowest tied step, 7 highest tied step (-1: none)
+void orc_trace_on_diag(int n, ldso_immature_t *pts, const float *dI, int w, int h, int n_hosts, const float *KRKi, const float *Kt, const float *aff,
+                       const ldso_trace_settings_t *s, int *counts, int *diag) {
     if (counts) for (int i = 0; i < 6; i++) counts[i] = 0;
     for (int i = 0; i < n; i++) {
         int hst = pts[i].host;
-        if (hst < 0 || hst >= n_hosts) continue;
-        int st = trace_on(pts[i], dI, w, h, KRKi + 9 * hst, Kt + 3 * hst, aff + 2 * hst, *s);
+        if (hst < 0 || hst >= n_hosts) { if (diag) for (int k = 0; k < 8; k++) diag[8 * i + k] = 0; continue; }
+        int st = trace_on(pts[i], dI, w, h, KRKi + 9 * hst, Kt + 3 * hst, aff + 2 * hst, *s, diag ? diag + 8 * i : nullptr);
         if (counts && st >= 0 && st < 6) counts[st]++;
     }
+}
+void orc_trace_on(int n, ldso_immature_t *pts, const float *dI, int w, int h, int n_hosts, const float *KRKi, const float *Kt, const float *aff,
+                  const ldso_trace_settings_t *s, int *counts) {
+    orc_trace_on_diag(n, pts, dI, w, h, n_hosts, KRKi, Kt, aff, s, counts, nullptr);
 }
 
 }  // extern "C"
@@ -191,8 +233,12 @@ namespace {
 struct TmpRes { int state_state; double state_energy; int state_NewState; double state_NewEnergy; int target; };
 enum { RS_IN = 0, RS_OOB = 1, RS_OUTLIER = 2 };
 
+// diag (nullable, orc_activate_points_diag): int32 [4] per point - residual evaluations that left at a pattern pixel k > 0 (Hdd / bd keep the partial sums),
+// non-finite taps at k == 0, non-finite taps at k > 0, OUTLIER verdicts of the first pass (slack 1000)
+enum { AD_MID_PATTERN = 0, AD_NONFINITE_FIRST, AD_NONFINITE_LATER, AD_FIRST_PASS_OUTLIER };
+
 double linearize_residual(const ldso_immature_t &p, const float *const *dI, int w, int h, const float *K4 /*fx fy cx cy*/, const float *pair,
-                          float huberTH, float outlierTHSlack, TmpRes &tr, float &Hdd, float &bd, float idepth) {
+                          float huberTH, float outlierTHSlack, TmpRes &tr, float &Hdd, float &bd, float idepth, int *diag) {
     if (tr.state_state == RS_OOB) { tr.state_NewState = RS_OOB; return tr.state_energy; }                      // :317-320
     const float *R = pair, *t = pair + 9, *aff = pair + 12;
     const float fx = K4[0], fy = K4[1], cx = K4[2], cy = K4[3], fxi = 1.0f / fx, fyi = 1.0f / fy;
@@ -208,10 +254,13 @@ double linearize_residual(const ldso_immature_t &p, const float *const *dI, int 
         bool ok = drescale > 0;
         float u = 0, v = 0, Ku = 0, Kv = 0;
         if (ok) { u = q0 * drescale; v = q1 * drescale; Ku = u * fx + cx; Kv = v * fy + cy; ok = Ku > 1.1f && Kv > 1.1f && Ku < w - 3 && Kv < h - 3; }
-        if (!ok) { tr.state_NewState = RS_OOB; return tr.state_energy; }
+        if (!ok) { if (diag && k > 0) diag[AD_MID_PATTERN]++; tr.state_NewState = RS_OOB; return tr.state_energy; }
         float hit[3];
         interp33(img, Ku, Kv, w, hit);
-        if (!std::isfinite(hit[0])) { tr.state_NewState = RS_OOB; return tr.state_energy; }
+        if (!std::isfinite(hit[0])) {
+            if (diag) { diag[k > 0 ? AD_NONFINITE_LATER : AD_NONFINITE_FIRST]++; if (k > 0) diag[AD_MID_PATTERN]++; }
+            tr.state_NewState = RS_OOB; return tr.state_energy;
+        }
         const float residual = hit[0] - (aff[0] * p.color[k] + aff[1]);
         float hw = fabsf(residual) < huberTH ? 1 : huberTH / fabsf(residual);
         energyLeft += p.weights[k] * p.weights[k] * hw * residual * residual * (2 - hw);
@@ -221,7 +270,7 @@ double linearize_residual(const ldso_immature_t &p, const float *const *dI, int 
         Hdd += (hw * d_idepth) * d_idepth;
         bd += (hw * residual) * d_idepth;
     }
-    if (energyLeft > p.energyTH * outlierTHSlack) { energyLeft = p.energyTH * outlierTHSlack; tr.state_NewState = RS_OUTLIER; }
+    if (energyLeft > p.energyTH * outlierTHSlack) { energyLeft = p.energyTH * outlierTHSlack; tr.state_NewState = RS_OUTLIER; if (diag && outlierTHSlack == 1000) diag[AD_FIRST_PASS_OUTLIER]++; }
     else tr.state_NewState = RS_IN;
     tr.state_NewEnergy = energyLeft;
     return energyLeft;
@@ -229,9 +278,12 @@ double linearize_residual(const ldso_immature_t &p, const float *const *dI, int 
 
 }  // namespace
 
-extern "C" void orc_activate_points(int n, const ldso_immature_t *pts, int F, const float *const *dI, int w, int h, const float *K4, const float *pairs,
-                                    float huberTH, float minIdepthH_act, int GNIts, int minObs, ldso_activation_t *out) {
+// diag_all: null, or int32 [n][4] (AD_* above)
+extern "C" void orc_activate_points_diag(int n, const ldso_immature_t *pts, int F, const float *const *dI, int w, int h, const float *K4, const float *pairs,
+                                         float huberTH, float minIdepthH_act, int GNIts, int minObs, ldso_activation_t *out, int *diag_all) {
     for (int i = 0; i < n; i++) {
+        int *diag = diag_all ? diag_all + 4 * i : nullptr;
+        if (diag) diag[0] = diag[1] = diag[2] = diag[3] = 0;
         const ldso_immature_t &p = pts[i];
         ldso_activation_t &o = out[i];
         memset(&o, 0, sizeof(o));
@@ -242,7 +294,7 @@ extern "C" void orc_activate_points(int n, const ldso_immature_t *pts, int F, co
         float lastEnergy = 0, lastHdd = 0, lastbd = 0;
         float currentIdepth = (p.idepth_max + p.idepth_min) * 0.5f;
         for (int r = 0; r < nres; r++) {
-            lastEnergy += linearize_residual(p, dI, w, h, K4, pairs + (size_t) (p.host * F + tr[r].target) * 14, huberTH, 1000, tr[r], lastHdd, lastbd, currentIdepth);
+            lastEnergy += linearize_residual(p, dI, w, h, K4, pairs + (size_t) (p.host * F + tr[r].target) * 14, huberTH, 1000, tr[r], lastHdd, lastbd, currentIdepth, diag);
             tr[r].state_state = tr[r].state_NewState; tr[r].state_energy = tr[r].state_NewEnergy;
         }
         bool failed = !std::isfinite(lastEnergy) || lastHdd < minIdepthH_act;                                       // return 0 (:924-926)
@@ -256,7 +308,7 @@ extern "C" void orc_activate_points(int n, const ldso_immature_t *pts, int F, co
             float newIdepth = currentIdepth - step;
             float newHdd = 0, newbd = 0, newEnergy = 0;
             for (int r = 0; r < nres; r++)
-                newEnergy += linearize_residual(p, dI, w, h, K4, pairs + (size_t) (p.host * F + tr[r].target) * 14, huberTH, 1, tr[r], newHdd, newbd, newIdepth);
+                newEnergy += linearize_residual(p, dI, w, h, K4, pairs + (size_t) (p.host * F + tr[r].target) * 14, huberTH, 1, tr[r], newHdd, newbd, newIdepth, diag);
             if (!std::isfinite(lastEnergy) || newHdd < minIdepthH_act) { failed = true; break; }                       // :945-947
             if (newEnergy < lastEnergy) {
                 currentIdepth = newIdepth; lastHdd = newHdd; lastbd = newbd; lastEnergy = newEnergy;
@@ -272,5 +324,9 @@ extern "C" void orc_activate_points(int n, const ldso_immature_t *pts, int F, co
         o.numGoodRes = good;
         o.ok = (!failed && std::isfinite(currentIdepth) && good >= minObs) ? 1 : 0;                                     // :968-980
     }
+}
+extern "C" void orc_activate_points(int n, const ldso_immature_t *pts, int F, const float *const *dI, int w, int h, const float *K4, const float *pairs,
+                                    float huberTH, float minIdepthH_act, int GNIts, int minObs, ldso_activation_t *out) {
+    orc_activate_points_diag(n, pts, F, dI, w, h, K4, pairs, huberTH, minIdepthH_act, GNIts, minObs, out, nullptr);
 }
 static_assert(sizeof(ldso_activation_t) == 96, "layout");

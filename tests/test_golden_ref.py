@@ -137,6 +137,17 @@ def test_oracle_trace_on_reproduces_reference_vectors():
     assert np.array_equal(counts, g["counts"]) and pts.tobytes() == g["records"].tobytes()
 
 
+def test_oracle_trace_branches_reproduce_reference_vectors():
+    """the branch scene (tests/trace_branch_common.py): more than 64 search steps, the clamp at 99, hand-made finite intervals, each with its second trace"""
+    import trace_branch_common as tb
+    g = np.load(os.path.join(G, "ref_trace_branches.npz"))
+    names = [c["name"] for c in tb.scene()["calls"] if c["golden"]]
+    assert {"inf85", "inf99", "finite"} <= set(names) and len(g.files) == 4 * len(names)
+    for name in names:
+        for t, (counts, records) in enumerate(tb.oracle(name)):
+            assert np.array_equal(counts, g[f"{name}_counts{t}"]) and records.tobytes() == g[f"{name}_records{t}"].tobytes(), (name, t)
+
+
 @pytest.mark.gpu
 def test_gpu_tracker_matches_reference_vectors():
     from ldso_amd import binding

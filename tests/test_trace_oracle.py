@@ -1,5 +1,6 @@
-"""Oracle restatement of ImmaturePoint::traceOn (oracle/trace.cc): the reference has no fixtures for it (parity unpinned), so
-the restatement is pinned by what the function is for - recovering the inverse depth of a pixel by an epipolar search."""
+"""Oracle restatement of ImmaturePoint::traceOn (oracle/trace.cc), checked here by what the function is for - recovering the inverse depth of a pixel by an
+epipolar search.  Its parity with the reference is pinned elsewhere: byte for byte against the reference's own translation unit (tests/test_ref_pin.py,
+tests/test_trace_branches_cpu.py) and against recorded reference vectors (tests/test_golden_ref.py)."""
 import numpy as np
 
 from ldso_amd import synth
