@@ -9,6 +9,7 @@
 // bounds half-way through its pattern - so idepth, energies and residual states are bit-identical to the CPU path.
 #include <hip/hip_runtime.h>
 #include "ba_host.h"
+#include "lane.h"
 
 struct ActArgs {
     const ldso_immature_t *pts;
@@ -19,13 +20,10 @@ struct ActArgs {
     const int32_t *nSel;
 };
 
-template <int CTRL> static __device__ __forceinline__ int act_dpp(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
-template <int CTRL> static __device__ __forceinline__ float act_dppf(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true)); }
 static __device__ __forceinline__ int min8(int v) {      // minimum over the 8 lanes of a slot, in all 8 lanes
-    v = min(v, act_dpp<0xB1>(v)); v = min(v, act_dpp<0x4E>(v)); v = min(v, act_dpp<0x141>(v));
+    v = min(v, dpp_mov<0xB1>(v)); v = min(v, dpp_mov<0x4E>(v)); v = min(v, dpp_mov<0x141>(v));
     return v;
 }
-static __device__ __forceinline__ float rl(float x, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l)); }
 
 template <int NSG>
 __global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_settings_t S, ActArgs A) {
@@ -102,9 +100,9 @@ __global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_setti
             termB[g] = contrib ? (hw * residual) * d_idepth : 0.0f;
             if (!contrib) eTerm = 0.0f;
             // energy of the residual in pattern order (only meaningful when no pixel was bad)
-            float e = act_dppf<0x117>(eTerm);
-            e = e + act_dppf<0x116>(eTerm); e = e + act_dppf<0x115>(eTerm); e = e + act_dppf<0x114>(eTerm);
-            e = e + act_dppf<0x113>(eTerm); e = e + act_dppf<0x112>(eTerm); e = e + act_dppf<0x111>(eTerm); e = e + eTerm;
+            float e = dpp_row_shr<7>(eTerm);
+            e = e + dpp_row_shr<6>(eTerm); e = e + dpp_row_shr<5>(eTerm); e = e + dpp_row_shr<4>(eTerm);
+            e = e + dpp_row_shr<3>(eTerm); e = e + dpp_row_shr<2>(eTerm); e = e + dpp_row_shr<1>(eTerm); e = e + eTerm;
             float energyLeft = __shfl(e, lane | 7, 64);
             if (!valid[g]) { ret[g] = 0; }
             else if (st[g] == 1) { nst[g] = 1; ret[g] = sten[g]; }                                       // :317-320
@@ -122,8 +120,8 @@ __global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_setti
             const int g = tgt >> 3, l0 = (tgt & 7) * 8;
 #pragma unroll
             for (int kk = 0; kk < 8; kk++) {
-                const float hH = (NSG == 1 || g == 0) ? rl(termH[0], l0 + kk) : rl(termH[NSG - 1], l0 + kk);
-                const float hB = (NSG == 1 || g == 0) ? rl(termB[0], l0 + kk) : rl(termB[NSG - 1], l0 + kk);
+                const float hH = (NSG == 1 || g == 0) ? lane_read(termH[0], l0 + kk) : lane_read(termH[NSG - 1], l0 + kk);
+                const float hB = (NSG == 1 || g == 0) ? lane_read(termB[0], l0 + kk) : lane_read(termB[NSG - 1], l0 + kk);
                 Hdd += hH; bd += hB;
             }
             const double r0 = (NSG == 1 || g == 0) ? ret[0] : ret[NSG - 1];

@@ -57,19 +57,6 @@ int ldso_frame_set_prior(ldso_frame_t *f, const ldso_settings_t *s) {
 
 // ---------------------------------------------------------------------------------------------------------
 }  // extern "C"
-template <class T> static int dalloc(ldso_ba *H, T **p, size_t n) {
-    void *q = nullptr;
-    CHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    // hipMemset on device memory is asynchronous (legacy null stream) and the handles work on NON-BLOCKING streams, which do not order themselves
-    // behind it: without the wait a zero-fill that is still queued (the null stream busy with another library's work, e.g. torch's) could land on top
-    // of data the handle's first uploads / kernels have already written
-    CHK(hipMemset(q, 0, std::max<size_t>(n, 1) * sizeof(T)));
-    CHK(hipStreamSynchronize(nullptr));
-    H->allocs.push_back(q);
-    *p = (T *) q;
-    return LDSO_OK;
-}
-#define DA(ptr, n) do { int r_ = dalloc(H, &(ptr), (n)); if (r_ != LDSO_OK) return r_; } while (0)
 // the fetch functions read the device tables through ONE pinned arena: reserve what the call needs (growth invalidates nothing: it happens before
 // the first copy is enqueued), enqueue the copies back to back, wait once, read in place.  (std::vector destinations are pageable memory: the
 // runtime stages them in small pieces - ldso_ba_get_residuals of a C3 window took 0.35 ms for 1 MB.)
@@ -101,26 +88,9 @@ extern "C" {
 
 static int alloc_set(ldso_ba *H, ResSet &S) {
     const size_t P = H->maxP, FS = H->FSmax, PS = P * FS, C = H->maxChunks;
-    DA(S.slot, PS); DA(S.pt, P); DA(S.acc, P); DA(S.candE, P);
-    DA(S.G, P * (8 * FS + LD_GEXTRA)); DA(S.topA, C * FS * LD_TOPN); DA(S.topL, C * FS * LD_TOPN);
-    DA(S.chunkEnergy, C); DA(S.chunkCnt, C * 2); DA(S.chunkNID, C * 2);
-    return LDSO_OK;
-}
-
-static int create_body(ldso_ba *H, int device, int w, int h, int max_frames, int max_points);
-
-int ldso_ba_create(int device, int w, int h, int max_frames, int max_points, ldso_ba_t **out) {
-    REQ(out && w > 8 && h > 8 && max_frames >= 2 && max_frames <= LD_MAXF && max_points > 0, "ldso_ba_create: bad arguments");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, "ldso_ba_create: device index out of range");
-    CHK(hipSetDevice(device));
-    ldso_ba *H = new ldso_ba();
-    { const char *e = getenv("LDSO_GN_GRAPHS"); if (e && e[0] == '0') H->gnUseGraphs = false; }
-    const int r = create_body(H, device, w, h, max_frames, max_points);
-    if (r != LDSO_OK) { const std::string keep = g_err; ldso_ba_destroy(H); g_err = keep; return r; }      // nothing of a half-built handle leaks
-    *out = H;
+    DALLOC(H->allocs, S.slot, PS); DALLOC(H->allocs, S.pt, P); DALLOC(H->allocs, S.acc, P); DALLOC(H->allocs, S.candE, P);
+    DALLOC(H->allocs, S.G, P * (8 * FS + LD_GEXTRA)); DALLOC(H->allocs, S.topA, C * FS * LD_TOPN); DALLOC(H->allocs, S.topL, C * FS * LD_TOPN);
+    DALLOC(H->allocs, S.chunkEnergy, C); DALLOC(H->allocs, S.chunkCnt, C * 2); DALLOC(H->allocs, S.chunkNID, C * 2);
     return LDSO_OK;
 }
 
@@ -141,28 +111,37 @@ static int create_body(ldso_ba *H, int device, int w, int h, int max_frames, int
     memset(&H->D, 0, sizeof(H->D));
     BaPtrs &B = H->B;
     const size_t F = max_frames, P = max_points, FS = H->FSmax, nmax = 8 * F + 4;
-    DA(B.frames, F); DA(B.calib, 1); DA(B.pairs, F * F); DA(B.pairRt, F * F * 12);
-    DA(B.adHost, F * F * 64); DA(B.adTarget, F * F * 64); DA(B.adHostF, F * F * 64); DA(B.adTargetF, F * F * 64);
-    DA(B.nsProj, nmax * 7); DA(B.HM, nmax * nmax); DA(B.bM, nmax);
-    DA(B.pgeo, P); DA(B.pcw, P * 8); DA(B.phost, P);
-    DA(B.rtab, P * FS);
-    DA(B.Jlin, P * FS); DA(B.rtz, P * FS * 8);
-    DA(B.chunk_p0, H->maxChunks); DA(B.chunk_n, H->maxChunks); DA(B.chunk_host, H->maxChunks);
-    DA(H->d_chunkStart, F + 2);
-    DA(H->d_waitCtr, 4);
-    DA(H->d_margFlags, P);
-    DA(B.pairC, 2 * F * F * LD_PAIRC);
+    DALLOC(H->allocs, B.frames, F); DALLOC(H->allocs, B.calib, 1); DALLOC(H->allocs, B.pairs, F * F); DALLOC(H->allocs, B.pairRt, F * F * 12);
+    DALLOC(H->allocs, B.adHost, F * F * 64); DALLOC(H->allocs, B.adTarget, F * F * 64); DALLOC(H->allocs, B.adHostF, F * F * 64); DALLOC(H->allocs, B.adTargetF, F * F * 64);
+    DALLOC(H->allocs, B.nsProj, nmax * 7); DALLOC(H->allocs, B.HM, nmax * nmax); DALLOC(H->allocs, B.bM, nmax);
+    DALLOC(H->allocs, B.pgeo, P); DALLOC(H->allocs, B.pcw, P * 8); DALLOC(H->allocs, B.phost, P);
+    DALLOC(H->allocs, B.rtab, P * FS);
+    DALLOC(H->allocs, B.Jlin, P * FS); DALLOC(H->allocs, B.rtz, P * FS * 8);
+    DALLOC(H->allocs, B.chunk_p0, H->maxChunks); DALLOC(H->allocs, B.chunk_n, H->maxChunks); DALLOC(H->allocs, B.chunk_host, H->maxChunks);
+    DALLOC(H->allocs, H->d_chunkStart, F + 2);
+    DALLOC(H->allocs, H->d_waitCtr, 4);
+    DALLOC(H->allocs, H->d_margFlags, P);
+    DALLOC(H->allocs, B.pairC, 2 * F * F * LD_PAIRC);
     const size_t GSPmax = (8 * FS + LD_GEXTRA + 15) / 16 * 16;
-    DA(B.scPart, (size_t) LD_SC_SPLITS * GSPmax * GSPmax);
-    DA(B.sys, 4 * (nmax * nmax + nmax));
-    DA(B.acc, nmax * nmax + nmax); H->ownAcc = B.acc;
-    DA(B.x, nmax); DA(B.xAd, F * F * 8); DA(B.xc, 4); DA(B.scalars, 16); DA(B.energyLog, 64);
-    DA(H->d_dumpJ, P * FS);
+    DALLOC(H->allocs, B.scPart, (size_t) LD_SC_SPLITS * GSPmax * GSPmax);
+    DALLOC(H->allocs, B.sys, 4 * (nmax * nmax + nmax));
+    DALLOC(H->allocs, B.acc, nmax * nmax + nmax); H->ownAcc = B.acc;
+    DALLOC(H->allocs, B.x, nmax); DALLOC(H->allocs, B.xAd, F * F * 8); DALLOC(H->allocs, B.xc, 4); DALLOC(H->allocs, B.scalars, 16); DALLOC(H->allocs, B.energyLog, 64);
+    DALLOC(H->allocs, H->d_dumpJ, P * FS);
     B.dumpJ = nullptr;
     int r;
     if ((r = alloc_set(H, H->sets[0])) != LDSO_OK) return r;
     if ((r = alloc_set(H, H->sets[1])) != LDSO_OK) return r;
     return LDSO_OK;
+}
+
+int ldso_ba_create(int device, int w, int h, int max_frames, int max_points, ldso_ba_t **out) {
+    REQ(out && w > 8 && h > 8 && max_frames >= 2 && max_frames <= LD_MAXF && max_points > 0, "ldso_ba_create: bad arguments");
+    *out = nullptr;
+    RUN(open_device(device, "ldso_ba_create"));
+    ldso_ba *H = new ldso_ba();
+    { const char *e = getenv("LDSO_GN_GRAPHS"); if (e && e[0] == '0') H->gnUseGraphs = false; }
+    return finish_create(create_body(H, device, w, h, max_frames, max_points), H, out, ldso_ba_destroy);      // nothing of a half-built handle leaks
 }
 
 int ldso_ba_destroy(ldso_ba_t *H) {
@@ -197,10 +176,7 @@ int ldso_ba_set_stream(ldso_ba_t *H, void *s) {
     // work of this handle that is still in flight on the OLD stream is not ordered against the new one: wait for it here - in particular a staged copy out of the
     // pinned arena (stageBusy, ldso_ba_set_prior), whose later "wait for H->stream" would otherwise wait on the wrong stream
     if (H->stream && (H->ownStream || H->stageBusy)) { CHK(hipStreamSynchronize(H->stream)); H->stageBusy = false; }
-    if (H->ownStream && H->stream && s) { hipStreamDestroy(H->stream); H->ownStream = false; }
-    if (s) { H->stream = (hipStream_t) s; H->ownStream = false; }
-    else if (!H->ownStream) { CHK(hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking)); H->ownStream = true; }
-    return LDSO_OK;
+    return swap_stream(H->stream, H->ownStream, s);
 }
 
 int ldso_ba_set_settings(ldso_ba_t *H, const ldso_settings_t *s) {
@@ -235,10 +211,8 @@ int ldso_ba_set_image_raw(ldso_ba_t *H, int slot, const float *irradiance) {
     CHK(hipSetDevice(H->device));
     const size_t n = (size_t) H->w * H->h;
     if (!H->imgOwned[slot]) { void *q; CHK(hipMalloc(&q, n * 12)); H->imgSlots[slot] = (float *) q; H->imgOwned[slot] = true; rebind_slot(H, slot); }
-    if (!H->d_color) CHK(hipMalloc(&H->d_color, n * sizeof(float)));
-    CHK(hipMemcpyAsync(H->d_color, irradiance, n * sizeof(float), hipMemcpyHostToDevice, H->stream));
     float *lv[1] = {H->imgSlots[slot]};
-    CHK(img_launch_make_images(H->d_color, H->w, H->h, 1, lv, H->stream));
+    RUN(raw_to_images(H->d_color, irradiance, H->w, H->h, 1, lv, H->stream));
     CHK(hipStreamSynchronize(H->stream));
     return LDSO_OK;
 }
@@ -268,9 +242,7 @@ int ldso_ba_set_image_device(ldso_ba_t *H, int slot, const void *dev) {
 // image slot from a resident ldso_pyramid_t (level 0 = FrameHessian::dI): zero-copy, ordered after the pyramid's build on this stream
 int ldso_ba_set_image_pyramid(ldso_ba_t *H, int slot, ldso_pyramid_t *pyr) {
     REQ(H && pyr && slot >= 0 && slot < H->maxF, "ldso_ba_set_image_pyramid: bad arguments");
-    REQ(pyr->built && pyr->device == H->device && pyr->w == H->w && pyr->h == H->h, "ldso_ba_set_image_pyramid: pyramid does not match the handle (device, size) or holds no image");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamWaitEvent(H->stream, pyr->ready, 0));
+    RUN(pyramid_wait(pyr, H->device, H->w, H->h, 1, H->stream, "ldso_ba_set_image_pyramid", "the handle (device, size)"));
     return ldso_ba_set_image_device(H, slot, pyr->lv[0]);
 }
 

@@ -170,8 +170,7 @@ int ldso_ba_p2p_window_alloc(ldso_ba_t *H, int n_ranks, void **window_out, void 
         const hipError_t e_ = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached);
         if (e_ != hipSuccess) { (void) hipGetLastError(); ldso_set_error(std::string("ldso_ba_p2p_window_alloc: uncached device memory unavailable (hipExtMallocWithFlags: ") + hipGetErrorString(e_) + ")"); return LDSO_E_UNSUPPORTED; }
     }
-    CHK(hipMemset(p, 0, bytes));
-    CHK(hipStreamSynchronize(nullptr));          // (asynchronous zero-fill, see dalloc)
+    RUN(zero_fill(p, bytes));
     if (ipc_handle_out) {
         hipIpcMemHandle_t hnd;
         const hipError_t e_ = hipIpcGetMemHandle(&hnd, p);

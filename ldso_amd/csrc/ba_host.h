@@ -2,21 +2,13 @@
 // handle structs, and the host helpers that cross files (hidden: none of them is part of the library's interface).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <vector>
-#include <string>
-#include <cstring>
 #include <cstdio>
-#include <cmath>
-#include <algorithm>
-#include "../../include/ldso_hip.h"
+#include "host_only.h"          // ldso_set_error, REQ, RUN
 #include "ba_dev.h"
 #include "pyramid.h"
 #include "ba_solve.h"
 
-void ldso_set_error(const std::string &s);          // ba_api.hip (thread-local, read by ldso_last_error)
 #define CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ldso_set_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LDSO_E_HIP; } } while (0)
-#define REQ(cond, msg) do { if (!(cond)) { ldso_set_error(msg); return LDSO_E_INVALID; } } while (0)
-#define RUN(x) do { int r_ = (x); if (r_ != LDSO_OK) return r_; } while (0)
 
 // A launch with dynamic LDS: above 48 KB the kernel's limit is raised first; the status of that call is no reason to skip the launch, whose own error the caller sees
 template <class Kernel, class... Args>
@@ -185,6 +177,53 @@ struct ldso_tracer {
 };
 
 #pragma GCC visibility push(hidden)
+// The head of a create function: a device must be visible, `device` must name one, and it becomes the current one.
+inline int open_device(int device, const char *who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
+    REQ(device >= 0 && device < ndev, std::string(who) + ": device index out of range");
+    CHK(hipSetDevice(device));
+    return LDSO_OK;
+}
+// The tail of a create function whose body may fail half-way: the handle's own destroy frees whatever a half-built handle holds, the error text of the failure is kept.
+template <class Handle, class Destroy> int finish_create(int r, Handle *H, Handle **out, Destroy destroy) {
+    if (r != LDSO_OK) { const std::string keep = ldso_last_error(); destroy(H); ldso_set_error(keep); return r; }
+    *out = H; return LDSO_OK;
+}
+// Zero-fill of fresh device memory, waited for: hipMemset on device memory is asynchronous (legacy null stream) and the handles work on NON-BLOCKING streams,
+// which do not order themselves behind it: without the wait a zero-fill that is still queued (the null stream busy with another library's work, e.g. torch's)
+// could land on top of data the handle's first uploads / kernels have already written
+inline int zero_fill(void *p, size_t bytes) { CHK(hipMemset(p, 0, bytes)); CHK(hipStreamSynchronize(nullptr)); return LDSO_OK; }
+// n zeroed elements of device memory, recorded in `allocs` (what the handle's destroy frees)
+template <class T> int dalloc(std::vector<void *> &allocs, T **p, size_t n) {
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    CHK(hipMalloc((void **) p, bytes));
+    allocs.push_back(*p);
+    return zero_fill(*p, bytes);
+}
+#define DALLOC(allocs, ptr, n) RUN(dalloc(allocs, &(ptr), (n)))
+// *_set_stream: the caller's stream `s` instead of the handle's own non-blocking one (which is drained and destroyed), or, with s == nullptr, an own one again
+inline int swap_stream(hipStream_t &stream, bool &ownStream, void *s) {
+    if (ownStream && stream) { hipStreamSynchronize(stream); if (s) { hipStreamDestroy(stream); ownStream = false; } }
+    if (s) { stream = (hipStream_t) s; ownStream = false; }
+    else if (!ownStream) { CHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); ownStream = true; }
+    return LDSO_OK;
+}
+// A resident pyramid handed to a consumer `what` (named in the message): it holds an image and matches in device, size and levels; then `st` waits for its build.
+inline int pyramid_wait(const ldso_pyramid *pyr, int device, int w, int h, int minLevels, hipStream_t st, const char *who, const char *what) {
+    REQ(pyr->built && pyr->device == device && pyr->w == w && pyr->h == h && pyr->levels >= minLevels, std::string(who) + ": pyramid does not match " + what + " or holds no image");
+    CHK(hipSetDevice(device));
+    CHK(hipStreamWaitEvent(st, pyr->ready, 0));
+    return LDSO_OK;
+}
+// Raw level-0 irradiance on the host (w * h floats) -> `levels` images (images.hip): staging buffer on first use, upload, kernels, all on `st`; the caller waits or not.
+inline int raw_to_images(float *&d_color, const float *irradiance, int w, int h, int levels, float *const *d_levels, hipStream_t st) {
+    if (!d_color) CHK(hipMalloc(&d_color, (size_t) w * h * sizeof(float)));
+    CHK(hipMemcpyAsync(d_color, irradiance, (size_t) w * h * sizeof(float), hipMemcpyHostToDevice, st));
+    CHK(img_launch_make_images(d_color, w, h, levels, d_levels, st));
+    return LDSO_OK;
+}
+
 // trace.hip: the compaction of the tracer's resident immature set with keep flags that lie in device memory (ldso_ba_select_activate_tracer, act_select.hip):
 // record i stays where d_keep8[i] != 0 / d_keep32[i] == keepValue (both null: everywhere) and its host is a frame of the window.  Enqueued on `st`;
 // trace_compact_finish swaps the buffers and takes the new count once the caller has synchronised `st`.

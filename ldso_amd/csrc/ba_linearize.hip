@@ -20,42 +20,15 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "ba_host.h"
+#include "lane.h"
 
 #define RES_IN 0
 #define RES_OOB 1
 #define RES_OUTLIER 2
 
-// value of lane (i-1) within the 16-lane row; callers zero it for k==0
-__device__ __forceinline__ float dpp_row_shr1(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x111, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_quad_xor1(float x) {   // quad_perm [1,0,3,2]
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_quad_xor2(float x) {   // quad_perm [2,3,0,1]
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_quad_xor3(float x) {   // quad_perm [3,2,1,0]
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x1B, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_half_mirror(float x) {   // lane i <-> 7-i within each 8-lane half row
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-}
-// sum over the 8 lanes of a slot group, result in all 8 lanes (tree order)
-__device__ __forceinline__ float sum8(float x) {
-    x += dpp_quad_xor1(x);
-    x += dpp_quad_xor2(x);
-    x += dpp_half_mirror(x);
-    return x;
-}
-// lane i receives lane i-J of its 16-lane row (0 when that leaves the row)
-template <int J> __device__ __forceinline__ float dpp_row_shr(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x110 + J, 0xF, 0xF, true));
-}
+__device__ __forceinline__ float dpp_quad_xor3(float x) { return dpp_mov<0x1B>(x); }   // quad_perm [3,2,1,0]
 // lane j (0..3) of each quad broadcast to its quad
-template <int J> __device__ __forceinline__ float dpp_quad_bcast(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), J * 0x55, 0xF, 0xF, true));
-}
+template <int J> __device__ __forceinline__ float dpp_quad_bcast(float x) { return dpp_mov<J * 0x55>(x); }
 // element J and element 4 + J of every 8-lane group, in all 8 lanes of the group (two DPP moves and two selects instead of two ds_bpermute)
 template <int J> __device__ __forceinline__ void group_bcast_pair(float x, int k, float &lo, float &hi) {
     const float a = dpp_quad_bcast<J>(x);           // lanes 0-3: x[J], lanes 4-7: x[4 + J]
@@ -108,15 +81,15 @@ __device__ __forceinline__ float seq8(float x, int k, int lane) {
 // butterflies (tree order; the sequential-order sums that decide residual states use seq8).  gfx950's v_permlane16_swap / v_permlane32_swap
 // butterflies were measured against this in rounds 3 and 4: bit-identical, 2 % slower in every configuration - removed.
 __device__ __forceinline__ float sum_slots(float x, int a16, int a32) {
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(a16, __builtin_bit_cast(int, x)));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(a32, __builtin_bit_cast(int, x)));
+    x += dpp_row_ror8(x);
+    x += lane_perm(x, a16);
+    x += lane_perm(x, a32);
     return x;
 }
 // sum over the 4 slots of a half-wave (lanes with equal k inside lanes 0..31 / 32..63), result in every lane of the half: the first two steps of sum_slots
 __device__ __forceinline__ float sum_half(float x, int a16) {
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(a16, __builtin_bit_cast(int, x)));
+    x += dpp_row_ror8(x);
+    x += lane_perm(x, a16);
     return x;
 }
 // ---- just-in-time pointer groups ------------------------------------------------------------------------------------------------
@@ -172,7 +145,8 @@ struct PtIn {
     float jp[NSG], m[NSG];        // this lane's pair of the slot record: JpJdF[k] and scalar k (LD_SM_*; integers as raw bits)
     const float *ls;              // where the point's records are parked in the wavefront's LDS (STASH, linearize_body): [64 lanes][rgeo, rrec, colour, weight] | [64 lanes][rflat, rlin, jp, m]
 };
-// dword i of a record held one-dword-per-lane (wave-uniform result: a scalar register)
+// dword i of a record held one-dword-per-lane (wave-uniform result: a scalar register).  Macros on purpose: through lane.h's lane_read (the same builtin as a
+// function) the compiler schedules and allocates these kernels differently
 #define RLF(v, i) __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, (v)), (i)))
 #define RLI(v, i) __builtin_amdgcn_readlane(__builtin_bit_cast(int, (v)), (i))
 // PtGeo dwords (ba_dev.h)

@@ -380,10 +380,7 @@ int ldso_feat_destroy(ldso_features_t *F) {
 
 int ldso_feat_create(int device, int w, int h, int max_features, const int32_t *orb_pattern, ldso_features_t **out) {
     REQ(out && w > 16 && h > 16 && max_features > 0 && (long long) w * h < (1ll << 30), "ldso_feat_create: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, "ldso_feat_create: device index out of range");
-    CHK(hipSetDevice(device));
+    RUN(open_device(device, "ldso_feat_create"));
     ldso_features *F = new ldso_features();
     F->device = device; F->w = w; F->h = h; F->maxFeat = max_features; F->umax = feat_umax();
     const size_t m = (size_t) max_features;
@@ -401,10 +398,7 @@ int ldso_feat_create(int device, int w, int h, int max_features, const int32_t *
 
 int ldso_feat_set_stream(ldso_features_t *F, void *s) {
     REQ(F, "ldso_feat_set_stream: null handle");
-    if (F->ownStream && F->stream) { hipStreamSynchronize(F->stream); if (s) { hipStreamDestroy(F->stream); F->ownStream = false; } }
-    if (s) { F->stream = (hipStream_t) s; F->ownStream = false; }
-    else if (!F->ownStream) { CHK(hipStreamCreateWithFlags(&F->stream, hipStreamNonBlocking)); F->ownStream = true; }
-    return LDSO_OK;
+    return swap_stream(F->stream, F->ownStream, s);
 }
 
 int ldso_feat_set_response(ldso_features_t *F, const float *B) {
@@ -424,15 +418,13 @@ int ldso_feat_profile(ldso_features_t *F, int enable, float us_out[4]) {
 
 int ldso_feat_detect(ldso_features_t *F, ldso_pyramid_t *pyr, int n_features, int host_index, int *n_features_out, int *n_corners_out) {
     REQ(F && pyr, "ldso_feat_detect: null argument");
-    REQ(pyr->built && pyr->device == F->device && pyr->w == F->w && pyr->h == F->h, "ldso_feat_detect: pyramid does not match the detector (device, size) or holds no image");
     REQ(n_features > 0 && n_features <= F->w * F->h, "ldso_feat_detect: n_features out of range");
     const FeatGrid G = feat_grid(F->w, F->h, n_features);
     const int nCells = G.nx * G.ny;
     REQ(nCells * G.perCell <= F->maxFeat, "ldso_feat_detect: the grid's capacity (ldso_feat_grid) exceeds max_features");
     if (G.gridsize > FEAT_MAX_GRID) { ldso_set_error("ldso_feat_detect: gridsize above 64 (too few features for this image size)"); return LDSO_E_UNSUPPORTED; }
-    CHK(hipSetDevice(F->device));
     hipStream_t st = F->stream;
-    CHK(hipStreamWaitEvent(st, pyr->ready, 0));
+    RUN(pyramid_wait(pyr, F->device, F->w, F->h, 1, st, "ldso_feat_detect", "the detector (device, size)"));
     CHK(hipMemsetAsync(F->d_ctl, 0, 8 * 4, st));
     FeatArgs A;
     A.img = pyr->lv[0]; A.w = F->w; A.h = F->h; A.G = G; A.B = F->hasB ? F->d_B : nullptr; A.pattern = F->hasPattern ? F->d_pattern : nullptr;

@@ -52,10 +52,7 @@ extern "C" {
 
 int ldso_pyr_create(int device, int w, int h, int levels, ldso_pyramid_t **out) {
     REQ(out && w > 16 && h > 16 && levels >= 1 && levels <= LDSO_PYR_LEVELS && (w >> (levels - 1)) > 2 && (h >> (levels - 1)) > 2, "ldso_pyr_create: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, "ldso_pyr_create: device index out of range");
-    CHK(hipSetDevice(device));
+    RUN(open_device(device, "ldso_pyr_create"));
     ldso_pyramid *P = new ldso_pyramid();
     P->device = device; P->w = w; P->h = h; P->levels = levels;
     size_t total = 0;

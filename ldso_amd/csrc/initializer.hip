@@ -21,77 +21,13 @@
 // depth of that order (a diagonal front through the raster: 200-590 passes per level at 640 x 480, 20-40 points wide) is what
 // a sweep costs, so a pass is made as short as it can be: optReg with two lanes per point and a fixed selection instead of a
 // count-dependent one (ini_sw2_point: 28 instructions, 0.11 us per pass; round 4: one lane, a 10-key sorting network, 0.38 us).
-#include "ba_host.h"
+#include "initializer.h"
 #include "lie_dev.h"
+#include "lane.h"
 
-#define INI_MAXL 5            // maxIterations[] has five entries (CoarseInitializer.cc:43)
-#define INI_NT 256            // threads of an eval block: 32 points x 8 pattern pixels
-#define INI_MAXBLK 256        // eval blocks (= partial rows) per launch
-#define INI_NPART 128         // floats per partial row
-#define INI_CT 1024           // threads of the control block (its per-point passes are latency bound: many loads in flight)
-#define INI_NB 12             // neighbour row pitch (10 used)
-// partial row layout
-#define PR_SC 45              // 8 x 9 Schur block
-#define PR_SC88 117
-#define PR_E 118
-#define PR_ECO 119
-#define PR_ECN 120
-#define PR_ECC 121
-#define PR_N 122
-
-struct IniLevel {
-    int n, w, h, nPass;
-    float fx, fy, cx, cy;
-    double Ki[9];
-    const float *first, *cur;           // dIp[lvl] of the first and of the new frame
-    float *u, *v, *idepth, *idepth_new, *iR, *iRSumNum, *lastHessian, *lastHessian_new, *maxstep, *energy0, *energy1, *energy_new0, *energy_new1, *outlierTH;
-    int *isGood, *isGood_new, *parent, *nb;
-    float *jb[2];                       // [n][10]
-    // resetPoints sweep (top level only; one lane per point):
-    const int *sched;                   // [nPass][64] point index or -1
-    const int *schedOff;                // [nPass][64] LDS byte offset of the point's key (dummy slot n*4 for idle lanes)
-    const int *schedNb;                 // [nPass][64][INI_NB] LDS byte offsets of the neighbours' keys in schedule order (dummy slot: none)
-    // optReg sweep (two lanes per point): schedule of passes of <= 32 points and the per-lane inputs ini_prep writes before every sweep
-    int nPass2;
-    int nIdle;
-    const int *slotOf;                  // [n] place of the point in the schedule: pass * 32 + position
-    const int *idleSlot;                // [nIdle] places (of nPass2 + INI_SWPAD passes) that hold no point
-    int4 *swRec;                        // [nPass2 + INI_SWPAD][64][2]: see SwRec
-    const int *childOff, *childIdx;     // children (points of level - 1) of every point of this level, ascending
-};
-
-struct IniCtl {
-    double Tcur[12], Tnew[12];
-    float aCur, bCur, aNew, bNew;
-    float inc[8];
-    float lambda;
-    float H[64], b[8], Hsc[64], bsc[8], resOld[3];
-    float Hn[64], bn[8], Hscn[64], bscn[8], resNew[3], ec[3];
-    int lvl, mode, iteration, fails, done, snapped, snappedAt, frameID, jbSel, applyPending, evals, ready;
-    int idleWritten;                    // the records of the schedule places that hold no point are written (ini_prep_idle)
-    int ldsBase;                        // LDS address of the control block's key array (the sweep records hold LDS addresses)
-    int sweepDue, upGoing;              // level + 1 whose optReg sweep (view: good points, applied depths) is the next control step's; in the propagateUp chain
-    int steps;                          // control steps of this frame so far (INI_STEP launches that did something)
-    int prepReady;                      // k_ini_prep has written the records of the level for the step this evaluation tried; consumed by the control step
-    long long dbgSweepTicks, dbgSweepPasses, dbgCtlTicks, dbgSweeps, dbgPrepTicks, dbgFrontTicks, dbgTailTicks, dbgSpare;     // LDSO_STAMPS builds only (100 MHz wall clock)
-};
-
-struct IniParams {
-    IniLevel L[INI_MAXL];
-    int levels, fixAffine;
-    float huberTH, firstExposure, newExposure;
-    IniCtl *ctl;
-    float *part;                        // [INI_MAXBLK][INI_NPART]
-};
-
-__device__ __forceinline__ float ini_dpp_xor1(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true)); }
-__device__ __forceinline__ float ini_dpp_xor2(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true)); }
-__device__ __forceinline__ float ini_dpp_hmir(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true)); }
-__device__ __forceinline__ float ini_dpp_rmir(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true)); }
-__device__ __forceinline__ float ini_dpp_ror8(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xF, 0xF, true)); }
-__device__ __forceinline__ float ini_sum8(float x) { x += ini_dpp_xor1(x); x += ini_dpp_xor2(x); x += ini_dpp_hmir(x); return x; }
-__device__ __forceinline__ float ini_min8(float x) { x = fminf(x, ini_dpp_xor1(x)); x = fminf(x, ini_dpp_xor2(x)); x = fminf(x, ini_dpp_hmir(x)); return x; }
-__device__ __forceinline__ float ini_sum16(float x) { x = ini_sum8(x); x += ini_dpp_rmir(x); return x; }
+__device__ __forceinline__ float dpp_row_mirror(float x) { return dpp_mov<0x140>(x); }        // lane i <-> 15-i within each 16-lane row
+__device__ __forceinline__ float min8(float x) { x = fminf(x, dpp_quad_xor1(x)); x = fminf(x, dpp_quad_xor2(x)); x = fminf(x, dpp_half_mirror(x)); return x; }
+__device__ __forceinline__ float sum16(float x) { x = sum8(x); x += dpp_row_mirror(x); return x; }
 
 __device__ __forceinline__ int ini_nblocks(int n, int gridCap) { const int nb = (n + 31) / 32; return nb < gridCap ? (nb < 1 ? 1 : nb) : gridCap; }
 
@@ -243,13 +179,13 @@ __global__ __launch_bounds__(INI_NT) void k_ini_eval(IniParams P, int stage) {
         const unsigned long long bm = __ballot(bad);
         const unsigned grp = (unsigned) (bm >> (lane & ~7)) & 0xFFu;
         const int firstBad = grp ? (__ffs(grp) - 1) : 8;
-        const float maxstepNew = ini_min8((k < firstBad) ? ms : 1e10f);
-        const float energy = ini_sum8(e);
+        const float maxstepNew = min8((k < firstBad) ? ms : 1e10f);
+        const float energy = sum8(e);
         const bool goodNew = valid && good && firstBad == 8 && !(energy > oTH * 20);
         float Jb[10];
 #pragma unroll
-        for (int q = 0; q < 9; q++) Jb[q] = ini_sum8(dp[q] * dd);
-        Jb[9] = ini_sum8(dd * dd);
+        for (int q = 0; q < 9; q++) Jb[q] = sum8(dp[q] * dd);
+        Jb[9] = sum8(dd * dd);
         float en0, en1;
         if (goodNew) {
 #pragma unroll
@@ -292,10 +228,10 @@ __global__ __launch_bounds__(INI_NT) void k_ini_eval(IniParams P, int stage) {
 
     // ---- block reduction -> one partial row ----
 #pragma unroll
-    for (int i = 0; i < 45; i++) acc[i] = ini_sum16(acc[i]);
-    accE = ini_sum16(accE); accEO = ini_sum16(accEO); accEN = ini_sum16(accEN); accEC = ini_sum16(accEC);
+    for (int i = 0; i < 45; i++) acc[i] = sum16(acc[i]);
+    accE = sum16(accE); accEO = sum16(accEO); accEN = sum16(accEN); accEC = sum16(accEC);
 #pragma unroll
-    for (int q = 0; q < 10; q++) accSC[q] += ini_dpp_ror8(accSC[q]);
+    for (int q = 0; q < 10; q++) accSC[q] += dpp_row_ror8(accSC[q]);
     const int row = wave * 4 + (lane >> 4);
     if ((lane & 15) == 0) {
 #pragma unroll
@@ -326,9 +262,6 @@ __global__ __launch_bounds__(INI_NT) void k_ini_eval(IniParams P, int stage) {
 // ---------------------------------------------------------------------------------------------------------
 // control block
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ini_shfl(float v, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v))); }
-__device__ __forceinline__ float ini_bcast(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
-
 // Eigen-style pivoted LDL^T solve (float) of the leading nn x nn block by one wavefront, lane i*8+j holds A[i][j]; x by lanes 0..7
 __device__ void ini_ldlt_wave(float a, float rhsLane, int nn, float *x /*LDS 8*/) {
     const int lane = threadIdx.x & 63, i = lane >> 3, j = lane & 7;
@@ -339,16 +272,16 @@ __device__ void ini_ldlt_wave(float a, float rhsLane, int nn, float *x /*LDS 8*/
         tr[kk] = kk;
         if (kk < nn) {
             int idx = kk;
-            float best = fabsf(ini_bcast(a, kk * 9));
+            float best = fabsf(lane_read(a, kk * 9));
 #pragma unroll
-            for (int q = kk + 1; q < 8; q++) { const float d = fabsf(ini_bcast(a, q * 9)); if (q < nn && d > best) { best = d; idx = q; } }
+            for (int q = kk + 1; q < 8; q++) { const float d = fabsf(lane_read(a, q * 9)); if (q < nn && d > best) { best = d; idx = q; } }
             tr[kk] = idx;
             if (idx != kk) {
                 const int si = (i == kk) ? idx : (i == idx) ? kk : i, sj = (j == kk) ? idx : (j == idx) ? kk : j;
-                a = ini_shfl(a, si * 8 + sj);
+                a = lane_shfl(a, si * 8 + sj);
             }
-            const float d = ini_bcast(a, kk * 9);
-            const float ci = ini_shfl(a, i * 8 + kk), cj = ini_shfl(a, j * 8 + kk);
+            const float d = lane_read(a, kk * 9);
+            const float ci = lane_shfl(a, i * 8 + kk), cj = lane_shfl(a, j * 8 + kk);
             if (fabsf(d) > 0.0f) {
                 if (i > kk && j > kk) a -= ci * (cj / d);
                 else if (j == kk && i > kk) a = ci / d;
@@ -358,14 +291,14 @@ __device__ void ini_ldlt_wave(float a, float rhsLane, int nn, float *x /*LDS 8*/
     }
     float xr = (lane < nn) ? rhsLane : 0.0f;
 #pragma unroll
-    for (int kk = 0; kk < 8; kk++) { const int t_ = tr[kk]; if (t_ != kk) { const int src = (lane == kk) ? t_ : (lane == t_) ? kk : lane; xr = ini_shfl(xr, src & 63); } }
+    for (int kk = 0; kk < 8; kk++) { const int t_ = tr[kk]; if (t_ != kk) { const int src = (lane == kk) ? t_ : (lane == t_) ? kk : lane; xr = lane_shfl(xr, src & 63); } }
 #pragma unroll
-    for (int c = 0; c < 7; c++) { const float xc = ini_bcast(xr, c); const float l = ini_shfl(a, (lane & 7) * 8 + c); if (lane < 8 && lane > c) xr -= l * xc; }
-    { const float dr = ini_shfl(a, (lane & 7) * 9); xr = (fabsf(dr) > 1.17549435e-38f) ? xr / dr : 0.0f; }
+    for (int c = 0; c < 7; c++) { const float xc = lane_read(xr, c); const float l = lane_shfl(a, (lane & 7) * 8 + c); if (lane < 8 && lane > c) xr -= l * xc; }
+    { const float dr = lane_shfl(a, (lane & 7) * 9); xr = (fabsf(dr) > 1.17549435e-38f) ? xr / dr : 0.0f; }
 #pragma unroll
-    for (int c = 7; c >= 1; c--) { const float xc = ini_bcast(xr, c); const float l = ini_shfl(a, c * 8 + (lane & 7)); if (lane < c) xr -= l * xc; }
+    for (int c = 7; c >= 1; c--) { const float xc = lane_read(xr, c); const float l = lane_shfl(a, c * 8 + (lane & 7)); if (lane < c) xr -= l * xc; }
 #pragma unroll
-    for (int kk = 7; kk >= 0; kk--) { const int t_ = tr[kk]; if (t_ != kk) { const int src = (lane == kk) ? t_ : (lane == t_) ? kk : lane; xr = ini_shfl(xr, src & 63); } }
+    for (int kk = 7; kk >= 0; kk--) { const int t_ = tr[kk]; if (t_ != kk) { const int src = (lane == kk) ? t_ : (lane == t_) ? kk : lane; xr = lane_shfl(xr, src & 63); } }
     if (lane < 8) x[lane] = (lane < nn) ? xr : 0.0f;
 }
 
@@ -374,11 +307,8 @@ __device__ void ini_ldlt_wave(float a, float rhsLane, int nn, float *x /*LDS 8*/
 // Order-preserving integer key of a (non-NaN) float: integer min/max need no NaN canonicalisation.  INI_NOKEY = point not good.
 #define INI_NOKEY 0x7fffffff
 #define INI_MINKEY ((int) 0x80000000)
-#define INI_LDS_EXTRA 3
 __device__ __forceinline__ int ini_key(float f) { const int b = __builtin_bit_cast(int, f); return b ^ ((b >> 31) & 0x7fffffff); }
 __device__ __forceinline__ float ini_unkey(int k) { return __builtin_bit_cast(float, k ^ ((k >> 31) & 0x7fffffff)); }
-// unconditional prefetch: the schedule arrays carry INI_SWPAD passes of padding (idle lanes) behind the last pass
-#define INI_SWPAD 16
 
 // ---- resetPoints' neighbour average (:629-641), one lane per point: a point that gets an average BECOMES good for the points behind it, and the float sum runs in
 // neighbour order - nothing of it can be prepared or split.  Top level only, once per frame.
@@ -438,7 +368,7 @@ __device__ __forceinline__ SwRec ini_sw2_load(const IniLevel &L, int p, int lane
 __device__ __forceinline__ int ini_min3(int a, int b, int c) { int r; asm("v_min3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ int ini_med3(int a, int b, int c) { int r; asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ int ini_max3(int a, int b, int c) { int r; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ int ini_pair(int x) { return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true); }      // the other lane of the pair
+__device__ __forceinline__ int ini_pair(int x) { return dpp_mov<0xB1>(x); }      // the other lane of the pair
 __device__ __forceinline__ void ini_sw2_point(const SwRec &r) {
     const float regWeight = 0.8f;
 #define GK(adr) (*(const ini_lds_int *) (unsigned long long) (unsigned) (adr))
@@ -579,10 +509,6 @@ __device__ void ini_flush_apply(const IniLevel &L) {   // applyStep (:673-687) f
     }
     __syncthreads();
 }
-
-#define INI_BEGIN 0
-#define INI_STEP 1
-#define INI_STAGE 2
 
 // propagateDown(lvl) (:498-522) into level lvl - 1
 __device__ void ini_propagate_down(const IniParams &P, int lvl) {
@@ -879,7 +805,6 @@ __global__ __launch_bounds__(INI_CT) void k_ini_ctl(IniParams P, int phase) {
 // The sweep inputs of the step an evaluation has just tried, by the whole chip instead of the control block (launched between k_ini_eval and k_ini_ctl): if the
 // control step accepts it, optReg (:137-138) sweeps the level in the view "good and still good after the step" with the new inverse depths - both final when
 // k_ini_eval ends.  Wasted when the step is rejected (a few us beside the evaluation).
-#define INI_PT 256
 __global__ __launch_bounds__(INI_PT) void k_ini_prep(IniParams P) {
     const IniCtl *ctl = P.ctl;
     // nothing to prepare: frame finished; optReg only resets iR before the snap (a step that snaps is prepared by the control step itself)
@@ -899,484 +824,8 @@ __global__ __launch_bounds__(INI_PT) void k_ini_prep(IniParams P) {
     if (blockIdx.x == 0 && threadIdx.x == 0) P.ctl->prepReady = 1;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// host
-// ---------------------------------------------------------------------------------------------------------
-struct ldso_initializer {
-    int device = 0, w = 0, h = 0, levels = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    IniParams P;
-    std::vector<void *> allocs, levelAllocs;
-    float *d_first[INI_MAXL] = {nullptr}, *d_new[INI_MAXL] = {nullptr};
-    float *d_color = nullptr;
-    int n[INI_MAXL] = {0};
-    size_t ldsBytes = 0;
-    int prepBlocks = 1;                 // k_ini_prep: one thread per point of the largest level
-    int lastSteps = 0, stepsTaken = 0;  // control steps of the previous frame / of the frame just read back (get_state)
-    int firstSteps = 0;                 // ldso_init_set_schedule: control steps of the first batch (0 = by the previous frame)
-    bool prepareOnGrid = true;          // ldso_init_set_schedule: k_ini_prep launches (false: the control block prepares every sweep)
-    bool frameDone = false;
-    bool snappedAtFrameStart = false;   // host copy of the state's snapped (get_state / set_state / set_first): before the snap optReg does not sweep and the
-                                        // k_ini_prep launches would be empty (the frame that snaps prepares its sweeps in the control block)
-    bool haveFirst = false, haveNew = false;
-};
-
-template <class T> static int ini_alloc(std::vector<void *> &v, T **p, size_t n) {
-    void *q = nullptr;
-    CHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    // hipMemset on device memory is asynchronous (legacy null stream) and the handles work on NON-BLOCKING streams, which do not order themselves
-    // behind it: without the wait a zero-fill that is still queued (the null stream busy with another library's work, e.g. torch's) could land on top
-    // of data the handle's first uploads / kernels have already written
-    CHK(hipMemset(q, 0, std::max<size_t>(n, 1) * sizeof(T)));
-    CHK(hipStreamSynchronize(nullptr));
-    v.push_back(q);
-    *p = (T *) q;
-    return LDSO_OK;
-}
-#define IA(vec, ptr, n) do { int r_ = ini_alloc(vec, &(ptr), (n)); if (r_ != LDSO_OK) return r_; } while (0)
-
-// upload helper: host vector -> new device array
-// The schedule of the optReg sweep: pass[i] for every point such that (a) every neighbour j < i of i sits in an EARLIER pass (i reads j's new value), (b) every
-// neighbour j > i of i sits in the SAME or a later pass (i reads j's old value; reads come before writes within a pass) and (c) no pass holds more than `width`
-// points.  The reference's in-place loop over i (CoarseInitializer.cc:430-459) is pass 0, 1, 2, ... of this schedule executed in order.
-// Two constructions, the shorter one wins: first fit in index order (both conditions only look at lower indices), and list scheduling by the length of the
-// chain that still hangs on a point (the dependency depth is a diagonal front through the raster; where it is wider than a pass, the points with the longest
-// tails go first).  640 x 480 (8.4k / 18.4k / 17.2k / 3.8k points, depth 341 / 586 / 412 / 196): first fit 341 / 719 / 654 / 196 passes, list 341 / 642 / 606 / 196.
-static bool ini_schedule_valid(int n, const int *nb, int width, const std::vector<int> &pass, int nPass) {
-    std::vector<int> cnt(std::max(nPass, 1), 0);
-    for (int i = 0; i < n; i++) {
-        if (pass[i] < 0 || pass[i] >= nPass || ++cnt[pass[i]] > width) return false;
-        for (int q = 0; q < 10; q++) {
-            const int j = nb[(size_t) i * 10 + q];
-            if (j < 0 || j == i) continue;
-            if (j < i ? !(pass[j] < pass[i]) : !(pass[j] >= pass[i])) return false;
-        }
-    }
-    return true;
-}
-static int ini_sweep_schedule(int n, const int *nb, int width, int *passOut) {
-    if (n <= 0) return 0;
-    // first fit
-    std::vector<int> ff(n, 0), rd(n, 0), fillOf;
-    for (int i = 0; i < n; i++) {
-        int e = rd[i];
-        for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * 10 + q]; if (j >= 0 && j < i) e = std::max(e, ff[j] + 1); }
-        while (e < (int) fillOf.size() && fillOf[e] >= width) e++;
-        if (e >= (int) fillOf.size()) fillOf.resize(e + 1, 0);
-        ff[i] = e;
-        for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * 10 + q]; if (j > i && j < n) rd[j] = std::max(rd[j], e); }
-        fillOf[e]++;
-    }
-    const int nFF = (int) fillOf.size();
-    // list scheduling.  after[j]: the points i > j that have j as a neighbour (i waits for j's pass to be over); before[j]: the readers i < j of j (j must not
-    // come before them); tail[i]: passes that must still follow the pass of i
-    std::vector<int> offA(n + 1, 0), offB(n + 1, 0), waits(n, 0);
-    for (int i = 0; i < n; i++) for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * 10 + q]; if (j < 0 || j >= n || j == i) continue; if (j < i) { offA[j + 1]++; waits[i]++; } else offB[j + 1]++; }
-    for (int i = 0; i < n; i++) { offA[i + 1] += offA[i]; offB[i + 1] += offB[i]; }
-    std::vector<int> after(offA[n]), before(offB[n]), curA(offA.begin(), offA.end() - 1), curB(offB.begin(), offB.end() - 1);
-    for (int i = 0; i < n; i++) for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * 10 + q]; if (j < 0 || j >= n || j == i) continue; if (j < i) after[curA[j]++] = i; else before[curB[j]++] = i; }
-    std::vector<int> tail(n, 0);
-    for (int i = n - 1; i >= 0; i--) {
-        int t = 0;
-        for (int a = offA[i]; a < offA[i + 1]; a++) t = std::max(t, tail[after[a]] + 1);
-        for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * 10 + q]; if (j > i && j < n) t = std::max(t, tail[j]); }
-        tail[i] = t;
-    }
-    std::vector<int> ls(n, -1), ready, chosen, deferred;
-    std::vector<char> inPass(n, 0);
-    for (int i = 0; i < n; i++) if (waits[i] == 0) ready.push_back(i);
-    int left = n, t = 0;
-    bool stuck = false;
-    while (left > 0 && !stuck) {
-        std::sort(ready.begin(), ready.end(), [&](int a, int b) { return tail[a] != tail[b] ? tail[a] > tail[b] : a < b; });
-        chosen.clear(); deferred.clear();
-        auto free_ = [&](int i) { for (int a = offB[i]; a < offB[i + 1]; a++) { const int k = before[a]; if (ls[k] < 0 && !inPass[k]) return false; } return true; };
-        for (int i : ready) { if ((int) chosen.size() < width && free_(i)) { chosen.push_back(i); inPass[i] = 1; } else deferred.push_back(i); }
-        for (bool again = true; again && (int) chosen.size() < width;) {          // readers chosen later in the priority order free the points they held back
-            again = false;
-            for (size_t d = 0; d < deferred.size(); d++) {
-                const int i = deferred[d];
-                if (i >= 0 && (int) chosen.size() < width && free_(i)) { chosen.push_back(i); inPass[i] = 1; deferred[d] = -1; again = true; }
-            }
-        }
-        if (chosen.empty()) { stuck = true; break; }
-        ready.clear();
-        for (int i : deferred) if (i >= 0) ready.push_back(i);
-        for (int i : chosen) { ls[i] = t; inPass[i] = 0; left--; }
-        for (int i : chosen) for (int a = offA[i]; a < offA[i + 1]; a++) if (--waits[after[a]] == 0) ready.push_back(after[a]);
-        t++;
-    }
-    const bool useList = !stuck && t < nFF && ini_schedule_valid(n, nb, width, ls, t);
-    for (int i = 0; i < n; i++) passOut[i] = useList ? ls[i] : ff[i];
-    return useList ? t : nFF;
-}
-
-template <class T> static int ini_upload(ldso_initializer *H, T **dst, const std::vector<T> &src) {
-    IA(H->levelAllocs, *dst, src.size());
-    if (!src.empty()) CHK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return LDSO_OK;
-}
-
-// SoA <-> record conversion
-#define INI_FIELDS(X) X(u) X(v) X(idepth) X(idepth_new) X(iR) X(iRSumNum) X(lastHessian) X(lastHessian_new) X(maxstep) X(outlierTH)
-
-static int ini_put_points(ldso_initializer *H, int l, const ldso_init_point_t *pts) {
-    IniLevel &L = H->P.L[l];
-    const int n = H->n[l];
-    std::vector<float> f(n);
-    std::vector<int> g(n);
-#define X(name) for (int i = 0; i < n; i++) f[i] = pts[i].name; if (n) CHK(hipMemcpy(L.name, f.data(), (size_t) n * 4, hipMemcpyHostToDevice));
-    INI_FIELDS(X)
-#undef X
-#define XE(dst, expr) for (int i = 0; i < n; i++) f[i] = pts[i].expr; if (n) CHK(hipMemcpy(L.dst, f.data(), (size_t) n * 4, hipMemcpyHostToDevice));
-    XE(energy0, energy[0]) XE(energy1, energy[1]) XE(energy_new0, energy_new[0]) XE(energy_new1, energy_new[1])
-#undef XE
-#define XI(dst, expr) for (int i = 0; i < n; i++) g[i] = pts[i].expr; if (n) CHK(hipMemcpy(L.dst, g.data(), (size_t) n * 4, hipMemcpyHostToDevice));
-    XI(isGood, isGood) XI(isGood_new, isGood_new)
-#undef XI
-    return LDSO_OK;
-}
-
-extern "C" {
-
-int ldso_init_create(int device, int w, int h, int levels, ldso_initializer_t **out) {
-    REQ(out && w > 16 && h > 16 && levels >= 1 && levels <= INI_MAXL && (w >> (levels - 1)) >= 8, "ldso_init_create: bad arguments (at most 5 pyramid levels)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, "ldso_init_create: device index out of range");
-    CHK(hipSetDevice(device));
-    ldso_initializer *H = new ldso_initializer();
-    H->device = device; H->w = w; H->h = h; H->levels = levels;
-    CHK(hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking));
-    H->ownStream = true;
-    memset(&H->P, 0, sizeof(H->P));
-    H->P.levels = levels; H->P.fixAffine = 1; H->P.huberTH = 9.0f; H->P.firstExposure = 1; H->P.newExposure = 1;
-    for (int l = 0; l < levels; l++) {
-        const size_t npx = (size_t) (w >> l) * (h >> l);
-        IA(H->allocs, H->d_first[l], npx * 3); IA(H->allocs, H->d_new[l], npx * 3);
-        H->P.L[l].first = H->d_first[l]; H->P.L[l].cur = H->d_new[l];
-        H->P.L[l].w = w >> l; H->P.L[l].h = h >> l;
-    }
-    IA(H->allocs, H->d_color, (size_t) w * h);
-    IA(H->allocs, H->P.ctl, 1);
-    IA(H->allocs, H->P.part, (size_t) INI_MAXBLK * INI_NPART);
-    IniCtl c; memset(&c, 0, sizeof(c));
-    c.Tcur[0] = c.Tcur[5] = c.Tcur[10] = 1.0; c.Tnew[0] = c.Tnew[5] = c.Tnew[10] = 1.0; c.frameID = -1; c.done = 1;
-    CHK(hipMemcpy(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
-    *out = H;
-    return LDSO_OK;
-}
-
-int ldso_init_destroy(ldso_initializer_t *H) {
-    if (!H) return LDSO_OK;
-    hipSetDevice(H->device);
-    hipDeviceSynchronize();
-    for (void *p : H->allocs) hipFree(p);
-    for (void *p : H->levelAllocs) hipFree(p);
-    if (H->ownStream && H->stream) hipStreamDestroy(H->stream);
-    delete H;
-    return LDSO_OK;
-}
-
-int ldso_init_set_stream(ldso_initializer_t *H, void *s) {
-    REQ(H, "null handle");
-    if (H->ownStream && H->stream) { hipStreamSynchronize(H->stream); if (s) { hipStreamDestroy(H->stream); H->ownStream = false; } }
-    if (s) { H->stream = (hipStream_t) s; H->ownStream = false; }
-    else if (!H->ownStream) { CHK(hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking)); H->ownStream = true; }
-    return LDSO_OK;
-}
-
-static int ini_images(ldso_initializer *H, const float *irr, float *const *levels) {
-    CHK(hipSetDevice(H->device));
-    CHK(hipMemcpyAsync(H->d_color, irr, (size_t) H->w * H->h * 4, hipMemcpyHostToDevice, H->stream));
-    CHK(img_launch_make_images(H->d_color, H->w, H->h, H->levels, levels, H->stream));
-    CHK(hipStreamSynchronize(H->stream));      // the host buffer may be reused by the caller
-    return LDSO_OK;
-}
-
-int ldso_init_set_first(ldso_initializer_t *H, const float calib[4], const float *irradiance, float ab_exposure,
-                        const ldso_init_point_t *const *points, const int *n_points, float huberTH, int fixAffine) {
-    REQ(H && calib && irradiance && points && n_points, "ldso_init_set_first: null argument");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamSynchronize(H->stream));
-    for (void *p : H->levelAllocs) hipFree(p);
-    H->levelAllocs.clear();
-    H->P.huberTH = huberTH; H->P.fixAffine = fixAffine ? 1 : 0; H->P.firstExposure = ab_exposure;
-    // makeK (:689-715): doubles from the float level-0 intrinsics
-    double fx[INI_MAXL], fy[INI_MAXL], cx[INI_MAXL], cy[INI_MAXL];
-    fx[0] = calib[0]; fy[0] = calib[1]; cx[0] = calib[2]; cy[0] = calib[3];
-    for (int l = 1; l < H->levels; l++) {
-        fx[l] = fx[l - 1] * 0.5; fy[l] = fy[l - 1] * 0.5;
-        cx[l] = (cx[0] + 0.5) / ((int) 1 << l) - 0.5; cy[l] = (cy[0] + 0.5) / ((int) 1 << l) - 0.5;
-    }
-    size_t maxN = 64;
-    for (int l = 0; l < H->levels; l++) {
-        IniLevel &L = H->P.L[l];
-        const int n = n_points[l];
-        REQ(n >= 0 && n <= 36000, "ldso_init_set_first: more than 36000 points on one level (LDS working set of the sweeps)");
-        REQ(n == 0 || points[l], "ldso_init_set_first: null point array");
-        H->n[l] = n; L.n = n;
-        maxN = std::max<size_t>(maxN, n);
-        L.fx = (float) fx[l]; L.fy = (float) fy[l]; L.cx = (float) cx[l]; L.cy = (float) cy[l];
-        // K^-1 of the upper-triangular K in double (Eigen's cofactor inverse gives the same entries up to 1 ulp of double)
-        for (int q = 0; q < 9; q++) L.Ki[q] = 0;
-        L.Ki[0] = 1.0 / fx[l]; L.Ki[2] = -cx[l] / fx[l]; L.Ki[4] = 1.0 / fy[l]; L.Ki[5] = -cy[l] / fy[l]; L.Ki[8] = 1.0;
-#define X(name) IA(H->levelAllocs, L.name, n);
-        INI_FIELDS(X)
-        X(energy0) X(energy1) X(energy_new0) X(energy_new1) X(isGood) X(isGood_new)
-#undef X
-        IA(H->levelAllocs, L.jb[0], (size_t) n * 10); IA(H->levelAllocs, L.jb[1], (size_t) n * 10);
-        const ldso_init_point_t *pts = points[l];
-        const int nUp = (l + 1 < H->levels) ? n_points[l + 1] : 0, nDown = (l > 0) ? n_points[l - 1] : 0;
-        std::vector<int> parent(n), nb((size_t) n * INI_NB, -1);
-        for (int i = 0; i < n; i++) {
-            parent[i] = pts[i].parent;
-            REQ(l + 1 >= H->levels || (parent[i] >= 0 && parent[i] < nUp), "ldso_init_set_first: parent index out of range");
-            for (int q = 0; q < 10; q++) {
-                const int j = pts[i].neighbours[q];
-                REQ(j >= -1 && j < n, "ldso_init_set_first: neighbour index out of range");
-                nb[(size_t) i * INI_NB + q] = j;
-            }
-        }
-        { int r_ = ini_upload(H, &L.parent, parent); if (r_ != LDSO_OK) return r_; }
-        { int r_ = ini_upload(H, &L.nb, nb); if (r_ != LDSO_OK) return r_; }
-        // optReg sweep schedule (all levels; two lanes per point: passes of <= 32 points): ini_sweep_schedule
-        {
-            std::vector<int> pass(n, 0), nb10((size_t) n * 10);
-            for (int i = 0; i < n; i++) for (int q = 0; q < 10; q++) nb10[(size_t) i * 10 + q] = nb[(size_t) i * INI_NB + q];
-            L.nPass2 = ini_sweep_schedule(n, nb10.data(), 32, pass.data());
-            std::vector<int> slotOf(n), at(L.nPass2, 0), idleSlot;
-            for (int i = 0; i < n; i++) slotOf[i] = pass[i] * 32 + at[pass[i]]++;
-            for (int p = 0; p < L.nPass2 + INI_SWPAD; p++) for (int q = (p < L.nPass2 ? at[p] : 0); q < 32; q++) idleSlot.push_back(p * 32 + q);
-            L.nIdle = (int) idleSlot.size();
-            { int *p = nullptr; int r_ = ini_upload(H, &p, slotOf); if (r_ != LDSO_OK) return r_; L.slotOf = p; }
-            { int *p = nullptr; int r_ = ini_upload(H, &p, idleSlot); if (r_ != LDSO_OK) return r_; L.idleSlot = p; }
-            IA(H->levelAllocs, L.swRec, (size_t) (L.nPass2 + INI_SWPAD) * 64 * 2);      // per-lane inputs: ini_prep writes them before every sweep (the places without a point: once)
-        }
-        if (l + 1 < H->levels) { L.nPass = 0; L.sched = nullptr; L.schedOff = nullptr; L.schedNb = nullptr; }
-        else {
-        // resetPoints sweep schedule (top level): dep(i) = max(dep(j) + 1 over neighbours j < i, dep(k) over readers k < i of i)
-        std::vector<int> dep(n, 0);
-        {
-            std::vector<int> rd(n, 0);      // max dep of the lower-indexed readers seen so far
-            for (int i = 0; i < n; i++) {
-                int d = rd[i];
-                for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * INI_NB + q]; if (j >= 0 && j < i) d = std::max(d, dep[j] + 1); }
-                dep[i] = d;
-                for (int q = 0; q < 10; q++) { const int j = nb[(size_t) i * INI_NB + q]; if (j > i) rd[j] = std::max(rd[j], d); }
-            }
-        }
-        int nDep = 0;
-        for (int i = 0; i < n; i++) nDep = std::max(nDep, dep[i] + 1);
-        std::vector<std::vector<int>> byDep(nDep);
-        for (int i = 0; i < n; i++) byDep[dep[i]].push_back(i);
-        std::vector<int> sched;
-        for (int d = 0; d < nDep; d++)
-            for (size_t o = 0; o < byDep[d].size(); o += 64) {
-                for (size_t q = 0; q < 64; q++) sched.push_back(o + q < byDep[d].size() ? byDep[d][o + q] : -1);
-            }
-        L.nPass = (int) (sched.size() / 64);
-        sched.resize(sched.size() + (size_t) INI_SWPAD * 64, -1);
-        { int *p = nullptr; int r_ = ini_upload(H, &p, sched); if (r_ != LDSO_OK) return r_; L.sched = p; }
-        {
-            const int dummy = n * 4;
-            std::vector<int> snb(sched.size() * INI_NB, dummy), soff(sched.size(), dummy);
-            for (size_t q = 0; q < sched.size(); q++)
-                if (sched[q] >= 0) {
-                    soff[q] = sched[q] * 4;
-                    for (int e = 0; e < 10; e++) { const int j = nb[(size_t) sched[q] * INI_NB + e]; snb[q * INI_NB + e] = (j >= 0) ? j * 4 : dummy; }
-                }
-            int *p = nullptr; int r_ = ini_upload(H, &p, snb); if (r_ != LDSO_OK) return r_; L.schedNb = p;
-            p = nullptr; r_ = ini_upload(H, &p, soff); if (r_ != LDSO_OK) return r_; L.schedOff = p;
-        }
-        }
-        // children lists (points of level l-1 whose parent is p), ascending child index
-        std::vector<int> off(n + 1, 0), idx(nDown);
-        if (l > 0) {
-            const ldso_init_point_t *ch = points[l - 1];
-            for (int c = 0; c < nDown; c++) { REQ(ch[c].parent >= 0 && ch[c].parent < n, "ldso_init_set_first: parent index out of range"); off[ch[c].parent + 1]++; }
-            for (int p = 0; p < n; p++) off[p + 1] += off[p];
-            std::vector<int> cur(off.begin(), off.end() - 1);
-            for (int c = 0; c < nDown; c++) idx[cur[ch[c].parent]++] = c;
-        }
-        { int *p = nullptr; int r_ = ini_upload(H, &p, off); if (r_ != LDSO_OK) return r_; L.childOff = p; }
-        { int *p = nullptr; int r_ = ini_upload(H, &p, idx); if (r_ != LDSO_OK) return r_; L.childIdx = p; }
-        { int r_ = ini_put_points(H, l, pts); if (r_ != LDSO_OK) return r_; }
-    }
-    H->ldsBytes = (maxN + INI_LDS_EXTRA) * sizeof(float);
-    H->prepBlocks = (int) std::max<size_t>(1, (maxN + INI_PT - 1) / INI_PT);
-    CHK(hipFuncSetAttribute((const void *) k_ini_ctl, hipFuncAttributeMaxDynamicSharedMemorySize, (int) H->ldsBytes));
-    H->snappedAtFrameStart = false;
-    // state of setFirst (:612-614)
-    IniCtl c; memset(&c, 0, sizeof(c));
-    c.Tcur[0] = c.Tcur[5] = c.Tcur[10] = 1.0; c.Tnew[0] = c.Tnew[5] = c.Tnew[10] = 1.0; c.done = 1;
-    CHK(hipMemcpy(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
-    { int r_ = ini_images(H, irradiance, H->d_first); if (r_ != LDSO_OK) return r_; }
-    H->haveFirst = true; H->haveNew = false;
-    return LDSO_OK;
-}
-
-int ldso_init_set_new_frame(ldso_initializer_t *H, const float *irradiance, float ab_exposure) {
-    REQ(H && irradiance, "ldso_init_set_new_frame: null argument");
-    REQ(H->haveFirst, "ldso_init_set_new_frame: no first frame");
-    H->P.newExposure = ab_exposure;
-    int r_ = ini_images(H, irradiance, H->d_new);
-    if (r_ != LDSO_OK) return r_;
-    H->haveNew = true;
-    return LDSO_OK;
-}
-
-int ldso_init_get_state(ldso_initializer_t *H, ldso_init_state_t *s) {
-    REQ(H && s, "null argument");
-    CHK(hipSetDevice(H->device));
-    IniCtl c;
-    CHK(hipMemcpyAsync(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost, H->stream));
-    CHK(hipStreamSynchronize(H->stream));
-    memcpy(s->thisToNext, c.Tcur, sizeof(c.Tcur));
-    H->snappedAtFrameStart = c.snapped != 0; H->frameDone = c.done != 0; H->stepsTaken = c.steps;
-    s->aff_a = c.aCur; s->aff_b = c.bCur; s->snapped = c.snapped; s->snappedAt = c.snappedAt; s->frameID = c.frameID;
-    s->ready = c.snapped && c.frameID > c.snappedAt + 5; s->evals = c.evals; s->pad_ = 0;
-    return LDSO_OK;
-}
-
-int ldso_init_set_state(ldso_initializer_t *H, const ldso_init_state_t *s) {
-    REQ(H && s, "null argument");
-    CHK(hipSetDevice(H->device));
-    IniCtl c;
-    CHK(hipMemcpyAsync(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost, H->stream));
-    CHK(hipStreamSynchronize(H->stream));
-    memcpy(c.Tcur, s->thisToNext, sizeof(c.Tcur)); memcpy(c.Tnew, s->thisToNext, sizeof(c.Tnew));
-    c.aCur = (float) s->aff_a; c.bCur = (float) s->aff_b; c.aNew = c.aCur; c.bNew = c.bCur;
-    c.snapped = s->snapped; c.snappedAt = s->snappedAt; c.frameID = s->frameID;
-    H->snappedAtFrameStart = c.snapped != 0;
-    CHK(hipMemcpyAsync(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice, H->stream));
-    CHK(hipStreamSynchronize(H->stream));
-    return LDSO_OK;
-}
-
-int ldso_init_track_frame(ldso_initializer_t *H, const float *irradiance, float ab_exposure, ldso_init_state_t *state_out) {
-    REQ(H, "null handle");
-    REQ(H->haveFirst, "ldso_init_track_frame: no first frame");
-    CHK(hipSetDevice(H->device));
-    if (irradiance) { int r_ = ldso_init_set_new_frame(H, irradiance, ab_exposure); if (r_ != LDSO_OK) return r_; }
-    REQ(H->haveNew, "ldso_init_track_frame: no new frame");
-    const int maxIterations[5] = {5, 5, 10, 30, 50};
-    int steps = 0;                                                          // the most control steps a frame can take
-    for (int l = 0; l < H->levels; l++) steps += maxIterations[l] + 2;
-    steps += 2 * (H->levels - 1);                                           // the transition steps of a snapped frame (down and up)
-    // Control steps behind the one that finishes the frame return at once, but each still costs a dispatch (2-3 us, three kernels per step): a frame takes 19-40 of
-    // the 58 possible steps at four levels.  So: enqueue what the previous frame took plus a margin, read the state back (the call does that anyway), and enqueue
-    // the rest only if the frame is not finished - one more round trip in the rare case, 10-30 empty steps fewer in the usual one.  (First frame: half of the maximum.)
-    int first = std::min(steps, H->firstSteps > 0 ? H->firstSteps : H->lastSteps > 0 ? H->lastSteps + H->lastSteps / 4 + 4 : (steps + 1) / 2);
-    const bool prep = H->snappedAtFrameStart && H->prepareOnGrid;
-    hipLaunchKernelGGL(k_ini_ctl, dim3(1), dim3(INI_CT), H->ldsBytes, H->stream, H->P, INI_BEGIN);
-    ldso_init_state_t st;
-    for (int from = 0; from < steps;) {
-        for (int p = from; p < first; p++) {
-            hipLaunchKernelGGL(k_ini_eval, dim3(INI_MAXBLK), dim3(INI_NT), 0, H->stream, H->P, 0);
-            if (prep) hipLaunchKernelGGL(k_ini_prep, dim3(H->prepBlocks), dim3(INI_PT), 0, H->stream, H->P);
-            hipLaunchKernelGGL(k_ini_ctl, dim3(1), dim3(INI_CT), H->ldsBytes, H->stream, H->P, INI_STEP);
-        }
-        CHK(hipGetLastError());
-        int r_ = ldso_init_get_state(H, &st);
-        if (r_ != LDSO_OK) return r_;
-        if (H->frameDone) break;
-        from = first; first = steps;
-    }
-    REQ(H->frameDone, "ldso_init_track_frame: the frame did not finish within the maximal number of control steps (internal)");
-    H->lastSteps = H->stepsTaken;
-    bool fin = true;
-    for (int q = 0; q < 12; q++) fin = fin && std::isfinite(st.thisToNext[q]);
-    if (state_out) *state_out = st;
-    if (!fin) { ldso_set_error("ldso_init_track_frame: non-finite pose"); return LDSO_E_NONFINITE; }
-    return LDSO_OK;
-}
-
-int ldso_init_set_schedule(ldso_initializer_t *H, int first_steps, int prepare_on_grid) {
-    REQ(H && first_steps >= 0, "ldso_init_set_schedule: bad argument");
-    H->firstSteps = first_steps; H->prepareOnGrid = prepare_on_grid != 0;
-    return LDSO_OK;
-}
-
-// host logic only (no device): the optReg sweep schedule ldso_init_set_first builds for a level
-int ldso_init_sweep_schedule(int n, const int *neighbours, int width, int *pass_out) {
-    REQ(n >= 0 && (n == 0 || (neighbours && pass_out)) && width >= 1, "ldso_init_sweep_schedule: bad argument");
-    for (size_t q = 0; q < (size_t) n * 10; q++) REQ(neighbours[q] >= -1 && neighbours[q] < n, "ldso_init_sweep_schedule: neighbour index out of range");
-    std::vector<int> pass(n);
-    const int np = ini_sweep_schedule(n, neighbours, width, pass.data());
-    REQ(ini_schedule_valid(n, neighbours, width, pass, np), "ldso_init_sweep_schedule: internal error (schedule violates the update order)");
-    for (int i = 0; i < n; i++) pass_out[i] = pass[i];
-    return np;
-}
-
-// debug (LDSO_STAMPS builds): accumulated device-side ticks (100 MHz): sweep ticks, sweep passes, control-kernel ticks, sweeps, fill + prepare ticks,
-// ticks up to the accept decision, ticks of the next increment (solve, exp), -
-int ldso_init_debug_counters(ldso_initializer_t *H, long long out[8]) {
-    REQ(H && out, "null argument");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamSynchronize(H->stream));
-    IniCtl c;
-    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
-    out[0] = c.dbgSweepTicks; out[1] = c.dbgSweepPasses; out[2] = c.dbgCtlTicks; out[3] = c.dbgSweeps; out[4] = c.dbgPrepTicks; out[5] = c.dbgFrontTicks; out[6] = c.dbgTailTicks; out[7] = c.dbgSpare;
-    return LDSO_OK;
-}
-
-int ldso_init_get_points(ldso_initializer_t *H, int l, ldso_init_point_t *out) {
-    REQ(H && out && l >= 0 && l < H->levels, "ldso_init_get_points: bad argument");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamSynchronize(H->stream));
-    IniCtl c;
-    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
-    REQ(!c.applyPending, "ldso_init_get_points: a step is pending (internal)");
-    const IniLevel &L = H->P.L[l];
-    const int n = H->n[l];
-    std::vector<float> f(n);
-    std::vector<int> g(n), nb((size_t) n * INI_NB);
-#define X(name) if (n) CHK(hipMemcpy(f.data(), L.name, n * 4, hipMemcpyDeviceToHost)); for (int i = 0; i < n; i++) out[i].name = f[i];
-    INI_FIELDS(X)
-#undef X
-#define XE(src, expr) if (n) CHK(hipMemcpy(f.data(), L.src, n * 4, hipMemcpyDeviceToHost)); for (int i = 0; i < n; i++) out[i].expr = f[i];
-    XE(energy0, energy[0]) XE(energy1, energy[1]) XE(energy_new0, energy_new[0]) XE(energy_new1, energy_new[1])
-#undef XE
-#define XI(src, expr) if (n) CHK(hipMemcpy(g.data(), L.src, n * 4, hipMemcpyDeviceToHost)); for (int i = 0; i < n; i++) out[i].expr = g[i];
-    XI(isGood, isGood) XI(isGood_new, isGood_new) XI(parent, parent)
-#undef XI
-    if (n) CHK(hipMemcpy(nb.data(), L.nb, (size_t) n * INI_NB * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; i++) for (int q = 0; q < 10; q++) out[i].neighbours[q] = nb[(size_t) i * INI_NB + q];
-    return LDSO_OK;
-}
-
-int ldso_init_set_points(ldso_initializer_t *H, int l, const ldso_init_point_t *pts) {
-    REQ(H && pts && l >= 0 && l < H->levels, "ldso_init_set_points: bad argument");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamSynchronize(H->stream));
-    return ini_put_points(H, l, pts);
-}
-
-int ldso_init_calc_res_and_gs(ldso_initializer_t *H, int lvl, const double refToNew[12], double aff_a, double aff_b,
-                              float *Hm, float *b, float *Hsc, float *bsc, float *res, float *ec) {
-    REQ(H && refToNew && lvl >= 0 && lvl < H->levels, "ldso_init_calc_res_and_gs: bad argument");
-    REQ(H->haveFirst && H->haveNew, "ldso_init_calc_res_and_gs: frames missing");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamSynchronize(H->stream));
-    IniCtl c;
-    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
-    memcpy(c.Tnew, refToNew, sizeof(c.Tnew));
-    c.aNew = (float) aff_a; c.bNew = (float) aff_b; c.lvl = lvl;
-    CHK(hipMemcpy(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_ini_eval, dim3(INI_MAXBLK), dim3(INI_NT), 0, H->stream, H->P, 1);
-    hipLaunchKernelGGL(k_ini_ctl, dim3(1), dim3(INI_CT), H->ldsBytes, H->stream, H->P, INI_STAGE);
-    CHK(hipGetLastError());
-    CHK(hipStreamSynchronize(H->stream));
-    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
-    if (Hm) memcpy(Hm, c.Hn, sizeof(c.Hn));
-    if (b) memcpy(b, c.bn, sizeof(c.bn));
-    if (Hsc) memcpy(Hsc, c.Hscn, sizeof(c.Hscn));
-    if (bsc) memcpy(bsc, c.bscn, sizeof(c.bscn));
-    if (res) memcpy(res, c.resNew, sizeof(c.resNew));
-    if (ec) memcpy(ec, c.ec, sizeof(c.ec));
-    return LDSO_OK;
-}
-
-}  // extern "C"
+// the launches (the host side is initializer_api.hip)
+hipError_t ini_ctl_reserve_lds(size_t ldsBytes) { return hipFuncSetAttribute((const void *) k_ini_ctl, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes); }
+void ini_launch_eval(const IniParams &P, int stage, hipStream_t st) { hipLaunchKernelGGL(k_ini_eval, dim3(INI_MAXBLK), dim3(INI_NT), 0, st, P, stage); }
+void ini_launch_prep(const IniParams &P, int blocks, hipStream_t st) { hipLaunchKernelGGL(k_ini_prep, dim3(blocks), dim3(INI_PT), 0, st, P); }
+void ini_launch_ctl(const IniParams &P, int phase, size_t ldsBytes, hipStream_t st) { hipLaunchKernelGGL(k_ini_ctl, dim3(1), dim3(INI_CT), ldsBytes, st, P, phase); }

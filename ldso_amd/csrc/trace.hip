@@ -357,29 +357,26 @@ int ldso_trace_settings_default(ldso_trace_settings_t *s) {
     return LDSO_OK;
 }
 
-int ldso_trace_create(int device, int w, int h, int max_points, ldso_tracer_t **out) {
-    REQ(out && w > 16 && h > 16 && max_points > 0, "ldso_trace_create: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, "ldso_trace_create: device index out of range");
-    CHK(hipSetDevice(device));
-    ldso_tracer *T = new ldso_tracer();
+static int trace_create_body(ldso_tracer *T, int device, int w, int h, int max_points) {
     T->device = device; T->w = w; T->h = h; T->maxPoints = max_points;
     ldso_trace_settings_default(&T->settings);
     CHK(hipStreamCreateWithFlags(&T->stream, hipStreamNonBlocking));
-    CHK(hipMalloc(&T->d_pts, (size_t) max_points * sizeof(ldso_immature_t)));
-    CHK(hipMalloc(&T->d_alt, (size_t) max_points * sizeof(ldso_immature_t)));
-    CHK(hipMalloc(&T->d_type, (size_t) max_points * 4));
-    CHK(hipMalloc(&T->d_typeAlt, (size_t) max_points * 4));
-    CHK(hipMalloc(&T->d_keep, (size_t) max_points));
-    CHK(hipMalloc(&T->d_flag, (size_t) max_points));
+    CHK(hipMalloc(&T->d_pts, (size_t) max_points * sizeof(ldso_immature_t))); CHK(hipMalloc(&T->d_alt, (size_t) max_points * sizeof(ldso_immature_t)));
+    CHK(hipMalloc(&T->d_type, (size_t) max_points * 4)); CHK(hipMalloc(&T->d_typeAlt, (size_t) max_points * 4));
+    CHK(hipMalloc(&T->d_keep, (size_t) max_points)); CHK(hipMalloc(&T->d_flag, (size_t) max_points));
     CHK(hipMalloc(&T->d_cmp, (size_t) (LDSO_MAX_FRAMES + 4 + (max_points + CMP_THREADS - 1) / CMP_THREADS) * 4));
     CHK(hipMalloc(&T->d_img, (size_t) w * h * 12));
     CHK(hipMalloc(&T->d_color, (size_t) w * h * 4));
     CHK(hipMalloc(&T->d_pose, (size_t) LDSO_MAX_FRAMES * 14 * 4));
     CHK(hipMalloc(&T->d_counts, 8 * 4));
-    *out = T;
     return LDSO_OK;
+}
+
+int ldso_trace_create(int device, int w, int h, int max_points, ldso_tracer_t **out) {
+    REQ(out && w > 16 && h > 16 && max_points > 0, "ldso_trace_create: bad arguments");
+    RUN(open_device(device, "ldso_trace_create"));
+    ldso_tracer *T = new ldso_tracer();
+    return finish_create(trace_create_body(T, device, w, h, max_points), T, out, ldso_trace_destroy);      // nothing of a half-built handle leaks
 }
 
 int ldso_trace_destroy(ldso_tracer_t *T) {
@@ -473,9 +470,8 @@ int ldso_trace_set_frame(ldso_tracer_t *T, const float *dI) {
 int ldso_trace_set_frame_raw(ldso_tracer_t *T, const float *irradiance) {
     REQ(T && irradiance, "ldso_trace_set_frame_raw: bad arguments");
     CHK(hipSetDevice(T->device));
-    CHK(hipMemcpyAsync(T->d_color, irradiance, (size_t) T->w * T->h * 4, hipMemcpyHostToDevice, T->stream));
     float *lv[1] = {T->d_img};
-    CHK(img_launch_make_images(T->d_color, T->w, T->h, 1, lv, T->stream));
+    RUN(raw_to_images(T->d_color, irradiance, T->w, T->h, 1, lv, T->stream));
     CHK(hipStreamSynchronize(T->stream));
     T->haveFrame = true; T->img = T->d_img;
     return LDSO_OK;
@@ -484,9 +480,7 @@ int ldso_trace_set_frame_raw(ldso_tracer_t *T, const float *irradiance) {
 // the new frame as a resident ldso_pyramid_t (zero-copy: ImmaturePoint::traceOn samples frame->dI = level 0)
 int ldso_trace_set_frame_pyramid(ldso_tracer_t *T, ldso_pyramid_t *pyr) {
     REQ(T && pyr, "ldso_trace_set_frame_pyramid: bad arguments");
-    REQ(pyr->built && pyr->device == T->device && pyr->w == T->w && pyr->h == T->h, "ldso_trace_set_frame_pyramid: pyramid does not match the tracer (device, size) or holds no image");
-    CHK(hipSetDevice(T->device));
-    CHK(hipStreamWaitEvent(T->stream, pyr->ready, 0));
+    RUN(pyramid_wait(pyr, T->device, T->w, T->h, 1, T->stream, "ldso_trace_set_frame_pyramid", "the tracer (device, size)"));
     T->haveFrame = true; T->img = pyr->lv[0];
     return LDSO_OK;
 }

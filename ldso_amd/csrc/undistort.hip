@@ -77,10 +77,7 @@ int ldso_undist_destroy(ldso_undistorter_t *U) {
 
 int ldso_undist_create(int device, int wOrg, int hOrg, int w, int h, ldso_undistorter_t **out) {
     REQ(out && wOrg > 1 && hOrg > 1 && w > 0 && h > 0 && (long long) wOrg * hOrg < (1ll << 30) && (long long) w * h < (1ll << 30), "ldso_undist_create: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, "ldso_undist_create: device index out of range");
-    CHK(hipSetDevice(device));
+    RUN(open_device(device, "ldso_undist_create"));
     ldso_undistorter *U = new ldso_undistorter();
     U->device = device; U->w = w; U->h = h; U->wOrg = wOrg; U->hOrg = hOrg;
     const size_t n = (size_t) w * h, nOrg = (size_t) wOrg * hOrg;
@@ -99,10 +96,7 @@ int ldso_undist_create(int device, int wOrg, int hOrg, int w, int h, ldso_undist
 
 int ldso_undist_set_stream(ldso_undistorter_t *U, void *s) {
     REQ(U, "ldso_undist_set_stream: null handle");
-    if (U->ownStream && U->stream) { hipStreamSynchronize(U->stream); if (s) { hipStreamDestroy(U->stream); U->ownStream = false; } }
-    if (s) { U->stream = (hipStream_t) s; U->ownStream = false; }
-    else if (!U->ownStream) { CHK(hipStreamCreateWithFlags(&U->stream, hipStreamNonBlocking)); U->ownStream = true; }
-    return LDSO_OK;
+    return swap_stream(U->stream, U->ownStream, s);
 }
 
 int ldso_undist_set_remap(ldso_undistorter_t *U, const float *remapX, const float *remapY) {

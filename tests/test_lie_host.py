@@ -1,4 +1,4 @@
-"""lie_dev.h on the host (the same header the kernels and the library's host code (ba_api.hip, tracker.hip, initializer.hip) include): se3_exp against the closed forms, across the switch between the
+"""lie_dev.h on the host (the same header the kernels and the library's host code (ba_api.hip, tracker.hip, tracker_api.hip, tracker_hyp.cpp, initializer.hip) include): se3_exp against the closed forms, across the switch between the
 coefficient series and sin / cos, and against scipy's matrix exponential; exp / log, mul / inv round trips.  The kernels' control steps call these on their critical
 lanes (gn_tail, the tracker's leader): the header is tuned for instruction count, this pins what it computes."""
 import os, subprocess, sys, tempfile
