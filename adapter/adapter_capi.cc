@@ -130,6 +130,68 @@ int adp_make_new_traces(void *b, void *fs_, void *fh_, const int *orb_pattern, i
         })
 }
 
+// fh = ref_fs_new_frame(window, ...): makeNewTraces with setting_pointSelection = 0 and setting_desiredImmatureDensity = density on one frame - b == nullptr:
+// the reference's own FullSystem::makeNewTraces (FullSystem.cc:1284-1304), else GpuBackend::makeNewTraces.  The reference's member reads absSquaredGrad and
+// levels 1-2, which ref_fs_new_frame does not build: for that leg the frame's images are made here by FrameHessian::makeImages from the irradiance of its level 0
+// (the rows of absSquaredGrad[1] / [2] that makeImages never writes zeroed, as ldso_hip.h defines them) and taken away again before the entry returns.
+// potential_inout = pixelSelector->currentPotential before / after.  Out as adp_make_new_traces: uv [cap][2], imm [cap] (host = the frame's window index or -1),
+// type [cap] = my_type; counts[4] = points made, 0, dropped, frame->features.size().  The three process-wide settings are restored before the entry returns.
+int adp_make_new_traces_pixsel(void *b, void *fs_, void *fh_, float density, const float *response, int *potential_inout, int cap, float *uv, ldso_immature_t *imm, float *type, int *counts) {
+    if (!fs_ || !fh_ || !potential_inout || !counts) return LDSO_E_INVALID;
+    const int savedSelection = setting_pointSelection; const float savedDensity = setting_desiredImmatureDensity; const int savedGamma = setting_gammaWeightsPixelSelect;
+    struct Restore { int s; float d; int g; ~Restore() { setting_pointSelection = s; setting_desiredImmatureDensity = d; setting_gammaWeightsPixelSelect = g; } } restore{savedSelection, savedDensity, savedGamma};
+    GUARD(
+        FullSystem &fs = *(FullSystem *) fs_; std::shared_ptr<FrameHessian> fh = *(std::shared_ptr<FrameHessian> *) fh_;
+        setting_pointSelection = 0; setting_desiredImmatureDensity = density; setting_gammaWeightsPixelSelect = 1;
+        if (response) for (int i = 0; i < 256; i++) fs.Hcalib->mpCH->B[i] = response[i];
+        fs.pixelSelector->currentPotential = *potential_inout;
+        fh->frame->features.clear();
+        for (int i = 0; i < 4; i++) counts[i] = 0;
+        if (b) {
+            GpuBackend &B = *(GpuBackend *) b;
+            B.makeNewTraces(fs, fh);
+            for (int i = 0; i < 3; i++) counts[i] = B.lastNewTraces[i];
+        } else {
+            Vec3f *level0 = fh->dIp[0];
+            std::vector<float> color((size_t) wG[0] * hG[0]);
+            for (size_t i = 0; i < color.size(); i++) color[i] = level0[i][0];
+            fh->makeImages(color.data(), fs.Hcalib->mpCH);
+            for (int l = 1; l < 3 && l < pyrLevelsUsed; l++) for (int x = 0; x < wG[l]; x++) fh->absSquaredGrad[l][x + (hG[l] - 1) * wG[l]] = 0;
+            fs.makeNewTraces(fh, nullptr);
+            for (int l = 0; l < pyrLevelsUsed; l++) { delete[] fh->dIp[l]; delete[] fh->absSquaredGrad[l]; fh->dIp[l] = nullptr; fh->absSquaredGrad[l] = nullptr; }
+            fh->dIp[0] = level0; fh->dI = level0;
+            fs.pixelSelector->gradHistFrame = nullptr;          // its histogram belongs to images that are gone
+            counts[0] = (int) fh->frame->features.size();
+        }
+        *potential_inout = fs.pixelSelector->currentPotential;
+        counts[3] = (int) fh->frame->features.size();
+        int hostIdx = -1;
+        for (size_t f = 0; f < fs.frames.size(); f++) if (fs.frames[f] == fh->frame) hostIdx = (int) f;
+        int k = 0;
+        for (auto &f : fh->frame->features) {
+            if (k >= cap) break;
+            uv[2 * k] = f->uv[0]; uv[2 * k + 1] = f->uv[1];
+            ldso_immature_t &q = imm[k];
+            memset(&q, 0, sizeof(q));
+            ImmaturePoint &ip = *f->ip;
+            q.u = f->uv[0]; q.v = f->uv[1];
+            memcpy(q.color, ip.color, sizeof(q.color)); memcpy(q.weights, ip.weights, sizeof(q.weights));
+            q.gradH[0] = ip.gradH(0, 0); q.gradH[1] = ip.gradH(0, 1); q.gradH[2] = ip.gradH(1, 0); q.gradH[3] = ip.gradH(1, 1);
+            q.energyTH = ip.energyTH; q.idepth_min = ip.idepth_min; q.idepth_max = ip.idepth_max; q.quality = ip.quality;
+            q.lastTraceStatus = (int32_t) ip.lastTraceStatus; q.lastTraceUV[0] = ip.lastTraceUV[0]; q.lastTraceUV[1] = ip.lastTraceUV[1];
+            q.lastTracePixelInterval = ip.lastTracePixelInterval; q.host = hostIdx;
+            type[k] = ip.my_type;
+            k++;
+        })
+}
+
+// the three process-wide settings the makeNewTraces entries write
+int adp_point_selection_settings(int *pointSelection, float *desiredImmatureDensity, int *gammaWeightsPixelSelect) {
+    if (!pointSelection || !desiredImmatureDensity || !gammaWeightsPixelSelect) return LDSO_E_INVALID;
+    *pointSelection = setting_pointSelection; *desiredImmatureDensity = setting_desiredImmatureDensity; *gammaWeightsPixelSelect = setting_gammaWeightsPixelSelect;
+    return 0;
+}
+
 // ---- raw camera frames (tests/test_undistort_adapter_gpu.py) ---------------------------------------------------------------------------------
 // GpuBackend::setUndistortion under the two settings it reads; the output size is the window's (wG[0] x hG[0])
 int adp_set_undistortion(void *b, int wOrg, int hOrg, const float *remapX, const float *remapY, const float *G, int GDepth, const float *vignetteMapInv, int photometricCalibration, int useExposure) {

@@ -104,6 +104,7 @@ GpuBackend::~GpuBackend() {
     for (auto &kv : trackers_) ldso_tr_destroy(kv.second);
     if (tracer_) ldso_trace_destroy(tracer_);
     if (features_) ldso_feat_destroy(features_);
+    if (pixsel_) ldso_pixsel_destroy(pixsel_);
     if (undist_) ldso_undist_destroy(undist_);
     if (ba_) ldso_ba_destroy(ba_);
     slotPyr_.clear(); tracerPyr_.reset(); trackerPyr_.clear(); pyr_.clear();          // the pyramids, after their consumers
@@ -1022,10 +1023,46 @@ void GpuBackend::traceNewCoarse(FullSystem &fs, shared_ptr<FrameHessian> fh) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
-// void FullSystem::makeNewTraces(shared_ptr<FrameHessian> newFrame, float *gtDepth), setting_pointSelection == 1 (FullSystem.cc:1272-1283)
+// void FullSystem::makeNewTraces(shared_ptr<FrameHessian> newFrame, float *gtDepth), setting_pointSelection == 1 (FullSystem.cc:1272-1283) and 0 (:1284-1304)
 // ------------------------------------------------------------------------------------------------------------------------------------
+// What both selection modes do with a fresh device record: the fields of the ImmaturePoint the reference's constructor built are replaced by the record's
+static void overwriteFromRecord(ImmaturePoint &ip, const ldso_immature_t &q) {
+    memcpy(ip.color, q.color, sizeof(q.color)); memcpy(ip.weights, q.weights, sizeof(q.weights));
+    ip.gradH(0, 0) = q.gradH[0]; ip.gradH(0, 1) = q.gradH[1]; ip.gradH(1, 0) = q.gradH[2]; ip.gradH(1, 1) = q.gradH[3];
+    ip.energyTH = q.energyTH; ip.idepth_min = q.idepth_min; ip.idepth_max = q.idepth_max; ip.quality = q.quality;
+    ip.lastTraceStatus = (ImmaturePointStatus) q.lastTraceStatus;
+    ip.lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip.lastTracePixelInterval = q.lastTracePixelInterval;
+}
+
+// Resident mode, both selection modes: the n records of a key frame go behind the tracer's rows as they lie in device memory (typeDev: their my_type, or null = 1),
+// the ones dropped for a non-finite energyTH are compacted away, and the ImmaturePoints kept (`fresh`) join the row list.
+void GpuBackend::appendFreshRecords(const std::vector<ldso_immature_t> &rec, const void *immDev, const void *typeDev, const std::vector<shared_ptr<ImmaturePoint>> &fresh, int hostIdx) {
+    const int n = (int) rec.size(), need = (int) who_.size() + n;
+    if (tracer_ && need > tracerCap_ && !who_.empty()) {
+        // the tracer has to grow: its state goes into the objects, and the next reconcile uploads the whole set (the new objects hold their records already)
+        downloadImmature(nullptr);
+        ensureTracer(need);
+        return;
+    }
+    ensureTracer(need);
+    // from here to the end the tracer's count and the row list move together: a failure in between forgets the rows, and the next reconcile uploads the set anew
+    try {
+        throwOn(ldso_trace_append_points_device(tracer_, n, immDev), "ldso_trace_append_points_device");
+        if (typeDev) throwOn(ldso_trace_set_tail_types_device(tracer_, n, typeDev), "ldso_trace_set_tail_types_device");
+        if (fresh.size() != rec.size()) {
+            std::vector<uint8_t> keep(who_.size() + (size_t) n, 1);
+            for (int i = 0; i < n; i++) if (!std::isfinite(rec[i].energyTH)) keep[who_.size() + i] = 0;
+            int nLeft = 0;
+            throwOn(ldso_trace_compact(tracer_, keep.data(), LDSO_MAX_FRAMES, nullptr, &nLeft), "ldso_trace_compact");
+            if (nLeft != (int) (who_.size() + fresh.size())) throw std::runtime_error("GpuBackend::makeNewTraces: the tracer's count after the compaction differs from the points kept");
+        }
+    } catch (...) { who_.clear(); whoHost_.clear(); throw; }
+    for (auto &ip : fresh) { who_.push_back(ip); whoHost_.push_back(hostIdx); }
+}
+
 void GpuBackend::makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame) {
-    if (setting_pointSelection != 1) throw std::runtime_error("GpuBackend::makeNewTraces: only setting_pointSelection == 1 (FeatureDetector::DetectCorners) runs on the device");
+    if (setting_pointSelection == 0) { makeNewTracesPixelSelector(fs, newFrame); return; }
+    if (setting_pointSelection != 1) throw std::runtime_error("GpuBackend::makeNewTraces: only setting_pointSelection == 0 (PixelSelector::makeMaps) and 1 (FeatureDetector::DetectCorners) run on the device");
     const int w = wG[0], h = hG[0], want = (int) setting_desiredImmatureDensity;
     int capacity = 0;
     throwOn(ldso_feat_grid(w, h, want, nullptr, nullptr, nullptr, nullptr, nullptr, &capacity), "ldso_feat_grid");
@@ -1064,41 +1101,71 @@ void GpuBackend::makeNewTraces(FullSystem &fs, shared_ptr<FrameHessian> newFrame
         feat->uv = Vec2f(uc, vc);
         shared_ptr<ImmaturePoint> ip(new ImmaturePoint(frame, feat, 1, calib));                       // :1280-1281
         feat->uv = Vec2f(g.u, g.v);
-        memcpy(ip->color, q.color, sizeof(q.color)); memcpy(ip->weights, q.weights, sizeof(q.weights));
-        ip->gradH(0, 0) = q.gradH[0]; ip->gradH(0, 1) = q.gradH[1]; ip->gradH(1, 0) = q.gradH[2]; ip->gradH(1, 1) = q.gradH[3];
-        ip->energyTH = q.energyTH; ip->idepth_min = q.idepth_min; ip->idepth_max = q.idepth_max; ip->quality = q.quality;
-        ip->lastTraceStatus = (ImmaturePointStatus) q.lastTraceStatus;
-        ip->lastTraceUV = Vec2f(q.lastTraceUV[0], q.lastTraceUV[1]); ip->lastTracePixelInterval = q.lastTracePixelInterval;
+        overwriteFromRecord(*ip, q);
         feat->ip = ip;
         frame->features.push_back(feat);
         fresh.push_back(ip);
     }
     if (!residentImmature || n == 0) return;
     // the records never leave the device: appended behind the tracer's rows as they lie in the detector's buffer, the dropped ones compacted away
-    const int need = (int) who_.size() + n;
-    if (tracer_ && need > tracerCap_ && !who_.empty()) {
-        // the tracer has to grow: its state goes into the objects, and the next reconcile uploads the whole set (the new objects hold their records already)
-        downloadImmature(nullptr);
-        ensureTracer(need);
-        return;
-    }
-    ensureTracer(need);
     const void *featDev = nullptr, *immDev = nullptr;
     int nDev = 0;
     throwOn(ldso_feat_device(features_, &featDev, &immDev, &nDev), "ldso_feat_device");
     if (nDev != n) throw std::runtime_error("GpuBackend::makeNewTraces: the detector's device buffer does not hold the features it reported");
-    // from here to the end the tracer's count and the row list move together: a failure in between forgets the rows, and the next reconcile uploads the set anew
-    try {
-        throwOn(ldso_trace_append_points_device(tracer_, n, immDev), "ldso_trace_append_points_device");
-        if (lastNewTraces[2] > 0) {
-            std::vector<uint8_t> keep(who_.size() + (size_t) n, 1);
-            for (int i = 0; i < n; i++) if (!std::isfinite(rec[i].energyTH)) keep[who_.size() + i] = 0;
-            int nLeft = 0;
-            throwOn(ldso_trace_compact(tracer_, keep.data(), LDSO_MAX_FRAMES, nullptr, &nLeft), "ldso_trace_compact");
-            if (nLeft != (int) (who_.size() + fresh.size())) throw std::runtime_error("GpuBackend::makeNewTraces: the tracer's count after the compaction differs from the features kept");
-        }
-    } catch (...) { who_.clear(); whoHost_.clear(); throw; }
-    for (auto &ip : fresh) { who_.push_back(ip); whoHost_.push_back(hostIdx); }
+    appendFreshRecords(rec, immDev, nullptr, fresh, hostIdx);
+}
+
+// setting_pointSelection == 0 (FullSystem.cc:1284-1304): PixelSelector::makeMaps, the raster scan of the map and the ImmaturePoint constructors on the device.
+// fs.pixelSelector stays the owner of currentPotential: read before the call and written back after it, so host and device calls can alternate.  Nothing of
+// the frame is read on the host but the positions and records that come back.
+void GpuBackend::makeNewTracesPixelSelector(FullSystem &fs, shared_ptr<FrameHessian> newFrame) {
+    const int w = wG[0], h = hG[0];
+    for (int i = 0; i < 3; i++) lastNewTraces[i] = 0;
+    if (pyrLevelsUsed < 3) throw std::runtime_error("GpuBackend::makeNewTraces: PixelSelector::select reads three pyramid levels");
+    shared_ptr<Frame> frame = newFrame->frame;
+    if (residentImmature) reconcileImmature(fs, false);
+    if (pixsel_ && (pixselPattern_ != fs.pixelSelector->randomPattern || pixselW_ != w || pixselH_ != h)) { ldso_pixsel_destroy(pixsel_); pixsel_ = nullptr; }
+    if (!pixsel_) {                                                                                  // the pattern goes up once per PixelSelector and image size
+        throwOn(ldso_pixsel_create(device_, w, h, fs.pixelSelector->randomPattern, &pixsel_), "ldso_pixsel_create");
+        pixselPattern_ = fs.pixelSelector->randomPattern; pixselW_ = w; pixselH_ = h;
+    }
+    shared_ptr<CalibHessian> calib = fs.Hcalib ? fs.Hcalib->mpCH : nullptr;
+    throwOn(ldso_pixsel_set_response(pixsel_, setting_gammaWeightsPixelSelect == 1 && calib ? calib->B : nullptr), "ldso_pixsel_set_response");
+    throwOn(ldso_pixsel_set_settings(pixsel_, setting_minGradHistCut, setting_minGradHistAdd, setting_gradDownweightPerLevel, setting_selectDirectionDistribution ? 1 : 0), "ldso_pixsel_set_settings");
+    throwOn(ldso_pixsel_set_potential(pixsel_, fs.pixelSelector->currentPotential), "ldso_pixsel_set_potential");
+    int hostIdx = (int) fs.frames.size();
+    for (size_t f = 0; f < fs.frames.size(); f++) if (fs.frames[f] == frame) hostIdx = (int) f;
+    PyrRef pyr = pyramidOf(newFrame);
+    fs.pixelSelector->allowFast = true;                                                              // :1286
+    int numPointsTotal = 0, n = 0;
+    throwOn(ldso_pixsel_make_maps(pixsel_, pyr->p, setting_desiredImmatureDensity, 1, 1.0f, &numPointsTotal, nullptr, nullptr), "ldso_pixsel_make_maps");          // :1287
+    throwOn(ldso_pixsel_get_potential(pixsel_, &fs.pixelSelector->currentPotential), "ldso_pixsel_get_potential");
+    frame->features.reserve(numPointsTotal);                                                         // :1288
+    const int rc = ldso_pixsel_make_points(pixsel_, pyr->p, hostIdx, &n);
+    if (rc != LDSO_E_NONFINITE) throwOn(rc, "ldso_pixsel_make_points");                              // a non-finite colour: those records are dropped below (:1298)
+    std::vector<ldso_immature_t> rec((size_t) n);
+    std::vector<float> types((size_t) n);
+    throwOn(ldso_pixsel_get_points(pixsel_, rec.data(), types.data()), "ldso_pixsel_get_points");
+    lastNewTraces[0] = n;
+    std::vector<shared_ptr<ImmaturePoint>> fresh;
+    for (int i = 0; i < n; i++) {
+        const ldso_immature_t &q = rec[i];
+        if (!std::isfinite(q.energyTH)) { lastNewTraces[2]++; continue; }
+        shared_ptr<Feature> feat(new Feature(q.u, q.v, frame));                                      // :1295
+        // the constructor samples the host image itself (3 <= x < w - 4: inside the image); its results are replaced by the device record's
+        shared_ptr<ImmaturePoint> ip(new ImmaturePoint(frame, feat, types[i], calib));               // :1296-1297
+        overwriteFromRecord(*ip, q);
+        feat->ip = ip;
+        frame->features.push_back(feat);
+        fresh.push_back(ip);
+    }
+    if (!residentImmature || n == 0) return;
+    // as the corner path: the records and their types go behind the tracer's rows device to device, the dropped ones are compacted away
+    const void *immDev = nullptr, *typeDev = nullptr;
+    int nDev = 0;
+    throwOn(ldso_pixsel_device(pixsel_, &immDev, &typeDev, &nDev), "ldso_pixsel_device");
+    if (nDev != n) throw std::runtime_error("GpuBackend::makeNewTraces: the selector's device buffer does not hold the points it reported");
+    appendFreshRecords(rec, immDev, typeDev, fresh, hostIdx);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@
 //   GpuBackend::activatePoints(fs, ...)             the optimizeImmaturePoint loop of activatePointsMT              FullSystem.cc:892-1010,1196-1206
 //   GpuBackend::activatePointsMT(fs)                void FullSystem::activatePointsMT() with CoarseDistanceMap      FullSystem.cc:1052-1189, CoarseTracker.cc:686-818
 //   GpuBackend::traceNewCoarse(fs, fh)              void FullSystem::traceNewCoarse(shared_ptr<FrameHessian>)       FullSystem.cc:1012-1050
-//   GpuBackend::makeNewTraces(fs, fh)               void FullSystem::makeNewTraces(fh, gtDepth), pointSelection == 1 FullSystem.cc:1272-1283
+//   GpuBackend::makeNewTraces(fs, fh)               void FullSystem::makeNewTraces(fh, gtDepth), pointSelection 0 / 1 FullSystem.cc:1272-1304
 //   GpuBackend::residentImmature / syncImmaturePoints   the three members above with the immature set resident on the device (no reference counterpart)
 //   GpuBackend::flagPointsForRemoval(fs)            the policy of void FullSystem::flagPointsForRemoval()           FullSystem.cc:1208-1270
 //   GpuBackend::marginalizePoints(fs)               void EnergyFunctional::marginalizePointsF() + FullSystem.cc:1241-1250   EnergyFunctional.cc:165-222
@@ -145,7 +145,11 @@ public:
     void syncImmaturePoints(FullSystem &fs);
 
     // ---- new features of a key frame: void FullSystem::makeNewTraces(shared_ptr<FrameHessian> newFrame, float *gtDepth)   FullSystem.cc:1272-1283
-    // for setting_pointSelection == 1 (any other value throws): FeatureDetector::DetectCorners(setting_desiredImmatureDensity, frame) and the ImmaturePoint
+    // for setting_pointSelection == 0: PixelSelector::makeMaps(newFrame, selectionMap, setting_desiredImmatureDensity) (:1287), the raster scan of :1290-1303 and
+    // the ImmaturePoint constructors on the device (ldso_pixsel_make_maps / _make_points on the frame's device pyramid; image sizes that are multiples of 32).
+    // fs.pixelSelector keeps currentPotential: read before and written after every call, so the reference's member and this one can alternate; its
+    // randomPattern goes up once.  frame->features gets one Feature(x, y) per point, in raster order, my_type = the map value; lastNewTraces[1] stays 0.
+    // for setting_pointSelection == 1 (2 throws): FeatureDetector::DetectCorners(setting_desiredImmatureDensity, frame) and the ImmaturePoint
     // constructors as ONE device call (ldso_feat_detect on the frame's device pyramid), then frame->features filled in the reference's order - uv, score,
     // isCorner, angle, descriptor - each with its ImmaturePoint (constructed, then its fields overwritten from the device record).  A feature whose record
     // has a non-finite energyTH is dropped, as :1298 does for the other selection modes.  The gamma weight of absSquaredGrad follows
@@ -196,6 +200,11 @@ private:
     ldso_features_t *features_ = nullptr;
     int featuresCap_ = 0;
     const int *featuresPattern_ = nullptr;
+    ldso_pixsel_t *pixsel_ = nullptr;                    // setting_pointSelection == 0: created at the first call with fs.pixelSelector's randomPattern
+    const unsigned char *pixselPattern_ = nullptr;      // ... which it is recreated for when another PixelSelector or image size comes along
+    int pixselW_ = 0, pixselH_ = 0;
+    void makeNewTracesPixelSelector(FullSystem &fs, shared_ptr<FrameHessian> newFrame);
+    void appendFreshRecords(const std::vector<ldso_immature_t> &rec, const void *immDev, const void *typeDev, const std::vector<shared_ptr<ImmaturePoint>> &fresh, int hostIdx);
     std::map<CoarseTracker *, ldso_tracker_t *> trackers_;          // the reference double-buffers two CoarseTrackers (FullSystem.h:296-297)
     std::map<unsigned long, int> slotOf_;                            // key frame (Frame::id: addresses get reused) -> image slot of the BA handle
     std::vector<long> slotOwner_;                                    // slot -> Frame::id, -1 = free

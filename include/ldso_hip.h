@@ -438,6 +438,9 @@ int ldso_trace_append_points_device(ldso_tracer_t *t, int n, const void *immatur
  * the records: ldso_trace_set_points resets it to 1 for its n records, ldso_trace_append_points_device sets 1 for the appended ones (FullSystem.cc:1281 constructs
  * the points of setting_pointSelection == 1 with my_type = 1).  my_type / out: one float per current record. */
 int ldso_trace_set_point_types(ldso_tracer_t *t, const float *my_type);
+/* my_type of the LAST n records from n floats in device memory (ldso_pixsel_device): behind ldso_trace_append_points_device for the points of
+ * setting_pointSelection == 0, whose my_type is their map value (FullSystem.cc:1297).  LDSO_E_INVALID when n exceeds the tracer's count. */
+int ldso_trace_set_tail_types_device(ldso_tracer_t *t, int n, const void *type_dev);
 int ldso_trace_get_point_types(ldso_tracer_t *t, float *out);
 /* What leaves the immature set leaves it on the device: a STABLE compaction of the records and their types.  Record i stays iff keep[i] != 0 (keep: n bytes of
  * host memory, NULL: all kept) and host_map[record.host] >= 0 (host_map: n_hosts entries, NULL: the identity); a record whose host is outside [0, n_hosts) is
@@ -495,6 +498,51 @@ int ldso_feat_device(ldso_features_t *f, const void **features_dev, const void *
 /* enable != 0: ldso_feat_detect brackets its kernels with HIP events; us_out[4] (optional) = microseconds of the last profiled call:
  * cells + compaction (FeatureDetector.cc:44-95), corners (:98-118), angle + descriptor (:120-128), records (ImmaturePoint.cc:14-38) */
 int ldso_feat_profile(ldso_features_t *f, int enable, float us_out[4]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * DSO's gradient pixels of a key frame: FullSystem::makeNewTraces for setting_pointSelection == 0 (FullSystem.cc:1284-1304) = PixelSelector::makeMaps
+ * (src/frontend/PixelSelector2.cc:111-168; makeHists :36-109, computeHistQuantil :27-34, select :170-315), the raster scan of the map and one ImmaturePoint
+ * constructor per hit (src/internal/ImmaturePoint.cc:14-38), on levels 0-2 of a resident pyramid.  Maps, counts, potentials and thresholds are exactly the
+ * reference's; two calls on the same input give byte-identical buffers.  Three reads the reference leaves undefined are defined here:
+ *   - the last row of absSquaredGrad[2] (never written: FrameHessian.cc:81 stops a row early, :49 clears bytes; read for y = h - 4) is 0;
+ *   - thsSmoothed[(x >> 5) + (y >> 5) * (w / 32)] runs past the table when w or h is no multiple of 32: such sizes give LDSO_E_UNSUPPORTED;
+ *   - a non-finite pixel (int(sqrtf(.)) is undefined there) gives LDSO_E_NONFINITE; a NaN never wins a comparison, as in ldso_feat_detect.
+ * Bins 50..90 of the gradient histogram, which computeHistQuantil can reach only for a cut near 1, are empty.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct ldso_pixsel ldso_pixsel_t;
+/* Host only, no device: LDSO_OK when the selector takes a w x h image (both multiples of 32), else LDSO_E_UNSUPPORTED */
+int ldso_pixsel_supported(int w, int h);
+/* Host only, no device: the scalar arithmetic of makeMaps :125-153 behind one select pass with counts (n2, n3, n4) at `potential`.  *action = 1: select
+ * again at *new_potential (:133-147); 0: done, *new_potential = the idealPotential :165 stores, *char_th = charTH of :153 or -1 when nothing is thinned. */
+int ldso_pixsel_plan(const int counts[3], float density, int potential, int recursions_left, int *action, int *new_potential, int *char_th);
+/* random_pattern: the w * h bytes of PixelSelector::randomPattern (:10-13: rand() & 0xFF after srand(3141592)), copied; currentPotential starts at 3 (:14) */
+int ldso_pixsel_create(int device, int w, int h, const unsigned char *random_pattern, ldso_pixsel_t **out);
+int ldso_pixsel_destroy(ldso_pixsel_t *p);
+int ldso_pixsel_set_stream(ldso_pixsel_t *p, void *hip_stream);
+/* CalibHessian::B for the gamma weight of absSquaredGrad, as ldso_feat_set_response */
+int ldso_pixsel_set_response(ldso_pixsel_t *p, const float *B_256_or_null);
+/* setting_minGradHistCut, setting_minGradHistAdd, setting_gradDownweightPerLevel, setting_selectDirectionDistribution (Setting.cc:83-87: 0.5, 7, 0.75, true) */
+int ldso_pixsel_set_settings(ldso_pixsel_t *p, float minGradHistCut, float minGradHistAdd, float gradDownweightPerLevel, int selectDirectionDistribution);
+/* PixelSelector::currentPotential, which one makeMaps leaves for the next (:165) */
+int ldso_pixsel_set_potential(ldso_pixsel_t *p, int potential);
+int ldso_pixsel_get_potential(ldso_pixsel_t *p, int *potential);
+/* makeMaps(fh, map, density, recursions_left, plot, th_factor) (:111-168): one histogram pass, one select pass per recursion (one wait each for the counts),
+ * the thinning.  *n_out = its return value, counts_out = (n2, n3, n4) of the last select pass, *potential_used = that pass's potential; outputs optional. */
+int ldso_pixsel_make_maps(ldso_pixsel_t *p, ldso_pyramid_t *pyr, float density, int recursions_left, float th_factor, int *n_out, int counts_out[3], int *potential_used);
+/* the map of the last ldso_pixsel_make_maps: w * h floats 0 / 1 / 2 / 4;  ths / thsSmoothed (:64, :107): (w / 32) * (h / 32) floats each, either optional */
+int ldso_pixsel_get_map(ldso_pixsel_t *p, float *map_out);
+int ldso_pixsel_get_thresholds(ldso_pixsel_t *p, float *ths_out, float *ths_smoothed_out);
+/* FullSystem.cc:1290-1303 on that map: one record per selected pixel with patternPadding + 1 <= x < w - patternPadding - 2 (likewise y), in raster order,
+ * host = host_index, my_type = the map value.  A record with a non-finite colour is kept, has energyTH = NaN and makes the call return LDSO_E_NONFINITE
+ * (:1298 drops it). */
+int ldso_pixsel_make_points(ldso_pixsel_t *p, ldso_pyramid_t *pyr, int host_index, int *n_out);
+/* the records of the last ldso_pixsel_make_points and their my_type on the host (type_out optional) / as device pointers (valid until the next make_points
+ * or destroy; immature_dev is what ldso_trace_append_points_device takes) */
+int ldso_pixsel_get_points(ldso_pixsel_t *p, ldso_immature_t *out, float *type_out_or_null);
+int ldso_pixsel_device(ldso_pixsel_t *p, const void **immature_dev, const void **type_dev, int *n);
+/* enable != 0: the calls bracket their kernels with HIP events; us_out[5] (optional) = microseconds of the last profiled make_maps + make_points:
+ * histogram (:36-109), masks + scan, select (both summed over the recursion's passes), thinning (:150-163), records */
+int ldso_pixsel_profile(ldso_pixsel_t *p, int enable, float us_out[5]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Raw camera frames: Undistort::undistort<T> (src/frontend/Undistort.cc:357-457) = PhotometricUndistorter::processFrame (:189-227) and the bilinear remap

@@ -16,6 +16,7 @@ _LIB = None
 
 E_NONFINITE = -3          # LDSO_E_NONFINITE (ldso_hip.h)
 E_INVALID = -1            # LDSO_E_INVALID
+E_UNSUPPORTED = -4        # LDSO_E_UNSUPPORTED
 MAX_FRAMES = 16           # LDSO_MAX_FRAMES (ldso_window.h)
 
 
@@ -170,6 +171,104 @@ class Features:
     def profile(self, enable=True):
         us = np.zeros(4, np.float32)
         _chk(self.L.ldso_feat_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
+        return us
+
+
+class PixelSelector:
+    """DSO's gradient pixels of a new key frame (ldso_pixsel_t): PixelSelector::makeMaps + the raster scan and ImmaturePoint constructors of makeNewTraces."""
+
+    def __init__(self, w, h, random_pattern, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        rp = np.ascontiguousarray(random_pattern, np.uint8)
+        assert rp.size == w * h
+        _chk(self.L.ldso_pixsel_create(C.c_int(device), C.c_int(w), C.c_int(h), _p(rp), C.byref(self.h)))
+        self.w, self.hh, self.n = w, h, 0
+
+    def close(self):
+        if self.h:
+            self.L.ldso_pixsel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def supported(w, h):
+        """host only: the return code of ldso_pixsel_supported (0, or E_UNSUPPORTED for sizes that are no multiples of 32)"""
+        return lib().ldso_pixsel_supported(C.c_int(w), C.c_int(h))
+
+    @staticmethod
+    def plan(counts, density, potential, recursions_left):
+        """host only: (action, new_potential, char_th) of makeMaps :125-153"""
+        c = np.ascontiguousarray(counts, np.int32)
+        v = [C.c_int() for _ in range(3)]
+        _chk(lib().ldso_pixsel_plan(_p(c), C.c_float(density), C.c_int(potential), C.c_int(recursions_left), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def set_stream(self, stream_ptr):
+        _chk(self.L.ldso_pixsel_set_stream(self.h, C.c_void_p(stream_ptr)))
+
+    def set_response(self, B):
+        b = None if B is None else np.ascontiguousarray(B, np.float32)
+        assert b is None or b.size == 256
+        _chk(self.L.ldso_pixsel_set_response(self.h, _p(b)))
+
+    def set_settings(self, min_grad_hist_cut=0.5, min_grad_hist_add=7.0, grad_downweight_per_level=0.75, select_direction_distribution=True):
+        _chk(self.L.ldso_pixsel_set_settings(self.h, C.c_float(min_grad_hist_cut), C.c_float(min_grad_hist_add), C.c_float(grad_downweight_per_level),
+                                             C.c_int(1 if select_direction_distribution else 0)))
+
+    @property
+    def potential(self):
+        v = C.c_int()
+        _chk(self.L.ldso_pixsel_get_potential(self.h, C.byref(v)))
+        return v.value
+
+    @potential.setter
+    def potential(self, value):
+        _chk(self.L.ldso_pixsel_set_potential(self.h, C.c_int(value)))
+
+    def make_maps(self, pyr: "Pyramid", density, recursions_left=1, th_factor=1.0):
+        """(return value of makeMaps, (n2, n3, n4), potential used); raises LdsoError (E_NONFINITE: the results can still be fetched)"""
+        n, used = C.c_int(), C.c_int()
+        counts = np.zeros(3, np.int32)
+        _chk(self.L.ldso_pixsel_make_maps(self.h, pyr.h, C.c_float(density), C.c_int(recursions_left), C.c_float(th_factor), C.byref(n), _p(counts), C.byref(used)))
+        return n.value, tuple(int(c) for c in counts), used.value
+
+    def get_map(self):
+        m = np.zeros((self.hh, self.w), np.float32)
+        _chk(self.L.ldso_pixsel_get_map(self.h, _p(m)))
+        return m
+
+    def get_thresholds(self):
+        a, b = np.zeros((self.hh // 32, self.w // 32), np.float32), np.zeros((self.hh // 32, self.w // 32), np.float32)
+        _chk(self.L.ldso_pixsel_get_thresholds(self.h, _p(a), _p(b)))
+        return a, b
+
+    def make_points(self, pyr: "Pyramid", host_index=0):
+        n = C.c_int()
+        code = self.L.ldso_pixsel_make_points(self.h, pyr.h, C.c_int(host_index), C.byref(n))
+        if code in (0, E_NONFINITE):
+            self.n = n.value
+        _chk(code)
+        return self.n
+
+    def get_points(self):
+        q, t = np.zeros(self.n, synth.IMMATURE_DTYPE), np.zeros(self.n, np.float32)
+        _chk(self.L.ldso_pixsel_get_points(self.h, _p(q), _p(t)))
+        return q, t
+
+    def device_ptrs(self):
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_int()
+        _chk(self.L.ldso_pixsel_device(self.h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
+
+    def profile(self, enable=True):
+        us = np.zeros(5, np.float32)
+        _chk(self.L.ldso_pixsel_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
         return us
 
 
@@ -887,6 +986,10 @@ class Tracer:
         """n immature records in device memory (Features.device_ptrs) behind the current points, device to device"""
         _chk(self.L.ldso_trace_append_points_device(self.h, C.c_int(n), C.c_void_p(immature_dev_ptr)))
         self.n += n
+
+    def set_tail_types_device(self, n, type_dev_ptr):
+        """my_type of the last n records from n floats in device memory (PixelSelector.device_ptrs)"""
+        _chk(self.L.ldso_trace_set_tail_types_device(self.h, C.c_int(n), C.c_void_p(type_dev_ptr)))
 
     def set_frame(self, dI_level0):
         a = np.ascontiguousarray(dI_level0, np.float32)

@@ -450,6 +450,15 @@ int ldso_trace_append_points_device(ldso_tracer_t *T, int n, const void *immatur
     return LDSO_OK;
 }
 
+// my_type of the last n records from device memory (ldso_pixsel_device): the points of setting_pointSelection == 0 carry their map value (FullSystem.cc:1297)
+int ldso_trace_set_tail_types_device(ldso_tracer_t *T, int n, const void *type_dev) {
+    REQ(T && n >= 0 && n <= T->n && (n == 0 || type_dev), "ldso_trace_set_tail_types_device: bad arguments");
+    CHK(hipSetDevice(T->device));
+    if (n) CHK(hipMemcpyAsync(T->d_type + (T->n - n), type_dev, (size_t) n * sizeof(float), hipMemcpyDeviceToDevice, T->stream));
+    CHK(hipStreamSynchronize(T->stream));
+    return LDSO_OK;
+}
+
 int ldso_trace_get_points(ldso_tracer_t *T, ldso_immature_t *out) {
     REQ(T && (T->n == 0 || out), "ldso_trace_get_points: bad arguments");
     CHK(hipSetDevice(T->device));

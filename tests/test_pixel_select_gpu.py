@@ -1,0 +1,140 @@
+"""GPU tests of ldso_amd/csrc/pixel_select.hip: PixelSelector::makeMaps and the points of FullSystem::makeNewTraces (setting_pointSelection == 0) on the device
+against the fixture recorded from the LDSO sources (tests/golden/ref_pixel_select.npz).  Everything compared is an integer or the result of the same IEEE
+operations in the same order: exact equality, no tolerance.  Three-level pyramids of 160 x 96 and 96 x 64."""
+import numpy as np
+import pytest
+
+import pixel_select_common as pc
+from ldso_amd import binding, synth
+
+pytestmark = pytest.mark.gpu
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+class Run:
+    """one selector and the calls of a fixture case on it"""
+
+    def __init__(self, name):
+        self.case = pc.load_case(name)
+        h, w = pc.image(self.case["calls"][0]["image"]).shape
+        self.w, self.h = w, h
+        self.sel = binding.PixelSelector(w, h, pc.golden()[f"pattern/{w}x{h}"])
+        s = self.case["settings"]
+        self.sel.set_settings(float(s[0]), float(s[1]), float(s[2]), bool(s[3]))
+        self.pyrs = []
+
+    def call(self, j, host=0):
+        c = self.case["calls"][j]
+        pyr = binding.Pyramid(self.w, self.h, 3).make_images(pc.image(c["image"]).astype(np.float32))
+        self.pyrs.append(pyr)
+        self.sel.set_response(pc.golden()["B"] if c["response"] else None)
+        if c["pot0"]:
+            self.sel.potential = c["pot0"]
+        n, counts, used = self.sel.make_maps(pyr, c["density"], c["rec"], c["th_factor"])
+        m = self.sel.get_map()
+        k = self.sel.make_points(pyr, host)
+        q, t = self.sel.get_points()
+        assert len(q) == k
+        return dict(n=n, counts=counts, used=used, left=self.sel.potential, map=m, ths=self.sel.get_thresholds(), imm=q, type=t, pyr=pyr)
+
+    def close(self):
+        self.sel.close()
+        for p in self.pyrs:
+            p.close()
+
+
+def check_call(r, c, host=0):
+    ret, n2, n3, n4, used, left = (int(x) for x in c["out"])
+    print("device", r["n"], r["counts"], r["used"], r["left"], "reference", c["out"], "map differences", int((r["map"] != c["map"]).sum()))
+    assert np.array_equal(bits(r["ths"][0].ravel()), bits(c["ths"])) and np.array_equal(bits(r["ths"][1].ravel()), bits(c["thsS"]))
+    assert r["counts"] == (n2, n3, n4) and r["used"] == used
+    assert r["map"].dtype == np.float32 and np.array_equal(r["map"], c["map"].astype(np.float32))
+    assert r["n"] == ret and r["left"] == left
+    # the points: raster order inside the border of FullSystem.cc:1290-1291, my_type = the map value
+    q = r["imm"]
+    assert len(q) == len(c["uv"])
+    assert np.array_equal(q["u"], c["uv"][:, 0].astype(np.float32)) and np.array_equal(q["v"], c["uv"][:, 1].astype(np.float32))
+    assert np.array_equal(r["type"], c["type"].astype(np.float32)) and np.all(q["host"] == host)
+    if c["imm"] is not None:
+        g = c["imm"]
+        assert np.array_equal(bits(q["color"]), bits(g[:, 2:10])) and np.array_equal(bits(q["weights"]), bits(g[:, 10:18]))
+        assert np.array_equal(bits(q["gradH"]).reshape(-1, 4), bits(g[:, 18:22])) and np.array_equal(bits(q["energyTH"]), bits(g[:, 22]))
+        assert np.all(q["idepth_min"] == 0) and np.isnan(q["idepth_max"]).all() and np.all(q["quality"] == 10000) and np.all(q["lastTraceStatus"] == 5)
+        assert np.all(q["lastTraceUV"] == -1)
+
+
+@pytest.mark.parametrize("name", pc.CASES)
+def test_against_reference_fixture(name):
+    R = Run(name)
+    try:
+        for j, c in enumerate(R.case["calls"]):
+            check_call(R.call(j, host=2), c, host=2)
+    finally:
+        R.close()
+
+
+def test_two_calls_are_byte_identical():
+    R = Run("thinning")
+    try:
+        a = R.call(0)
+        b = R.call(0)
+        assert a["map"].tobytes() == b["map"].tobytes() and a["imm"].tobytes() == b["imm"].tobytes() and a["type"].tobytes() == b["type"].tobytes()
+        assert (a["n"], a["counts"], a["used"], a["left"]) == (b["n"], b["counts"], b["used"], b["left"]) and len(a["imm"]) > 100
+        assert a["ths"][0].tobytes() == b["ths"][0].tobytes() and a["ths"][1].tobytes() == b["ths"][1].tobytes()
+    finally:
+        R.close()
+
+
+def test_append_points_device():
+    R = Run("natural")
+    try:
+        r = R.call(0, host=1)
+        win = synth.make_window(F=2, P=50, w=R.w, h=R.h, fx=R.w * 0.6, seed=71)
+        a, _ = synth.make_immature_points(win, 5)
+        n = len(r["imm"])
+        tr = binding.Tracer(R.w, R.h, len(a) + n + 3)
+        tr.set_points(a)
+        imm_dev, type_dev, cnt = R.sel.device_ptrs()
+        assert cnt == n > 500 and imm_dev and type_dev
+        tr.append_points_device(cnt, imm_dev)
+        got = tr.get_points()
+        assert len(got) == len(a) + n and got.tobytes() == np.concatenate([a, r["imm"]]).tobytes()
+        assert np.all(tr.get_point_types() == 1)
+        tr.set_tail_types_device(cnt, type_dev)
+        assert np.array_equal(tr.get_point_types(), np.concatenate([np.ones(len(a), np.float32), r["type"]])) and set(r["type"]) - {1.0}
+        with pytest.raises(binding.LdsoError) as e:
+            tr.set_tail_types_device(len(got) + 1, type_dev)
+        assert e.value.code == binding.E_INVALID
+        tr.close()
+    finally:
+        R.close()
+
+
+def test_nonfinite_pixel():
+    w, h = 160, 96
+    bad = pc.image("scene").astype(np.float32)
+    bad[40, 77] = np.nan
+    sel = binding.PixelSelector(w, h, pc.golden()[f"pattern/{w}x{h}"])
+    pyr = binding.Pyramid(w, h, 3).make_images(bad)
+    with pytest.raises(binding.LdsoError) as e:
+        sel.make_maps(pyr, 800.0, 1, 1.0)
+    assert e.value.code == binding.E_NONFINITE and "ldso_pixsel_make_maps" in str(e.value)
+    m = sel.get_map()
+    assert set(np.unique(m)) <= {0.0, 1.0, 2.0, 4.0} and (m != 0).sum() > 100          # the rest of the image is still selected from
+    sel.close(); pyr.close()
+
+
+def test_refusals():
+    with pytest.raises(binding.LdsoError) as e:
+        binding.PixelSelector(100, 64, np.zeros(6400, np.uint8))
+    assert e.value.code == binding.E_UNSUPPORTED
+    w, h = 96, 64
+    sel = binding.PixelSelector(w, h, pc.golden()[f"pattern/{w}x{h}"])
+    pyr = binding.Pyramid(w, h, 2).make_images(pc.image("small").astype(np.float32))          # select reads three levels
+    with pytest.raises(binding.LdsoError) as e:
+        sel.make_maps(pyr, 100.0)
+    assert e.value.code == binding.E_INVALID and "ldso_pixsel_make_maps" in str(e.value)
+    sel.close(); pyr.close()
