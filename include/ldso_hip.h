@@ -583,7 +583,8 @@ int ldso_undist_profile(ldso_undistorter_t *u, int enable, float us_out[3]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Monocular initialiser: CoarseInitializer (src/frontend/CoarseInitializer.cc, include/frontend/CoarseInitializer.h).
- * Replaces setFirst (:547-619, minus the pixel selection and the kd-tree of makeNN, whose results arrive as the point records),
+ * Replaces setFirst (:547-619) twice over: ldso_init_set_first takes finished point records (selection and neighbours are the caller's), ldso_init_set_first_frame
+ * further down takes a resident pyramid and does the pixel selection of every level, the records and the k-d tree searches of makeNN itself;
  * trackFrame (:40-178) and what it calls: calcResAndGS (:181-405), calcEC (:412-428), optReg (:430-459), propagateUp/Down
  * (:462-522), resetPoints (:621-643), doStep (:645-671), applyStep (:673-687), makeK (:689-715).
  * The whole Levenberg-Marquardt loop of one trackFrame runs on the device without a host round trip.
@@ -620,6 +621,75 @@ int ldso_init_set_schedule(ldso_initializer_t *t, int first_steps, int prepare_o
 int ldso_init_sweep_schedule(int n, const int *neighbours, int width, int *pass_out);
 /* debug builds (LDSO_STAMPS=1): accumulated device-side counters, zeros otherwise */
 int ldso_init_debug_counters(ldso_initializer_t *t, long long out[8]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * setFirst from a resident pyramid (CoarseInitializer.cc:547-619): the pixel selection of every level (level 0: PixelSelector::makeMaps with thFactor 2
+ * on the caller's selector; levels >= 1: makePixelStatus, include/frontend/PixelSelector2.h:63-277), the Pnt records (:567-603) and makeNN (:717-783) with the
+ * k-d tree built and searched as nanoflann does it (include/frontend/nanoflann.h): on pixel grids most rows have equally distant candidates for their last
+ * places, and which of them a row keeps is decided by the tree's leaf order and traversal, not by any tie rule.  Selection, records and searches run on the
+ * device; the tree is built on the host (sequential in the reference as well: planeSplit permutes one array in place), as are the sweep schedules of
+ * ldso_init_set_first, which this entry reuses.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* The members of Pnt that setFirst and makeNN leave uninitialised (the reference allocates with new Pnt[npts]) are DEFINED here, once, as the existing
+ * records of ldso_init_set_first's callers have them: idepth_new = 1, everything else 0. */
+#define LDSO_INIT_POINT_FILL_UNSET(p) do { (p).idepth_new = 1.0f; (p).maxstep = 0.0f; (p).iRSumNum = 0.0f; (p).isGood_new = 0; \
+                                           (p).energy_new[0] = 0.0f; (p).energy_new[1] = 0.0f; (p).pad_ = 0.0f; } while (0)
+/* One node of the tree, in nanoflann's allocation order (a node, then child1's subtree, then child2's; node 0 is the root).
+ * Leaf: child1 = child2 = -1, the points are vind[left_or_feat .. right).  Inner node: left_or_feat = divfeat (0: u, 1: v), divlow / divhigh as :1036-1037. */
+typedef struct ldso_nn_node {
+    int32_t child1, child2;
+    int32_t left_or_feat, right;
+    float divlow, divhigh;
+} ldso_nn_node_t;                     /* 24 bytes */
+typedef struct ldso_nn_tree ldso_nn_tree_t;
+/* Host only, no device.  buildIndex (:827-834) with leaf size 5 over n > 0 points (uv: n pairs u, v; copied).  LDSO_E_INVALID for a non-finite position. */
+int ldso_init_nn_build(int n, const float *uv, ldso_nn_tree_t **out);
+int ldso_init_nn_free(ldso_nn_tree_t *tree);
+/* every output optional.  depth = inner nodes above the deepest leaf (what a search's stack must hold); root_box = low u, high u, low v, high v */
+int ldso_init_nn_info(const ldso_nn_tree_t *tree, int *n, int *n_nodes, int *depth, float root_box[4]);
+/* the node array (n_nodes entries) and nanoflann's permuted index array vind (n entries), either optional */
+int ldso_init_nn_get(const ldso_nn_tree_t *tree, ldso_nn_node_t *nodes_out, int32_t *vind_out);
+/* findNeighbors (:869-881) with a KNNResultSet of k entries for n_query positions: idx_out / dist_out [n_query][k], the squared distances ascending, places
+ * the tree could not fill hold -1 / FLT_MAX.  k is 1 or 10, the two sizes makeNN uses (LDSO_E_UNSUPPORTED otherwise). */
+int ldso_init_nn_search_host(const ldso_nn_tree_t *tree, int n_query, const float *query_uv, int k, int32_t *idx_out, float *dist_out);
+/* Host only, no device: the scalar arithmetic of makePixelStatus :253-276 behind one gridMaxSelection pass that set n_good pixels with block size `sparsity`
+ * (>= 1) and th_fac.  *action = 1: select again with *new_sparsity and *new_th_fac, recs_left - 1; 0: done.  *new_sparsity is what sparsityFactor becomes
+ * either way. */
+int ldso_init_pixel_status_plan(int n_good, float desired, int sparsity, int recs_left, float th_fac, int *action, int *new_sparsity, float *new_th_fac);
+/* sparsityFactor (a process-wide global in the reference, 5 in Setting.cc:126) is state of the handle: it starts at 5 and is carried from level to level and
+ * from one first frame to the next, as the global is. */
+int ldso_init_set_sparsity(ldso_initializer_t *t, int sparsity);
+int ldso_init_get_sparsity(ldso_initializer_t *t, int *sparsity);
+/* Stage entry: makePixelStatus(dIp[lvl], map, w >> lvl, h >> lvl, desired_density, recs_left, th_fac) on level lvl >= 1 of the pyramid (same device and size
+ * as the handle), from the handle's sparsity, which it updates.  One wait per pass.  *n_out = its return value (pixels set anywhere on the level, not the record
+ * count), *passes_out = gridMaxSelection passes run.  A non-finite gradient gives LDSO_E_NONFINITE (the map is still there; a NaN never wins a comparison); a pyramid
+ * built by this library holds none above level 0's intensity, makeImages zeroes a non-finite dx / dy (FrameHessian.cc:86-87). */
+int ldso_init_pixel_status(ldso_initializer_t *t, ldso_pyramid_t *pyr, int lvl, float desired_density, int recs_left, float th_fac, int *n_out, int *passes_out);
+/* the byte map (0 / 1) of the last pixel-status pass, (w >> lvl) * (h >> lvl) bytes of the level it ran on; *lvl_out optional */
+int ldso_init_get_status_map(ldso_initializer_t *t, unsigned char *map_out, int *lvl_out);
+/* Stage entry: the searches of makeNN on the device for arbitrary positions.  uv[l] = n[l] pairs (copied), n[l] >= 10.  The trees are built on the host, one
+ * lane searches for one point.  Per level, each optional: nb_idx / nb_dist [n][10] = the 10 nearest of the same level and their squared distances in result
+ * order; parent_idx / parent_dist [n] = the nearest point of level l + 1 to (u, v) * 0.5 - (0.25, 0.25) (level n_levels - 1: -1 / -1).
+ * LDSO_E_UNSUPPORTED, before anything is launched, for a level with fewer than 10 points or a tree deeper than 64. */
+int ldso_init_make_nn(ldso_initializer_t *t, int n_levels, const float *const *uv, const int *n, int32_t *const *nb_idx_out, float *const *nb_dist_out,
+                      int32_t *const *parent_idx_out, float *const *parent_dist_out);
+/* makeK + setFirst on the frame the pyramid holds (built by ldso_pyr_make_images or ldso_undist_frame; at least the handle's levels and three, same device and
+ * size): level 0 through ldso_pixsel_set_potential(3) and ldso_pixsel_make_maps(0.03 * w * h, 1, th_factor 2) on `pixsel`, levels >= 1 through makePixelStatus
+ * with densities {0.03, 0.05, 0.15, 0.5, 1}[lvl] * w * h, the records in raster order over patternPadding + 1 <= x < wl - patternPadding - 2 (likewise y),
+ * the searches; then everything ldso_init_set_first does with finished records.  The handle's first-frame images are device copies of the pyramid's levels.
+ * n_points_out[lvl] (optional) = numPoints[lvl].  ldso_init_get_points afterwards returns all fields of the records, neighboursDist, parentDist and my_type
+ * included.  Two calls on the same input leave byte-identical records and maps.  Defined where the reference is not:
+ *   - more than 5 levels (densities[5] is read past the array): LDSO_E_UNSUPPORTED.  ldso_init_create already refuses such a handle;
+ *   - a level with fewer than 10 records (makeNN copies stale ret_index entries into the neighbour list): LDSO_E_UNSUPPORTED, before any search is launched;
+ *   - a width or height that is no multiple of 32: the code of ldso_pixsel_make_maps, passed on;
+ *   - more than 36000 records on a level: LDSO_E_INVALID, as ldso_init_set_first;
+ *   - a non-finite gradient: LDSO_E_NONFINITE, by the rule of ldso_pixsel_make_maps (a NaN never wins a comparison).
+ * After any of these the handle holds no first frame and takes the next one as a fresh handle would; the sparsity keeps what the passes that ran left. */
+int ldso_init_set_first_frame(ldso_initializer_t *t, const float calib[4], ldso_pyramid_t *pyr, float ab_exposure, ldso_pixsel_t *pixsel, float huberTH,
+                              int fixAffine, int n_points_out[]);
+/* enable != 0: ldso_init_set_first_frame times its stages (each ends in a wait; host clock between the waits); us_out[6] (optional) = microseconds of the last
+ * profiled call: level-0 maps, coarser-level maps, records, tree build on the host, searches, schedule build with its uploads and the image copies */
+int ldso_init_first_profile(ldso_initializer_t *t, int enable, float us_out[6]);
 
 #ifdef __cplusplus
 }

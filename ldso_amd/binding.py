@@ -1093,3 +1093,103 @@ class Initializer:
         res = np.zeros(3, np.float32); ec = np.zeros(3, np.float32)
         _chk(self.L.ldso_init_calc_res_and_gs(self.h, C.c_int(lvl), _p(T), C.c_double(a), C.c_double(b), _p(H), _p(bo), _p(Hsc), _p(bsc), _p(res), _p(ec)))
         return H, bo, Hsc, bsc, res, ec
+
+    # ---- setFirst from a resident pyramid (ldso_amd/csrc/init_first.hip) --------------------------------------------------------------------------
+    @property
+    def sparsity(self):
+        """sparsityFactor of makePixelStatus: state of the handle, 5 at creation, carried from level to level and from one first frame to the next"""
+        v = C.c_int()
+        _chk(self.L.ldso_init_get_sparsity(self.h, C.byref(v)))
+        return v.value
+
+    @sparsity.setter
+    def sparsity(self, value):
+        _chk(self.L.ldso_init_set_sparsity(self.h, C.c_int(value)))
+
+    def pixel_status(self, pyr: "Pyramid", lvl, desired_density, recs_left=5, th_fac=1.0):
+        """makePixelStatus on level lvl >= 1 -> (return value, gridMaxSelection passes); raises LdsoError (E_NONFINITE: the map can still be fetched)"""
+        n, passes = C.c_int(), C.c_int()
+        self._status_shape = (self.hh >> lvl, self.w >> lvl)
+        _chk(self.L.ldso_init_pixel_status(self.h, pyr.h, C.c_int(lvl), C.c_float(desired_density), C.c_int(recs_left), C.c_float(th_fac), C.byref(n), C.byref(passes)))
+        return n.value, passes.value
+
+    def status_map(self):
+        """the byte map of the last pixel-status pass, uint8 [h >> lvl, w >> lvl]"""
+        out = np.zeros(self._status_shape, np.uint8)
+        _chk(self.L.ldso_init_get_status_map(self.h, _p(out), None))
+        return out
+
+    def make_nn(self, uv):
+        """the searches of makeNN for one float32 [n, 2] position array per level -> per level (nb_idx [n, 10], nb_dist, parent_idx [n], parent_dist); squared distances"""
+        uv = [np.ascontiguousarray(a, np.float32).reshape(-1, 2) for a in uv]
+        L = len(uv)
+        n = np.array([len(a) for a in uv], np.int32)
+        out = [(np.zeros((len(a), 10), np.int32), np.zeros((len(a), 10), np.float32), np.zeros(len(a), np.int32), np.zeros(len(a), np.float32)) for a in uv]
+        arr = lambda xs: (C.c_void_p * L)(*[x.ctypes.data for x in xs])
+        _chk(self.L.ldso_init_make_nn(self.h, C.c_int(L), arr(uv), _p(n), arr([o[0] for o in out]), arr([o[1] for o in out]), arr([o[2] for o in out]),
+                                      arr([o[3] for o in out])))
+        return out
+
+    def set_first_frame(self, K4, pyr: "Pyramid", pixsel: "PixelSelector", exposure=1.0, huberTH=9.0, fixAffine=True):
+        """setFirst on the frame the pyramid holds: selection, records and neighbours on the device.  Returns numPoints per level."""
+        k = np.ascontiguousarray(K4, np.float32)
+        n = np.zeros(self.levels, np.int32)
+        self.n = [0] * self.levels
+        _chk(self.L.ldso_init_set_first_frame(self.h, _p(k), pyr.h, C.c_float(exposure), pixsel.h, C.c_float(huberTH), C.c_int(1 if fixAffine else 0), _p(n)))
+        self.n = [int(x) for x in n]
+        self._status_shape = (self.hh >> (self.levels - 1), self.w >> (self.levels - 1))          # the last pixel-status pass ran on the coarsest level
+        return self.n
+
+    def first_profile(self, enable=True):
+        """microseconds of the last profiled set_first_frame: level-0 maps, coarser maps, records, tree build (host), searches, schedules + uploads"""
+        us = np.zeros(6, np.float32)
+        _chk(self.L.ldso_init_first_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
+        return us
+
+
+# ---- host-only entries of the initialiser's first frame (no device) ------------------------------------------------------------------------------
+NN_NODE_DTYPE = np.dtype([("child1", np.int32), ("child2", np.int32), ("left_or_feat", np.int32), ("right", np.int32), ("divlow", np.float32), ("divhigh", np.float32)])
+
+
+def init_pixel_status_plan(n_good, desired, sparsity, recs_left, th_fac):
+    """(action, new_sparsity, new_th_fac) of makePixelStatus behind one gridMaxSelection pass"""
+    a, s, t = C.c_int(), C.c_int(), C.c_float()
+    _chk(lib().ldso_init_pixel_status_plan(C.c_int(n_good), C.c_float(desired), C.c_int(sparsity), C.c_int(recs_left), C.c_float(th_fac), C.byref(a), C.byref(s), C.byref(t)))
+    return a.value, s.value, t.value
+
+
+class NNTree:
+    """nanoflann's k-d tree over float32 [n, 2] positions, built and searched on the host (ldso_init_nn_*)"""
+
+    def __init__(self, uv):
+        self.L = lib()
+        self.h = C.c_void_p()
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        _chk(self.L.ldso_init_nn_build(C.c_int(len(uv)), _p(uv), C.byref(self.h)))
+        n, nn, d = C.c_int(), C.c_int(), C.c_int()
+        self.root_box = np.zeros(4, np.float32)
+        _chk(self.L.ldso_init_nn_info(self.h, C.byref(n), C.byref(nn), C.byref(d), _p(self.root_box)))
+        self.n, self.n_nodes, self.depth = n.value, nn.value, d.value
+
+    def close(self):
+        if self.h:
+            self.L.ldso_init_nn_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def arrays(self):
+        """(nodes as NN_NODE_DTYPE in allocation order, vind)"""
+        nodes, vind = np.zeros(self.n_nodes, NN_NODE_DTYPE), np.zeros(self.n, np.int32)
+        _chk(self.L.ldso_init_nn_get(self.h, _p(nodes), _p(vind)))
+        return nodes, vind
+
+    def search(self, query_uv, k=10):
+        q = np.ascontiguousarray(query_uv, np.float32).reshape(-1, 2)
+        idx, dist = np.zeros((len(q), k), np.int32), np.zeros((len(q), k), np.float32)
+        _chk(self.L.ldso_init_nn_search_host(self.h, C.c_int(len(q)), _p(q), C.c_int(k), _p(idx), _p(dist)))
+        return idx, dist

@@ -87,6 +87,18 @@ struct ldso_initializer {
     bool snappedAtFrameStart = false;   // host copy of the state's snapped (get_state / set_state / set_first): before the snap optReg does not sweep and the
                                         // k_ini_prep launches would be empty (the frame that snaps prepares its sweeps in the control block)
     bool haveFirst = false, haveNew = false;
+    // setFirst from a pyramid (init_first.hip): sparsityFactor, the byte map of makePixelStatus with its counters, the records and positions of every level
+    int sparsity = 5;                   // Setting.cc:126
+    std::vector<void *> firstAllocs;    // freed by destroy
+    unsigned char *d_status = nullptr;  // (w / 2) * (h / 2) bytes
+    int statusLvl = 0;                  // the level the map was last written for
+    int *d_fctl = nullptr, *d_rowCount = nullptr, *d_rowStart = nullptr;
+    ldso_init_point_t *d_rec[INI_MAXL] = {nullptr};
+    float *d_uv[INI_MAXL] = {nullptr};
+    int recCap[INI_MAXL] = {0};
+    std::vector<ldso_init_point_t> firstRec[INI_MAXL];      // the records as set_first_frame built them (weights and my_type are not part of the SoA)
+    bool profileFirst = false;
+    float usFirst[6] = {0, 0, 0, 0, 0, 0};
 };
 
 #pragma GCC visibility push(hidden)
@@ -95,4 +107,8 @@ hipError_t ini_ctl_reserve_lds(size_t ldsBytes);
 void ini_launch_eval(const IniParams &P, int stage, hipStream_t st);
 void ini_launch_prep(const IniParams &P, int blocks, hipStream_t st);
 void ini_launch_ctl(const IniParams &P, int phase, size_t ldsBytes, hipStream_t st);
+// initializer_api.hip: ldso_init_set_first without its image build - levels, schedules, records and the state of setFirst (the caller fills d_first and sets haveFirst)
+int ini_set_first_records(ldso_initializer *H, const float calib[4], float ab_exposure, const ldso_init_point_t *const *points, const int *n_points, float huberTH, int fixAffine);
+// pixel_select.hip: the byte map (0 / 1 / 2 / 4) of the selector's last make_maps, its size and stream
+const unsigned char *pix_map_device(const struct ldso_pixsel *P, int *w, int *h, int *device);
 #pragma GCC visibility pop

@@ -63,6 +63,7 @@ int ldso_init_destroy(ldso_initializer_t *H) {
     hipDeviceSynchronize();
     for (void *p : H->allocs) hipFree(p);
     for (void *p : H->levelAllocs) hipFree(p);
+    for (void *p : H->firstAllocs) hipFree(p);
     if (H->ownStream && H->stream) hipStreamDestroy(H->stream);
     delete H;
     return LDSO_OK;
@@ -83,6 +84,15 @@ static int ini_images(ldso_initializer *H, const float *irr, float *const *level
 int ldso_init_set_first(ldso_initializer_t *H, const float calib[4], const float *irradiance, float ab_exposure,
                         const ldso_init_point_t *const *points, const int *n_points, float huberTH, int fixAffine) {
     REQ(H && calib && irradiance && points && n_points, "ldso_init_set_first: null argument");
+    RUN(ini_set_first_records(H, calib, ab_exposure, points, n_points, huberTH, fixAffine));
+    RUN(ini_images(H, irradiance, H->d_first));
+    H->haveFirst = true; H->haveNew = false;
+    return LDSO_OK;
+}
+
+}  // extern "C"
+
+int ini_set_first_records(ldso_initializer *H, const float calib[4], float ab_exposure, const ldso_init_point_t *const *points, const int *n_points, float huberTH, int fixAffine) {
     CHK(hipSetDevice(H->device));
     CHK(hipStreamSynchronize(H->stream));
     for (void *p : H->levelAllocs) hipFree(p);
@@ -197,10 +207,11 @@ int ldso_init_set_first(ldso_initializer_t *H, const float calib[4], const float
     IniCtl c; memset(&c, 0, sizeof(c));
     c.Tcur[0] = c.Tcur[5] = c.Tcur[10] = 1.0; c.Tnew[0] = c.Tnew[5] = c.Tnew[10] = 1.0; c.done = 1;
     CHK(hipMemcpy(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
-    RUN(ini_images(H, irradiance, H->d_first));
-    H->haveFirst = true; H->haveNew = false;
+    for (int l = 0; l < INI_MAXL; l++) H->firstRec[l].clear();
     return LDSO_OK;
 }
+
+extern "C" {
 
 int ldso_init_set_new_frame(ldso_initializer_t *H, const float *irradiance, float ab_exposure) {
     REQ(H && irradiance, "ldso_init_set_new_frame: null argument");
@@ -315,6 +326,13 @@ int ldso_init_get_points(ldso_initializer_t *H, int l, ldso_init_point_t *out) {
 #undef XI
     if (n) CHK(hipMemcpy(nb.data(), L.nb, (size_t) n * INI_NB * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) for (int q = 0; q < 10; q++) out[i].neighbours[q] = nb[(size_t) i * INI_NB + q];
+    // what the device arrays do not carry comes from the records ldso_init_set_first_frame built, where it built them
+    if ((int) H->firstRec[l].size() == n)
+        for (int i = 0; i < n; i++) {
+            const ldso_init_point_t &r = H->firstRec[l][i];
+            out[i].parentDist = r.parentDist; out[i].my_type = r.my_type; out[i].pad_ = r.pad_;
+            for (int q = 0; q < 10; q++) out[i].neighboursDist[q] = r.neighboursDist[q];
+        }
     return LDSO_OK;
 }
 

@@ -621,3 +621,9 @@ int ldso_pixsel_device(ldso_pixsel_t *P, const void **immature_dev, const void *
 }
 
 }  // extern "C"
+
+// for ldso_init_set_first_frame (init_first.hip), which scans the level-0 map where it lies
+__attribute__((visibility("hidden"))) const unsigned char *pix_map_device(const ldso_pixsel *P, int *w, int *h, int *device) {
+    *w = P->w; *h = P->h; *device = P->device;
+    return P->d_map;
+}
