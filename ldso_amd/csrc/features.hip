@@ -7,7 +7,7 @@
 //                    cell maximum -> gradTH -> candidates; every candidate's 64 Shi-Tomasi taps are summed by ONE lane in the reference's order (three float
 //                    accumulators); the k best by (score descending, idx ascending) go to the cell's slots; the global maximum score over ALL
 //                    candidates is an integer atomicMax on the bits of max(s, 0) (exact, order-independent)
-//   k_feat_compact   one workgroup: prefix sum over the cells' counts (cells gx-major, gy inner = the reference's loop order), features to their final
+//   k_feat_compact   one workgroup: prefix sum over the cells' counts (segment_scan256; cells gx-major, gy inner = the reference's loop order), features to their final
 //                    places, corner candidates score > float(0.01 * double(maxScore))
 //   k_feat_corners   the all-pairs suppression :107-118 through LDS tiles; it never rereads isCorner, so it is a pure function of (u, v, score, index)
 //   k_feat_describe  one wavefront per corner: the 31 x 31 intensity patch staged in LDS, lane 0 accumulates the moments in the reference's order,
@@ -19,10 +19,11 @@
 // an immature record whose taps leave the image gets a NaN colour and energyTH = NaN.  Rows 0 and h-1 have zero gradients (images.hip).
 #include "ba_host.h"
 #include "immature_record.h"
+#include "lane.h"
+#include "select_dev.h"
 
 #define FEAT_HP 15                      // HALF_PATCH_SIZE, FeatureDetector.h:20
 #define FEAT_MAX_GRID 64                // largest gridsize the cell kernel stages in LDS
-#define FEAT_FLAG_NONFINITE 1
 
 struct FeatGrid { int gridsize, gridX, gridY, skip, perCell, nx, ny; float nfeatInGrid; };
 
@@ -60,11 +61,6 @@ static __device__ __forceinline__ unsigned feat_key(float s) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-static __device__ __forceinline__ unsigned long long feat_wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = __shfl_xor(v, o, 64); if (x > v) v = x; }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_feat_cells(FeatArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int g = A.G.gridsize, P = g + 8, w = A.w, h = A.h, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -82,24 +78,16 @@ __global__ __launch_bounds__(256) void k_feat_cells(FeatArgs A) {
         pdx[p] = dx; pdy[p] = dy;
     }
     __syncthreads();
-    // absSquaredGrad (FrameHessian.cc:91-96) and the cell's maximum (:50-55)
+    // absSquaredGrad and the cell's maximum (:50-55)
     float m = 0;
     for (int p = tid; p < g * g; p += 256) {
         const int x = p % g, y = p / g, q = (y + 4) * P + x + 4;
-        float d = pdx[q] * pdx[q] + pdy[q] * pdy[q];
         const float I = A.img[3 * ((size_t) (y0 + y) * w + x0 + x)];          // the cell lies inside the image (gx < gridX - skip, skip >= 1)
-        if (!isfinite(I)) bad = true;
-        if (A.B) {
-            int c = isfinite(I) ? (int) (I + 0.5f) : 5;            // CalibHessian::getBGradOnly (CalibHessian.h:102-111)
-            if (c < 5) c = 5;
-            if (c > 250) c = 250;
-            const float gw = A.B[c + 1] - A.B[c];
-            d *= gw * gw;
-        }
+        const float d = abs_sq_grad(I, pdx[q], pdy[q], A.B, bad);
         sc[p] = d;
         if (d > m) m = d;
     }
-    for (int o = 32; o > 0; o >>= 1) { const float x = __shfl_xor(m, o, 64); if (x > m) m = x; }
+    m = wave_max(m);
     if (lane == 0) ((float *) red)[wave] = m;
     __syncthreads();
     m = ((float *) red)[0];
@@ -134,26 +122,26 @@ __global__ __launch_bounds__(256) void k_feat_cells(FeatArgs A) {
         }
         key[p] = k;
     }
-    for (int o = 32; o > 0; o >>= 1) { const float x = __shfl_xor(smax, o, 64); if (x > smax) smax = x; }
+    smax = wave_max(smax);
     if (lane == 0 && smax > 0) atomicMax(&A.ctl[0], __float_as_int(smax));
-    if (__any(bad) && lane == 0) atomicOr(&A.ctl[1], FEAT_FLAG_NONFINITE);
+    report_nonfinite(bad, &A.ctl[1]);
     __syncthreads();
     // the k best: score descending, equal scores lower idx first (:78-92)
     int picked = 0;
     for (int r = 0; r < A.G.perCell; r++) {
         unsigned long long best = 0;
         for (int p = tid; p < g * g; p += 256) {
-            const unsigned long long c = ((unsigned long long) key[p] << 32) | (unsigned) (0x7fffffff - p);
+            const unsigned long long c = argmax_key(key[p], p);
             if (key[p] && c > best) best = c;
         }
-        best = feat_wave_max(best);
+        best = wave_max(best);
         if (lane == 0) red[wave] = best;
         __syncthreads();
         best = red[0];
         for (int i = 1; i < 4; i++) if (red[i] > best) best = red[i];
         __syncthreads();
         if (best == 0) break;
-        const int idx = 0x7fffffff - (int) (unsigned) (best & 0xffffffffu);
+        const int idx = argmax_index(best);
         if (tid == 0) {
             ldso_feature_t f;
             memset(&f, 0, sizeof(f));
@@ -170,17 +158,11 @@ __global__ __launch_bounds__(256) void k_feat_cells(FeatArgs A) {
 // one workgroup of 256: exclusive prefix sum of the cells' counts, features to their places in the reference's order
 __global__ __launch_bounds__(256) void k_feat_compact(FeatArgs A, int nCells) {
     __shared__ int part[256];
-    const int tid = threadIdx.x, per = (nCells + 255) / 256, b = tid * per, e = min(b + per, nCells);
-    int s = 0;
-    for (int c = b; c < e; c++) s += A.cellCount[c];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) { int a = 0; for (int i = 0; i < 256; i++) { const int t = part[i]; part[i] = a; a += t; } A.ctl[2] = a; }
-    __syncthreads();
+    const Segment s = segment_scan256(A.cellCount, nCells, part, &A.ctl[2]);
     const float maxScore = __int_as_float(A.ctl[0]);
     const float scoreTH = (float) (0.01 * (double) maxScore);     // :98
-    int off = part[tid];
-    for (int c = b; c < e; c++) {
+    int off = s.off;
+    for (int c = s.b; c < s.e; c++) {
         const int n = A.cellCount[c];
         for (int r = 0; r < n; r++) {
             ldso_feature_t f = A.cellFeat[(size_t) c * A.G.perCell + r];
@@ -261,7 +243,7 @@ __global__ __launch_bounds__(256) void k_feat_describe(FeatArgs A, FeatUmax U) {
         F->angle = angle;
     }
     angle = __shfl(angle, 0, 64);
-    if (__any(bad || !isfinite(angle)) && lane == 0) atomicOr(&A.ctl[1], FEAT_FLAG_NONFINITE);
+    report_nonfinite(bad || !isfinite(angle), &A.ctl[1]);
     if (!A.pattern) return;
     const float factorPI = (float) (3.1415926535897932384626433832795 / 180.f);
     const float ang = angle * factorPI;                            // the reference converts the radian value once more (:136): followed
@@ -289,7 +271,7 @@ __global__ __launch_bounds__(256) void k_feat_records(FeatArgs A) {
     if (i >= n) return;
     bool bad = false;
     A.imm[i] = imm_record(A.img, A.feat[i].u, A.feat[i].v, A.w, A.h, A.hostIndex, bad);
-    if (bad) atomicOr(&A.ctl[1], FEAT_FLAG_NONFINITE);
+    if (bad) atomicOr(&A.ctl[1], SEL_FLAG_NONFINITE);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -430,7 +412,7 @@ int ldso_feat_detect(ldso_features_t *F, ldso_pyramid_t *pyr, int n_features, in
     F->n = ctl[2]; F->nCorners = ctl[3];
     if (n_features_out) *n_features_out = F->n;
     if (n_corners_out) *n_corners_out = F->nCorners;
-    if (ctl[1] & FEAT_FLAG_NONFINITE) { ldso_set_error("ldso_feat_detect: non-finite pixel, score, angle or colour"); return LDSO_E_NONFINITE; }
+    if (ctl[1] & SEL_FLAG_NONFINITE) { ldso_set_error("ldso_feat_detect: non-finite pixel, score, angle or colour"); return LDSO_E_NONFINITE; }
     return LDSO_OK;
 }
 

@@ -1,25 +1,25 @@
 // init_first.hip — CoarseInitializer::setFirst from a resident pyramid (include/ldso_hip.h, "setFirst from a resident pyramid"): makePixelStatus for the
-// levels >= 1 (k_ini_gridmax + the host recursion), the Pnt records of every level (k_ini_rows / k_ini_rowscan / k_ini_records), the searches of makeNN over
+// levels >= 1 (k_ini_gridmax + the host recursion), the Pnt records of every level (the raster scan of raster_scan.h + k_ini_records), the searches of makeNN over
 // the host-built k-d trees (k_ini_nn; the search itself is nn_search.h, the build init_nn_tree.cpp), and ldso_init_set_first_frame, which strings them together
 // and hands the finished records to the code behind ldso_init_set_first (initializer_api.hip).
 #include <chrono>
 #include "initializer.h"
 #include "pyramid.h"
 #include "nn_search.h"
+#include "raster_scan.h"
 
 #define FC_COUNT 0            // d_fctl: pixels set by the gridMaxSelection pass
-#define FC_FLAGS 1            // bit 0: a non-finite gradient was read
+#define FC_FLAGS 1            // SEL_FLAG_NONFINITE: a non-finite gradient was read
 #define FC_TOTAL 2            // records of the scanned rectangle
 #define NN_MAX_DEPTH 64       // 64 lanes x 64 entries x 16 bytes = 64 KB of LDS
 #define INI_MAX_POINTS 36000  // ldso_init_set_first's limit per level
 
 // ---------------------------------------------------------------------------------------------------------
-// gridMaxSelection (PixelSelector2.h:63-225; the templated variants and the generic one are the same arithmetic): G = 1, 4, 16 or 64 lanes per pot x pot block.
+// gridMaxSelection (PixelSelector2.h:63-225; the templated variants and the generic one are the same arithmetic): G = lanes_per_block(pot) lanes per pot x pot block.
 // The reference scans a block with dx in the outer loop and dy in the inner one and keeps the FIRST strict maximum, so among equal values the smallest
-// c = dx * pot + dy wins.  A lane walks its cells in ascending c (first strict maximum again); across the lanes the maximum of (value bits, ~c) picks the
+// c = dx * pot + dy wins.  A lane walks its cells in ascending c (first strict maximum again); across the lanes the maximum of argmax_key(value, c) picks the
 // largest value and, among equals, the smallest c.  A value has to exceed the initial best of 0, and a NaN never does.
 // ---------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ unsigned long long gm_key(float v, int c) { return ((unsigned long long) (unsigned) __float_as_int(v) << 32) | (unsigned) (0x7fffffff - c); }
 
 __global__ __launch_bounds__(256) void k_ini_gridmax(const float *__restrict__ img, unsigned char *__restrict__ map, int w, int h, int pot, int nbx, int nby, int G, float THFac,
                                                      int *__restrict__ ctl) {
@@ -28,12 +28,12 @@ __global__ __launch_bounds__(256) void k_ini_gridmax(const float *__restrict__ i
     const long long blk = gid / G;
     const bool live = blk < (long long) nbx * nby;
     const float TH = THFac * 10.0f * 0.75f, TH2 = TH * TH;
-    unsigned long long k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+    unsigned long long k[4] = {0, 0, 0, 0};          // the best of |gx|, |gy|, |gx - gy|, |gx + gy|
     bool bad = false;
     int x0 = 0, y0 = 0;
     if (live) {
         x0 = 1 + (int) (blk % nbx) * pot; y0 = 1 + (int) (blk / nbx) * pot;          // x0 + pot - 1 <= w - 2, y0 + pot - 1 <= h - 2: nbx = (w - 2) / pot
-        float b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+        float best[4] = {0, 0, 0, 0};
         for (int c = sub; c < pot * pot; c += G) {
             const int dx = c / pot, dy = c - dx * pot;
             const size_t i = ((size_t) (y0 + dy) * w + (x0 + dx)) * 3;
@@ -41,26 +41,22 @@ __global__ __launch_bounds__(256) void k_ini_gridmax(const float *__restrict__ i
             bad = bad || !isfinite(gx) || !isfinite(gy);
             const float sqgd = gx * gx + gy * gy;
             if (sqgd > TH2) {
-                const float agx = fabsf(gx), agy = fabsf(gy), gxpy = fabsf(gx - gy), gxmy = fabsf(gx + gy);
-                if (agx > b0) { b0 = agx; k0 = gm_key(agx, c); }
-                if (agy > b1) { b1 = agy; k1 = gm_key(agy, c); }
-                if (gxpy > b2) { b2 = gxpy; k2 = gm_key(gxpy, c); }
-                if (gxmy > b3) { b3 = gxmy; k3 = gm_key(gxmy, c); }
+                const float a[4] = {fabsf(gx), fabsf(gy), fabsf(gx - gy), fabsf(gx + gy)};
+#pragma unroll
+                for (int q = 0; q < 4; q++) if (a[q] > best[q]) { best[q] = a[q]; k[q] = argmax_key(a[q], c); }
             }
         }
     }
     for (int o = G >> 1; o > 0; o >>= 1) {          // G divides 64: the butterfly stays inside the block's lanes
-        k0 = max(k0, (unsigned long long) __shfl_xor((long long) k0, o, 64)); k1 = max(k1, (unsigned long long) __shfl_xor((long long) k1, o, 64));
-        k2 = max(k2, (unsigned long long) __shfl_xor((long long) k2, o, 64)); k3 = max(k3, (unsigned long long) __shfl_xor((long long) k3, o, 64));
+#pragma unroll
+        for (int q = 0; q < 4; q++) k[q] = max(k[q], (unsigned long long) __shfl_xor((long long) k[q], o, 64));
     }
     int set = 0;
     if (live && sub == 0) {
-        const int c0 = k0 ? 0x7fffffff - (int) (unsigned) k0 : -1, c1 = k1 ? 0x7fffffff - (int) (unsigned) k1 : -1;
-        const int c2 = k2 ? 0x7fffffff - (int) (unsigned) k2 : -1, c3 = k3 ? 0x7fffffff - (int) (unsigned) k3 : -1;
-        const int cs[4] = {c0, c1, c2, c3};
+        int cs[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const int c = cs[q];
+            const int c = cs[q] = k[q] ? argmax_index(k[q]) : -1;
             if (c < 0) continue;
             bool seen = false;
 #pragma unroll
@@ -71,63 +67,33 @@ __global__ __launch_bounds__(256) void k_ini_gridmax(const float *__restrict__ i
             set++;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) set += __shfl_xor(set, o, 64);
-    const int lane = threadIdx.x & 63;
-    if (lane == 0 && set) atomicAdd(&ctl[FC_COUNT], set);
-    if (__any(bad) && lane == 0) atomicOr(&ctl[FC_FLAGS], 1);
+    set = wave_sum(set);
+    if ((threadIdx.x & 63) == 0 && set) atomicAdd(&ctl[FC_COUNT], set);
+    report_nonfinite(bad, &ctl[FC_FLAGS]);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// the records (:567-603): set pixels per row of the scanned rectangle, their prefix sum, one record per set pixel in raster order
+// the records (:567-603): one record per set pixel of the scanned rectangle in raster order
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ini_rows(const unsigned char *__restrict__ map, int w, int h, int x0, int x1, int y0, int y1, int *__restrict__ rowCount) {
-    const int lane = threadIdx.x & 63, y = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (y >= h) return;
-    int c = 0;
-    if (y >= y0 && y < y1) for (int x = x0 + lane; x < x1; x += 64) c += map[(size_t) y * w + x] != 0;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) rowCount[y] = c;
-}
-
-__global__ __launch_bounds__(256) void k_ini_rowscan(const int *__restrict__ rowCount, int *__restrict__ rowStart, int h, int *__restrict__ ctl) {
-    __shared__ int part[256];
-    const int tid = threadIdx.x, per = (h + 255) / 256, b = min(tid * per, h), e = min(b + per, h);
-    int s = 0;
-    for (int y = b; y < e; y++) s += rowCount[y];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) { int a = 0; for (int i = 0; i < 256; i++) { const int t = part[i]; part[i] = a; a += t; } ctl[FC_TOTAL] = a; }
-    __syncthreads();
-    int off = part[tid];
-    for (int y = b; y < e; y++) { rowStart[y] = off; off += rowCount[y]; }
-}
-
-__global__ __launch_bounds__(256) void k_ini_records(const unsigned char *__restrict__ map, int w, int x0, int x1, int y0, int y1, const int *__restrict__ rowStart, int typeFromMap,
+__global__ __launch_bounds__(256) void k_ini_records(const unsigned char *__restrict__ map, int w, ScanRect r, const int *__restrict__ rowStart, int typeFromMap,
                                                      ldso_init_point_t *__restrict__ rec, float *__restrict__ uv, int cap) {
-    const int lane = threadIdx.x & 63, y = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (y < y0 || y >= y1) return;
-    int base = rowStart[y];
-    for (int xb = x0; xb < x1; xb += 64) {
-        const int x = xb + lane;
-        const int v = x < x1 ? map[(size_t) y * w + x] : 0;
-        const unsigned long long bal = __ballot(v != 0);
-        const int r = base + __popcll(bal & ((1ull << lane) - 1));
-        if (v != 0 && r < cap) {
-            ldso_init_point_t p;
-            p.u = (float) (x + 0.1); p.v = (float) (y + 0.1);          // int + double, then rounded to float (:578-579)
-            p.idepth = 1.0f; p.iR = 1.0f; p.isGood = 1;
-            p.energy[0] = p.energy[1] = 0.0f; p.lastHessian = 0.0f; p.lastHessian_new = 0.0f;
-            p.my_type = typeFromMap ? (float) v : 1.0f;
-            p.outlierTH = 8 * (12.0f * 12.0f);                         // patternNum * setting_outlierTH (Settings.h: 8; Setting.cc: 12 * 12)
-            p.parent = -1; p.parentDist = -1.0f;
+    const int y = raster_row();
+    if (y < r.y0 || y >= r.y1) return;
+    raster_walk(map, w, r.x0, r.x1, y, rowStart, [&](int x, int v, int rank) {
+        if (rank >= cap) return;
+        ldso_init_point_t p;
+        p.u = (float) (x + 0.1); p.v = (float) (y + 0.1);              // int + double, then rounded to float (:578-579)
+        p.idepth = 1.0f; p.iR = 1.0f; p.isGood = 1;
+        p.energy[0] = p.energy[1] = 0.0f; p.lastHessian = 0.0f; p.lastHessian_new = 0.0f;
+        p.my_type = typeFromMap ? (float) v : 1.0f;
+        p.outlierTH = 8 * (12.0f * 12.0f);                             // patternNum * setting_outlierTH (Settings.h: 8; Setting.cc: 12 * 12)
+        p.parent = -1; p.parentDist = -1.0f;
 #pragma unroll
-            for (int q = 0; q < 10; q++) { p.neighbours[q] = -1; p.neighboursDist[q] = 0.0f; }
-            LDSO_INIT_POINT_FILL_UNSET(p);
-            rec[r] = p;
-            uv[2 * r] = p.u; uv[2 * r + 1] = p.v;
-        }
-        base += __popcll(bal);
-    }
+        for (int q = 0; q < 10; q++) { p.neighbours[q] = -1; p.neighboursDist[q] = 0.0f; }
+        LDSO_INIT_POINT_FILL_UNSET(p);
+        rec[rank] = p;
+        uv[2 * rank] = p.u; uv[2 * rank + 1] = p.v;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -201,7 +167,7 @@ static int pixel_status(ldso_initializer *H, const float *img, int wl, int hl, f
         if (H->sparsity < 1) H->sparsity = 1;                          // :230
         const int pot = H->sparsity;
         const int nbx = wl - 2 >= pot ? (wl - 2) / pot : 0, nby = hl - 2 >= pot ? (hl - 2) / pot : 0;          // blocks at 1 + i * pot < wl - pot
-        const int G = pot <= 1 ? 1 : pot == 2 ? 4 : pot <= 4 ? 16 : 64;
+        const int G = lanes_per_block(pot);
         CHK(hipMemsetAsync(H->d_fctl, 0, 4 * sizeof(int), st));
         CHK(hipMemsetAsync(H->d_status, 0, (size_t) wl * hl, st));
         const long long lanes = (long long) nbx * nby * G;
@@ -228,19 +194,14 @@ static int pixel_status(ldso_initializer *H, const float *img, int wl, int hl, f
 // the raster scan of `map` (wl x hl bytes) into the records of level l; *nOut = numPoints[l]
 static int make_records(ldso_initializer *H, int l, const unsigned char *map, int wl, int hl, int typeFromMap, int *nOut) {
     hipStream_t st = H->stream;
-    const int x0 = 3, x1 = wl - 4, y0 = 3, y1 = hl - 4;          // patternPadding + 1 <= x < wl - patternPadding - 2 (patternPadding = 2, Settings.h:164)
+    const ScanRect r = scan_rect(wl, hl);
+    int n = 0;
     CHK(hipMemsetAsync(H->d_fctl, 0, 4 * sizeof(int), st));
-    hipLaunchKernelGGL(k_ini_rows, dim3((hl + 3) / 4), dim3(256), 0, st, map, wl, hl, x0, x1, y0, y1, H->d_rowCount);
-    hipLaunchKernelGGL(k_ini_rowscan, dim3(1), dim3(256), 0, st, H->d_rowCount, H->d_rowStart, hl, H->d_fctl);
-    CHK(hipGetLastError());
-    int ctl[4] = {0, 0, 0, 0};
-    CHK(hipMemcpyAsync(ctl, H->d_fctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
-    CHK(hipStreamSynchronize(st));
-    const int n = ctl[FC_TOTAL];
+    RUN(raster_count(map, wl, hl, r, H->d_rowCount, H->d_rowStart, H->d_fctl + FC_TOTAL, st, &n));
     *nOut = n;
     if (n > INI_MAX_POINTS || n == 0) return LDSO_OK;                  // the caller refuses both
     RUN(first_reserve(H, l, n));
-    hipLaunchKernelGGL(k_ini_records, dim3((hl + 3) / 4), dim3(256), 0, st, map, wl, x0, x1, y0, y1, H->d_rowStart, typeFromMap, H->d_rec[l], H->d_uv[l], H->recCap[l]);
+    hipLaunchKernelGGL(k_ini_records, raster_grid(hl), dim3(256), 0, st, map, wl, r, H->d_rowStart, typeFromMap, H->d_rec[l], H->d_uv[l], H->recCap[l]);
     CHK(hipGetLastError());
     return LDSO_OK;
 }
@@ -314,7 +275,7 @@ int ldso_init_pixel_status(ldso_initializer_t *H, ldso_pyramid_t *pyr, int lvl, 
     int flags = 0;
     H->statusLvl = lvl;
     RUN(pixel_status(H, pyr->lv[lvl], H->w >> lvl, H->h >> lvl, desired_density, recs_left, th_fac, n_out, passes_out, &flags));
-    if (flags & 1) { ldso_set_error("ldso_init_pixel_status: non-finite gradient"); return LDSO_E_NONFINITE; }
+    if (flags & SEL_FLAG_NONFINITE) { ldso_set_error("ldso_init_pixel_status: non-finite gradient"); return LDSO_E_NONFINITE; }
     return LDSO_OK;
 }
 
@@ -396,7 +357,7 @@ int ldso_init_set_first_frame(ldso_initializer_t *H, const float calib[4], ldso_
             int flags = 0;
             H->statusLvl = l;
             RUN(pixel_status(H, pyr->lv[l], wl, hl, densities[l] * H->w * H->h, 5, 1.0f, nullptr, nullptr, &flags));
-            nonfinite = nonfinite || (flags & 1);
+            nonfinite = nonfinite || (flags & SEL_FLAG_NONFINITE);
         }
         const auto b = clk::now();
         RUN(make_records(H, l, l ? H->d_status : map0, wl, hl, l == 0, &n[l]));

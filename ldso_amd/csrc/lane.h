@@ -1,5 +1,6 @@
 // lane.h — the lane-exchange wrappers of the kernels (wave64): one name for each builtin and for each DPP control word that more than one kernel file uses.
-// A wrapper is the builtin with the float <-> int bit casts around it and nothing else; reductions that add in an order of their own stay with their kernel.
+// A wrapper is the builtin with the float <-> int bit casts around it and nothing else.  A floating-point sum across lanes adds in an order of its own and stays
+// with its kernel; integer sums and maxima do not depend on the order, so their butterflies over the wavefront are here (wave_sum, wave_max).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,3 +22,7 @@ __device__ __forceinline__ float lane_read(float x, int l) { return __builtin_bi
 // ds_bpermute_b32: every lane reads x of the lane its byte address (lane << 2) names
 __device__ __forceinline__ float lane_perm(float x, int byteAddr) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(byteAddr, __builtin_bit_cast(int, x))); }
 __device__ __forceinline__ float lane_shfl(float x, int lane) { return lane_perm(x, lane << 2); }
+// xor butterflies over the 64 lanes, result in every lane
+__device__ __forceinline__ int wave_sum(int x) { for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64); return x; }
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long m) { for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = __shfl_xor(m, o, 64); if (x > m) m = x; } return m; }
+__device__ __forceinline__ float wave_max(float m) { for (int o = 32; o > 0; o >>= 1) { const float x = __shfl_xor(m, o, 64); if (x > m) m = x; } return m; }          // a NaN never wins

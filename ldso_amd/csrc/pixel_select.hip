@@ -6,14 +6,14 @@
 //   k_pix_hist     one workgroup per 32 x 32 cell: 50-bin integer histogram of int(sqrtf(absSquaredGrad[0])) in LDS (integer atomics), quantile -> ths
 //   k_pix_smooth   one lane per cell: thsSmoothed = square of the 3 x 3 mean, summed in the reference's order (:67-108)
 //   k_pix_masks    per pot block a 16-bit mask: under which of the 16 directions does the block select at level 1 (a pixel passes the threshold AND its score
-//                  |g . dir| is > 0)?  L lanes share a block (L = 1, 4, 16, 64 by pot), an OR across them; masks are stored in the reference's NESTED order
+//                  |g . dir| is > 0)?  L = lanes_per_block(pot) lanes share a block, an OR across them; masks are stored in the reference's NESTED order
 //   k_pix_scan     one wavefront: n2 (level-1 selections so far, :215/:224/:233) at every pot block, 64 blocks per step.  A step whose masks are all 0 or
 //                  0xffff is a ballot; otherwise the 64 blocks are resolved one after another on scalar registers, the next 64 pattern bytes held in a vector
 //                  register.  Output: the direction index randomPattern[n2] & 15 of every pot block
 //   k_pix_select   one wavefront per 4 pot block: the three rules of select with the directions known; a pot / 2 pot / 4 pot block of any size is walked
 //                  by the 64 lanes (nothing is staged in LDS), the winner is a 64-bit integer maximum of (score bits, first in the reference's order)
-//   k_pix_rows / k_pix_rowscan / k_pix_thin / k_pix_points   raster rank of the selected pixels (per-row counts, one prefix sum, ballots inside a row):
-//                  the thinning of :150-163 and the records of FullSystem.cc:1290-1303
+//   k_pix_thin / k_pix_points   the thinning of :150-163 and the records of FullSystem.cc:1290-1303, each one statement per selected pixel in raster rank
+//                  order: the rank (per-row counts, one prefix sum, ballots inside a row) is the raster scan of raster_scan.h
 //
 // select decomposes because bestVal2 is reset per pot block, a 2 pot block reaches its level-2 result only if none of its pot blocks selected, and a 4 pot
 // block its level-3 result only if nothing inside selected; the one sequential quantity is n2.  Every float expression keeps the reference's operand order
@@ -21,8 +21,8 @@
 // absSquaredGrad[2] is 0, sizes that are no multiples of 32 are refused, a non-finite pixel gives LDSO_E_NONFINITE (and never wins a comparison).
 #include "ba_host.h"
 #include "immature_record.h"
+#include "raster_scan.h"
 
-#define PIX_FLAG_NONFINITE 1
 #define PIX_RP_LDS 65536                // bytes of the random pattern k_pix_scan stages in LDS
 enum { PIX_FLAGS = 0, PIX_N2 = 1, PIX_N3 = 2, PIX_N4 = 3, PIX_REMOVED = 4, PIX_TOTAL = 5, PIX_SCAN_N2 = 6 };
 
@@ -34,7 +34,7 @@ struct PixArgs {
     float cut, add, dw1, thFactor; int sdd;
     int pot, nbx, nby;
     unsigned short *mask; unsigned char *dir, *map;
-    int32_t *rowCount, *rowStart, *ctl;
+    int32_t *rowStart, *ctl;
 };
 
 // select's 16 directions (:185-201), converted from the same double literals
@@ -51,28 +51,6 @@ static __host__ __device__ inline int pix_order(int bx, int by, int nbx, int nby
     return Y4 * 4 * nbx + X4 * 4 * cy + y2 * 2 * cx + x2 * 2 * c2y + (ly & 1) * c2x + (lx & 1);
 }
 
-// absSquaredGrad[lvl][i] (FrameHessian.cc:91-96)
-static __device__ __forceinline__ float pix_ag(const float *img, size_t i, const float *B, bool &bad, float &dx, float &dy) {
-    const float *px = img + 3 * i;
-    const float I = px[0];
-    dx = px[1]; dy = px[2];
-    if (!isfinite(I) || !isfinite(dx) || !isfinite(dy)) bad = true;
-    float d = dx * dx + dy * dy;
-    if (B) {
-        int c = isfinite(I) ? (int) (I + 0.5f) : 5;                // CalibHessian::getBGradOnly (CalibHessian.h:102-111)
-        if (c < 5) c = 5;
-        if (c > 250) c = 250;
-        const float gw = B[c + 1] - B[c];
-        d *= gw * gw;
-    }
-    return d;
-}
-
-static __device__ __forceinline__ unsigned long long pix_wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = __shfl_xor(v, o, 64); if (x > v) v = x; }
-    return v;
-}
-
 // makeHists :47-65
 __global__ __launch_bounds__(256) void k_pix_hist(PixArgs A) {
     __shared__ int hist[64];
@@ -83,14 +61,14 @@ __global__ __launch_bounds__(256) void k_pix_hist(PixArgs A) {
     for (int p = tid; p < 1024; p += 256) {
         const int it = (p & 31) + 32 * cx, jt = (p >> 5) + 32 * cy;
         float dx, dy;
-        const float ag = pix_ag(A.lv[0], (size_t) jt * w + it, A.B, bad, dx, dy);
+        const float ag = abs_sq_grad(A.lv[0] + 3 * ((size_t) jt * w + it), A.B, bad, dx, dy);
         if (it > w - 2 || jt > h - 2 || it < 1 || jt < 1) continue;
         const float s = __fsqrt_rn(ag);
         const int g = s < 48.0f ? (int) s : 48;                    // `if (g > 48) g = 48`; a NaN lands here too
         atomicAdd(&hist[g + 1], 1);
     }
     __syncthreads();
-    if (__any(bad) && (tid & 63) == 0) atomicOr(&A.ctl[PIX_FLAGS], PIX_FLAG_NONFINITE);
+    report_nonfinite(bad, &A.ctl[PIX_FLAGS]);
     if (tid == 0) {
         int total = 0;
         for (int i = 1; i < 50; i++) total += hist[i];
@@ -130,7 +108,7 @@ __global__ __launch_bounds__(256) void k_pix_smooth(PixArgs A) {
 // the pixels select never looks at (:242)
 static __device__ __forceinline__ bool pix_outside(int xf, int yf, int w, int h) { return xf < 4 || xf >= w - 5 || yf < 4 || yf > h - 4; }
 
-// L lanes per pot block (L a power of two up to 64; 256 / L blocks per workgroup)
+// L = lanes_per_block(pot) lanes per pot block (256 / L blocks per workgroup)
 __global__ __launch_bounds__(256) void k_pix_masks(PixArgs A, int L) {
     const long long gid = (long long) blockIdx.x * 256 + threadIdx.x;
     const int b = (int) (gid / L), sub = (int) (gid % L), w = A.w, h = A.h, pot = A.pot;
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(256) void k_pix_masks(PixArgs A, int L) {
             if (pix_outside(xf, yf, w, h)) continue;
             const float th0 = A.thsSmoothed[(xf >> 5) + (yf >> 5) * A.w32];
             float dx, dy;
-            const float ag0 = pix_ag(A.lv[0], (size_t) yf * w + xf, A.B, bad, dx, dy);
+            const float ag0 = abs_sq_grad(A.lv[0] + 3 * ((size_t) yf * w + xf), A.B, bad, dx, dy);
             if (ag0 > th0 * A.thFactor) {
                 if (!A.sdd) { if (ag0 > 0) m = 0xffffu; }
                 else for (int d = 0; d < 16; d++) if (fabsf(dx * PIX_DX[d] + dy * PIX_DY[d]) > 0) m |= 1u << d;
@@ -154,7 +132,7 @@ __global__ __launch_bounds__(256) void k_pix_masks(PixArgs A, int L) {
     }
     for (int o = L >> 1; o > 0; o >>= 1) m |= (unsigned) __shfl_xor((int) m, o, 64);
     if (valid && sub == 0) A.mask[pix_order(bx, by, A.nbx, A.nby)] = (unsigned short) m;
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&A.ctl[PIX_FLAGS], PIX_FLAG_NONFINITE);
+    report_nonfinite(bad, &A.ctl[PIX_FLAGS]);
 }
 
 // One workgroup; all of it stages the head of the random pattern in LDS, then wavefront 0 walks the pot blocks in the reference's order, 64 per step.
@@ -196,6 +174,7 @@ __global__ __launch_bounds__(1024) void k_pix_scan(PixArgs A, int NB, int rpn) {
 }
 
 // candidate key: larger score first, then the earlier place in the reference's order; 0 = none (scores are > 0, so their bits order as integers)
+// (not select_dev.h's argmax_key: `order` is an unsigned place running across the pot blocks of a 4 pot block, biased by 0xffffffff)
 static __device__ __forceinline__ unsigned long long pix_key(float s, unsigned order) { return ((unsigned long long) (unsigned) __float_as_int(s) << 32) | (0xffffffffu - order); }
 
 // one wavefront per 4 pot block (:209-311)
@@ -243,20 +222,20 @@ __global__ __launch_bounds__(256) void k_pix_select(PixArgs A) {
                     const float pixelTH1 = pixelTH0 * dw1;
                     const float pixelTH2 = pixelTH1 * dw2;
                     float dx, dy, ex, ey;
-                    const float ag0 = pix_ag(A.lv[0], (size_t) idx, A.B, bad, dx, dy);
+                    const float ag0 = abs_sq_grad(A.lv[0] + 3 * (size_t) idx, A.B, bad, dx, dy);
                     if (sel1 && ag0 > pixelTH0 * thF) {
                         const float s = A.sdd ? fabsf(dx * d2x + dy * d2y) : ag0;
                         if (s > 0) { const unsigned long long k = pix_key(s, (unsigned) p); if (k > best2) { best2 = k; idx2 = idx; } }
                     }
                     if (need2) {
-                        const float ag1 = pix_ag(A.lv[1], (size_t) ((int) (xf * 0.5f + 0.25f) + (int) (yf * 0.5f + 0.25f) * A.w1), A.B, bad, ex, ey);
+                        const float ag1 = abs_sq_grad(A.lv[1] + 3 * (size_t) ((int) (xf * 0.5f + 0.25f) + (int) (yf * 0.5f + 0.25f) * A.w1), A.B, bad, ex, ey);
                         if (ag1 > pixelTH1 * thF) {
                             const float s = A.sdd ? fabsf(dx * d3x + dy * d3y) : ag1;
                             if (s > 0) { const unsigned long long k = pix_key(s, ord + (unsigned) p); if (k > best3) { best3 = k; idx3 = idx; } }
                         }
                     }
                     if (need3) {
-                        const float ag2 = pix_ag(A.lv[2], (size_t) ((int) (xf * 0.25f + 0.125) + (int) (yf * 0.25f + 0.125) * A.w2), A.B, bad, ex, ey);
+                        const float ag2 = abs_sq_grad(A.lv[2] + 3 * (size_t) ((int) (xf * 0.25f + 0.125) + (int) (yf * 0.25f + 0.125) * A.w2), A.B, bad, ex, ey);
                         if (ag2 > pixelTH2 * thF) {
                             const float s = A.sdd ? fabsf(dx * d4x + dy * d4y) : ag2;
                             if (s > 0) { const unsigned long long k = pix_key(s, ord + (unsigned) p); if (k > best4) { best4 = k; idx4 = idx; } }
@@ -264,80 +243,44 @@ __global__ __launch_bounds__(256) void k_pix_select(PixArgs A) {
                     }
                 }
                 if (sel1) {
-                    const unsigned long long top = pix_wave_max(best2);
+                    const unsigned long long top = wave_max(best2);
                     if (top != 0 && top == best2) { A.map[idx2] = 1; atomicAdd(&A.ctl[PIX_N2], 1); }
                 }
             }
             ord += (unsigned) np;
         }
         if (need2) {
-            const unsigned long long top = pix_wave_max(best3);
+            const unsigned long long top = wave_max(best3);
             if (top != 0) any2 = true;
             if (top != 0 && top == best3) { A.map[idx3] = 2; atomicAdd(&A.ctl[PIX_N3], 1); }
         }
     }
     if (need3 && !any2) {
-        const unsigned long long top = pix_wave_max(best4);
+        const unsigned long long top = wave_max(best4);
         if (top != 0 && top == best4) { A.map[idx4] = 4; atomicAdd(&A.ctl[PIX_N4], 1); }
     }
-    if (__any(bad) && lane == 0) atomicOr(&A.ctl[PIX_FLAGS], PIX_FLAG_NONFINITE);
-}
-
-// selected pixels per row inside [x0, x1) x [y0, y1): one wavefront per row
-__global__ __launch_bounds__(256) void k_pix_rows(PixArgs A, int x0, int x1, int y0, int y1) {
-    const int lane = threadIdx.x & 63, y = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (y >= A.h) return;
-    int c = 0;
-    if (y >= y0 && y < y1) for (int x = x0 + lane; x < x1; x += 64) c += A.map[(size_t) y * A.w + x] != 0;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) A.rowCount[y] = c;
-}
-
-// one workgroup of 256: exclusive prefix sum of the rows' counts
-__global__ __launch_bounds__(256) void k_pix_rowscan(PixArgs A) {
-    __shared__ int part[256];
-    const int tid = threadIdx.x, per = (A.h + 255) / 256, b = min(tid * per, A.h), e = min(b + per, A.h);
-    int s = 0;
-    for (int y = b; y < e; y++) s += A.rowCount[y];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) { int a = 0; for (int i = 0; i < 256; i++) { const int t = part[i]; part[i] = a; a += t; } A.ctl[PIX_TOTAL] = a; }
-    __syncthreads();
-    int off = part[tid];
-    for (int y = b; y < e; y++) { A.rowStart[y] = off; off += A.rowCount[y]; }
+    report_nonfinite(bad, &A.ctl[PIX_FLAGS]);
 }
 
 // makeMaps :150-163: the selected pixel of raster rank rn goes when randomPattern[rn] > charTH
 __global__ __launch_bounds__(256) void k_pix_thin(PixArgs A, int charTH) {
-    const int lane = threadIdx.x & 63, y = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int y = raster_row();
     if (y >= A.h) return;
-    int base = A.rowStart[y], gone = 0;
-    for (int xb = 0; xb < A.w; xb += 64) {
-        const int x = xb + lane;
-        const bool on = x < A.w && A.map[(size_t) y * A.w + x] != 0;
-        const unsigned long long bal = __ballot(on);
-        if (on && (int) A.rp[base + __popcll(bal & ((1ull << lane) - 1))] > charTH) { A.map[(size_t) y * A.w + x] = 0; gone++; }
-        base += __popcll(bal);
-    }
-    for (int o = 32; o > 0; o >>= 1) gone += __shfl_xor(gone, o, 64);
-    if (lane == 0 && gone) atomicAdd(&A.ctl[PIX_REMOVED], gone);
+    int gone = 0;
+    raster_walk(A.map, A.w, 0, A.w, y, A.rowStart, [&](int x, int, int rank) { if ((int) A.rp[rank] > charTH) { A.map[(size_t) y * A.w + x] = 0; gone++; } });
+    gone = wave_sum(gone);
+    if ((threadIdx.x & 63) == 0 && gone) atomicAdd(&A.ctl[PIX_REMOVED], gone);
 }
 
 // FullSystem.cc:1290-1303: one record per selected pixel of the scanned rectangle, in raster order; my_type = the map value
-__global__ __launch_bounds__(256) void k_pix_points(PixArgs A, int x0, int x1, int y0, int y1, int hostIndex, ldso_immature_t *imm, float *type, int cap) {
-    const int lane = threadIdx.x & 63, y = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (y < y0 || y >= y1) return;
-    int base = A.rowStart[y];
+__global__ __launch_bounds__(256) void k_pix_points(PixArgs A, ScanRect r, int hostIndex, ldso_immature_t *imm, float *type, int cap) {
+    const int y = raster_row();
+    if (y < r.y0 || y >= r.y1) return;
     bool bad = false;
-    for (int xb = x0; xb < x1; xb += 64) {
-        const int x = xb + lane;
-        const int v = x < x1 ? A.map[(size_t) y * A.w + x] : 0;
-        const unsigned long long bal = __ballot(v != 0);
-        const int r = base + __popcll(bal & ((1ull << lane) - 1));
-        if (v != 0 && r < cap) { imm[r] = imm_record(A.lv[0], (float) x, (float) y, A.w, A.h, hostIndex, bad); type[r] = (float) v; }
-        base += __popcll(bal);
-    }
-    if (__any(bad) && lane == 0) atomicOr(&A.ctl[PIX_FLAGS], PIX_FLAG_NONFINITE);
+    raster_walk(A.map, A.w, r.x0, r.x1, y, A.rowStart, [&](int x, int v, int rank) {
+        if (rank < cap) { imm[rank] = imm_record(A.lv[0], (float) x, (float) y, A.w, A.h, hostIndex, bad); type[rank] = (float) v; }
+    });
+    report_nonfinite(bad, &A.ctl[PIX_FLAGS]);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -369,7 +312,7 @@ static PixArgs pix_args(const ldso_pixsel *P, const ldso_pyramid *pyr, int pot, 
     A.cut = P->cut; A.add = P->add; A.dw1 = P->dw1; A.thFactor = thFactor; A.sdd = P->sdd;
     A.pot = pot; A.nbx = (P->w + pot - 1) / pot; A.nby = (P->h + pot - 1) / pot;
     A.mask = P->d_mask; A.dir = P->d_dir; A.map = P->d_map;
-    A.rowCount = P->d_rowCount; A.rowStart = P->d_rowStart; A.ctl = P->d_ctl;
+    A.rowStart = P->d_rowStart; A.ctl = P->d_ctl;
     return A;
 }
 
@@ -497,7 +440,7 @@ int ldso_pixsel_make_maps(ldso_pixsel_t *P, ldso_pyramid_t *pyr, float density, 
     int act = 0, ideal = pot, charTH = -1, counts[3] = {0, 0, 0};
     for (bool first = true;; first = false) {
         A = pix_args(P, pyr, pot, th_factor);
-        const int NB = A.nbx * A.nby, L = pot <= 1 ? 1 : pot == 2 ? 4 : pot <= 4 ? 16 : 64;
+        const int NB = A.nbx * A.nby, L = lanes_per_block(pot);
         if (!first) { CHK(hipMemsetAsync(P->d_ctl + PIX_N2, 0, 3 * 4, st)); if (prof) CHK(hipEventRecord(P->ev[1], st)); }
         CHK(hipMemsetAsync(P->d_map, 0, wh, st));
         hipLaunchKernelGGL(k_pix_masks, dim3((unsigned) (((long long) NB * L + 255) / 256)), dim3(256), 0, st, A, L);
@@ -522,9 +465,8 @@ int ldso_pixsel_make_maps(ldso_pixsel_t *P, ldso_pyramid_t *pyr, float density, 
     int n = counts[0] + counts[1] + counts[2];
     if (charTH >= 0 && n > 0) {
         if (prof) CHK(hipEventRecord(P->ev[3], st));
-        hipLaunchKernelGGL(k_pix_rows, dim3((P->h + 3) / 4), dim3(256), 0, st, A, 0, P->w, 0, P->h);
-        hipLaunchKernelGGL(k_pix_rowscan, dim3(1), dim3(256), 0, st, A);
-        hipLaunchKernelGGL(k_pix_thin, dim3((P->h + 3) / 4), dim3(256), 0, st, A, charTH);
+        RUN(raster_count(P->d_map, P->w, P->h, ScanRect{0, P->w, 0, P->h}, P->d_rowCount, P->d_rowStart, P->d_ctl + PIX_TOTAL, st, nullptr));          // the whole image; no total on the host
+        hipLaunchKernelGGL(k_pix_thin, raster_grid(P->h), dim3(256), 0, st, A, charTH);
         CHK(hipGetLastError());
         if (prof) CHK(hipEventRecord(P->ev[4], st));
         CHK(hipMemcpyAsync(ctl, P->d_ctl, 8 * 4, hipMemcpyDeviceToHost, st));
@@ -537,7 +479,7 @@ int ldso_pixsel_make_maps(ldso_pixsel_t *P, ldso_pyramid_t *pyr, float density, 
     if (n_out) *n_out = n;
     if (counts_out) for (int i = 0; i < 3; i++) counts_out[i] = counts[i];
     if (potential_used) *potential_used = pot;
-    if (flags & PIX_FLAG_NONFINITE) { ldso_set_error("ldso_pixsel_make_maps: non-finite pixel"); return LDSO_E_NONFINITE; }
+    if (flags & SEL_FLAG_NONFINITE) { ldso_set_error("ldso_pixsel_make_maps: non-finite pixel"); return LDSO_E_NONFINITE; }
     return LDSO_OK;
 }
 
@@ -567,17 +509,12 @@ int ldso_pixsel_make_points(ldso_pixsel_t *P, ldso_pyramid_t *pyr, int host_inde
     hipStream_t st = P->stream;
     RUN(pyramid_wait(pyr, P->device, P->w, P->h, 1, st, "ldso_pixsel_make_points", "the selector (device, size)"));
     PixArgs A = pix_args(P, pyr, 1, 1.0f);
-    const int x0 = 3, x1 = P->w - 4, y0 = 3, y1 = P->h - 4;          // patternPadding + 1 <= x < w - patternPadding - 2 (patternPadding = 2, Settings.h:164)
+    const ScanRect r = scan_rect(P->w, P->h);
     const bool prof = P->profile;
     CHK(hipMemsetAsync(P->d_ctl, 0, 8 * 4, st));
     if (prof) CHK(hipEventRecord(P->ev[4], st));
-    hipLaunchKernelGGL(k_pix_rows, dim3((P->h + 3) / 4), dim3(256), 0, st, A, x0, x1, y0, y1);
-    hipLaunchKernelGGL(k_pix_rowscan, dim3(1), dim3(256), 0, st, A);
-    CHK(hipGetLastError());
-    int ctl[8] = {0};
-    CHK(hipMemcpyAsync(ctl, P->d_ctl, 8 * 4, hipMemcpyDeviceToHost, st));
-    CHK(hipStreamSynchronize(st));
-    const int n = ctl[PIX_TOTAL];
+    int n = 0, ctl[8] = {0};
+    RUN(raster_count(P->d_map, P->w, P->h, r, P->d_rowCount, P->d_rowStart, P->d_ctl + PIX_TOTAL, st, &n));
     if (n > P->cap) {                                              // the record buffers grow to what a call needs
         (void) hipFree(P->d_imm); (void) hipFree(P->d_type);
         P->d_imm = nullptr; P->d_type = nullptr; P->cap = 0;
@@ -588,7 +525,7 @@ int ldso_pixsel_make_points(ldso_pixsel_t *P, ldso_pyramid_t *pyr, int host_inde
     }
     P->n = 0;
     if (n > 0) {
-        hipLaunchKernelGGL(k_pix_points, dim3((P->h + 3) / 4), dim3(256), 0, st, A, x0, x1, y0, y1, host_index, P->d_imm, P->d_type, P->cap);
+        hipLaunchKernelGGL(k_pix_points, raster_grid(P->h), dim3(256), 0, st, A, r, host_index, P->d_imm, P->d_type, P->cap);
         CHK(hipGetLastError());
     }
     if (prof) CHK(hipEventRecord(P->ev[5], st));
@@ -597,7 +534,7 @@ int ldso_pixsel_make_points(ldso_pixsel_t *P, ldso_pyramid_t *pyr, int host_inde
     if (prof) { float ms = 0; CHK(hipEventElapsedTime(&ms, P->ev[4], P->ev[5])); P->us[4] = ms * 1e3f; }
     P->n = n;
     if (n_out) *n_out = n;
-    if (ctl[PIX_FLAGS] & PIX_FLAG_NONFINITE) { ldso_set_error("ldso_pixsel_make_points: non-finite colour"); return LDSO_E_NONFINITE; }
+    if (ctl[PIX_FLAGS] & SEL_FLAG_NONFINITE) { ldso_set_error("ldso_pixsel_make_points: non-finite colour"); return LDSO_E_NONFINITE; }
     return LDSO_OK;
 }
 

@@ -9,6 +9,7 @@
 // short Gauss-Newton refinement (<= 3 iterations of 8 samples) and the scalar bookkeeping run uniformly in all lanes.
 // Memory: per point 128 B record in / out + 4-byte taps of the level-0 image along the epipolar line (L2 resident).
 #include "ba_host.h"
+#include "lane.h"
 
 struct TraceArgs {
     ldso_immature_t *pts;
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_move(CompactArgs A) {
     // the workgroups in front of this one, and all of them
     int before = 0, total = 0;
     for (int j = tid; j < nBlocks; j += CMP_THREADS) { const int c = A.blockCount[j]; total += c; if (j < (int) blockIdx.x) before += c; }
-    for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o, 64); total += __shfl_xor(total, o, 64); }
+    before = wave_sum(before); total = wave_sum(total);
     const int i = blockIdx.x * CMP_THREADS + tid;
     const bool keep = i < A.n && A.flag[i] != 0;
     const unsigned long long bm = __ballot(keep);

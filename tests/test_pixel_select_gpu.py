@@ -88,6 +88,32 @@ def test_two_calls_are_byte_identical():
         R.close()
 
 
+def test_raster_scan_two_rows_per_thread():
+    """96 x 288: the row scan's 256 threads own two rows each (per = 2) and the threads from 144 on own none; the scanned columns 3..91 take two 64-column
+    steps, the second one ragged.  The map's equality with the reference is the fixture cases' business; here the records are checked against the device's own
+    map, and the thinning against its own count."""
+    w, h, pot = 96, 288, 3
+    sel = binding.PixelSelector(w, h, np.random.default_rng(5).integers(0, 256, w * h).astype(np.uint8))
+    pyr = binding.Pyramid(w, h, 3).make_images(pc.steps_image(w, h).astype(np.float32))
+    try:
+        sel.potential = pot
+        n, counts, used = sel.make_maps(pyr, 1e6, 0)          # quotia >= 0.95: nothing is thinned
+        m = sel.get_map()
+        assert used == pot and n == sum(counts) == (m != 0).sum()
+        k = sel.make_points(pyr, 0)
+        q, t = sel.get_points()
+        vu = np.argwhere(m[3:h - 4, 3:w - 4] != 0) + 3          # raster order
+        assert k == len(q) == len(vu)
+        u, v = q["u"].astype(np.int64), q["v"].astype(np.int64)
+        assert np.array_equal(q["u"], vu[:, 1].astype(np.float32)) and np.array_equal(q["v"], vu[:, 0].astype(np.float32)) and np.array_equal(t, m[vu[:, 0], vu[:, 1]])
+        assert (v >= 256).any() and ((v >= 257) & (v % 2 == 1)).any() and (u < 67).any() and (u >= 67).any()
+        sel.potential = pot
+        n2, counts2, _ = sel.make_maps(pyr, 0.6 * sum(counts), 0)          # quotia = 0.6: thinned, no recursion
+        assert counts2 == counts and 0 < n2 < sum(counts) and (sel.get_map() != 0).sum() == n2
+    finally:
+        sel.close(); pyr.close()
+
+
 def test_append_points_device():
     R = Run("natural")
     try:
