@@ -1,6 +1,8 @@
-"""Record tests/golden/ref_init_first.npz from the LDSO sources' own CoarseInitializer::setFirst, makePixelStatus and CoarseInitializer::makeNN.
+"""Record tests/golden/ref_init_first.npz, or with --large tests/golden/ref_init_first_large.npz (setFirst on the 384 x 320 frame, the other file is left alone),
+from the LDSO sources' own CoarseInitializer::setFirst, makePixelStatus and CoarseInitializer::makeNN.
 
-    python scripts/golden/make_ref_init_first.py --ref <LDSO source tree> [--time]
+    make -C oracle ref REF=<LDSO source tree>
+    python scripts/golden/make_ref_init_first.py --ref <LDSO source tree> [--large | --time]
 
 scripts/golden/init_first_driver.cc is compiled against the header stand-ins of oracle/ref_shim and linked with the objects `make -C oracle ref` left in
 oracle/_ref (CoarseInitializer.o, PixelSelector2.o, FrameHessian.o ... are among them), in a temporary directory.  Same flags as the pin library: -O2 -msse4.2
@@ -134,11 +136,21 @@ def record_nn(R, ic, uv, key, out):
     return res
 
 
+def binding_depth(uv):
+    """depth of our own k-d tree over uv (the reference's tree does not say its depth)"""
+    from ldso_amd import binding
+    t = binding.NNTree(uv)
+    d = t.depth
+    t.close()
+    return d
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True)
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "ref_init_first.npz"))
+    ap.add_argument("--large", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import feature_detect_common as fc
     import init_first_common as ic
@@ -158,7 +170,7 @@ def main():
         out = {}
         # ---- setFirst on the frames, in one process: the sparsityFactor is carried ------------------------------------------------------------------
         L.if_set_sparsity(C.c_int(5))
-        for name, levels in ic.FRAMES:
+        for name, levels in (ic.FRAMES_LARGE if a.large else ic.FRAMES):
             img = ic.image(name)
             h, w = img.shape
             R = Ref(L, w, h, levels, ic.K4[w])
@@ -171,7 +183,7 @@ def main():
             const = None
             for l, r in enumerate(lv):
                 fl = r["fields"]
-                xy = np.floor(fl[:, :2]).astype(np.uint8)
+                xy = np.floor(fl[:, :2]).astype(np.uint16 if a.large else np.uint8)
                 assert np.array_equal(ic.pos(xy), fl[:, :2]) and n[l] >= 10
                 c8 = np.array([*fl[0, 2:8], fl[0, 9], r["good"][0]], f32)
                 assert np.all(fl[:, 2:8] == fl[0, 2:8]) and np.all(fl[:, 9] == fl[0, 9]) and np.all(r["good"] == 1) and (const is None or np.array_equal(const, c8))
@@ -185,6 +197,16 @@ def main():
                 assert np.array_equal(res[l]["nb"], r["nb"]) and np.array_equal(res[l]["par"], r["par"]) and np.array_equal(res[l]["nbd"], r["nbd"]) and np.array_equal(res[l]["pard"], r["pard"])
             print("setFirst", name, "numPoints", n.tolist(), "sparsity", s0, "->", s1)
             L.if_frame_free(f)
+        if a.large:
+            path = a.out or ic.GOLDEN_LARGE
+            depth = binding_depth(ic.pos(out["first/large_scene/0/xy"]))
+            print("depth of the level-0 tree:", depth)
+            assert depth >= ic.LARGE_MIN_DEPTH
+            np.savez_compressed(path, **out)
+            print(f"{path}: {os.path.getsize(path)} bytes")
+            assert os.path.getsize(path) <= 600 * 1024
+            return
+        a.out = a.out or ic.GOLDEN
         assert int(out["first/scene/meta"][4]) != 5, "the first frame must move the sparsity, or the second one covers no carried value"
         # ---- makePixelStatus cases -----------------------------------------------------------------------------------------------------------------
         found = {}

@@ -1,6 +1,8 @@
-"""Record tests/golden/ref_pixel_select.npz from the LDSO sources' own FrameHessian::makeImages, PixelSelector and ImmaturePoint constructor.
+"""Record tests/golden/ref_pixel_select.npz, or with --large tests/golden/ref_pixel_select_large.npz (the 384 x 320 cases, the other file is left alone), from
+the LDSO sources' own FrameHessian::makeImages, PixelSelector and ImmaturePoint constructor.
 
-    python scripts/golden/make_ref_pixel_select.py --ref <LDSO source tree> [--time]
+    make -C oracle ref REF=<LDSO source tree>
+    python scripts/golden/make_ref_pixel_select.py --ref <LDSO source tree> [--large | --time]
 
 scripts/golden/pixel_select_driver.cc is compiled against the header stand-ins of oracle/ref_shim and linked with the objects `make -C oracle ref` left in
 oracle/_ref (PixelSelector2.o, FrameHessian.o, ImmaturePoint.o ... are among them), in a temporary directory.  Same flags as the pin library: -O2 -msse4.2
@@ -120,7 +122,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True)
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "ref_pixel_select.npz"))
+    ap.add_argument("--large", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import feature_detect_common as fc
     import pixel_select_common as pc
@@ -139,14 +142,15 @@ def main():
         B = fc.bent_response()
         out["B"] = B
 
-        def record(R, name, calls, settings=pc.DEFAULT_SETTINGS):
-            """calls: list of (image name, potential to set or 0, density or (pot, lo, hi) for density_for, recursions_left, th_factor, response)"""
+        def record(R, name, calls, settings=pc.DEFAULT_SETTINGS, large=False, before=None):
+            """calls: list of (image name, potential to set or 0, density or (pot, lo, hi) for density_for, recursions_left, th_factor, response)
+            large: the layout and the properties of pc.LARGE_CASES (one call each); before: the unthinned map of the same select pass -> returns the call's map"""
             L.ps_settings(p(np.array(settings, f32)))
             s = R.selector()
             out[f"pattern/{R.w}x{R.h}"] = R.pattern(s)
             done = []
             for j, (img, pot0, dens, rec, thf, resp) in enumerate(calls):
-                out["img/" + img] = pc.image(img)
+                out["crc/" + img if large else "img/" + img] = pc.crc(pc.image(img)) if large else pc.image(img)
                 f = R.frame(pc.image(img), B if resp else None)
                 if pot0:
                     L.ps_set_potential(s, C.c_int(pot0))
@@ -158,18 +162,46 @@ def main():
                 k = f"{name}/{j}/"
                 out[k + "image"] = np.array(img); out[k + "args"] = np.array([dens, thf], f32); out[k + "iargs"] = np.array([pot0, rec, int(resp)], np.int32)
                 out[k + "map"] = r["map"].astype(np.uint8); out[k + "out"] = r["out"]; out[k + "ths"] = r["ths"]; out[k + "thsS"] = r["thsS"]
-                out[k + "uv"] = imm[:, :2].astype(np.uint8); out[k + "type"] = typ.astype(np.uint8)
+                out[k + "uv"] = imm[:, :2].astype(np.uint16 if large else np.uint8); out[k + "type"] = typ.astype(np.uint8)
                 assert np.array_equal(out[k + "uv"].astype(f32), imm[:, :2]) and np.array_equal(out[k + "type"].astype(f32), typ)
-                if name in pc.RECORD_CASES:          # the constructor's fields: kept for a few cases, the file stays small
+                if name in pc.RECORD_CASES + pc.LARGE_RECORD_CASES:          # the constructor's fields: kept for a few cases, the file stays small
                     out[k + "imm"] = imm
+                elif large:          # every 101st record: ranks above 65 536 are among them
+                    out[k + "imm_every101"] = imm[::101]
+                    assert np.isfinite(imm).all()
                 assert np.array_equal(out[k + "map"].astype(f32), r["map"]) and set(np.unique(out[k + "map"])) <= {0, 1, 2, 4}
                 done.append(dict(out=r["out"], pot0=start, density=dens, rec=rec, thsS=r["thsS"]))
                 print(name, j, "density", dens, "out", r["out"], "points", len(imm), "quotia", pc.quotia(dens, r["out"][1:4]))
             out[f"{name}/settings"] = np.array(settings, f32)
+            if large:
+                if before is not None:
+                    assert np.array_equal(r["before"], before)
+                pc.check_large_property(name, r["out"], start, dens, r["map"], before, r["thsS"])
+                L.ps_selector_free(s)
+                return r["map"]
             npass = pc.passing_level0(pc.image(calls[0][0]), done[0]["thsS"]) if name == "steps" else None
             pc.check_property(name, done, npass)
             L.ps_selector_free(s)
 
+        if a.large:
+            path = a.out or pc.GOLDEN_LARGE
+            R = Ref(L, pc.LARGE_W, pc.LARGE_H)
+            record(R, "large_stripes_p1", [("stripes", 1, 1e6, 0, 1.0, False)], large=True)
+            unthinned = record(R, "large_mixed_p1", [("stripes_noise", 1, 1e6, 0, 1.0, False)], large=True)
+            record(R, "large_mixed_thinned", [("stripes_noise", 1, (0.5, 0.6), 0, 1.0, False)], large=True, before=unthinned)
+            record(R, "large_natural", [("large_scene", 3, (1.0, 1.2), 1, 1.0, False)], large=True)
+            record(R, "large_recurse", [("large_scene", 3, (1.6, 2.0), 2, 1.0, False)], large=True)
+            del out["B"]
+            for k in out:          # the records column by column on disk (same shape and type when loaded): a column of positions or colours compresses, a row does not
+                if k.endswith(("/uv", "/imm", "/imm_every101")):
+                    out[k] = np.asfortranarray(out[k])
+            assert set(pc.LARGE_CASES) == {k.split("/")[0] for k in out if k.endswith("/settings")} and {k[4:] for k in out if k.startswith("crc/")} == set(pc.LARGE_IMAGES)
+            np.savez_compressed(path, **out)
+            print(f"{path}: {os.path.getsize(path)} bytes")
+            # the pattern (random bytes: 120 KB) and the 23 constructor fields of large_natural's 6163 records (206 KB) do not compress further
+            assert os.path.getsize(path) < 600 * 1024
+            return
+        a.out = a.out or pc.GOLDEN
         R = Ref(L, 160, 96)
         record(R, "natural", [("scene", 3, (1.0, 1.2), 1, 1.0, False)])
         record(R, "recurse_smaller", [("scene", 3, (1.6, 2.0), 1, 1.0, False)])

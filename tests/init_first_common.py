@@ -16,7 +16,10 @@ Keys of the fixture:
   status/{case}/out        int32 [return value, passes, sparsity after]        status/{case}/map    packed bits of the bool map
   plan_in int32 [rows, 3] = n_good, sparsity, recs_left; plan_f float32 [rows, 2] = desired, THFac; plan_out int32 [rows, 2] = action (-1: not visible from
   outside makePixelStatus), sparsityFactor after the first pass
-  nn/{set}/levels          int32 number of levels;  nn/{set}/{l}/xy  uint16 [n, 2];  /nb int16 [n, 10]; /par int16 [n]; /d10, /d1 as above"""
+  nn/{set}/levels          int32 number of levels;  nn/{set}/{l}/xy  uint16 [n, 2];  /nb int16 [n, 10]; /par int16 [n]; /d10, /d1 as above
+
+tests/golden/ref_init_first_large.npz holds the first/... keys of FRAMES_LARGE alone (recorded from sparsityFactor 5), xy as uint16: large_scene, 384 x 320 with 4 levels
+(the coarsest is 48 x 40), whose level-0 tree is deeper than any of the other inputs' (LARGE_MIN_DEPTH)."""
 import functools
 import os
 
@@ -26,9 +29,12 @@ import pixel_select_common as pc
 
 f32 = np.float32
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_init_first.npz")
+GOLDEN_LARGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_init_first_large.npz")
 FRAMES = (("scene", 4), ("scene_flip", 4), ("small", 3))          # (image, levels), recorded in this order
+FRAMES_LARGE = (("large_scene", 4),)
+LARGE_MIN_DEPTH = 10                                              # the deepest tree among FRAMES and NN_SETS is 9
 DENSITIES = (f32(0.03), f32(0.05), f32(0.15), f32(0.5), f32(1))
-K4 = {160: (150.0, 150.0, 79.5, 47.5), 96: (90.0, 90.0, 47.5, 31.5)}
+K4 = {160: (150.0, 150.0, 79.5, 47.5), 96: (90.0, 90.0, 47.5, 31.5), 384: (360.0, 360.0, 191.5, 159.5)}
 # (case, image, level, sparsity before, recsLeft, THFac, what sets the density)
 STATUS_CASES = (
     ("pot1", "scene", 1, 1, 0, 1.0, 400.0), ("pot2", "scene", 1, 2, 0, 1.0, 400.0), ("pot3_clipped", "scene", 2, 3, 0, 1.0, 100.0),
@@ -40,8 +46,8 @@ NN_SETS = ("n10", "n11", "n64", "n65", "row", "column", "grid", "clusters", "par
 
 
 @functools.lru_cache(maxsize=None)
-def golden():
-    return np.load(GOLDEN)
+def golden(path=GOLDEN):
+    return np.load(path)
 
 
 @functools.lru_cache(maxsize=None)
@@ -53,7 +59,7 @@ def image(name):
 
 
 def levels_of(name):
-    return dict(FRAMES).get(name, 3 if image(name).shape[1] == 96 else 4)
+    return dict(FRAMES + FRAMES_LARGE).get(name, 3 if image(name).shape[1] == 96 else 4)
 
 
 def pos(xy):
@@ -136,8 +142,8 @@ def check_status_property(case, w, h, pot0, out, rec, natural_passes):
         assert passes >= 2 and pot0 == 1 and left >= 1, out
 
 
-def load_frame(name):
-    g = golden()
+def load_frame(name, path=GOLDEN):
+    g = golden(path)
     k = f"first/{name}/"
     meta = [int(x) for x in g[k + "meta"]]
     lv = []
@@ -161,6 +167,9 @@ def nn_inputs():
     sets = {}
     for name, _ in FRAMES:
         sets["first/" + name] = ([pos(lv["xy"]) for lv in load_frame(name)["lv"]], load_frame(name)["lv"])
+    for name, _ in FRAMES_LARGE:
+        lv = load_frame(name, GOLDEN_LARGE)["lv"]
+        sets["first/" + name] = ([pos(a["xy"]) for a in lv], lv)
     for name in NN_SETS:
         sets["nn/" + name] = ([pos(a) for a in nn_set(name)], load_nn(name))
     return sets

@@ -59,7 +59,16 @@ def nn_inputs():
     return NN
 
 
-@pytest.mark.parametrize("name", ["first/" + n for n, _ in ic.FRAMES] + ["nn/" + n for n in ic.NN_SETS])
+def test_the_large_frame_is_deeper_than_every_other_input():
+    depth = {name: max(binding.NNTree(a).depth for a in uv) for name, (uv, _) in nn_inputs().items()}
+    large = depth.pop("first/large_scene")
+    assert max(depth.values()) == ic.LARGE_MIN_DEPTH - 1 and large >= ic.LARGE_MIN_DEPTH, (large, depth)
+    r = ic.load_frame("large_scene", ic.GOLDEN_LARGE)
+    assert (r["w"], r["h"], r["levels"], r["sparsity_in"]) == (384, 320, 4, 5) and r["lv"][0]["xy"].dtype == np.uint16
+    assert all(int((lv["xy"][:, 0] >= 256).sum()) > 0 for lv in r["lv"][:1]) and int(r["lv"][0]["xy"][:, 1].max()) >= 256
+
+
+@pytest.mark.parametrize("name", ["first/" + n for n, _ in ic.FRAMES + ic.FRAMES_LARGE] + ["nn/" + n for n in ic.NN_SETS])
 def test_tree_and_host_search_equal_the_reference(name):
     uv, ref = nn_inputs()[name]
     trees = [binding.NNTree(a) for a in uv]

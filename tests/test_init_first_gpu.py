@@ -3,7 +3,8 @@ the fixture recorded from the LDSO sources (tests/golden/ref_init_first.npz, scr
 distances are integers or the result of the same IEEE operations in the same order: exact equality.  The three weight fields (neighboursDist, parentDist) go
 through expf, which neither library rounds correctly (both document at most 1 ulp): two expf results can differ by 2 ulp, their sums by about as much, then one
 division and one multiplication each round - about 6 ulp, so the limit is 1e-6 relative.  The largest deviation seen is printed.
-Shapes: 160 x 96 with 4 levels (the coarsest is 20 x 12) and 96 x 64 with 3."""
+Shapes: 160 x 96 with 4 levels (the coarsest is 20 x 12) and 96 x 64 with 3; one frame of 384 x 320 with 4 levels (tests/golden/ref_init_first_large.npz: the
+selector's 64 KB pattern staging and 320 rows, 4000-6000 records a level, a level-0 tree deeper than 9)."""
 import numpy as np
 import pytest
 
@@ -26,8 +27,8 @@ def make_pyr(img, levels):
     return binding.Pyramid(w, h, max(levels, 3)).make_images(np.ascontiguousarray(img, f32))
 
 
-def selector(w, h):
-    return binding.PixelSelector(w, h, pc.golden()[f"pattern/{w}x{h}"])
+def selector(w, h, path=pc.GOLDEN):
+    return binding.PixelSelector(w, h, pc.golden(path)[f"pattern/{w}x{h}"])
 
 
 @pytest.mark.parametrize("case", [c[0] for c in ic.STATUS_CASES])
@@ -70,7 +71,7 @@ def nn_inputs():
     return NN
 
 
-@pytest.mark.parametrize("name", ["first/" + n for n, _ in ic.FRAMES] + ["nn/" + n for n in ic.NN_SETS])
+@pytest.mark.parametrize("name", ["first/" + n for n, _ in ic.FRAMES + ic.FRAMES_LARGE] + ["nn/" + n for n in ic.NN_SETS])
 def test_make_nn_equals_the_host_search(name):
     uv, ref = nn_inputs()[name]
     ini = binding.Initializer(160, 96, 4)
@@ -98,9 +99,9 @@ def test_make_nn_refuses_a_level_with_fewer_than_10_points():
     ini.close()
 
 
-def check_frame(ini, n, name):
+def check_frame(ini, n, name, path=ic.GOLDEN):
     """every record field of every level against the recorded setFirst; returns the largest relative deviation of the weight fields"""
-    r = ic.load_frame(name)
+    r = ic.load_frame(name, path)
     assert list(n) == [int(x) for x in r["n"]] and ini.sparsity == r["sparsity_out"], (n, r["n"], ini.sparsity, r["sparsity_out"])
     idepth, iR, e0, e1, lh, lhn, oth, good = (float(x) for x in r["const"])
     worst = 0.0
@@ -140,6 +141,26 @@ def test_set_first_frame_equals_the_reference_and_carries_the_sparsity():
     ini.sparsity = ic.load_frame("small")["sparsity_in"]
     pyr = make_pyr(ic.image("small"), 3)
     worst = max(worst, check_frame(ini, ini.set_first_frame(ic.K4[96], pyr, sel), "small"))
+    print("largest relative deviation of neighboursDist / parentDist:", worst)
+    assert worst <= WEIGHT_RTOL
+    ini.close(); sel.close(); pyr.close()
+
+
+def test_set_first_frame_large():
+    """large_scene, 384 x 320 with 4 levels, from the sparsityFactor 5 of a new handle"""
+    w, h = pc.LARGE_W, pc.LARGE_H
+    r = ic.load_frame("large_scene", ic.GOLDEN_LARGE)
+    assert (r["w"], r["h"], r["levels"], r["sparsity_in"]) == (w, h, 4, 5)
+    tree = binding.NNTree(ic.pos(r["lv"][0]["xy"]))
+    print("depth of the level-0 tree:", tree.depth, "records per level:", [int(x) for x in r["n"]])
+    assert tree.depth >= ic.LARGE_MIN_DEPTH          # the search's stack goes deeper than with any other input of the suite
+    tree.close()
+    ini, sel = binding.Initializer(w, h, 4), selector(w, h, pc.GOLDEN_LARGE)
+    assert ini.sparsity == 5
+    pyr = make_pyr(ic.image("large_scene"), 4)
+    n = ini.set_first_frame(ic.K4[w], pyr, sel)
+    assert (sel.get_map()[256:] != 0).any()          # level 0 selects in the rows the row scan's threads reach second
+    worst = check_frame(ini, n, "large_scene", ic.GOLDEN_LARGE)
     print("largest relative deviation of neighboursDist / parentDist:", worst)
     assert worst <= WEIGHT_RTOL
     ini.close(); sel.close(); pyr.close()

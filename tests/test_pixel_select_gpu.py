@@ -1,6 +1,9 @@
 """GPU tests of ldso_amd/csrc/pixel_select.hip: PixelSelector::makeMaps and the points of FullSystem::makeNewTraces (setting_pointSelection == 0) on the device
 against the fixture recorded from the LDSO sources (tests/golden/ref_pixel_select.npz).  Everything compared is an integer or the result of the same IEEE
-operations in the same order: exact equality, no tolerance.  Three-level pyramids of 160 x 96 and 96 x 64."""
+operations in the same order: exact equality, no tolerance.  Three-level pyramids of 160 x 96 and 96 x 64, and of 384 x 320 for pc.LARGE_CASES
+(tests/golden/ref_pixel_select_large.npz): 122 880 bytes of random pattern, of which k_pix_scan stages the first 65 536 in LDS and reads the rest from global
+memory, 320 rows for the row scan's 256 threads, raster ranks above 65 536 in the thinning, record buffers of about 100 000 entries.  Each of those cases has to
+show its property (pc.check_large_property) on the device's own output too, so that a run that never crossed the 64 KB boundary fails."""
 import numpy as np
 import pytest
 
@@ -17,17 +20,19 @@ def bits(a):
 class Run:
     """one selector and the calls of a fixture case on it"""
 
-    def __init__(self, name):
-        self.case = pc.load_case(name)
+    def __init__(self, name, path=pc.GOLDEN):
+        self.case = pc.load_case(name, path)
         h, w = pc.image(self.case["calls"][0]["image"]).shape
         self.w, self.h = w, h
-        self.sel = binding.PixelSelector(w, h, pc.golden()[f"pattern/{w}x{h}"])
+        self.sel = binding.PixelSelector(w, h, pc.golden(path)[f"pattern/{w}x{h}"])
         s = self.case["settings"]
         self.sel.set_settings(float(s[0]), float(s[1]), float(s[2]), bool(s[3]))
         self.pyrs = []
 
-    def call(self, j, host=0):
+    def call(self, j, host=0, density=None):
         c = self.case["calls"][j]
+        if density is not None:
+            c = dict(c, density=density)
         pyr = binding.Pyramid(self.w, self.h, 3).make_images(pc.image(c["image"]).astype(np.float32))
         self.pyrs.append(pyr)
         self.sel.set_response(pc.golden()["B"] if c["response"] else None)
@@ -64,14 +69,25 @@ def check_call(r, c, host=0):
         assert np.array_equal(bits(q["gradH"]).reshape(-1, 4), bits(g[:, 18:22])) and np.array_equal(bits(q["energyTH"]), bits(g[:, 22]))
         assert np.all(q["idepth_min"] == 0) and np.isnan(q["idepth_max"]).all() and np.all(q["quality"] == 10000) and np.all(q["lastTraceStatus"] == 5)
         assert np.all(q["lastTraceUV"] == -1)
+    if c["imm_every101"] is not None:          # every 101st record of a large case
+        g, q = c["imm_every101"], q[::101]
+        assert len(g) == len(q) and np.array_equal(q["u"], g[:, 0]) and np.array_equal(q["v"], g[:, 1])
+        assert np.array_equal(bits(q["color"]), bits(g[:, 2:10])) and np.array_equal(bits(q["weights"]), bits(g[:, 10:18]))
+        assert np.array_equal(bits(q["gradH"]).reshape(-1, 4), bits(g[:, 18:22])) and np.array_equal(bits(q["energyTH"]), bits(g[:, 22]))
 
 
-@pytest.mark.parametrize("name", pc.CASES)
+@pytest.mark.parametrize("name", pc.CASES + pc.LARGE_CASES)
 def test_against_reference_fixture(name):
-    R = Run(name)
+    large = name in pc.LARGE_CASES
+    R = Run(name, pc.GOLDEN_LARGE if large else pc.GOLDEN)
     try:
         for j, c in enumerate(R.case["calls"]):
-            check_call(R.call(j, host=2), c, host=2)
+            r = R.call(j, host=2)
+            if large:          # the case's property on what the device gave, before anything is compared
+                print(name, "device n2", r["counts"][0], "reference n2", int(c["out"][1]), "records", len(r["imm"]), "past the pattern in LDS:", r["counts"][0] - pc.RP_LDS)
+                before = R.call(j, host=2, density=1e6)["map"] if name == "large_mixed_thinned" else None          # the same select pass, nothing thinned
+                pc.check_large_property(name, (r["n"], *r["counts"], r["used"], r["left"]), c["pot0"], c["density"], r["map"], before, r["ths"][1].ravel())
+            check_call(r, c, host=2)
     finally:
         R.close()
 
@@ -83,6 +99,19 @@ def test_two_calls_are_byte_identical():
         b = R.call(0)
         assert a["map"].tobytes() == b["map"].tobytes() and a["imm"].tobytes() == b["imm"].tobytes() and a["type"].tobytes() == b["type"].tobytes()
         assert (a["n"], a["counts"], a["used"], a["left"]) == (b["n"], b["counts"], b["used"], b["left"]) and len(a["imm"]) > 100
+        assert a["ths"][0].tobytes() == b["ths"][0].tobytes() and a["ths"][1].tobytes() == b["ths"][1].tobytes()
+    finally:
+        R.close()
+
+
+def test_two_calls_are_byte_identical_large():
+    """large_mixed_p1: the scan reads the pattern from LDS and from global memory, block by block and by ballot"""
+    R = Run("large_mixed_p1", pc.GOLDEN_LARGE)
+    try:
+        a = R.call(0)
+        b = R.call(0)
+        assert a["map"].tobytes() == b["map"].tobytes() and a["imm"].tobytes() == b["imm"].tobytes() and a["type"].tobytes() == b["type"].tobytes()
+        assert (a["n"], a["counts"], a["used"], a["left"]) == (b["n"], b["counts"], b["used"], b["left"]) and a["counts"][0] >= pc.N2_PAST_LDS
         assert a["ths"][0].tobytes() == b["ths"][0].tobytes() and a["ths"][1].tobytes() == b["ths"][1].tobytes()
     finally:
         R.close()
@@ -134,6 +163,28 @@ def test_append_points_device():
         with pytest.raises(binding.LdsoError) as e:
             tr.set_tail_types_device(len(got) + 1, type_dev)
         assert e.value.code == binding.E_INVALID
+        tr.close()
+    finally:
+        R.close()
+
+
+def test_append_points_device_large():
+    """the records of large_mixed_p1 (about 92 000: the selector's buffer grown far past its first 4096 entries, the tracer's sized to match) appended once"""
+    R = Run("large_mixed_p1", pc.GOLDEN_LARGE)
+    try:
+        r = R.call(0, host=1)
+        win = synth.make_window(F=2, P=50, w=R.w, h=R.h, fx=R.w * 0.6, seed=71)
+        a, _ = synth.make_immature_points(win, 5)
+        n = len(r["imm"])
+        tr = binding.Tracer(R.w, R.h, len(a) + n)
+        tr.set_points(a)
+        imm_dev, type_dev, cnt = R.sel.device_ptrs()
+        assert cnt == n == len(R.case["calls"][0]["uv"]) > pc.RP_LDS and imm_dev and type_dev
+        tr.append_points_device(cnt, imm_dev)
+        got = tr.get_points()
+        assert len(got) == len(a) + n and got.tobytes() == np.concatenate([a, r["imm"]]).tobytes()
+        tr.set_tail_types_device(cnt, type_dev)
+        assert np.array_equal(tr.get_point_types(), np.concatenate([np.ones(len(a), np.float32), r["type"]])) and set(r["type"]) - {1.0}
         tr.close()
     finally:
         R.close()
