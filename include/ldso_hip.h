@@ -280,6 +280,20 @@ int ldso_ba_batch_enqueue_gn(ldso_ba_batch_t *b, int first_iteration, int iters)
  * getters, ldso_ba_get_energy_log, ldso_ba_marginalize_points / _frame and a second ldso_ba_batch_optimize work on it.
  * Beyond ldso_ba_batch_create's conditions: every window has at least 2 key frames and at most 8 (the 8-slot table). */
 int ldso_ba_batch_optimize(ldso_ba_batch_t *b, int mnumOptIts, int force_all_iterations, float *rmse_out /*n*/, int *iterations_out /*n*/, int *status_out /*n*/);
+/* The two steps FullSystem::makeKeyFrame runs right behind optimize(), for every window of the batch, with a number of launches and host <-> device copies that
+ * does not depend on n (three launches for the points, one for the frames; one upload, one download and one host synchronisation each).
+ * ldso_ba_batch_marginalize_points: EnergyFunctional::marginalizePointsF (EnergyFunctional.cc:165-222; FullSystem.cc:527) with the re-linearise + fixLinearizationF
+ * pass of FullSystem::flagPointsForRemoval (FullSystem.cc:1241-1250) - per window exactly what ldso_ba_marginalize_points(handle_i, flags[i], ...) gives: flags[i] holds
+ * P_i entries; the applied state is unchanged, the handle's prior becomes H_M += margWeightFac (M - Msc), b_M += margWeightFac (Mb - Mbsc) (from zero where it had
+ * none) and counts as present from then on, also for the next ldso_ba_batch_optimize / _enqueue_gn.  flags[i] == NULL: window i takes no part - its prior and its
+ * output slots stay untouched.  HM_out / bM_out ((8 F_i + 4)^2 row-major, 8 F_i + 4 doubles): NULL as arrays or per entry where the result is not wanted.
+ * ldso_ba_batch_marginalize_frame: EnergyFunctional::marginalizeFrame (EnergyFunctional.cc:72-151; FullSystem.cc:574-583) - per window exactly what
+ * ldso_ba_marginalize_frame(handle_i, frame_idx[i], HM_out[i], bM_out[i]) gives ((8 (F_i - 1) + 4)^2 row-major, 8 (F_i - 1) + 4 doubles); the handles keep their priors
+ * and windows.  frame_idx[i] < 0: window i takes no part.
+ * Both refuse (LDSO_E_INVALID) a NULL batch, NULL flags / frame_idx, a frame index >= F_i, a window with a pending ldso_ba_linearize_all result, a sharded handle
+ * and windows of more than 8 key frames (the 8-slot table, as ldso_ba_batch_optimize). */
+int ldso_ba_batch_marginalize_points(ldso_ba_batch_t *b, const int32_t *const *flags /*n*/, double *const *HM_out /*n or NULL*/, double *const *bM_out /*n or NULL*/);
+int ldso_ba_batch_marginalize_frame(ldso_ba_batch_t *b, const int32_t *frame_idx /*n*/, double *const *HM_out /*n*/, double *const *bM_out /*n*/);
 int ldso_ba_batch_destroy(ldso_ba_batch_t *b);
 /* points per workgroup ldso_ba_batch_create gave the windows of the batch - since round 6 the AVERAGE, rounded: the cuts are uneven, ldso_ba_get_chunk_cuts has
  * them - (0: their single-window chunking was kept; ldso_ba_batch_destroy restores it) */

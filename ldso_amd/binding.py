@@ -764,6 +764,42 @@ class BABatch:
             _chk(code)
         return rm, it, st
 
+    def _marg_out(self, sizes):
+        """per window (HM, bM) of the given side, or None, and the two pointer arrays the C entries take"""
+        n = len(self.handles)
+        out = [None if k is None else (np.zeros((k, k)), np.zeros(k)) for k in sizes]
+        PH, Pb = (C.c_void_p * n)(), (C.c_void_p * n)()
+        for i, o in enumerate(out):
+            if o is not None:
+                PH[i], Pb[i] = o[0].ctypes.data, o[1].ctypes.data
+        return out, PH, Pb
+
+    def marginalize_points(self, flags_list):
+        """EnergyFunctional::marginalizePointsF for every window of the batch (ldso_ba_batch_marginalize_points): flags_list[i] = the P_i flags of window i,
+        or None for a window that takes no part -> [(HM, bM) or None]"""
+        n = len(self.handles)
+        assert len(flags_list) == n
+        fl = [None if f is None else np.ascontiguousarray(f, np.int32) for f in flags_list]
+        for f, h in zip(fl, self.handles):
+            assert f is None or len(f) == h.P
+        out, PH, Pb = self._marg_out([None if f is None else 8 * h.F + 4 for f, h in zip(fl, self.handles)])
+        PF = (C.c_void_p * n)()
+        for i, f in enumerate(fl):
+            if f is not None:
+                PF[i] = f.ctypes.data
+        _chk(self.L.ldso_ba_batch_marginalize_points(self.h, PF, PH, Pb))
+        return out
+
+    def marginalize_frame(self, idx_list):
+        """EnergyFunctional::marginalizeFrame on the device prior of every window of the batch (ldso_ba_batch_marginalize_frame): idx_list[i] = the frame of
+        window i, or None / -1 for a window that takes no part -> [(HM, bM) of the window without that frame, or None]"""
+        n = len(self.handles)
+        assert len(idx_list) == n
+        idx = np.array([-1 if k is None or k < 0 else int(k) for k in idx_list], np.int32)
+        out, PH, Pb = self._marg_out([None if k < 0 else 8 * (h.F - 1) + 4 for k, h in zip(idx, self.handles)])
+        _chk(self.L.ldso_ba_batch_marginalize_frame(self.h, _p(idx), PH, Pb))
+        return out
+
     def sync(self):
         self.handles[0].sync()
 

@@ -3,6 +3,8 @@
 // independent windows (several agents / sequences / hypotheses) with three launches per iteration for ALL of them: k_reduce_batch
 // (every window's reduce workgroups) -> k_gn_solve_batch (two control workgroups per window) -> k_linearize_batch (every window's
 // chunks).  Per-window arithmetic is exactly that of ldso_ba_enqueue_gn's split schedule; the windows only share the launches.
+// Behind optimize(), the key frame's two marginalisations for the whole batch: k_linearize_batch_marg -> k_reduce_batch_marg -> k_marg_gather_update_batch
+// (ldso_ba_batch_marginalize_points) and k_marg_frame_batch (ldso_ba_batch_marginalize_frame), per window the arithmetic of the single-window entries.
 #include "ba_host.h"
 
 static int batch_refresh(ldso_ba_batch *Bt) {
@@ -259,6 +261,8 @@ int ldso_ba_batch_destroy(ldso_ba_batch_t *Bt) {
     if (Bt->h_scalars) hipHostFree(Bt->h_scalars);
     if (Bt->d_blocks) hipFree(Bt->d_blocks);
     if (Bt->d_wg) hipFree(Bt->d_wg);
+    if (Bt->d_marg) hipFree(Bt->d_marg);
+    if (Bt->h_marg) hipHostFree(Bt->h_marg);
     // back to the single-window chunking (handles that were re-chunked by ldso_ba_batch_create)
     if (Bt->balanced) { for (ldso_ba *H : Bt->h) { H->chunkCuts.clear(); if (H->D.P > 0) rechunk(H); } }
     else if (Bt->chunkPoints > 0) for (ldso_ba *H : Bt->h) if (H->chunkPoints == 0 && H->D.P > 0) rechunk(H);
@@ -369,6 +373,141 @@ int ldso_ba_batch_optimize(ldso_ba_batch_t *Bt, int mnumOptIts, int force_all_it
         if (status_out) status_out[i] = bad ? LDSO_E_NONFINITE : LDSO_OK;
     }
     return rc;
+}
+
+}  // extern "C"
+
+// The staging arena of the two batched marginalisations: `up` bytes go up ([n MargWin | flags]), `down` bytes come down behind them.  Grown on demand; both streams are
+// idle when it is replaced (every user of the arena ends with a wait on the batch's stream).
+static int marg_stage(ldso_ba_batch *Bt, size_t up, size_t down) {
+    const size_t need = up + down;
+    if (need <= Bt->margCap) return LDSO_OK;
+    CHK(hipStreamSynchronize(Bt->h[0]->stream));
+    if (Bt->d_marg) (void) hipFree(Bt->d_marg);
+    if (Bt->h_marg) (void) hipHostFree(Bt->h_marg);
+    Bt->d_marg = nullptr; Bt->h_marg = nullptr; Bt->margCap = 0;
+    const size_t cap = need + need / 2;
+    void *q = nullptr;
+    CHK(hipMalloc(&q, cap));
+    Bt->d_marg = (char *) q;
+    CHK(hipHostMalloc(&q, cap, hipHostMallocDefault));
+    Bt->h_marg = (char *) q;
+    Bt->margCap = cap;
+    return LDSO_OK;
+}
+// what both entries refuse, worded like ldso_ba_batch_optimize; `solo`: the single-window entry the message points to, `part(i)`: does window i take part
+template <class Part> static int marg_checks(ldso_ba_batch *Bt, const char *who, const char *solo, Part part) {
+    const std::string w(who);
+    REQ(Bt->FS == 8, w + ": windows of more than 8 key frames are not supported in a batched marginalisation (every window needs F <= 8): run them with " + solo);
+    for (size_t i = 0; i < Bt->h.size(); i++) {
+        const ldso_ba *H = Bt->h[i];
+        if (!part((int) i)) continue;
+        REQ(H->D.P > 0 && H->D.F >= 2, w + ": a window of the batch is not set");
+        REQ(!H->pendingApply, w + ": a window has a pending linearizeAll result (ldso_ba_apply_res first)");
+        REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, w + ": not available on a sharded handle");
+    }
+    return LDSO_OK;
+}
+
+extern "C" {
+
+// EnergyFunctional::marginalizePointsF (EnergyFunctional.cc:165-222) with the re-linearise + fixLinearizationF pass of FullSystem::flagPointsForRemoval
+// (FullSystem.cc:1241-1250) for every window i of the batch with flags[i] != NULL: per window what ldso_ba_marginalize_points gives on its handle alone.  One
+// upload (the window table and all flags), three launches (k_linearize_batch_marg -> k_reduce_batch_marg -> k_marg_gather_update_batch), one download, one wait,
+// whatever the number of windows.
+int ldso_ba_batch_marginalize_points(ldso_ba_batch_t *Bt, const int32_t *const *flags, double *const *HM_out, double *const *bM_out) {
+    REQ(Bt, "ldso_ba_batch_marginalize_points: null batch");
+    REQ(flags, "ldso_ba_batch_marginalize_points: null flags");
+    RUN(marg_checks(Bt, "ldso_ba_batch_marginalize_points", "ldso_ba_marginalize_points", [&](int i) { return flags[i] != nullptr; }));
+    ldso_ba *H0 = Bt->h[0];
+    const int n = (int) Bt->h.size();
+    CHK(hipSetDevice(H0->device));
+    RUN(batch_refresh(Bt));
+    size_t nFlags = 0, nOut = 0;
+    int red = 0, maxGSP = 0, maxN = 0, taking = 0;
+    std::vector<MargWin> tab((size_t) n);
+    for (int i = 0; i < n; i++) {
+        const ldso_ba *H = Bt->h[i];
+        MargWin &m = tab[(size_t) i];
+        memset(&m, 0, sizeof(m));
+        m.active = flags[i] != nullptr ? 1 : 0; m.flagOff = (int32_t) nFlags; m.frameIdx = -1; m.redBlock0 = red; m.outOff = (int32_t) nOut;
+        if (!m.active) continue;
+        taking++;
+        nFlags += (size_t) H->D.P; nOut += (size_t) H->D.n * H->D.n + H->D.n;
+        red += reduce_pairs(H->D.F, false) + LD_SC_SPLITS;
+        maxGSP = std::max(maxGSP, H->GSP); maxN = std::max(maxN, (int) H->D.n);
+    }
+    if (taking == 0) return LDSO_OK;
+    const size_t up = (n * sizeof(MargWin) + nFlags * sizeof(int32_t) + 7) & ~(size_t) 7, down = nOut * sizeof(double);
+    RUN(marg_stage(Bt, up, down));
+    memcpy(Bt->h_marg, tab.data(), n * sizeof(MargWin));
+    int32_t *h_flags = (int32_t *) (Bt->h_marg + n * sizeof(MargWin));
+    for (int i = 0; i < n; i++) if (tab[(size_t) i].active) memcpy(h_flags + tab[(size_t) i].flagOff, flags[i], (size_t) Bt->h[i]->D.P * sizeof(int32_t));
+    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, up, hipMemcpyHostToDevice, H0->stream));
+    const MargWin *d_mw = (const MargWin *) Bt->d_marg;
+    const int32_t *d_flags = (const int32_t *) (Bt->d_marg + n * sizeof(MargWin));
+    double *d_out = (double *) (Bt->d_marg + up);
+    CHK(ba_launch_linearize_batch_marg(Bt->d_items, Bt->d_blocks, Bt->totalChunks, Bt->balanced ? Bt->d_wg + Bt->wgOff[0] : nullptr, Bt->nWG[0], d_mw, d_flags, H0->settings, H0->stream));
+    CHK(ba_launch_reduce_batch_marg(Bt->d_items, d_mw, n, red, maxGSP, H0->stream));
+    CHK(ba_launch_marg_gather_update_batch(Bt->d_items, d_mw, n, maxN, (double) H0->settings.margWeightFac, d_out, H0->stream));
+    for (int i = 0; i < n; i++) if (tab[(size_t) i].active) Bt->h[i]->hasPrior = true;          // the next batch_refresh / refresh_item hands it to the iteration kernels
+    CHK(hipMemcpyAsync(Bt->h_marg + up, d_out, down, hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipStreamSynchronize(H0->stream));
+    const double *h_out = (const double *) (Bt->h_marg + up);
+    for (int i = 0; i < n; i++) {
+        const MargWin &m = tab[(size_t) i];
+        if (!m.active) continue;
+        const size_t nn = (size_t) Bt->h[i]->D.n;
+        if (HM_out && HM_out[i]) memcpy(HM_out[i], h_out + m.outOff, nn * nn * sizeof(double));
+        if (bM_out && bM_out[i]) memcpy(bM_out[i], h_out + m.outOff + nn * nn, nn * sizeof(double));
+    }
+    return LDSO_OK;
+}
+
+// EnergyFunctional::marginalizeFrame (EnergyFunctional.cc:72-151) on the device prior of every window i of the batch with frame_idx[i] >= 0: per window what
+// ldso_ba_marginalize_frame(handle_i, frame_idx[i], ...) gives ((8(F-1)+4)^2 row-major, 8(F-1)+4); the handles keep their priors and windows.  One upload, one
+// launch (k_marg_frame_batch, a workgroup per window), one download, one wait.
+int ldso_ba_batch_marginalize_frame(ldso_ba_batch_t *Bt, const int32_t *frame_idx, double *const *HM_out, double *const *bM_out) {
+    REQ(Bt, "ldso_ba_batch_marginalize_frame: null batch");
+    REQ(frame_idx, "ldso_ba_batch_marginalize_frame: null frame_idx");
+    RUN(marg_checks(Bt, "ldso_ba_batch_marginalize_frame", "ldso_ba_marginalize_frame", [&](int i) { return frame_idx[i] >= 0; }));
+    ldso_ba *H0 = Bt->h[0];
+    const int n = (int) Bt->h.size();
+    size_t nOut = 0;
+    int taking = 0;
+    std::vector<MargWin> tab((size_t) n);
+    for (int i = 0; i < n; i++) {
+        const ldso_ba *H = Bt->h[i];
+        MargWin &m = tab[(size_t) i];
+        memset(&m, 0, sizeof(m));
+        m.active = frame_idx[i] >= 0 ? 1 : 0; m.frameIdx = frame_idx[i]; m.outOff = (int32_t) nOut;
+        if (!m.active) continue;
+        REQ(frame_idx[i] < H->D.F, "ldso_ba_batch_marginalize_frame: a frame index is not a key frame of its window (frame_idx[i] < F_i)");
+        REQ(HM_out && bM_out && HM_out[i] && bM_out[i], "ldso_ba_batch_marginalize_frame: a window that takes part needs its HM_out[i] and bM_out[i]");
+        taking++;
+        const size_t nd = (size_t) H->D.n - 8;
+        nOut += nd * nd + nd;
+    }
+    if (taking == 0) return LDSO_OK;
+    CHK(hipSetDevice(H0->device));
+    RUN(batch_refresh(Bt));
+    const size_t up = (n * sizeof(MargWin) + 7) & ~(size_t) 7, down = nOut * sizeof(double);
+    RUN(marg_stage(Bt, up, down));
+    memcpy(Bt->h_marg, tab.data(), n * sizeof(MargWin));
+    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, up, hipMemcpyHostToDevice, H0->stream));
+    double *d_out = (double *) (Bt->d_marg + up);
+    CHK(ba_launch_marg_frame_batch(Bt->d_items, n, (const MargWin *) Bt->d_marg, d_out, H0->stream));
+    CHK(hipMemcpyAsync(Bt->h_marg + up, d_out, down, hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipStreamSynchronize(H0->stream));
+    const double *h_out = (const double *) (Bt->h_marg + up);
+    for (int i = 0; i < n; i++) {
+        const MargWin &m = tab[(size_t) i];
+        if (!m.active) continue;
+        const size_t nd = (size_t) Bt->h[i]->D.n - 8;
+        memcpy(HM_out[i], h_out + m.outOff, nd * nd * sizeof(double));
+        memcpy(bM_out[i], h_out + m.outOff + nd * nd, nd * sizeof(double));
+    }
+    return LDSO_OK;
 }
 
 // average duration of the batched k_linearize for bench.py's roofline: `reps` back-to-back launches on the applied state (read set ->

@@ -182,6 +182,12 @@ struct BatchItem {
     int32_t outSlot, pad_;
 };
 
+// One window of a batched marginalisation (ldso_ba_batch_marginalize_points / _frame), beside its BatchItem and apart from it: the layout of a BatchItem is what
+// the three iteration kernels fetch with scalar loads.  active = the window takes part (the workgroups of the others return at once); flagOff = where its flags
+// start in the call's concatenated flag array; frameIdx = the frame ldso_ba_batch_marginalize_frame removes; redBlock0 = its first workgroup in the batched
+// non-atomic reduce (a window that takes no part owns none); outOff = where its (H_M | b_M) goes in the call's staging area, in doubles.
+struct MargWin { int32_t active, flagOff, frameIdx, redBlock0, outOff, pad_[3]; };
+
 // GN fast path: what k_linearize needs to initialise B.acc for the solve that follows it
 struct GnInit {
     int enable, hasPrior;

@@ -38,6 +38,11 @@ hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const Ba
 hipError_t ba_launch_batch_begin(const BatchItem *d_items, int nWin, int mnumOptIts, int forceAll, hipStream_t st);
 hipError_t ba_launch_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, const ldso_settings_t &St, unsigned flags, int phase, double *d_scalarsOut, hipStream_t st);
 hipError_t ba_launch_linearize_batch_fix(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, const ldso_settings_t &S, float calibPrior, hipStream_t st);
+// ldso_ba_batch_marginalize_points / _frame: the MARG linearisation, the non-atomic reduce and the fused gather + prior update of every window that takes part; k_marg_frame per window
+hipError_t ba_launch_linearize_batch_marg(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, const MargWin *d_mw, const int32_t *d_flags, const ldso_settings_t &S, hipStream_t st);
+hipError_t ba_launch_reduce_batch_marg(const BatchItem *d_items, const MargWin *d_mw, int nWin, int totalBlocks, int maxGSP, hipStream_t st);
+hipError_t ba_launch_marg_gather_update_batch(const BatchItem *d_items, const MargWin *d_mw, int nWin, int maxN, double w, double *d_out, hipStream_t st);
+hipError_t ba_launch_marg_frame_batch(const BatchItem *d_items, int nWin, const MargWin *d_mw, double *d_out, hipStream_t st);
 hipError_t ba_launch_lm_energies(const BaPtrs &B, const BaDims &D, const ResSet &S, float calibPrior, bool hasPrior, hipStream_t st);
 hipError_t ba_launch_marg_update(const BaPtrs &B, const BaDims &D, double w, hipStream_t st);
 hipError_t ba_launch_gn_solve(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, const SolveArgs &A, hipStream_t st);
@@ -158,6 +163,10 @@ struct ldso_ba_batch {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evEnd = nullptr;
     BaDims Dmax;
     double *d_scalars = nullptr, *h_scalars = nullptr;      // [n][16]: every window's scalars after ldso_ba_batch_optimize (device block, pinned host copy)
+    // ldso_ba_batch_marginalize_points / _frame: one pinned arena and its device twin, grown on demand: [n MargWin | the flags of all windows | pad to 8] go up in one
+    // copy, [the windows' (H_M | b_M) in doubles] come down in one
+    char *h_marg = nullptr, *d_marg = nullptr;
+    size_t margCap = 0;
 };
 
 // the immature-point tracer (trace.hip)

@@ -1061,7 +1061,8 @@ static __device__ __forceinline__ void linearize_body(const BaPtrs &B, const BaD
         // (qa = qb, qb = qc: 16 vector moves per point of an issue-bound loop; LDS instructions have their own issue port)
         // (the batched kernel only: in k_linearize_one a wavefront has one to three points - nothing to amortise the LDS round trips and the peeled copy of the loop
         // body against; measured at C4, 12 points per chunk: 16.36 us with the stash, 15.85 without, profiles/r06_linearize_peel_stash_ab.log)
-        constexpr bool STASH = DESC && !ONE && NSG == 1 && !HAS_L && !FIX;
+        // (nor for the batched marginalisation pass, k_linearize_batch_marg: once per key frame - it takes the pipeline the batched fixing pass runs, records rotated through registers)
+        constexpr bool STASH = DESC && !ONE && NSG == 1 && !HAS_L && !FIX && !MARG;
         int par = 0;
         float *const wRec = sRec + wave * 1024;                      // [parity][half][lane][4 dwords]
         float *const myRec = wRec + lane * 4;
@@ -1296,6 +1297,25 @@ __global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch_fix(const Bat
     }
 }
 
+// The marginalizePointsF accumulate (MARG, see linearize_body) of every window of a batch that takes part in ldso_ba_batch_marginalize_points: each window reads its
+// applied set (BatchItem::set[0]) and writes its scratch set, one slot group per point; its flags start at flagsAll + mw[window].flagOff.  The blocks of a window
+// that takes no part are passed over.  Per point and per chunk the arithmetic of k_linearize<1, false, false, true>.
+__global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch_marg(const BatchItem *__restrict__ items, const BatchBlock *__restrict__ blocks, const int32_t *__restrict__ wgStart,
+                                                                        const MargWin *__restrict__ mw, const int32_t *__restrict__ flagsAll, ldso_settings_t S) {
+    int b0 = (int) blockIdx.x, b1 = b0 + 1;
+    if (wgStart != nullptr) { b0 = wgStart[blockIdx.x]; b1 = wgStart[blockIdx.x + 1]; }
+#pragma clang loop unroll(disable)
+    for (int b = b0; b < b1; b++) {
+        const BatchBlock bb = blocks[b];
+        const MargWin m = mw[bb.win];
+        if (!m.active) continue;                                    // (workgroup-uniform: nobody of this workgroup is inside the body, no barrier is skipped by a part of it)
+        const BatchItem &it = items[bb.win];
+        GnInit gi; gi.enable = 0; gi.hasPrior = 0; gi.calibPrior = 0.0f; gi.itCheck = -1;
+        linearize_body<1, false, false, true, true>(it.B, it.D, it.set[0], it.set[1], S, 0, gi, flagsAll + m.flagOff, bb.host_chunk >> 8, it.D.nChunks, bb.p0, bb.np, bb.host_chunk & 0xFF);
+        __syncthreads();
+    }
+}
+
 // The GN-iteration linearisation of ONE window with everything a workgroup needs before its first operand load in the KERNEL ARGUMENTS: the whole
 // descriptor (BaPtrs / BaDims / the two residual sets) by value - it stays in the kernarg segment, the body fetches its pointer groups from there just
 // in time exactly as from a BatchItem in device memory (DESC = true: `&B` is an address in the constant kernarg segment) - and the chunk of the
@@ -1378,6 +1398,15 @@ hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock 
     if (grid <= 0) return hipSuccess;
     if (FS == 8) return launch_lds(k_linearize_batch<1>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
     return launch_lds(k_linearize_batch<2>, dim3(grid), dim3(64 * LD_WAVES), lds, st, d_items, d_blocks, d_wgStart, cur, S, stepMode, calibPrior, itCheck);
+}
+
+// ldso_ba_batch_marginalize_points: windows of at most 8 key frames (the caller has checked)
+hipError_t ba_launch_linearize_batch_marg(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, const MargWin *d_mw, const int32_t *d_flags,
+                                          const ldso_settings_t &S, hipStream_t st) {
+    if (totalChunks == 0) return hipSuccess;
+    const int grid = d_wgStart != nullptr ? nWG : totalChunks;
+    if (grid <= 0) return hipSuccess;
+    return launch_lds(k_linearize_batch_marg, dim3(grid), dim3(64 * LD_WAVES), ba_linearize_lds_bytes(8, false, true), st, d_items, d_blocks, d_wgStart, d_mw, d_flags, S);
 }
 
 hipError_t ba_launch_linearize_batch_fix(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, const ldso_settings_t &S, float calibPrior, hipStream_t st) {

@@ -11,7 +11,8 @@
 //   small dense Hessian accumulate").  Fast path: one block per (16x16 tile, K-split), results added with fp64 atomics straight
 //   into HFinal / bFinal (B.acc); step-wise path: LD_SC_SPLITS K-range blocks write partial matrices for k_gather.
 // Also here: k_gather (assembly of H_A,b_A,H_L,b_L,H_sc,b_sc,HFinal,bFinal for the step-wise path and the old all-reduce layout),
-// k_marg_update / k_marg_frame (EnergyFunctional::marginalizePointsF tail, marginalizeFrame), k_acc_init.
+// k_marg_update / k_marg_frame (EnergyFunctional::marginalizePointsF tail, marginalizeFrame) and their batched twins (k_reduce_batch_marg,
+// k_marg_gather_update_batch, k_marg_frame_batch: ldso_ba_batch_marginalize_points / _frame), k_acc_init.
 #include <hip/hip_runtime.h>
 #include "ba_host.h"
 
@@ -175,13 +176,66 @@ hipError_t ba_launch_marg_update(const BaPtrs &B, const BaDims &D, double w, hip
     return hipGetLastError();
 }
 
+// ---- ldso_ba_batch_marginalize_points: the two launches behind k_linearize_batch_marg, for every window of the batch that takes part ----------------------------------
+// k_reduce in the mode of ldso_ba_marginalize_points (no atomics, no linearised residuals, l1 = il = 1, no prior) on every window's scratch set (BatchItem::set[1]):
+// reduce_pairs(F, false) + LD_SC_SPLITS workgroups per window, numbered from mw[window].redBlock0; the LDS is sized for the largest GSP of the batch.
+__global__ __launch_bounds__(256) void k_reduce_batch_marg(const BatchItem *__restrict__ items, const MargWin *__restrict__ mw, int nWin) {
+    int w = 0;
+    for (int i = 1; i < nWin; i++) if ((int) blockIdx.x >= mw[i].redBlock0) w = i;          // (a window without workgroups shares its redBlock0 with the next one, which wins)
+    const MargWin m = mw[w];
+    if (!m.active) return;
+    const BatchItem &it = items[w];
+    reduce_body(it.B, it.D, it.set[1], it.cs, 0, it.GSP, 0, 0, 0.0f, 1.0, 1.0, -1, (int) blockIdx.x - m.redBlock0);
+}
+
+hipError_t ba_launch_reduce_batch_marg(const BatchItem *d_items, const MargWin *d_mw, int nWin, int totalBlocks, int maxGSP, hipStream_t st) {
+    if (totalBlocks <= 0) return hipSuccess;
+    return launch_lds(k_reduce_batch_marg, dim3(totalBlocks), dim3(256), (size_t) (SC_SLAB * maxGSP) * sizeof(float), st, d_items, d_mw, nWin);
+}
+
+// k_gather (mode 0: the top entry in its fixed summation order, the LD_SC_SPLITS Schur partials in theirs) and k_marg_update in one pass, one thread per entry of
+// (H_M | b_M), blockIdx.y = the window: HM += w (M - Msc), bM += w (Mb - Mbsc) in double (EnergyFunctional.cc:203-216).  A window without a prior starts from
+// zero here, not from a fill per window; the new prior also goes to mw[window].outOff of the call's staging area (n^2 | n).  B.sys is not written: the assembled
+// M / Msc have no other reader.
+__global__ __launch_bounds__(256) void k_marg_gather_update_batch(const BatchItem *__restrict__ items, const MargWin *__restrict__ mw, double w, double *__restrict__ out) {
+    const MargWin m = mw[blockIdx.y];
+    if (!m.active) return;
+    const BatchItem &it = items[blockIdx.y];
+    const int F = it.D.F, n = it.D.n, FS = it.D.FS, GSP = it.GSP;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * n + n) return;
+    const int i = (e < n * n) ? e / n : (e - n * n), j = (e < n * n) ? e % n : -1;
+    const double vA = top_entry(it.B.pairC, F, i, j);
+    // Schur: only upper-triangular 16x16 tiles are stored; a diagonal tile holds both triangles (k_gather)
+    const int ci = g_col(i, FS), cj = (j >= 0) ? g_col(j, FS) : (8 * FS + 4);
+    const int r = min(ci, cj), c = max(ci, cj);
+    const size_t off = (r / 16 == c / 16) ? ((size_t) ci * GSP + cj) : ((size_t) r * GSP + c);
+    float q[LD_SC_SPLITS];
+#pragma unroll
+    for (int sp = 0; sp < LD_SC_SPLITS; sp++) q[sp] = it.B.scPart[(size_t) sp * GSP * GSP + off];
+    double vS = 0;
+#pragma unroll
+    for (int sp = 0; sp < LD_SC_SPLITS; sp++) vS += (double) q[sp];
+    double *dst = (j >= 0) ? it.B.HM + e : it.B.bM + i;
+    double v = it.hasPrior ? *dst : 0.0;
+    v += (vA - vS) * w;
+    *dst = v;
+    out[(size_t) m.outOff + e] = v;
+}
+
+hipError_t ba_launch_marg_gather_update_batch(const BatchItem *d_items, const MargWin *d_mw, int nWin, int maxN, double w, double *d_out, hipStream_t st) {
+    const int N = maxN * maxN + maxN;
+    hipLaunchKernelGGL(k_marg_gather_update_batch, dim3((N + 255) / 256, nWin), dim3(256), 0, st, d_items, d_mw, w, d_out);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // EnergyFunctional::marginalizeFrame (EnergyFunctional.cc:72-151) on the device prior H_M / b_M: move the frame's 8 rows /
 // columns to the end, add its prior, scale by (|diag|+10)^-1/2, eliminate the 8x8 block (inverse by partial-pivot LU like Eigen's
 // fixed-size inverse()), unscale, symmetrise the result (the result only: see the 8x8 block below).  One workgroup; the matrices live in global memory (n <= 132), W = n*n + n doubles
 // of scratch.  Output: (n-8)^2 row-major + (n-8).  Per key frame, not per iteration: written for clarity, not speed.
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_marg_frame(BaPtrs B, BaDims D, int idx, double *W, double *outH, double *outb) {
+static __device__ __forceinline__ void marg_frame_body(BaPtrs B, BaDims D, int idx, double *W, double *outH, double *outb) {
     const int tid = threadIdx.x, n = D.n, nd = n - 8;
     double *Hs = W, *bs = W + (size_t) n * n;
     __shared__ double sSV[8 * LD_MAXF + 4], sHpi[64], sLU[64], sBLI[(8 * LD_MAXF + 4) * 8];
@@ -255,6 +309,32 @@ __global__ __launch_bounds__(256) void k_marg_frame(BaPtrs B, BaDims D, int idx,
         outH[e] = 0.5 * (sSV[i] * Hs[(size_t) i * n + j] * sSV[j] + sSV[j] * Hs[(size_t) j * n + i] * sSV[i]);
     }
     for (int i = tid; i < nd; i += 256) outb[i] = sSV[i] * bs[i];
+}
+
+__global__ __launch_bounds__(256) void k_marg_frame(BaPtrs B, BaDims D, int idx, double *W, double *outH, double *outb) {
+    marg_frame_body(B, D, idx, W, outH, outb);
+}
+
+// ldso_ba_batch_marginalize_frame: one workgroup per window of the batch, each with its own B.sys as scratch (as ldso_ba_marginalize_frame has it) and its result
+// at mw[window].outOff of the call's staging area: (n - 8)^2 | n - 8.  A window without a prior starts from a zero H_M / b_M, written here as the solo call's
+// fills write it; a window with frameIdx < 0 takes no part.
+__global__ __launch_bounds__(256) void k_marg_frame_batch(const BatchItem *__restrict__ items, const MargWin *__restrict__ mw, double *__restrict__ out) {
+    const MargWin m = mw[blockIdx.x];
+    if (!m.active) return;
+    const BatchItem &it = items[blockIdx.x];
+    const int n = it.D.n, nd = n - 8;
+    if (!it.hasPrior) {
+        for (int e = threadIdx.x; e < n * n; e += 256) it.B.HM[e] = 0.0;
+        for (int e = threadIdx.x; e < n; e += 256) it.B.bM[e] = 0.0;
+        __syncthreads();
+    }
+    double *oH = out + m.outOff;
+    marg_frame_body(it.B, it.D, m.frameIdx, it.B.sys, oH, oH + (size_t) nd * nd);
+}
+
+hipError_t ba_launch_marg_frame_batch(const BatchItem *d_items, int nWin, const MargWin *d_mw, double *d_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_marg_frame_batch, dim3(nWin), dim3(256), 0, st, d_items, d_mw, d_out);
+    return hipGetLastError();
 }
 
 hipError_t ba_launch_marg_frame(const BaPtrs &B, const BaDims &D, int idx, double *work, double *outH, double *outb, hipStream_t st) {
