@@ -294,6 +294,31 @@ int ldso_ba_batch_optimize(ldso_ba_batch_t *b, int mnumOptIts, int force_all_ite
  * and windows of more than 8 key frames (the 8-slot table, as ldso_ba_batch_optimize). */
 int ldso_ba_batch_marginalize_points(ldso_ba_batch_t *b, const int32_t *const *flags /*n*/, double *const *HM_out /*n or NULL*/, double *const *bM_out /*n or NULL*/);
 int ldso_ba_batch_marginalize_frame(ldso_ba_batch_t *b, const int32_t *frame_idx /*n*/, double *const *HM_out /*n*/, double *const *bM_out /*n*/);
+/* The next step of FullSystem::makeKeyFrame, activatePointsMT (FullSystem.cc:1052-1189; CoarseTracker.cc:686-818 the distance map), for every window of the batch, with
+ * a number of launches that does not depend on n (one per kernel) and one upload, one download and one host synchronisation per call.  Per window each entry gives
+ * exactly - byte for byte - what its single-window counterpart gives on that handle alone: the same device functions run on the same bytes.
+ * ldso_ba_batch_activate_points = ldso_ba_activate_points(handle_i, n[i], points[i], ..., out[i]); n[i] == 0 or points[i] == NULL: window i takes no part.
+ * ldso_ba_batch_select_candidates = ldso_ba_select_candidates(handle_i, <jobs[i]>, minTraceQuality, ...), ldso_ba_batch_select_activate_points =
+ * ldso_ba_select_activate_points(handle_i, <jobs[i]>, ...): the arguments and outputs of the single-window entries, per window in a ldso_act_job_t (selected_out
+ * may be NULL in the first, as there).  jobs[i].n_hosts == 0: window i takes no part.  A window may bring no candidates (n == 0: it builds its map only) or no seeds.
+ * The windows may differ in image size; a distance map that does not fit into a workgroup's LDS is kept in global memory, window by window, in the same launch.
+ * Afterwards ldso_ba_get_distance_map(handle_i) returns the map the call left for window i.  A window that takes no part keeps its outputs, its handle and its map.
+ * All three refuse (LDSO_E_INVALID, nothing enqueued, no output written): a NULL batch or array, a participating window without its arrays, a candidate or seed whose
+ * host is outside [0, n_hosts), a sharded handle, windows of more than 8 key frames (the 8-slot table, as ldso_ba_batch_optimize); the two that activate also
+ * n_hosts != F_i and a missing key-frame image, as their single-window counterparts. */
+typedef struct {            /* one window's share of a batched selection */
+    int n_seeds; const ldso_act_seed_t *seeds;
+    int n; const ldso_immature_t *points; const float *my_type;
+    int n_hosts; const float *KRKi, *Kt; const int32_t *host_flagged;
+    float currentMinActDist;
+    int32_t *decision_out /*n*/, *selected_out /*n*/; int n_selected;          /* out */
+    ldso_activation_t *out;                                                    /* out [n]: ldso_ba_batch_select_activate_points only */
+} ldso_act_job_t;
+int ldso_ba_batch_activate_points(ldso_ba_batch_t *b, const int *n /*n_win*/, const ldso_immature_t *const *points /*n_win*/, int min_obs, float min_idepth_hessian,
+                                  int gn_iterations, ldso_activation_t *const *out /*n_win*/);
+int ldso_ba_batch_select_candidates(ldso_ba_batch_t *b, ldso_act_job_t *jobs /*n_win*/, float minTraceQuality);
+int ldso_ba_batch_select_activate_points(ldso_ba_batch_t *b, ldso_act_job_t *jobs /*n_win*/, float minTraceQuality, int min_obs, float min_idepth_hessian,
+                                         int gn_iterations);
 int ldso_ba_batch_destroy(ldso_ba_batch_t *b);
 /* points per workgroup ldso_ba_batch_create gave the windows of the batch - since round 6 the AVERAGE, rounded: the cuts are uneven, ldso_ba_get_chunk_cuts has
  * them - (0: their single-window chunking was kept; ldso_ba_batch_destroy restores it) */

@@ -741,6 +741,13 @@ class BA:
         return ms.value, n.value
 
 
+class ActJob(C.Structure):
+    """ldso_act_job_t (ldso_hip.h): one window's share of a batched selection"""
+    _fields_ = [("n_seeds", C.c_int), ("seeds", C.c_void_p), ("n", C.c_int), ("points", C.c_void_p), ("my_type", C.c_void_p), ("n_hosts", C.c_int), ("KRKi", C.c_void_p),
+                ("Kt", C.c_void_p), ("host_flagged", C.c_void_p), ("currentMinActDist", C.c_float), ("decision_out", C.c_void_p), ("selected_out", C.c_void_p),
+                ("n_selected", C.c_int), ("out", C.c_void_p)]
+
+
 class BABatch:
     """ldso_ba_batch_*: the GN iteration of several independent windows per launch."""
 
@@ -799,6 +806,63 @@ class BABatch:
         out, PH, Pb = self._marg_out([None if k < 0 else 8 * (h.F - 1) + 4 for k, h in zip(idx, self.handles)])
         _chk(self.L.ldso_ba_batch_marginalize_frame(self.h, _p(idx), PH, Pb))
         return out
+
+    def activate_points(self, pts_list, min_obs=1, min_idepth_hessian=100.0, gn_iterations=3):
+        """FullSystem::optimizeImmaturePoint against every window of the batch (ldso_ba_batch_activate_points): pts_list[i] = the immature records for window i, or
+        None / an empty array for a window that takes no part -> [activation records or None]"""
+        n = len(self.handles)
+        assert len(pts_list) == n
+        pts = [None if a is None or len(a) == 0 else np.ascontiguousarray(a) for a in pts_list]
+        out = [None if a is None else np.zeros(len(a), synth.ACTIVATION_DTYPE) for a in pts]
+        cnt = np.array([0 if a is None else len(a) for a in pts], np.int32)
+        PP, PO = (C.c_void_p * n)(), (C.c_void_p * n)()
+        for i, a in enumerate(pts):
+            if a is not None:
+                assert a.dtype == synth.IMMATURE_DTYPE
+                PP[i], PO[i] = a.ctypes.data, out[i].ctypes.data
+        _chk(self.L.ldso_ba_batch_activate_points(self.h, _p(cnt), PP, C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations), PO))
+        return out
+
+    def _jobs(self, jobs, with_records):
+        """the ldso_act_job_t array of a batched selection and the arrays it points into; jobs[i]: a dict with the keys seeds, cand, my_type, KRKi, Kt, flagged,
+        min_act_dist, or None for a window that takes no part"""
+        n = len(self.handles)
+        assert len(jobs) == n
+        J = (ActJob * n)()
+        keep = []
+        for i, job in enumerate(jobs):
+            if job is None:
+                keep.append(None)
+                continue
+            sd = np.ascontiguousarray(job["seeds"]); a = np.ascontiguousarray(job["cand"])
+            assert sd.dtype == synth.ACT_SEED_DTYPE and a.dtype == synth.IMMATURE_DTYPE
+            mt = np.ascontiguousarray(job["my_type"], np.float32)
+            K1 = None if job.get("KRKi") is None else np.ascontiguousarray(job["KRKi"], np.float32).reshape(-1, 9)
+            K2 = None if job.get("Kt") is None else np.ascontiguousarray(job["Kt"], np.float32).reshape(-1, 3)
+            fl = np.ascontiguousarray(job["flagged"], np.int32)
+            assert len(mt) == len(a)
+            dec = np.zeros(len(a), np.int32); sel = np.zeros(len(a), np.int32); rec = np.zeros(len(a), synth.ACTIVATION_DTYPE) if with_records else None
+            keep.append((sd, a, mt, K1, K2, fl, dec, sel, rec))
+            j = J[i]
+            j.n_seeds, j.seeds, j.n, j.points, j.my_type = len(sd), sd.ctypes.data, len(a), a.ctypes.data, mt.ctypes.data
+            j.n_hosts, j.KRKi, j.Kt, j.host_flagged = len(fl), (None if K1 is None else K1.ctypes.data), (None if K2 is None else K2.ctypes.data), fl.ctypes.data
+            j.currentMinActDist = float(job["min_act_dist"])
+            j.decision_out, j.selected_out, j.out = dec.ctypes.data, sel.ctypes.data, (rec.ctypes.data if with_records else None)
+        return J, keep
+
+    def select_candidates(self, jobs, min_trace_quality=3.0):
+        """distance map + candidate selection of FullSystem::activatePointsMT for every window of the batch (ldso_ba_batch_select_candidates)
+        -> [(decision, selected) or None]; BA.get_distance_map() of a member returns the map the call left for it"""
+        J, keep = self._jobs(jobs, False)
+        _chk(self.L.ldso_ba_batch_select_candidates(self.h, J, C.c_float(min_trace_quality)))
+        return [None if k is None else (k[6], k[7][:J[i].n_selected].copy()) for i, k in enumerate(keep)]
+
+    def select_activate_points(self, jobs, min_trace_quality=3.0, min_obs=1, min_idepth_hessian=100.0, gn_iterations=3):
+        """the selection and the activation of the selected candidates for every window of the batch in one enqueue (ldso_ba_batch_select_activate_points)
+        -> [(decision, selected, activation records of the selected) or None]"""
+        J, keep = self._jobs(jobs, True)
+        _chk(self.L.ldso_ba_batch_select_activate_points(self.h, J, C.c_float(min_trace_quality), C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations)))
+        return [None if k is None else (k[6], k[7][:J[i].n_selected].copy(), k[8][:J[i].n_selected].copy()) for i, k in enumerate(keep)]
 
     def sync(self):
         self.handles[0].sync()

@@ -10,6 +10,8 @@
 //   phase B (wave 0)     the pending candidates in order; an accepted one is inserted as addIntoDistFinal does: cell = 0, then the pruned BFS from that single
 //                        seed over a frontier list (a cell joins the next frontier only when the round lowered it), until the frontier is empty.
 // Float projections in the reference's operation order, no contraction, IEEE division, int conversion by truncation after + 0.5f (as trace.hip, ba_activate.hip).
+// For a batch of windows (ldso_ba_batch_select_candidates / _select_activate_points / _activate_points, at the end of the file) the same body runs as one workgroup per
+// window in one launch, k_act_select_batch, each window with its own sizes and map placement.
 #include <hip/hip_runtime.h>
 #include "ba_host.h"
 
@@ -36,6 +38,7 @@ struct SelArgs {
     int nWin;
     int newestHost;                               // candidates hosted by this frame are no candidates (FullSystem.cc:1089): KEEP, never touched; < 0: none
     unsigned char *gmap;                          // [w1 * h1] the map in global memory: the working copy of the large path, the final map of both
+    int ldsMap;                                   // k_act_select_batch: this window's working map lies in LDS (k_act_select has the choice as its template argument)
     int32_t *decision, *selected, *nSelected, *cell;
     float *frac, *thr;
 };
@@ -95,9 +98,9 @@ static __device__ void insert_seed(unsigned char *map, uint32_t *listA, uint32_t
     }
 }
 
+// One window's selection by one workgroup: the body of k_act_select and k_act_select_batch.  sel_lds: the workgroup's dynamic LDS, [frontier lists | the map if LDS].
 template <bool LDS>
-__global__ __launch_bounds__(SEL_THREADS) void k_act_select(SelArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sel_lds[];
+static __device__ __forceinline__ void act_select_body(const SelArgs &A, unsigned char *sel_lds) {
     uint32_t *listA = (uint32_t *) sel_lds, *listB = listA + SEL_FRONTIER;
     unsigned char *map = LDS ? sel_lds + SEL_LIST_BYTES : A.gmap;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
@@ -198,6 +201,26 @@ __global__ __launch_bounds__(SEL_THREADS) void k_act_select(SelArgs A) {
     if (LDS) for (int i = tid; i < wh; i += nt) A.gmap[i] = map[i];
 }
 
+template <bool LDS>
+__global__ __launch_bounds__(SEL_THREADS) void k_act_select(SelArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sel_lds[];
+    act_select_body<LDS>(A, sel_lds);
+}
+
+// The windows of a batch in one launch (ldso_ba_batch_select_candidates / _select_activate_points): workgroup b runs the selection tab[b] describes, sizes and map
+// placement its own.  The launch's dynamic LDS is that of the largest map that lies in LDS.
+__global__ __launch_bounds__(SEL_THREADS) void k_act_select_batch(const SelArgs *tab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sel_lds[];
+    SelArgs A = tab[blockIdx.x];
+    // pointers that come out of a table are generic to the compiler; all of these lie in global memory, and saying so keeps the body on global_load / global_store
+#define SEL_GLOBAL(p) p = (decltype(p)) (__attribute__((address_space(1))) void *) (uintptr_t) (p)
+    SEL_GLOBAL(A.seeds); SEL_GLOBAL(A.pts); SEL_GLOBAL(A.myType); SEL_GLOBAL(A.KRKi); SEL_GLOBAL(A.Kt); SEL_GLOBAL(A.flagged); SEL_GLOBAL(A.gmap); SEL_GLOBAL(A.decision);
+    SEL_GLOBAL(A.selected); SEL_GLOBAL(A.nSelected); SEL_GLOBAL(A.cell); SEL_GLOBAL(A.frac); SEL_GLOBAL(A.thr);
+#undef SEL_GLOBAL
+    if (A.ldsMap) act_select_body<true>(A, sel_lds);
+    else act_select_body<false>(A, sel_lds);
+}
+
 struct SelBuffers {                // the carve-up of ldso_ba::d_sel for one call
     char *in = nullptr; size_t inBytes = 0;                       // [points | seeds | my_type | KRKi | Kt | flagged]: one upload
     char *out = nullptr; size_t outBytes = 0;                     // [n_selected (16 B) | decision | selected | activation records]: one download
@@ -260,7 +283,7 @@ static int sel_enqueue(ldso_ba *H, const char *who, const SelSource &I, int n_ho
     A.seeds = S.seeds; A.pts = I.d_points ? I.d_points : S.pts; A.myType = I.d_points ? I.d_myType : S.myType; A.KRKi = S.KRKi; A.Kt = S.Kt; A.flagged = S.flagged;
     A.nSeeds = n_seeds; A.n = n; A.nHosts = n_hosts; A.w1 = w1; A.h1 = h1; A.minDist = currentMinActDist; A.minQuality = minTraceQuality;
     A.pgeo = I.windowSeeds ? H->B.pgeo : nullptr; A.phost = I.windowSeeds ? H->B.phost : nullptr; A.nWin = I.windowSeeds ? H->D.P : 0; A.newestHost = I.newestHost;
-    A.gmap = S.gmap; A.decision = S.decision; A.selected = S.selected; A.nSelected = S.nSelected; A.cell = S.cell; A.frac = S.frac; A.thr = S.thr;
+    A.gmap = S.gmap; A.ldsMap = 0; A.decision = S.decision; A.selected = S.selected; A.nSelected = S.nSelected; A.cell = S.cell; A.frac = S.frac; A.thr = S.thr;
     // the map in LDS where the workgroup can have that much (beside the kernel's own static bytes), in global memory otherwise
     const size_t ldsBytes = SEL_LIST_BYTES + up16(wh);
     if (H->selLdsLimit < 0) {
@@ -401,6 +424,221 @@ int ldso_ba_select_activate_tracer(ldso_ba_t *H, ldso_tracer_t *T, int n_hosts, 
     sel_unpack_activations(H, n, *n_selected_out, out);
     if (n_left_out) *n_left_out = T->n;
     return LDSO_OK;
+}
+
+}  // extern "C"
+
+// ---- the batch: activatePointsMT (FullSystem.cc:1052-1189) for every window of a ldso_ba_batch, one launch per kernel whatever the number of windows ----------------
+namespace {
+
+struct SelPlan {                   // a participating window's share of the call's arena; offsets in bytes into the upload, the download and the scratch region
+    int win = 0, w1 = 0, h1 = 0;
+    size_t oPts = 0, oSeeds = 0, oType = 0, oKRKi = 0, oKt = 0, oFlag = 0, oOut = 0, oDec = 0, oSel = 0, oAct = 0, oCell = 0, oFrac = 0, oThr = 0, mapBytes = 0;
+};
+
+// what every batched activation entry refuses: for the batch as a whole, and for a window that takes part (`images`: the entry reads the resident window); `solo`: the
+// single-window entry the message points to
+int batch_act_checks(const ldso_ba_batch *Bt, const std::string &w, const char *solo) {
+    REQ(Bt->FS == 8, w + ": windows of more than 8 key frames are not supported in a batched activation (every window needs F <= 8): run them with " + solo);
+    return LDSO_OK;
+}
+int batch_act_window_checks(const ldso_ba *H, const std::string &w, bool images) {
+    REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, w + ": not available on a sharded handle (ldso_ba_set_shard)");
+    if (images) {
+        REQ(H->D.F >= 2, w + ": set the window and the frames first");
+        for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, w + ": a key-frame image is missing");
+    }
+    return LDSO_OK;
+}
+
+// the map of window H for a batched selection: in the handle's own arena, where ldso_ba_get_distance_map looks for it
+int batch_sel_map(ldso_ba *H, size_t mapBytes, unsigned char **gmap) {
+    if (mapBytes > H->selCap) {
+        if (H->d_sel) hipFree(H->d_sel);
+        H->d_sel = nullptr; H->selCap = 0; H->selW1 = 0; H->selH1 = 0;
+        CHK(hipMalloc(&H->d_sel, mapBytes));
+        H->selCap = mapBytes;
+    }
+    *gmap = (unsigned char *) H->d_sel;
+    return LDSO_OK;
+}
+
+int batch_select_run(ldso_ba_batch *Bt, const char *who, const char *solo, ldso_act_job_t *jobs, float minTraceQuality, bool activate, int min_obs, float min_idepth_hessian,
+                     int gn_iterations) {
+    const std::string w(who);
+    REQ(Bt, w + ": null batch");
+    REQ(jobs && gn_iterations >= 0, w + ": bad arguments (null jobs)");
+    RUN(batch_act_checks(Bt, w, solo));
+    const int n = (int) Bt->h.size();
+    ldso_ba *H0 = Bt->h[0];
+    // ---- every refusal, before anything is enqueued or written; the regions of the arena on the way ----
+    std::vector<SelPlan> plan;
+    size_t in = 0, down = 0, scratch = 0, cands = 0;
+    int nAct = 0;
+    for (int i = 0; i < n; i++) {
+        const ldso_act_job_t &J = jobs[i];
+        if (J.n_hosts == 0) continue;
+        const ldso_ba *H = Bt->h[i];
+        REQ(J.n_seeds >= 0 && J.n >= 0 && J.n_hosts >= 1 && J.n_hosts <= LDSO_MAX_FRAMES && J.KRKi && J.Kt && J.host_flagged && (J.n_seeds == 0 || J.seeds)
+            && (J.n == 0 || (J.points && J.my_type && J.decision_out)) && (!activate || J.n == 0 || (J.selected_out && J.out)),
+            w + ": a window that takes part needs its arrays (seeds, points, my_type, KRKi, Kt, host_flagged and the outputs)");
+        RUN(batch_act_window_checks(H, w, false));
+        if (activate) RUN(act_preconditions(H, who, J.n_hosts));
+        SelPlan p;
+        p.win = i; p.w1 = H->w >> 1; p.h1 = H->h >> 1;
+        REQ(p.w1 >= 3 && p.h1 >= 3 && p.w1 < 65536 && p.h1 < 65536, w + ": image size out of range");
+        for (int k = 0; k < J.n; k++) REQ(J.points[k].host >= 0 && J.points[k].host < J.n_hosts, w + ": a candidate's host is not a frame of the window");
+        for (int k = 0; k < J.n_seeds; k++) REQ(J.seeds[k].host >= 0 && J.seeds[k].host < J.n_hosts, w + ": a seed's host is not a frame of the window");
+        const size_t nn = (size_t) J.n;
+        p.oPts = in; p.oSeeds = p.oPts + nn * sizeof(ldso_immature_t); p.oType = p.oSeeds + up16((size_t) J.n_seeds * sizeof(ldso_act_seed_t)); p.oKRKi = p.oType + up16(nn * 4);
+        p.oKt = p.oKRKi + up16((size_t) J.n_hosts * 36); p.oFlag = p.oKt + up16((size_t) J.n_hosts * 12); in = p.oFlag + up16((size_t) J.n_hosts * 4);
+        p.oOut = down; p.oDec = p.oOut + 16; p.oSel = p.oDec + up16(nn * 4); p.oAct = p.oSel + up16(nn * 4); down = p.oAct + (activate ? nn * sizeof(ldso_activation_t) : 0);
+        p.oCell = scratch; p.oFrac = p.oCell + up16(nn * 4); p.oThr = p.oFrac + up16(nn * 4); scratch = p.oThr + up16(nn * 4);
+        p.mapBytes = up16((size_t) p.w1 * p.h1);
+        if (activate && J.n > 0) nAct++;
+        cands += nn;
+        plan.push_back(p);
+    }
+    REQ(cands < (size_t) 1 << 30, w + ": too many candidates");
+    const int nPart = (int) plan.size();
+    if (nPart == 0) return LDSO_OK;
+    CHK(hipSetDevice(H0->device));
+    if (activate) RUN(batch_refresh(Bt));
+    // the upload: [nPart SelArgs | nAct ActWin | nAct + 1 wavefront offsets | every window's inputs]
+    const size_t oTab = 0, oAct = oTab + up16((size_t) nPart * sizeof(SelArgs)), oWave = oAct + up16((size_t) nAct * sizeof(ActWin)), oIn = oWave + up16(((size_t) nAct + 1) * 4), up = oIn + in;
+    RUN(batch_stage(Bt, up, down + scratch));
+    if (Bt->selLdsLimit < 0) {
+        hipFuncAttributes fa; int perBlock = 0;
+        CHK(hipFuncGetAttributes(&fa, (const void *) k_act_select_batch));
+        CHK(hipDeviceGetAttribute(&perBlock, hipDeviceAttributeMaxSharedMemoryPerBlock, H0->device));
+        Bt->selLdsLimit = std::max(0, std::min(perBlock, SEL_LDS_MAX) - (int) fa.sharedSizeBytes);
+    }
+    char *hs = Bt->h_marg, *d = Bt->d_marg, *dIn = d + oIn, *dOut = d + up, *dScr = d + up + down;
+    SelArgs *tab = (SelArgs *) (hs + oTab);
+    ActWin *act = (ActWin *) (hs + oAct);
+    int32_t *wave = (int32_t *) (hs + oWave);
+    size_t ldsBytes = SEL_LIST_BYTES;
+    int waves = 0, ia = 0;
+    for (int k = 0; k < nPart; k++) {
+        const SelPlan &p = plan[(size_t) k];
+        const ldso_act_job_t &J = jobs[p.win];
+        ldso_ba *H = Bt->h[(size_t) p.win];
+        const size_t nn = (size_t) J.n;
+        char *hi = hs + oIn;
+        if (J.n) { memcpy(hi + p.oPts, J.points, nn * sizeof(ldso_immature_t)); memcpy(hi + p.oType, J.my_type, nn * 4); }
+        if (J.n_seeds) memcpy(hi + p.oSeeds, J.seeds, (size_t) J.n_seeds * sizeof(ldso_act_seed_t));
+        memcpy(hi + p.oKRKi, J.KRKi, (size_t) J.n_hosts * 36); memcpy(hi + p.oKt, J.Kt, (size_t) J.n_hosts * 12); memcpy(hi + p.oFlag, J.host_flagged, (size_t) J.n_hosts * 4);
+        SelArgs &A = tab[k];
+        memset(&A, 0, sizeof(A));
+        A.seeds = (const ldso_act_seed_t *) (dIn + p.oSeeds); A.pts = (const ldso_immature_t *) (dIn + p.oPts); A.myType = (const float *) (dIn + p.oType);
+        A.KRKi = (const float *) (dIn + p.oKRKi); A.Kt = (const float *) (dIn + p.oKt); A.flagged = (const int32_t *) (dIn + p.oFlag);
+        A.nSeeds = J.n_seeds; A.n = J.n; A.nHosts = J.n_hosts; A.w1 = p.w1; A.h1 = p.h1; A.minDist = J.currentMinActDist; A.minQuality = minTraceQuality;
+        A.pgeo = nullptr; A.phost = nullptr; A.nWin = 0; A.newestHost = -1;
+        RUN(batch_sel_map(H, p.mapBytes, &A.gmap));
+        // the map in LDS where the workgroup can have that much, in global memory otherwise: the rule of the single-window entry, window by window
+        A.ldsMap = SEL_LIST_BYTES + p.mapBytes <= (size_t) Bt->selLdsLimit ? 1 : 0;
+        if (A.ldsMap) ldsBytes = std::max(ldsBytes, SEL_LIST_BYTES + p.mapBytes);
+        A.nSelected = (int32_t *) (dOut + p.oOut); A.decision = (int32_t *) (dOut + p.oDec); A.selected = (int32_t *) (dOut + p.oSel);
+        A.cell = (int32_t *) (dScr + p.oCell); A.frac = (float *) (dScr + p.oFrac); A.thr = (float *) (dScr + p.oThr);
+        if (activate && J.n > 0) {
+            ActWin &T = act[ia];
+            memset(&T, 0, sizeof(T));
+            T.A.pts = A.pts; T.A.out = (ldso_activation_t *) (dOut + p.oAct); T.A.n = J.n; T.A.minObs = min_obs; T.A.GNIts = gn_iterations; T.A.minIdepthH_act = min_idepth_hessian;
+            T.A.sel = A.selected; T.A.nSel = A.nSelected; T.item = p.win;
+            wave[ia++] = waves; waves += J.n;
+        }
+    }
+    wave[ia] = waves;
+    CHK(hipMemcpyAsync(d, hs, up, hipMemcpyHostToDevice, H0->stream));
+    if ((int) ldsBytes > Bt->selLdsSet) { CHK(hipFuncSetAttribute((const void *) k_act_select_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes)); Bt->selLdsSet = (int) ldsBytes; }
+    hipLaunchKernelGGL(k_act_select_batch, dim3(nPart), dim3(SEL_THREADS), ldsBytes, H0->stream, (const SelArgs *) (d + oTab));
+    CHK(hipGetLastError());
+    for (const SelPlan &p : plan) { ldso_ba *H = Bt->h[(size_t) p.win]; H->selW1 = p.w1; H->selH1 = p.h1; H->selMapOffset = 0; }
+    if (activate) CHK(ba_launch_activate_batch(Bt->d_items, (const ActWin *) (d + oAct), (const int32_t *) (d + oWave), nAct, waves, Bt->Dmax.nsg, H0->settings, H0->stream));
+    CHK(hipMemcpyAsync(hs + up, dOut, down, hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipStreamSynchronize(H0->stream));
+    for (const SelPlan &p : plan) {
+        ldso_act_job_t &J = jobs[p.win];
+        const char *ho = hs + up;
+        const int ns = std::min(std::max(*(const int32_t *) (ho + p.oOut), 0), J.n);
+        if (J.n) memcpy(J.decision_out, ho + p.oDec, (size_t) J.n * 4);
+        if (J.selected_out && ns > 0) memcpy(J.selected_out, ho + p.oSel, (size_t) ns * 4);
+        if (activate && ns > 0) memcpy(J.out, ho + p.oAct, (size_t) ns * sizeof(ldso_activation_t));
+        J.n_selected = ns;
+    }
+    return LDSO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// FullSystem::optimizeImmaturePoint (FullSystem.cc:892-1010) for the candidates of every window i of the batch with n[i] > 0 and points[i] != NULL: per window what
+// ldso_ba_activate_points gives on its handle alone.  One upload (the window table, the wavefront offsets, all records), one launch (k_activate_batch), one
+// download, one wait.
+int ldso_ba_batch_activate_points(ldso_ba_batch_t *Bt, const int *n_pts, const ldso_immature_t *const *points, int min_obs, float min_idepth_hessian, int gn_iterations,
+                                  ldso_activation_t *const *out) {
+    const std::string w("ldso_ba_batch_activate_points");
+    REQ(Bt, w + ": null batch");
+    REQ(n_pts && points && out && gn_iterations >= 0, w + ": bad arguments (null array)");
+    RUN(batch_act_checks(Bt, w, "ldso_ba_activate_points"));
+    const int n = (int) Bt->h.size();
+    ldso_ba *H0 = Bt->h[0];
+    std::vector<int> part;
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (n_pts[i] == 0 || points[i] == nullptr) continue;
+        REQ(n_pts[i] > 0 && out[i], w + ": a window that takes part needs n[i] > 0 and its out[i]");
+        RUN(batch_act_window_checks(Bt->h[(size_t) i], w, true));
+        part.push_back(i);
+        total += (size_t) n_pts[i];
+    }
+    const int nTab = (int) part.size();
+    if (nTab == 0) return LDSO_OK;
+    REQ(total < (size_t) 1 << 30, w + ": too many candidates");
+    CHK(hipSetDevice(H0->device));
+    RUN(batch_refresh(Bt));
+    const size_t oWave = up16((size_t) nTab * sizeof(ActWin)), oPts = oWave + up16(((size_t) nTab + 1) * 4), up = oPts + total * sizeof(ldso_immature_t), down = total * sizeof(ldso_activation_t);
+    RUN(batch_stage(Bt, up, down));
+    char *hs = Bt->h_marg, *d = Bt->d_marg;
+    ActWin *tab = (ActWin *) hs;
+    int32_t *wave = (int32_t *) (hs + oWave);
+    size_t at = 0;
+    for (int k = 0; k < nTab; k++) {
+        const int i = part[(size_t) k];
+        ActWin &T = tab[k];
+        memset(&T, 0, sizeof(T));
+        memcpy(hs + oPts + at * sizeof(ldso_immature_t), points[i], (size_t) n_pts[i] * sizeof(ldso_immature_t));
+        T.A.pts = (const ldso_immature_t *) (d + oPts) + at; T.A.out = (ldso_activation_t *) (d + up) + at; T.A.n = n_pts[i]; T.A.minObs = min_obs; T.A.GNIts = gn_iterations;
+        T.A.minIdepthH_act = min_idepth_hessian; T.A.sel = nullptr; T.A.nSel = nullptr; T.item = i;
+        wave[k] = (int32_t) at;
+        at += (size_t) n_pts[i];
+    }
+    wave[nTab] = (int32_t) at;
+    CHK(hipMemcpyAsync(d, hs, up, hipMemcpyHostToDevice, H0->stream));
+    CHK(ba_launch_activate_batch(Bt->d_items, (const ActWin *) d, (const int32_t *) (d + oWave), nTab, (int) at, Bt->Dmax.nsg, H0->settings, H0->stream));
+    CHK(hipMemcpyAsync(hs + up, d + up, down, hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipStreamSynchronize(H0->stream));
+    at = 0;
+    for (int k = 0; k < nTab; k++) {
+        const int i = part[(size_t) k];
+        memcpy(out[i], hs + up + at * sizeof(ldso_activation_t), (size_t) n_pts[i] * sizeof(ldso_activation_t));
+        at += (size_t) n_pts[i];
+    }
+    return LDSO_OK;
+}
+
+// makeDistanceMap + the selection loop of FullSystem::activatePointsMT (FullSystem.cc:1080-1152, CoarseTracker.cc:686-818) for every window i of the batch with
+// jobs[i].n_hosts != 0: per window what ldso_ba_select_candidates gives on its handle alone, its final map where ldso_ba_get_distance_map(handle_i) reads it.  One
+// upload (the argument table and all inputs), one launch (k_act_select_batch: a workgroup per window), one download, one wait.
+int ldso_ba_batch_select_candidates(ldso_ba_batch_t *Bt, ldso_act_job_t *jobs, float minTraceQuality) {
+    return batch_select_run(Bt, "ldso_ba_batch_select_candidates", "ldso_ba_select_candidates", jobs, minTraceQuality, false, 0, 0.0f, 0);
+}
+
+// ... followed by the optimizeImmaturePoint loop (FullSystem.cc:1154-1164, 892-1010) on every window's selected list where the selection left it (k_activate_batch:
+// the wavefronts beyond a window's count leave at once): per window what ldso_ba_select_activate_points gives.  Two launches, one wait.
+int ldso_ba_batch_select_activate_points(ldso_ba_batch_t *Bt, ldso_act_job_t *jobs, float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations) {
+    return batch_select_run(Bt, "ldso_ba_batch_select_activate_points", "ldso_ba_select_activate_points", jobs, minTraceQuality, true, min_obs, min_idepth_hessian, gn_iterations);
 }
 
 // debug: CoarseDistanceMap::fwdWarpedIDDistFinal as the last selection left it, (w >> 1) * (h >> 1) floats, 0..39 and 1000

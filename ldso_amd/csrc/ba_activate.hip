@@ -11,24 +11,15 @@
 #include "ba_host.h"
 #include "lane.h"
 
-struct ActArgs {
-    const ldso_immature_t *pts;
-    ldso_activation_t *out;
-    int n, minObs, GNIts;
-    float minIdepthH_act;
-    const int32_t *sel;      // non-null: wavefront i works on pts[sel[i]] for i < *nSel (the list act_select.hip left on the device), out[i] is its record
-    const int32_t *nSel;
-};
-
 static __device__ __forceinline__ int min8(int v) {      // minimum over the 8 lanes of a slot, in all 8 lanes
     v = min(v, dpp_mov<0xB1>(v)); v = min(v, dpp_mov<0x4E>(v)); v = min(v, dpp_mov<0x141>(v));
     return v;
 }
 
+// One wavefront on candidate i of A against the window (B, D): the body of k_activate and k_activate_batch.
 template <int NSG>
-__global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_settings_t S, ActArgs A) {
+static __device__ __forceinline__ void activate_body(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ActArgs &A, const int i) {
     const int lane = threadIdx.x & 63, s = lane >> 3, k = lane & 7;
-    const int i = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     if (i >= A.n) return;
     if (A.sel && i >= *A.nSel) return;
     const ldso_immature_t &P = A.pts[A.sel ? A.sel[i] : i];
@@ -173,6 +164,25 @@ __global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_setti
     }
 }
 
+template <int NSG>
+__global__ __launch_bounds__(256) void k_activate(BaPtrs B, BaDims D, ldso_settings_t S, ActArgs A) {
+    activate_body<NSG>(B, D, S, A, __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6)));
+}
+
+// The same for the windows of a batch in one launch (ldso_ba_batch_activate_points / _select_activate_points): wavefront w of the launch belongs to the entry j of
+// `tab` with waveOff[j] <= w < waveOff[j + 1] (waveOff: nTab + 1 ascending offsets) and is that window's wavefront w - waveOff[j]; the window's pointers and
+// dimensions are those of its BatchItem.  The four wavefronts of a workgroup decide each for itself: a workgroup may straddle two windows.
+template <int NSG>
+__global__ __launch_bounds__(256) void k_activate_batch(const BatchItem *items, const ActWin *tab, const int32_t *waveOff, int nTab, ldso_settings_t S) {
+    const int w = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (w >= waveOff[nTab]) return;
+    int lo = 0, hi = nTab;          // the last entry that starts at or before w: entries without wavefronts share their offset with the next one and are passed over
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (waveOff[mid] <= w) lo = mid; else hi = mid; }
+    const ActWin &T = tab[lo];
+    const BatchItem &it = items[T.item];
+    activate_body<NSG>(it.B, it.D, S, T.A, w - waveOff[lo]);
+}
+
 hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs,
                               float minIdepthH_act, int GNIts, hipStream_t st) {
     if (n <= 0) return hipSuccess;
@@ -191,5 +201,14 @@ hipError_t ba_launch_activate_selected(const BaPtrs &B, const BaDims &D, const l
     const int blocks = (nMax + 3) / 4;
     if (D.nsg == 1) hipLaunchKernelGGL(k_activate<1>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
     else hipLaunchKernelGGL(k_activate<2>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
+    return hipGetLastError();
+}
+
+// every window of `d_tab` (nTab entries, totalWaves = the last of the nTab + 1 offsets in d_waveOff) in one launch; nsg as BaDims::nsg of the batch's slot-table width
+hipError_t ba_launch_activate_batch(const BatchItem *d_items, const ActWin *d_tab, const int32_t *d_waveOff, int nTab, int totalWaves, int nsg, const ldso_settings_t &S, hipStream_t st) {
+    if (nTab <= 0 || totalWaves <= 0) return hipSuccess;
+    const int blocks = (totalWaves + 3) / 4;
+    if (nsg == 1) hipLaunchKernelGGL(k_activate_batch<1>, dim3(blocks), dim3(256), 0, st, d_items, d_tab, d_waveOff, nTab, S);
+    else hipLaunchKernelGGL(k_activate_batch<2>, dim3(blocks), dim3(256), 0, st, d_items, d_tab, d_waveOff, nTab, S);
     return hipGetLastError();
 }

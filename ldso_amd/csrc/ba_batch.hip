@@ -4,10 +4,11 @@
 // (every window's reduce workgroups) -> k_gn_solve_batch (two control workgroups per window) -> k_linearize_batch (every window's
 // chunks).  Per-window arithmetic is exactly that of ldso_ba_enqueue_gn's split schedule; the windows only share the launches.
 // Behind optimize(), the key frame's two marginalisations for the whole batch: k_linearize_batch_marg -> k_reduce_batch_marg -> k_marg_gather_update_batch
-// (ldso_ba_batch_marginalize_points) and k_marg_frame_batch (ldso_ba_batch_marginalize_frame), per window the arithmetic of the single-window entries.
+// (ldso_ba_batch_marginalize_points) and k_marg_frame_batch (ldso_ba_batch_marginalize_frame), per window the arithmetic of the single-window entries.  The step behind
+// them, activatePointsMT for the batch (ldso_ba_batch_activate_points / _select_candidates / _select_activate_points), lives in act_select.hip beside the selection's buffers.
 #include "ba_host.h"
 
-static int batch_refresh(ldso_ba_batch *Bt) {
+int batch_refresh(ldso_ba_batch *Bt) {
     ldso_ba *H0 = Bt->h[0];
     const size_t n = Bt->h.size();
     for (int pass = 0; pass < 2; pass++) {          // pass 0: blocks numbered over the whole batch; pass 1: per half
@@ -377,9 +378,9 @@ int ldso_ba_batch_optimize(ldso_ba_batch_t *Bt, int mnumOptIts, int force_all_it
 
 }  // extern "C"
 
-// The staging arena of the two batched marginalisations: `up` bytes go up ([n MargWin | flags]), `down` bytes come down behind them.  Grown on demand; both streams are
-// idle when it is replaced (every user of the arena ends with a wait on the batch's stream).
-static int marg_stage(ldso_ba_batch *Bt, size_t up, size_t down) {
+// The staging arena of the batched marginalisations and activations: `up` bytes go up (the marginalisations: [n MargWin | flags]), `down` bytes come down behind
+// them.  Grown on demand; both streams are idle when it is replaced (every user of the arena ends with a wait on the batch's stream).
+int batch_stage(ldso_ba_batch *Bt, size_t up, size_t down) {
     const size_t need = up + down;
     if (need <= Bt->margCap) return LDSO_OK;
     CHK(hipStreamSynchronize(Bt->h[0]->stream));
@@ -439,7 +440,7 @@ int ldso_ba_batch_marginalize_points(ldso_ba_batch_t *Bt, const int32_t *const *
     }
     if (taking == 0) return LDSO_OK;
     const size_t up = (n * sizeof(MargWin) + nFlags * sizeof(int32_t) + 7) & ~(size_t) 7, down = nOut * sizeof(double);
-    RUN(marg_stage(Bt, up, down));
+    RUN(batch_stage(Bt, up, down));
     memcpy(Bt->h_marg, tab.data(), n * sizeof(MargWin));
     int32_t *h_flags = (int32_t *) (Bt->h_marg + n * sizeof(MargWin));
     for (int i = 0; i < n; i++) if (tab[(size_t) i].active) memcpy(h_flags + tab[(size_t) i].flagOff, flags[i], (size_t) Bt->h[i]->D.P * sizeof(int32_t));
@@ -492,7 +493,7 @@ int ldso_ba_batch_marginalize_frame(ldso_ba_batch_t *Bt, const int32_t *frame_id
     CHK(hipSetDevice(H0->device));
     RUN(batch_refresh(Bt));
     const size_t up = (n * sizeof(MargWin) + 7) & ~(size_t) 7, down = nOut * sizeof(double);
-    RUN(marg_stage(Bt, up, down));
+    RUN(batch_stage(Bt, up, down));
     memcpy(Bt->h_marg, tab.data(), n * sizeof(MargWin));
     CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, up, hipMemcpyHostToDevice, H0->stream));
     double *d_out = (double *) (Bt->d_marg + up);

@@ -18,6 +18,17 @@ hipError_t launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t ldsBytes, hip
     return hipGetLastError();
 }
 
+// k_activate's view of a call (ba_activate.hip), and one window's share of a batched one (k_activate_batch): `item` = the window's BatchItem in ldso_ba_batch::d_items
+struct ActArgs {
+    const ldso_immature_t *pts;
+    ldso_activation_t *out;
+    int n, minObs, GNIts;
+    float minIdepthH_act;
+    const int32_t *sel;      // non-null: wavefront i works on pts[sel[i]] for i < *nSel (the list act_select.hip left on the device), out[i] is its record
+    const int32_t *nSel;
+};
+struct ActWin { ActArgs A; int32_t item, pad_[3]; };
+
 // the launchers, defined beside their kernels (ba_linearize / ba_reduce / ba_solve / ba_activate .hip)
 hipError_t ba_launch_linearize(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, bool hasL, bool fix, int stepMode, const GnInit &gi, hipStream_t st);
 hipError_t ba_launch_reduce(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, bool hasL, int GSP, int atomicMode, bool hasPrior, float calibPrior, double l1, double il, int itCheck, hipStream_t st);
@@ -31,6 +42,7 @@ hipError_t ba_launch_acc_init(const BaPtrs &B, const BaDims &D, const GnInit &gi
 hipError_t ba_launch_gn_export(const BaPtrs &B, const BaDims &D, const ResSet &S, double *tail, hipStream_t st);
 hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
 hipError_t ba_launch_activate_selected(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, const int32_t *d_sel, const int32_t *d_nSel, ldso_activation_t *d_out, int nMax, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
+hipError_t ba_launch_activate_batch(const BatchItem *d_items, const ActWin *d_tab, const int32_t *d_waveOff, int nTab, int totalWaves, int nsg, const ldso_settings_t &S, hipStream_t st);
 hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, int FS, int cur, const ldso_settings_t &S, int stepMode, float calibPrior, hipStream_t st, int itCheck = -1);
 hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st, int itCheck = -1);
 hipError_t ba_launch_gn_solve_batch(const BatchItem *d_items, int nWin, const BaDims &Dmax, int cur, const ldso_settings_t &St, int iteration, double lambda, hipStream_t st, int logIdx = -1, int itCheck = -1);
@@ -163,10 +175,12 @@ struct ldso_ba_batch {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evEnd = nullptr;
     BaDims Dmax;
     double *d_scalars = nullptr, *h_scalars = nullptr;      // [n][16]: every window's scalars after ldso_ba_batch_optimize (device block, pinned host copy)
-    // ldso_ba_batch_marginalize_points / _frame: one pinned arena and its device twin, grown on demand: [n MargWin | the flags of all windows | pad to 8] go up in one
-    // copy, [the windows' (H_M | b_M) in doubles] come down in one
+    // The staging arena of the batched key-frame steps (batch_stage): one pinned arena and its device twin, grown on demand.  ldso_ba_batch_marginalize_points /
+    // _frame: [n MargWin | the flags of all windows | pad to 8] go up in one copy, [the windows' (H_M | b_M) in doubles] come down in one; the batched activation
+    // entries (act_select.hip): [tables | every window's inputs] up, [every window's results] down, the selection's scratch behind them on the device
     char *h_marg = nullptr, *d_marg = nullptr;
     size_t margCap = 0;
+    int selLdsLimit = -1, selLdsSet = 0; // dynamic LDS k_act_select_batch may have on this device (-1: not asked yet), and what its attribute was last raised to
 };
 
 // the immature-point tracer (trace.hip)
@@ -238,6 +252,9 @@ inline int raw_to_images(float *&d_color, const float *irradiance, int w, int h,
 // trace_compact_finish swaps the buffers and takes the new count once the caller has synchronised `st`.
 int trace_compact_enqueue(ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, bool haveMap, hipStream_t st);
 void trace_compact_finish(ldso_tracer *T);
+// ba_batch.hip: the windows' descriptors as they are now into ldso_ba_batch::d_items; the batch's staging arena with room for `up` + `down` bytes
+int batch_refresh(ldso_ba_batch *Bt);
+int batch_stage(ldso_ba_batch *Bt, size_t up, size_t down);
 int build_chunks(ldso_ba *H);          // ba_window.hip
 int rechunk(ldso_ba *H);
 // ba_optimize.hip: the launch helpers (with optional HIP-event timing) and what every caller of a launcher fills in the same way
