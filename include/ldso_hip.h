@@ -319,6 +319,38 @@ int ldso_ba_batch_activate_points(ldso_ba_batch_t *b, const int *n /*n_win*/, co
 int ldso_ba_batch_select_candidates(ldso_ba_batch_t *b, ldso_act_job_t *jobs /*n_win*/, float minTraceQuality);
 int ldso_ba_batch_select_activate_points(ldso_ba_batch_t *b, ldso_act_job_t *jobs /*n_win*/, float minTraceQuality, int min_obs, float min_idepth_hessian,
                                          int gn_iterations);
+/* The step that closes the key-frame loop: every window of the batch becomes the next one, with a number of launches, copies and host synchronisations that does not
+ * depend on n, and the batch stays usable (it re-cuts itself).
+ * ldso_ba_batch_update_windows = ldso_ba_update_window(handle_i, <jobs[i]>) for every window with jobs[i].frame_from != NULL: the arguments of the single-window entry in a
+ * ldso_win_job_t; per window the result is byte for byte what that entry leaves on the handle alone (window image, zero fills, prior reset, no applied linearisation).  One
+ * upload through the batch's arena (every window's delta, chunk tables and one transfer table), three launches (k_win_rebuild_batch -> k_win_scatter_batch ->
+ * k_point_stats_batch), one wait.  Validation comes first and is all-or-nothing: the checks of ldso_ba_update_window run for every participating window before anything is
+ * written; LDSO_E_INVALID leaves every handle and the batch as they were.  Also refused: a NULL batch or job array, a handle with a pending linearisation or linearised
+ * residuals, a sharded handle, a new F whose slot-table width differs from the batch's (in practice F > 8), a call in which no window takes part.
+ * The batch then re-runs the chunk policy of ldso_ba_batch_create on the new point counts (it may change between balanced and regular chunks) and re-cuts every window.
+ * The cost of sitting out: a window with jobs[i].frame_from == NULL keeps its window bytes and its applied state, but is re-cut like the others - one re-linearisation
+ * launch, its own small chunk-table copies and wait, and its ping-pong parity flips, as in ldso_ba_batch_create.
+ * A failure behind the validation (allocation, launch) leaves the participating handles without a window and the batch refusing every call but ldso_ba_batch_destroy.
+ * ldso_ba_update_window on a member outside this call is still refused by the next batched call of a balanced batch.
+ * ldso_ba_batch_set_frames = ldso_ba_set_frames(handle_i, frames, calib) followed by ldso_ba_set_prior(handle_i, HM, bM) for every window with jobs[i].frames != NULL
+ * (HM / bM NULL = zero; the prior counts as present when either is given, as ldso_ba_set_prior has it): one upload, one distributing launch, one launch for the adjoints
+ * and the precalc values of all windows, one wait; per window the device state is byte for byte that of the two single-window calls. */
+typedef struct {            /* one window's share of ldso_ba_batch_update_windows: the arguments of ldso_ba_update_window */
+    int F; const int32_t *image_slot, *frame_from;                             /* frame_from == NULL: the window takes no part */
+    int P; const int32_t *point_from; const uint32_t *res_mask;
+    int n_fresh; const ldso_point_t *fresh;
+    int n_fresh_res; const ldso_residual_t *fresh_res; const float *fresh_mrb; const int32_t *fresh_ngr;
+} ldso_win_job_t;
+typedef struct {            /* one window's share of ldso_ba_batch_set_frames */
+    const ldso_frame_t *frames; const ldso_calib_t *calib;                     /* frames == NULL: the window takes no part */
+    const double *HM, *bM;                                                     /* (8F+4)^2 row-major, 8F+4; NULL = zero */
+} ldso_frames_job_t;
+int ldso_ba_batch_update_windows(ldso_ba_batch_t *b, const ldso_win_job_t *jobs /*n_win*/);
+int ldso_ba_batch_set_frames(ldso_ba_batch_t *b, const ldso_frames_job_t *jobs /*n_win*/);
+/* 1: the batch runs balanced cuts (one workgroup per CU and launch works through a run of chunks cut to measure), 0: regular chunks (ldso_ba_batch_chunk_points) */
+int ldso_ba_batch_balanced(ldso_ba_batch_t *b, int *balanced);
+/* the marginalisation prior as the handle holds it on the device ((8F+4)^2 row-major, 8F+4; either may be NULL), and whether it counts as present */
+int ldso_ba_get_prior(ldso_ba_t *h, double *HM, double *bM, int *has_prior);
 int ldso_ba_batch_destroy(ldso_ba_batch_t *b);
 /* points per workgroup ldso_ba_batch_create gave the windows of the batch - since round 6 the AVERAGE, rounded: the cuts are uneven, ldso_ba_get_chunk_cuts has
  * them - (0: their single-window chunking was kept; ldso_ba_batch_destroy restores it) */

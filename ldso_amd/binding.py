@@ -467,6 +467,13 @@ class BA:
         bM = np.ascontiguousarray(bM, np.float64) if bM is not None else None
         _chk(self.L.ldso_ba_set_prior(self.h, _p(HM), _p(bM)))
 
+    def get_prior(self):
+        """the marginalisation prior as the device holds it (ldso_ba_get_prior) -> (HM, bM, has_prior)"""
+        n = 8 * self.F + 4
+        HM, bM, has = np.zeros((n, n)), np.zeros(n), C.c_int()
+        _chk(self.L.ldso_ba_get_prior(self.h, _p(HM), _p(bM), C.byref(has)))
+        return HM, bM, bool(has.value)
+
     def load_window(self, win: synth.Window):
         self.set_settings(win.settings)
         for f in range(win.F):
@@ -748,6 +755,17 @@ class ActJob(C.Structure):
                 ("n_selected", C.c_int), ("out", C.c_void_p)]
 
 
+class WinJob(C.Structure):
+    """ldso_win_job_t (ldso_hip.h): one window's share of ldso_ba_batch_update_windows = the arguments of ldso_ba_update_window"""
+    _fields_ = [("F", C.c_int), ("image_slot", C.c_void_p), ("frame_from", C.c_void_p), ("P", C.c_int), ("point_from", C.c_void_p), ("res_mask", C.c_void_p),
+                ("n_fresh", C.c_int), ("fresh", C.c_void_p), ("n_fresh_res", C.c_int), ("fresh_res", C.c_void_p), ("fresh_mrb", C.c_void_p), ("fresh_ngr", C.c_void_p)]
+
+
+class FramesJob(C.Structure):
+    """ldso_frames_job_t (ldso_hip.h): one window's share of ldso_ba_batch_set_frames"""
+    _fields_ = [("frames", C.c_void_p), ("calib", C.c_void_p), ("HM", C.c_void_p), ("bM", C.c_void_p)]
+
+
 class BABatch:
     """ldso_ba_batch_*: the GN iteration of several independent windows per launch."""
 
@@ -863,6 +881,66 @@ class BABatch:
         J, keep = self._jobs(jobs, True)
         _chk(self.L.ldso_ba_batch_select_activate_points(self.h, J, C.c_float(min_trace_quality), C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations)))
         return [None if k is None else (k[6], k[7][:J[i].n_selected].copy(), k[8][:J[i].n_selected].copy()) for i, k in enumerate(keep)]
+
+    def update_windows(self, jobs):
+        """ldso_ba_batch_update_windows: every window of the batch becomes its next one in one call.  jobs[i]: the arguments of BA.update_window as a tuple / list
+        (image_slots, frame_from, point_from, res_mask[, fresh, fresh_res, fresh_mrb, fresh_ngr]) or a dict with those names, or None for a window that sits out
+        (a tuple whose frame_from is None sits out too).  The handles' F / P / R are refreshed afterwards, as BA.update_window does."""
+        n = len(self.handles)
+        assert len(jobs) == n
+        names = ("image_slots", "frame_from", "point_from", "res_mask", "fresh", "fresh_res", "fresh_mrb", "fresh_ngr")
+        J = (WinJob * n)()
+        keep = []
+        for i, job in enumerate(jobs):
+            if job is None:
+                continue
+            a = [job.get(k) for k in names] if isinstance(job, dict) else (list(job) + [None] * 8)[:8]
+            if a[1] is None:
+                continue
+            sl = np.ascontiguousarray(a[0], np.int32); ff = np.ascontiguousarray(a[1], np.int32)
+            pf = np.ascontiguousarray(a[2], np.int32); mk = np.ascontiguousarray(a[3], np.uint32)
+            assert len(sl) == len(ff) and len(pf) == len(mk)
+            nf = 0 if a[4] is None else len(a[4]); nr = 0 if a[5] is None else len(a[5])
+            fp = np.ascontiguousarray(a[4]) if nf else None; fr = np.ascontiguousarray(a[5]) if nr else None
+            fm = np.ascontiguousarray(a[6], np.float32) if nf else None; fg = np.ascontiguousarray(a[7], np.int32) if nf else None
+            keep.append((sl, ff, pf, mk, fp, fr, fm, fg))
+            j = J[i]
+            j.F, j.image_slot, j.frame_from, j.P, j.point_from, j.res_mask = len(sl), sl.ctypes.data, ff.ctypes.data, len(pf), pf.ctypes.data, mk.ctypes.data
+            j.n_fresh, j.fresh, j.n_fresh_res, j.fresh_res = nf, (fp.ctypes.data if nf else None), nr, (fr.ctypes.data if nr else None)
+            j.fresh_mrb, j.fresh_ngr = (fm.ctypes.data if nf else None), (fg.ctypes.data if nf else None)
+        try:
+            _chk(self.L.ldso_ba_batch_update_windows(self.h, J))
+        finally:
+            for h in self.handles:
+                h._sync_dims()
+
+    def set_frames(self, frames_list, calib_list, priors=None):
+        """ldso_ba_batch_set_frames: BA.set_frames(frames, calib) followed by BA.set_prior(HM, bM) on every window with frames_list[i] not None; priors[i] = (HM, bM),
+        either may be None (zero), or None for a zero prior; priors=None: zero priors everywhere."""
+        n = len(self.handles)
+        assert len(frames_list) == n and len(calib_list) == n and (priors is None or len(priors) == n)
+        J = (FramesJob * n)()
+        keep = []
+        for i, fr in enumerate(frames_list):
+            if fr is None:
+                continue
+            fr = np.ascontiguousarray(fr); c = np.ascontiguousarray(calib_list[i])
+            assert len(fr) == self.handles[i].F
+            HM, bM = (None, None) if priors is None or priors[i] is None else priors[i]
+            HM = np.ascontiguousarray(HM, np.float64) if HM is not None else None
+            bM = np.ascontiguousarray(bM, np.float64) if bM is not None else None
+            k = 8 * self.handles[i].F + 4
+            assert (HM is None or HM.size == k * k) and (bM is None or bM.size == k)
+            keep.append((fr, c, HM, bM))
+            J[i].frames, J[i].calib = fr.ctypes.data, c.ctypes.data
+            J[i].HM, J[i].bM = (None if HM is None else HM.ctypes.data), (None if bM is None else bM.ctypes.data)
+        _chk(self.L.ldso_ba_batch_set_frames(self.h, J))
+
+    def balanced(self):
+        """True: the batch runs balanced cuts (ldso_ba_batch_balanced), False: regular chunks of chunk_points() points"""
+        b = C.c_int()
+        _chk(self.L.ldso_ba_batch_balanced(self.h, C.byref(b)))
+        return bool(b.value)
 
     def sync(self):
         self.handles[0].sync()

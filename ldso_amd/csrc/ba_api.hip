@@ -7,6 +7,24 @@
 static thread_local std::string g_err;
 void ldso_set_error(const std::string &s) { g_err = s; }
 
+// the device records of the frames and the calibration as ldso_ba_set_frames / ldso_ba_batch_set_frames upload them
+void fill_dev_frames(const ldso_ba *H, const ldso_frame_t *fr, const ldso_calib_t *calib, DevFrame *df, DevCalib *dc) {
+    const int F = H->D.F;
+    for (int f = 0; f < F; f++) {
+        DevFrame &d = df[f];
+        memset(&d, 0, sizeof(d));
+        memcpy(d.evalPT, fr[f].worldToCam_evalPT, sizeof(d.evalPT));
+        memcpy(d.state, fr[f].state, sizeof(d.state)); memcpy(d.state_zero, fr[f].state_zero, sizeof(d.state_zero));
+        memcpy(d.state_backup, fr[f].state, sizeof(d.state));
+        memcpy(d.prior, fr[f].prior, sizeof(d.prior));
+        memcpy(d.ns_pose, fr[f].nullspaces_pose, sizeof(d.ns_pose)); memcpy(d.ns_scale, fr[f].nullspaces_scale, sizeof(d.ns_scale));
+        memcpy(d.ns_affine, fr[f].nullspaces_affine, sizeof(d.ns_affine));
+        d.ab_exposure = fr[f].ab_exposure; d.frameEnergyTH = fr[f].frameEnergyTH; d.frameID = fr[f].frameID; d.imgSlot = H->imageSlot[f];
+    }
+    memset(dc, 0, sizeof(*dc));
+    for (int i = 0; i < 4; i++) { dc->value[i] = calib->value[i]; dc->value_zero[i] = calib->value_zero[i]; dc->value_backup[i] = calib->value[i]; }
+}
+
 extern "C" {
 
 int ldso_version(void) { return 100; }
@@ -259,20 +277,8 @@ int ldso_ba_set_frames(ldso_ba_t *H, const ldso_frame_t *fr, const ldso_calib_t 
     CHK(hipSetDevice(H->device));
     const int F = H->D.F;
     std::vector<DevFrame> df(F);
-    for (int f = 0; f < F; f++) {
-        DevFrame &d = df[f];
-        memset(&d, 0, sizeof(d));
-        memcpy(d.evalPT, fr[f].worldToCam_evalPT, sizeof(d.evalPT));
-        memcpy(d.state, fr[f].state, sizeof(d.state)); memcpy(d.state_zero, fr[f].state_zero, sizeof(d.state_zero));
-        memcpy(d.state_backup, fr[f].state, sizeof(d.state));
-        memcpy(d.prior, fr[f].prior, sizeof(d.prior));
-        memcpy(d.ns_pose, fr[f].nullspaces_pose, sizeof(d.ns_pose)); memcpy(d.ns_scale, fr[f].nullspaces_scale, sizeof(d.ns_scale));
-        memcpy(d.ns_affine, fr[f].nullspaces_affine, sizeof(d.ns_affine));
-        d.ab_exposure = fr[f].ab_exposure; d.frameEnergyTH = fr[f].frameEnergyTH; d.frameID = fr[f].frameID; d.imgSlot = H->imageSlot[f];
-    }
     DevCalib dc;
-    memset(&dc, 0, sizeof(dc));
-    for (int i = 0; i < 4; i++) { dc.value[i] = calib->value[i]; dc.value_zero[i] = calib->value_zero[i]; dc.value_backup[i] = calib->value[i]; }
+    fill_dev_frames(H, fr, calib, df.data(), &dc);
     CHK(hipMemcpyAsync(H->B.frames, df.data(), F * sizeof(DevFrame), hipMemcpyHostToDevice, H->stream));
     CHK(hipMemcpyAsync(H->B.calib, &dc, sizeof(dc), hipMemcpyHostToDevice, H->stream));
     CHK(hipStreamSynchronize(H->stream));
@@ -298,6 +304,17 @@ int ldso_ba_set_prior(ldso_ba_t *H, const double *HM, const double *bM) {
     if (HM) CHK(hipMemcpyAsync(H->B.HM, HM, bytesH, hipMemcpyHostToDevice, H->stream)); else CHK(hipMemsetAsync(H->B.HM, 0, bytesH, H->stream));
     if (bM) CHK(hipMemcpyAsync(H->B.bM, bM, bytesB, hipMemcpyHostToDevice, H->stream)); else CHK(hipMemsetAsync(H->B.bM, 0, bytesB, H->stream));
     CHK(hipStreamSynchronize(H->stream));
+    return LDSO_OK;
+}
+
+int ldso_ba_get_prior(ldso_ba_t *H, double *HM, double *bM, int *has_prior) {
+    REQ(H && H->D.P > 0 && H->D.n > 0, "ldso_ba_get_prior: set the window first");
+    CHK(hipSetDevice(H->device));
+    const size_t n = H->D.n;
+    if (HM) CHK(hipMemcpyAsync(HM, H->B.HM, n * n * 8, hipMemcpyDeviceToHost, H->stream));
+    if (bM) CHK(hipMemcpyAsync(bM, H->B.bM, n * 8, hipMemcpyDeviceToHost, H->stream));
+    CHK(hipStreamSynchronize(H->stream));
+    if (has_prior) *has_prior = H->hasPrior ? 1 : 0;
     return LDSO_OK;
 }
 

@@ -5,10 +5,13 @@
 // chunks).  Per-window arithmetic is exactly that of ldso_ba_enqueue_gn's split schedule; the windows only share the launches.
 // Behind optimize(), the key frame's two marginalisations for the whole batch: k_linearize_batch_marg -> k_reduce_batch_marg -> k_marg_gather_update_batch
 // (ldso_ba_batch_marginalize_points) and k_marg_frame_batch (ldso_ba_batch_marginalize_frame), per window the arithmetic of the single-window entries.  The step behind
-// them, activatePointsMT for the batch (ldso_ba_batch_activate_points / _select_candidates / _select_activate_points), lives in act_select.hip beside the selection's buffers.
+// them, activatePointsMT for the batch (ldso_ba_batch_activate_points / _select_candidates / _select_activate_points), lives in act_select.hip beside the selection's buffers, and
+// the step that closes the loop - every window becomes its next one (ldso_ba_batch_update_windows / _set_frames) - in ba_window.hip beside the single-window update it shares its
+// pieces with; the chunk policy it re-runs is batch_chunk_policy here.
 #include "ba_host.h"
 
 int batch_refresh(ldso_ba_batch *Bt) {
+    REQ(!Bt->lost, "ldso_ba_batch: a ldso_ba_batch_update_windows that failed behind its validation left windows of the batch unset: destroy and re-create the batch");
     ldso_ba *H0 = Bt->h[0];
     const size_t n = Bt->h.size();
     for (int pass = 0; pass < 2; pass++) {          // pass 0: blocks numbered over the whole batch; pass 1: per half
@@ -115,6 +118,49 @@ static void balance_batch(ldso_ba *const *handles, int i0, int i1, int nWG, int 
     }
     balance_segments(segs, nWG, c0, &cuts, &wg, nullptr);
 }
+// Chunking of a batch: the launch is filled by all windows together, so a workgroup takes several points per wavefront (its fixed
+// costs - operand staging, block reduction, ~4.5 us - are then a fraction of its life) while the grid still holds a few workgroups
+// per CU for balance.  Handles with an explicit ldso_ba_set_chunk_points keep theirs.  Host logic on the windows' point counts and host
+// runs (D.P, h_phost); ldso_ba_batch_create applies it with rechunk, ldso_ba_batch_update_windows re-runs it on the new windows.
+void batch_chunk_policy(ldso_ba *const *handles, int n, BatchCuts &C) {
+    ldso_ba *H0 = handles[0];
+    C.balanced = false; C.CH = 0;
+    C.cuts.assign((size_t) n, std::vector<int32_t>());
+    for (int u = 0; u < 3; u++) C.wg[u].clear();
+    long total = 0;
+    for (int i = 0; i < n; i++) total += handles[i]->D.P;
+    int ppw = (int) (total / ((long) H0->numCU * LD_WAVES));               // points per wavefront slot of the chip
+    bool every = true;
+    for (int i = 0; i < n; i++) every = every && handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty();
+    if (ppw > 1 && every) {
+        // Round 6: every workgroup of a launch gets the SAME load.  With regular chunks the batched launch ran as ceil(chunks / CUs) rounds of equal
+        // workgroups - 1344 on 256 CUs: the last round a quarter full - and every chunk paid its fixed costs (staging, pipeline fill, block reduction:
+        // about two points per wavefront) for six points per wavefront.  Now one workgroup per CU and launch works through a run of chunks cut to measure.
+        const int c0 = 2 * LD_WAVES;          // fixed cost of a chunk in points (two rounds of the workgroup's wavefronts)
+        const int n0 = (n >= 4) ? n / 2 : n;
+        // A half-batch launch does not take every CU: the other half's k_reduce_batch_dense / k_gn_solve_batch run beside it (two streams), and a workgroup that
+        // owns its CU for the whole launch leaves them nothing to start on.  Measured (32 windows, MI355X): 128 / 192 / 208 / 224 / 240 / 256 workgroups per half
+        // -> 141.6 / 159.2 / 162.2 / 168.3 / 167.7 / 149.5 k window-iterations/s (profiles/r06_batch_sweeps.log).
+        const int nWG = (n >= 4) ? std::max(1, H0->numCU * 7 / 8) : H0->numCU;
+        balance_batch(handles, 0, n0, nWG, c0, C.cuts, C.wg[1]);
+        if (n0 < n) balance_batch(handles, n0, n, nWG, c0, C.cuts, C.wg[2]);
+        // the whole-batch launch (ldso_ba_batch_time_linearize) runs the two halves' workgroups one after the other
+        C.wg[0] = C.wg[1];
+        if (n0 < n) for (size_t u = 1; u < C.wg[2].size(); u++) C.wg[0].push_back(C.wg[1].back() + C.wg[2][u]);
+        C.balanced = true;
+    } else {
+        // regular chunks of up to 6 points per wavefront (round 4, B = 32: 122.0 / 139.3 / 128.6 k window-iterations/s at 4 / 6 / 8)
+        ppw = ppw < 1 ? 1 : ppw > 6 ? 6 : ppw;
+        C.CH = ppw > 1 ? ppw * LD_WAVES : 0;          // ppw == 1: the single-window chunking already is the right one
+    }
+}
+// what ldso_ba_batch_chunk_points reports for windows cut by the policy: the regular chunk, or the rounded average of the balanced cuts
+int batch_chunk_points(ldso_ba *const *handles, int n, const BatchCuts &C) {
+    if (!C.balanced) return C.CH;
+    long total = 0, chunks = 0;
+    for (int i = 0; i < n; i++) { total += handles[i]->D.P; chunks += handles[i]->D.nChunks; }
+    return (int) std::max<long>(1, (total + chunks / 2) / std::max<long>(chunks, 1));
+}
 extern "C" {
 
 // host logic, no device: `n_seg` segments of seg_points[i] points each (in launch order; a chunk never spans two segments), `n_wg` workgroups, `chunk_cost` points of fixed
@@ -152,56 +198,16 @@ int ldso_ba_batch_create(ldso_ba_t *const *handles, int n, ldso_ba_batch_t **out
         REQ(H->chunkPoints == H0->chunkPoints, "ldso_ba_batch_create: the handles of a batch share one chunking policy (ldso_ba_set_chunk_points: all automatic or all the same value)");
     }
     CHK(hipSetDevice(H0->device));
-    // Chunking of a batch: the launch is filled by all windows together, so a workgroup takes several points per wavefront (its fixed
-    // costs - operand staging, block reduction, ~4.5 us - are then a fraction of its life) while the grid still holds a few workgroups
-    // per CU for balance.  Handles with an explicit ldso_ba_set_chunk_points keep theirs.
-    int Bt_chunk = 0;
-    bool balanced = false;
-    std::vector<int32_t> wgTab[3];
-    {
-        long total = 0;
-        for (int i = 0; i < n; i++) total += handles[i]->D.P;
-        int ppw = (int) (total / ((long) H0->numCU * LD_WAVES));               // points per wavefront slot of the chip
-        bool every = true;
-        for (int i = 0; i < n; i++) every = every && handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty();
-        if (ppw > 1 && every) {
-            // Round 6: every workgroup of a launch gets the SAME load.  With regular chunks the batched launch ran as ceil(chunks / CUs) rounds of equal
-            // workgroups - 1344 on 256 CUs: the last round a quarter full - and every chunk paid its fixed costs (staging, pipeline fill, block reduction:
-            // about two points per wavefront) for six points per wavefront.  Now one workgroup per CU and launch works through a run of chunks cut to measure.
-            const int c0 = 2 * LD_WAVES;          // fixed cost of a chunk in points (two rounds of the workgroup's wavefronts)
-            const int n0 = (n >= 4) ? n / 2 : n;
-            // A half-batch launch does not take every CU: the other half's k_reduce_batch_dense / k_gn_solve_batch run beside it (two streams), and a workgroup that
-            // owns its CU for the whole launch leaves them nothing to start on.  Measured (32 windows, MI355X): 128 / 192 / 208 / 224 / 240 / 256 workgroups per half
-            // -> 141.6 / 159.2 / 162.2 / 168.3 / 167.7 / 149.5 k window-iterations/s (profiles/r06_batch_sweeps.log).
-            const int nWG = (n >= 4) ? std::max(1, H0->numCU * 7 / 8) : H0->numCU;
-            std::vector<std::vector<int32_t>> cuts((size_t) n);
-            balance_batch(handles, 0, n0, nWG, c0, cuts, wgTab[1]);
-            if (n0 < n) balance_batch(handles, n0, n, nWG, c0, cuts, wgTab[2]);
-            // the whole-batch launch (ldso_ba_batch_time_linearize) runs the two halves' workgroups one after the other
-            wgTab[0] = wgTab[1];
-            if (n0 < n) for (size_t u = 1; u < wgTab[2].size(); u++) wgTab[0].push_back(wgTab[1].back() + wgTab[2][u]);
-            for (int i = 0; i < n; i++) {
-                handles[i]->chunkCuts = cuts[i];
-                const int r_ = rechunk(handles[i]);
-                if (r_ != LDSO_OK) { for (int k = 0; k <= i; k++) { handles[k]->chunkCuts.clear(); rechunk(handles[k]); } return r_; }      // leave nobody with the batch's chunks
-            }
-            long chunks = 0;
-            for (int i = 0; i < n; i++) chunks += handles[i]->D.nChunks;
-            Bt_chunk = (int) std::max<long>(1, (total + chunks / 2) / chunks);
-            balanced = true;
-        } else {
-            // regular chunks of up to 6 points per wavefront (round 4, B = 32: 122.0 / 139.3 / 128.6 k window-iterations/s at 4 / 6 / 8)
-            ppw = ppw < 1 ? 1 : ppw > 6 ? 6 : ppw;
-            const int CH = ppw * LD_WAVES;
-            Bt_chunk = ppw > 1 ? CH : 0;
-            for (int i = 0; i < n; i++) if (handles[i]->chunkPoints == 0 && handles[i]->chunkCuts.empty() && ppw > 1) {      // ppw == 1: the single-window chunking already is the right one
-                handles[i]->chunkPoints = CH;
-                const int r_ = rechunk(handles[i]);
-                handles[i]->chunkPoints = 0;                                         // the policy stays "automatic": the next ldso_ba_set_window re-chunks for a single window
-                if (r_ != LDSO_OK) { for (int k = 0; k <= i; k++) rechunk(handles[k]); return r_; }      // leave nobody with the batch's chunks
-            }
-        }
+    // the chunk policy (batch_chunk_policy), applied: a window's applied state is re-formed under its new chunks (rechunk)
+    BatchCuts cutsOf;
+    batch_chunk_policy(handles, n, cutsOf);
+    for (int i = 0; i < n; i++) {
+        const int r_ = batch_cut_window(handles[i], i, cutsOf, false, rechunk);
+        if (r_ != LDSO_OK) { for (int k = 0; k <= i; k++) { if (cutsOf.balanced) handles[k]->chunkCuts.clear(); rechunk(handles[k]); } return r_; }      // leave nobody with the batch's chunks
     }
+    const int Bt_chunk = batch_chunk_points(handles, n, cutsOf);
+    const bool balanced = cutsOf.balanced;
+    const std::vector<int32_t> *wgTab = cutsOf.wg;
     ldso_ba_batch *Bt = new ldso_ba_batch();
     Bt->chunkPoints = Bt_chunk;
     Bt->balanced = balanced;
@@ -246,6 +252,12 @@ int ldso_ba_batch_reduce_splits(ldso_ba_batch_t *Bt, int *splits) {
 int ldso_ba_batch_chunk_points(ldso_ba_batch_t *Bt, int *points_per_workgroup) {
     REQ(Bt && points_per_workgroup, "ldso_ba_batch_chunk_points: null argument");
     *points_per_workgroup = Bt->chunkPoints;
+    return LDSO_OK;
+}
+// which of the policy's two modes the batch is in: 1 = balanced cuts (one workgroup per CU works through a run of chunks), 0 = regular chunks
+int ldso_ba_batch_balanced(ldso_ba_batch_t *Bt, int *balanced) {
+    REQ(Bt && balanced, "ldso_ba_batch_balanced: null argument");
+    *balanced = Bt->balanced ? 1 : 0;
     return LDSO_OK;
 }
 

@@ -181,6 +181,23 @@ struct ldso_ba_batch {
     char *h_marg = nullptr, *d_marg = nullptr;
     size_t margCap = 0;
     int selLdsLimit = -1, selLdsSet = 0; // dynamic LDS k_act_select_batch may have on this device (-1: not asked yet), and what its attribute was last raised to
+    bool lost = false;                 // a ldso_ba_batch_update_windows failed behind its validation: members hold no window, batch_refresh refuses, ldso_ba_batch_destroy cleans up
+};
+
+// A call that replaces the window of a handle and fails half way (bad indices, allocation) must not leave the dimensions of the NEW window over the data of the
+// old one: the handle then holds no window (every entry point that needs one says so).  ldso_ba_set_window, ldso_ba_update_window, ldso_ba_batch_update_windows.
+struct WinGuard {
+    ldso_ba *H; bool ok;
+    ~WinGuard() { if (!ok) { H->D.P = 0; H->D.R = 0; H->R = 0; H->appliedValid = false; H->itemValid = false; } }
+};
+
+// The chunking of a batch as its policy decides it (ba_batch.hip: batch_chunk_policy; ldso_ba_batch_create and ldso_ba_batch_update_windows): balanced cuts per window
+// and the workgroup tables of the three launches (whole batch | half A | half B), or regular chunks of CH points (0: the single-window chunking is the right one).
+struct BatchCuts {
+    bool balanced = false;
+    int CH = 0;
+    std::vector<std::vector<int32_t>> cuts;
+    std::vector<int32_t> wg[3];
 };
 
 // the immature-point tracer (trace.hip)
@@ -257,6 +274,23 @@ int batch_refresh(ldso_ba_batch *Bt);
 int batch_stage(ldso_ba_batch *Bt, size_t up, size_t down);
 int build_chunks(ldso_ba *H);          // ba_window.hip
 int rechunk(ldso_ba *H);
+// ba_batch.hip: the chunk policy of a batch from the windows' point counts and host runs (host logic; nothing is applied), how one window takes its share of it
+// (`cut` = rechunk for a window with a resident applied state, a host-only plan inside ldso_ba_batch_update_windows; `always`: cut even where the policy leaves the
+// single-window chunking alone), and the points per workgroup the batch reports once its windows are cut
+void batch_chunk_policy(ldso_ba *const *handles, int n, BatchCuts &C);
+template <class Cut> int batch_cut_window(ldso_ba *H, int i, const BatchCuts &C, bool always, Cut cut) {
+    if (C.balanced) { H->chunkCuts = C.cuts[(size_t) i]; return cut(H); }
+    if (C.CH > 0 && H->chunkPoints == 0 && H->chunkCuts.empty()) {
+        H->chunkPoints = C.CH;
+        const int r_ = cut(H);
+        H->chunkPoints = 0;                                         // the policy stays "automatic": the next ldso_ba_set_window re-chunks for a single window
+        return r_;
+    }
+    return always ? cut(H) : LDSO_OK;                               // CH == 0: the single-window chunking already is the right one
+}
+int batch_chunk_points(ldso_ba *const *handles, int n, const BatchCuts &C);
+// ba_api.hip: the device records of ldso_ba_set_frames for the resident window of H (df: F entries)
+void fill_dev_frames(const ldso_ba *H, const ldso_frame_t *fr, const ldso_calib_t *calib, DevFrame *df, DevCalib *dc);
 // ba_optimize.hip: the launch helpers (with optional HIP-event timing) and what every caller of a launcher fills in the same way
 void t_begin(ldso_ba *H, int which);
 void t_end(ldso_ba *H);

@@ -1,5 +1,6 @@
 // ba_window.hip — the window of a handle: upload through the staging arena (ldso_ba_set_window), the delta against the resident window
-// (ldso_ba_update_window and the edit API that records one), the flattening into chunks.
+// (ldso_ba_update_window and the edit API that records one), the flattening into chunks; the same delta, and the frames / prior behind it, for every window of a batch
+// (ldso_ba_batch_update_windows, ldso_ba_batch_set_frames).
 #include "ba_host.h"
 
 // One entry of the upload table at the head of the staging arena: copy `words` 32-bit words from arena offset `src` (bytes) to `dst`,
@@ -20,11 +21,34 @@ __global__ __launch_bounds__(256) void k_win_scatter(const char *__restrict__ ar
         }
     }
 }
+// The scatter of a whole batch of windows (ldso_ba_batch_update_windows / _set_frames): ONE table over all windows.  With 32 x ~25 entries a workgroup that walked every
+// entry (k_win_scatter) would spend its life in the loop head, so the WORDS are dealt out instead: a work unit is LD_XFER_UNIT consecutive words of one entry, unit0[e]
+// the first unit of entry e (unit0[nEntries] = the grid), and a workgroup finds its entry by bisection (uniform: scalar loads).  16-byte accesses where both sides allow.
+#define LD_XFER_UNIT 4096
+__global__ __launch_bounds__(256) void k_win_scatter_batch(const char *__restrict__ arena, const WinXfer *__restrict__ tab, const int32_t *__restrict__ unit0, int nEntries) {
+    const int u = blockIdx.x;
+    int lo = 0, hi = nEntries - 1;          // the last entry whose first unit is <= u
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (unit0[mid] <= u) lo = mid; else hi = mid - 1; }
+    const WinXfer x = tab[lo];
+    const size_t w0 = (size_t) (u - unit0[lo]) * LD_XFER_UNIT;
+    if (w0 >= (size_t) x.words) return;
+    const size_t left = (size_t) x.words - w0, n = left < (size_t) LD_XFER_UNIT ? left : (size_t) LD_XFER_UNIT;
+    unsigned *dst = static_cast<unsigned *>(x.dst) + w0;
+    const bool zero = x.src == LD_XFER_ZERO;
+    const unsigned *src = zero ? nullptr : reinterpret_cast<const unsigned *>(arena + x.src) + w0;
+    const bool wide = ((reinterpret_cast<size_t>(dst) | (zero ? (size_t) 0 : reinterpret_cast<size_t>(src))) & 15) == 0;
+    const size_t n4 = wide ? n / 4 : 0;
+    for (size_t i = threadIdx.x; i < n4; i += blockDim.x) reinterpret_cast<uint4 *>(dst)[i] = zero ? make_uint4(0u, 0u, 0u, 0u) : reinterpret_cast<const uint4 *>(src)[i];
+    for (size_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) dst[i] = zero ? 0u : src[i];
+}
+static __device__ __forceinline__ void point_stats_one(PtRec *__restrict__ a, PtRec *__restrict__ b, const float *__restrict__ mrb, const int32_t *__restrict__ ngr, const int i) {
+    const float m = mrb[i]; const int32_t g = ngr[i];
+    a[i].maxRelBS = m; a[i].numGood = g; b[i].maxRelBS = m; b[i].numGood = g;
+}
 __global__ __launch_bounds__(256) void k_point_stats(PtRec *__restrict__ a, PtRec *__restrict__ b, const float *__restrict__ mrb, const int32_t *__restrict__ ngr, int P) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    const float m = mrb[i]; const int32_t g = ngr[i];
-    a[i].maxRelBS = m; a[i].numGood = g; b[i].maxRelBS = m; b[i].numGood = g;
+    point_stats_one(a, b, mrb, ngr, i);
 }
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 // ldso_ba_update_window: the staging image a full ldso_ba_set_window of the SAME window would have uploaded, built ON THE DEVICE from the resident window
@@ -48,10 +72,10 @@ struct WinDelta {
     int F, FS, P;
     // the image (written)
     PtGeo *geo; PtCw *pcw; int32_t *phost; SlotTab *tab; SlotRec *sr; float *mrb; int32_t *ngr;
+    // the PtRecs of both sets that take mrb / ngr once the scatter has zeroed them (k_point_stats_batch)
+    PtRec *pt0, *pt1;
 };
-__global__ __launch_bounds__(256) void k_win_rebuild(WinDelta W) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= W.P * W.FS) return;
+static __device__ __forceinline__ void win_rebuild_pair(const WinDelta &W, const int q) {          // one (point, slot) pair of the image: the body of both kernels below
     const int row = q / W.FS, col = q - row * W.FS;
     const int from = W.pointFrom[row];
     const uint32_t mask = W.resMask[row];
@@ -102,13 +126,32 @@ __global__ __launch_bounds__(256) void k_win_rebuild(WinDelta W) {
         W.geo[row] = g; W.phost[row] = host;
     }
 }
+__global__ __launch_bounds__(256) void k_win_rebuild(WinDelta W) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= W.P * W.FS) return;
+    win_rebuild_pair(W, q);
+}
+// every window of a batched update in one grid: blockIdx.y = the window's entry in the staged WinDelta table, blockIdx.x covers the largest window's pairs
+__global__ __launch_bounds__(256) void k_win_rebuild_batch(const WinDelta *__restrict__ tab) {
+    const WinDelta &W = tab[blockIdx.y];
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= W.P * W.FS) return;
+    win_rebuild_pair(W, q);
+}
+__global__ __launch_bounds__(256) void k_point_stats_batch(const WinDelta *__restrict__ tab) {
+    const WinDelta &W = tab[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W.P) return;
+    point_stats_one(W.pt0, W.pt1, W.mrb, W.ngr, i);
+}
 
 // host side of the arena: reserve (16-byte aligned) room, remember where it goes
 struct WinStage {
     char *base; size_t cap, used; WinXfer *tab; int n;
+    int maxN = LD_XFER_MAX;          // entries `tab` has room for (a batch brings a table of its own size)
     template <class T> T *put(T *dst, size_t count) {          // room for `count` elements that will land at dst; returns where to write them
         const size_t bytes = (count * sizeof(T) + 15) & ~(size_t) 15;
-        if (n >= LD_XFER_MAX || used + bytes > cap) return nullptr;
+        if (n >= maxN || used + bytes > cap) return nullptr;
         T *p = reinterpret_cast<T *>(base + used);
         if (count) { tab[n].dst = dst; tab[n].src = used; tab[n].words = count * sizeof(T) / 4; n++; }
         used += bytes;
@@ -122,12 +165,12 @@ struct WinStage {
         return p;
     }
     template <class T> bool again(T *dst, const T *staged, size_t count) {      // the same staged data to a second destination
-        if (n >= LD_XFER_MAX) return false;
+        if (n >= maxN) return false;
         if (count) { tab[n].dst = dst; tab[n].src = (size_t) (reinterpret_cast<const char *>(staged) - base); tab[n].words = count * sizeof(T) / 4; n++; }
         return true;
     }
     template <class T> bool zero(T *dst, size_t count) {
-        if (n >= LD_XFER_MAX) return false;
+        if (n >= maxN) return false;
         if (count) { tab[n].dst = dst; tab[n].src = LD_XFER_ZERO; tab[n].words = count * sizeof(T) / 4; n++; }
         return true;
     }
@@ -140,9 +183,14 @@ template <class T> static int h2d(ldso_ba *H, T *dst, const std::vector<T> &src)
 }
 #define H2D(dst, vec) do { int r_ = h2d(H, (dst), (vec)); if (r_ != LDSO_OK) return r_; } while (0)
 
-int build_chunks(ldso_ba *H) {
+// The chunks of a window in two parts.  plan_chunks: host logic - the tables (first point, size and host of every chunk, first chunk of every host) from the
+// window's host runs and the handle's chunk policy; adopt_chunks: the handle's own copies of them (block records, chunk starts, the closed form k_linearize_one
+// reads).  How the tables reach the device is the caller's: build_chunks copies them on the handle's stream and waits, ldso_ba_batch_update_windows stages them
+// with every other window's into the batch's one upload.
+struct ChunkPlan { std::vector<int32_t> p0, cn, ch, cs; int CH; };
+static int plan_chunks(ldso_ba *H, ChunkPlan &C) {
     // host-major chunks over the local shard [pBegin,pEnd)
-    BaDims &D = H->D;
+    const BaDims &D = H->D;
     // smallest multiple of 4 points per chunk that keeps the grid within one wave of workgroups (one per CU)
     int CH = 4;
     if (!H->chunkCuts.empty() && H->chunkCuts.back() != D.pEnd) H->chunkCuts.clear();          // cuts made for another window: back to the regular policy
@@ -155,7 +203,9 @@ int build_chunks(ldso_ba *H) {
         cnt += (run + CH - 1) / CH;
         if (cnt <= H->numCU || CH >= 1024) break;
     }
-    std::vector<int32_t> p0, cn, ch, cs(D.F + 1, 0);
+    std::vector<int32_t> &p0 = C.p0, &cn = C.cn, &ch = C.ch, &cs = C.cs;
+    p0.clear(); cn.clear(); ch.clear(); cs.assign(D.F + 1, 0);
+    C.CH = CH;
     int p = D.pBegin;
     size_t ci = 0;
     for (int hst = 0; hst < D.F; hst++) {
@@ -172,11 +222,15 @@ int build_chunks(ldso_ba *H) {
     cs[D.F] = (int) p0.size();
     REQ(p == D.pEnd, "ldso_ba_set_window: points must be ordered by host frame (EnergyFunctional::allPoints order)");
     REQ((int) p0.size() <= H->maxChunks, "too many chunks");
+    return LDSO_OK;
+}
+static void adopt_chunks(ldso_ba *H, const ChunkPlan &C) {
+    BaDims &D = H->D;
+    const std::vector<int32_t> &p0 = C.p0, &cn = C.cn, &ch = C.ch, &cs = C.cs;
+    const int CH = C.CH;
     D.nChunks = (int) p0.size();
-    H2D(H->B.chunk_p0, p0); H2D(H->B.chunk_n, cn); H2D(H->B.chunk_host, ch); H2D(H->d_chunkStart, cs);
     H->h_blocks.resize(p0.size());
     for (size_t i = 0; i < p0.size(); i++) H->h_blocks[i] = BatchBlock{0, p0[i], cn[i], ch[i] | ((int32_t) i << 8)};
-    CHK(hipMemcpyAsync(H->d_blocks, H->h_blocks.data(), p0.size() * sizeof(BatchBlock), hipMemcpyHostToDevice, H->stream));
     for (int i = 0; i <= LD_MAXF; i++) H->chunkStarts.v[i] = (i <= D.F) ? cs[i] : cs[D.F];
     {
         LinHead &L = H->linHead;
@@ -196,6 +250,13 @@ int build_chunks(ldso_ba *H) {
         }
         H->linHeadOk = ok;
     }
+}
+int build_chunks(ldso_ba *H) {
+    ChunkPlan C;
+    RUN(plan_chunks(H, C));
+    adopt_chunks(H, C);
+    H2D(H->B.chunk_p0, C.p0); H2D(H->B.chunk_n, C.cn); H2D(H->B.chunk_host, C.ch); H2D(H->d_chunkStart, C.cs);
+    CHK(hipMemcpyAsync(H->d_blocks, H->h_blocks.data(), H->h_blocks.size() * sizeof(BatchBlock), hipMemcpyHostToDevice, H->stream));
     CHK(hipStreamSynchronize(H->stream));
     return LDSO_OK;
 }
@@ -211,6 +272,157 @@ int rechunk(ldso_ba *H) {
     return LDSO_OK;
 }
 
+// ---- the pieces of ldso_ba_update_window, shared with ldso_ba_batch_update_windows (one window's delta is a ldso_win_job_t in both) ----
+static inline size_t A16(size_t b) { return (b + 15) & ~(size_t) 15; }
+// what the validation derives on the way: the flat residual index of every point's first residual, of every fresh point's first record, the new host of every point
+struct WinPlan { std::vector<int32_t> resBegin, freshResBegin, newHost; int R = 0; };
+// The checks of a delta against the resident window of H (indices only; nothing of the resident data is read back, nothing is written).  `who` names the entry.
+static int check_window_delta(const ldso_ba *H, const char *who_, const ldso_win_job_t &J, WinPlan &Pl) {
+    const std::string who(who_);
+    const int F = J.F, P = J.P, n_fresh = J.n_fresh, n_fresh_res = J.n_fresh_res;
+    const int32_t *image_slot = J.image_slot, *frame_from = J.frame_from, *point_from = J.point_from;
+    const uint32_t *res_mask = J.res_mask;
+    const ldso_point_t *fresh = J.fresh;
+    const ldso_residual_t *fresh_res = J.fresh_res;
+    REQ(H && image_slot && frame_from && point_from && res_mask, who + ": null argument");
+    REQ(H->D.P > 0 && !H->pendingApply, who + ": no resident window, or a linearisation is pending (ldso_ba_apply_res first)");
+    REQ(!H->hasL, who + ": the resident window holds linearised residuals (use ldso_ba_set_window)");
+    REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, who + ": sharded window");
+    REQ(F >= 2 && F <= H->maxF && P >= 1 && P <= H->maxP && n_fresh >= 0 && n_fresh_res >= 0, who + ": window exceeds the handle's capacity");
+    REQ(n_fresh == 0 || (fresh && J.fresh_mrb && J.fresh_ngr), who + ": fresh points without records");
+    REQ(n_fresh_res == 0 || fresh_res, who + ": fresh residuals without records");
+    const BaDims &oD = H->D;
+    {
+        std::vector<char> seen(oD.F, 0);
+        for (int f = 0; f < F; f++) {
+            REQ(frame_from[f] >= -1 && frame_from[f] < oD.F, who + ": frame_from out of range");
+            if (frame_from[f] >= 0) { REQ(!seen[frame_from[f]], who + ": an old frame appears twice"); seen[frame_from[f]] = 1; }
+            REQ(f == 0 || frame_from[f] < 0 || frame_from[f - 1] < frame_from[f], who + ": surviving frames must keep their order, inserted frames come last");
+            REQ(image_slot[f] >= 0 && image_slot[f] < H->maxF && H->imgSlots[image_slot[f]] != nullptr, who + ": image slot not set");
+        }
+    }
+    std::vector<int32_t> &resBegin = Pl.resBegin, &freshResBegin = Pl.freshResBegin, &newHost = Pl.newHost;
+    resBegin.assign((size_t) P + 1, 0); freshResBegin.assign((size_t) n_fresh + 1, 0); newHost.assign((size_t) P, 0);
+    {
+        std::vector<int32_t> oldToNew(oD.F, -1);
+        for (int f = 0; f < F; f++) if (frame_from[f] >= 0) oldToNew[frame_from[f]] = f;
+        int lastOld = -1, nextFresh = 0, acc = 0;
+        const uint32_t fmask = (F >= 32) ? 0xFFFFFFFFu : ((1u << F) - 1u);
+        int fr = 0;
+        for (int i = 0; i < P; i++) {
+            const int from = point_from[i];
+            int host;
+            if (from >= 0) {
+                REQ(from < oD.P && from > lastOld, who + ": surviving points must keep their order");
+                lastOld = from;
+                host = oldToNew[H->h_phost[from]];
+                REQ(host >= 0, who + ": a surviving point is hosted by a frame that left the window");
+            } else {
+                REQ(-1 - from == nextFresh && nextFresh < n_fresh, who + ": fresh points must be numbered in window order");
+                host = fresh[nextFresh].host;
+                REQ(host >= 0 && host < F, who + ": fresh point host out of range");
+                const int cnt = __builtin_popcount(res_mask[i]);
+                freshResBegin[nextFresh] = fr;
+                for (int c = 0; c < cnt; c++) {
+                    REQ(fr < n_fresh_res && fresh_res[fr].target >= 0 && fresh_res[fr].target < F && fresh_res[fr].host == host,
+                        who + ": fresh residual names a target outside the window or another host than its point's");
+                    REQ(fresh_res[fr].point == nextFresh && !fresh_res[fr].is_linearized && ((res_mask[i] >> fresh_res[fr].target) & 1u)
+                        && (c == 0 || fresh_res[fr - 1].target < fresh_res[fr].target), who + ": fresh residuals must be point-major, target-ascending and match res_mask");
+                    fr++;
+                }
+                nextFresh++;
+            }
+            REQ((res_mask[i] & ~fmask) == 0 && !((res_mask[i] >> host) & 1u), who + ": res_mask names a frame outside the window or the host itself");
+            REQ(i == 0 || newHost[i - 1] <= host, who + ": points must be ordered by host frame (EnergyFunctional::allPoints order)");
+            newHost[i] = host;
+            resBegin[i] = acc; acc += __builtin_popcount(res_mask[i]);
+        }
+        resBegin[P] = acc;
+        freshResBegin[n_fresh] = fr;
+        REQ(nextFresh == n_fresh && fr == n_fresh_res, who + ": unused fresh points / residuals");
+    }
+    Pl.R = resBegin[P];
+    return LDSO_OK;
+}
+// arena bytes of one window: the delta (crosses PCIe) and the image (written on the device)
+static size_t delta_bytes(const ldso_win_job_t &J) {
+    const size_t F = (size_t) J.F, P = (size_t) J.P, nf = (size_t) J.n_fresh, nr = (size_t) J.n_fresh_res;
+    return A16(F * 4) + 2 * A16(P * 4) + A16((P + 1) * 4) + A16(nf * sizeof(ldso_point_t)) + A16(nr * sizeof(ldso_residual_t)) + A16((nf + 1) * 4) + 2 * A16(nf * 4);
+}
+static size_t image_bytes(const ldso_win_job_t &J) {
+    const size_t P = (size_t) J.P, PS = P * (size_t) ((J.F + 7) / 8 * 8);
+    return A16(P * sizeof(PtGeo)) + A16(P * 8 * sizeof(PtCw)) + A16(P * 4) + A16(PS * sizeof(SlotTab)) + A16(PS * sizeof(SlotRec)) + 2 * A16(P * 4);
+}
+// what k_win_rebuild reads of the resident window: taken BEFORE the handle adopts the new one
+static void delta_resident(const ldso_ba *H, WinDelta &Wd) {
+    const BaPtrs &B = H->B;
+    const ResSet &So = H->sets[H->cur];
+    Wd.oGeo = B.pgeo; Wd.oPcw = B.pcw; Wd.oHost = B.phost; Wd.oTab = B.rtab; Wd.oSlot = So.slot; Wd.oPt = So.pt; Wd.oF = H->D.F; Wd.oFS = H->D.FS; Wd.oP = H->D.P;
+}
+// room for the delta behind what the arena holds, filled; Wd receives its device addresses (`devBase` = the arena's device twin).  false: arena too small
+static bool stage_delta(WinStage &W, const ldso_win_job_t &J, const WinPlan &Pl, const char *devBase, WinDelta &Wd) {
+    const int F = J.F, P = J.P, n_fresh = J.n_fresh, n_fresh_res = J.n_fresh_res;
+    int32_t *hFrameFrom = W.raw<int32_t>(F), *hPointFrom = W.raw<int32_t>(P);
+    uint32_t *hMask = W.raw<uint32_t>(P);
+    int32_t *hResBegin = W.raw<int32_t>((size_t) P + 1);
+    ldso_point_t *hFresh = W.raw<ldso_point_t>(n_fresh);
+    ldso_residual_t *hFreshRes = W.raw<ldso_residual_t>(n_fresh_res);
+    int32_t *hFreshResBegin = W.raw<int32_t>((size_t) n_fresh + 1);
+    float *hMrb = W.raw<float>(n_fresh); int32_t *hNgr = W.raw<int32_t>(n_fresh);
+    if (!(hFrameFrom && hPointFrom && hMask && hResBegin && hFresh && hFreshRes && hFreshResBegin && hMrb && hNgr)) return false;
+    memcpy(hFrameFrom, J.frame_from, (size_t) F * 4); memcpy(hPointFrom, J.point_from, (size_t) P * 4); memcpy(hMask, J.res_mask, (size_t) P * 4);
+    memcpy(hResBegin, Pl.resBegin.data(), ((size_t) P + 1) * 4); memcpy(hFreshResBegin, Pl.freshResBegin.data(), ((size_t) n_fresh + 1) * 4);
+    if (n_fresh) { memcpy(hFresh, J.fresh, (size_t) n_fresh * sizeof(ldso_point_t)); memcpy(hMrb, J.fresh_mrb, (size_t) n_fresh * 4); memcpy(hNgr, J.fresh_ngr, (size_t) n_fresh * 4); }
+    if (n_fresh_res) memcpy(hFreshRes, J.fresh_res, (size_t) n_fresh_res * sizeof(ldso_residual_t));
+    auto dev = [&](const void *hp) { return devBase + (reinterpret_cast<const char *>(hp) - W.base); };
+    Wd.frameFrom = (const int32_t *) dev(hFrameFrom); Wd.pointFrom = (const int32_t *) dev(hPointFrom); Wd.resMask = (const uint32_t *) dev(hMask); Wd.resBegin = (const int32_t *) dev(hResBegin);
+    Wd.fresh = (const ldso_point_t *) dev(hFresh); Wd.freshRes = (const ldso_residual_t *) dev(hFreshRes); Wd.freshResBegin = (const int32_t *) dev(hFreshResBegin);
+    Wd.freshMrb = (const float *) dev(hMrb); Wd.freshNgr = (const int32_t *) dev(hNgr);
+    Wd.F = F; Wd.FS = (F + 7) / 8 * 8; Wd.P = P;
+    return true;
+}
+// the handle describes the new window: dimensions, image slots, host-side tables; no applied linearisation, no prior (the caller holds a WinGuard)
+static void adopt_window(ldso_ba *H, const ldso_win_job_t &J, const WinPlan &Pl) {
+    const int F = J.F, P = J.P, R = Pl.R, FS = (F + 7) / 8 * 8;
+    BaDims &D = H->D;
+    D.F = F; D.FS = FS; D.P = P; D.R = R; D.n = 8 * F + 4; D.GS = 8 * D.FS + LD_GEXTRA; D.w = H->w; D.h = H->h; D.nsg = D.FS / 8; D.ks = H->reduceSplits;
+    D.pBegin = 0; D.pEnd = P; D.wM3G = (float) (H->w - 3); D.hM3G = (float) (H->h - 3); D.nL = 0;
+    H->GSP = (D.GS + 15) / 16 * 16;
+    H->R = R;
+    H->imageSlot.assign(J.image_slot, J.image_slot + F);
+    for (int f = 0; f < F; f++) H->B.img[f] = H->imgSlots[J.image_slot[f]];
+    H->h_phost.assign(Pl.newHost.begin(), Pl.newHost.end());
+    H->flat2slot.assign(R, -1);
+    for (int i = 0; i < P; i++) { int k = Pl.resBegin[i]; for (int t = 0; t < F; t++) if ((J.res_mask[i] >> t) & 1u) H->flat2slot[k++] = (int32_t) ((size_t) i * FS + t); }
+    H->hasL = false; H->cur = 0; H->pendingApply = false; H->appliedValid = false; H->itemValid = false;
+    H->hasPrior = false;
+}
+// the image region of the window H has adopted: same destinations, same order, same zero fills as ldso_ba_set_window.  false: arena or table too small
+static bool stage_image(ldso_ba *H, WinStage &W, const char *devBase, WinDelta &Wd) {
+    BaPtrs &B = H->B;
+    const BaDims &D = H->D;
+    const size_t P = (size_t) D.P, PS = P * (size_t) D.FS;
+    PtGeo *geo = W.put(B.pgeo, P);
+    PtCw *pcw = W.put(B.pcw, P * 8);
+    int32_t *phost = W.put(B.phost, P);
+    SlotTab *tab = W.put(B.rtab, PS);
+    SlotRec *sr = W.put(H->sets[0].slot, PS);
+    if (!(geo && pcw && phost && tab && sr)) return false;
+    float *mrb = W.raw<float>(P); int32_t *ngr = W.raw<int32_t>(P);
+    if (!(mrb && ngr)) return false;
+    auto dev = [&](const void *hp) { return const_cast<char *>(devBase) + (reinterpret_cast<const char *>(hp) - W.base); };
+    Wd.geo = (PtGeo *) dev(geo); Wd.pcw = (PtCw *) dev(pcw); Wd.phost = (int32_t *) dev(phost); Wd.tab = (SlotTab *) dev(tab); Wd.sr = (SlotRec *) dev(sr); Wd.mrb = (float *) dev(mrb); Wd.ngr = (int32_t *) dev(ngr);
+    Wd.pt0 = H->sets[0].pt; Wd.pt1 = H->sets[1].pt;
+    bool okT = W.again(H->sets[1].slot, sr, PS);
+    for (int s_ = 0; s_ < 2; s_++) {
+        ResSet &S = H->sets[s_];
+        okT = okT && W.zero(S.pt, P) && W.zero(S.acc, P) && W.zero(S.G, P * D.GS);
+    }
+    // a new window has a new dimension 8F+4: the marginalisation prior starts at zero
+    okT = okT && W.zero(B.HM, (size_t) D.n * D.n) && W.zero(B.bM, (size_t) D.n) && W.zero(B.scalars, (size_t) 16) && W.zero(B.scPart, (size_t) LD_SC_SPLITS * H->GSP * H->GSP);
+    return okT;
+}
+
 extern "C" {
 
 int ldso_ba_set_window(ldso_ba_t *H, int F, const int32_t *image_slot, int P, const ldso_point_t *pts, int R, const ldso_residual_t *res,
@@ -220,9 +432,7 @@ int ldso_ba_set_window(ldso_ba_t *H, int F, const int32_t *image_slot, int P, co
     CHK(hipSetDevice(H->device));
     BaDims &D = H->D;
     BaPtrs &B = H->B;
-    // a call that fails half way (bad indices, allocation) must not leave the dimensions of the NEW window over the data of the old one:
-    // the handle then holds no window (every entry point that needs one says so)
-    struct WinGuard { ldso_ba *H; bool ok; ~WinGuard() { if (!ok) { H->D.P = 0; H->D.R = 0; H->R = 0; H->appliedValid = false; H->itemValid = false; } } } guard{H, false};
+    WinGuard guard{H, false};          // a failure from here on leaves the handle without a window (ba_host.h)
     D.F = F; D.FS = (F + 7) / 8 * 8; D.P = P; D.R = R; D.n = 8 * F + 4; D.GS = 8 * D.FS + LD_GEXTRA; D.w = H->w; D.h = H->h; D.nsg = D.FS / 8; D.ks = H->reduceSplits;
     D.pBegin = 0; D.pEnd = P; D.wM3G = (float) (H->w - 3); D.hM3G = (float) (H->h - 3);
     H->GSP = (D.GS + 15) / 16 * 16;
@@ -352,75 +562,13 @@ int ldso_ba_set_point_stats(ldso_ba_t *H, const float *maxRelBaseline, const int
 // ldso_ba_set_point_stats of the same objects produces, byte for byte; ldso_ba_set_frames / ldso_ba_set_prior follow as they do there.
 int ldso_ba_update_window(ldso_ba_t *H, int F, const int32_t *image_slot, const int32_t *frame_from, int P, const int32_t *point_from, const uint32_t *res_mask,
                           int n_fresh, const ldso_point_t *fresh, int n_fresh_res, const ldso_residual_t *fresh_res, const float *fresh_mrb, const int32_t *fresh_ngr) {
-    REQ(H && image_slot && frame_from && point_from && res_mask, "ldso_ba_update_window: null argument");
-    REQ(H->D.P > 0 && !H->pendingApply, "ldso_ba_update_window: no resident window, or a linearisation is pending (ldso_ba_apply_res first)");
-    REQ(!H->hasL, "ldso_ba_update_window: the resident window holds linearised residuals (use ldso_ba_set_window)");
-    REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, "ldso_ba_update_window: sharded window");
-    REQ(F >= 2 && F <= H->maxF && P >= 1 && P <= H->maxP && n_fresh >= 0 && n_fresh_res >= 0, "ldso_ba_update_window: window exceeds the handle's capacity");
-    REQ(n_fresh == 0 || (fresh && fresh_mrb && fresh_ngr), "ldso_ba_update_window: fresh points without records");
-    REQ(n_fresh_res == 0 || fresh_res, "ldso_ba_update_window: fresh residuals without records");
+    const ldso_win_job_t J{F, image_slot, frame_from, P, point_from, res_mask, n_fresh, fresh, n_fresh_res, fresh_res, fresh_mrb, fresh_ngr};
+    WinPlan Pl;
+    RUN(check_window_delta(H, "ldso_ba_update_window", J, Pl));
     CHK(hipSetDevice(H->device));
-    const BaDims oD = H->D;
-    const int FS = (F + 7) / 8 * 8;
-    const size_t PS = (size_t) P * FS;
-    // ---- validate the delta on the host (indices only; nothing of the resident data is read back) ----
-    {
-        std::vector<char> seen(oD.F, 0);
-        for (int f = 0; f < F; f++) {
-            REQ(frame_from[f] >= -1 && frame_from[f] < oD.F, "ldso_ba_update_window: frame_from out of range");
-            if (frame_from[f] >= 0) { REQ(!seen[frame_from[f]], "ldso_ba_update_window: an old frame appears twice"); seen[frame_from[f]] = 1; }
-            REQ(f == 0 || frame_from[f] < 0 || frame_from[f - 1] < frame_from[f], "ldso_ba_update_window: surviving frames must keep their order, inserted frames come last");
-            REQ(image_slot[f] >= 0 && image_slot[f] < H->maxF && H->imgSlots[image_slot[f]] != nullptr, "ldso_ba_update_window: image slot not set");
-        }
-    }
-    std::vector<int32_t> resBegin((size_t) P + 1), freshResBegin((size_t) n_fresh + 1, 0), newHost((size_t) P);
-    {
-        std::vector<int32_t> oldToNew(oD.F, -1);
-        for (int f = 0; f < F; f++) if (frame_from[f] >= 0) oldToNew[frame_from[f]] = f;
-        int lastOld = -1, nextFresh = 0, acc = 0;
-        const uint32_t fmask = (F >= 32) ? 0xFFFFFFFFu : ((1u << F) - 1u);
-        for (int k = 0; k < n_fresh; k++) freshResBegin[k + 1] = 0;
-        int fr = 0;
-        for (int i = 0; i < P; i++) {
-            const int from = point_from[i];
-            int host;
-            if (from >= 0) {
-                REQ(from < oD.P && from > lastOld, "ldso_ba_update_window: surviving points must keep their order");
-                lastOld = from;
-                host = oldToNew[H->h_phost[from]];
-                REQ(host >= 0, "ldso_ba_update_window: a surviving point is hosted by a frame that left the window");
-            } else {
-                REQ(-1 - from == nextFresh && nextFresh < n_fresh, "ldso_ba_update_window: fresh points must be numbered in window order");
-                host = fresh[nextFresh].host;
-                REQ(host >= 0 && host < F, "ldso_ba_update_window: fresh point host out of range");
-                const int cnt = __builtin_popcount(res_mask[i]);
-                freshResBegin[nextFresh] = fr;
-                for (int c = 0; c < cnt; c++) {
-                    REQ(fr < n_fresh_res && fresh_res[fr].target >= 0 && fresh_res[fr].target < F && fresh_res[fr].host == host,
-                        "ldso_ba_update_window: fresh residual names a target outside the window or another host than its point's");
-                    REQ(fresh_res[fr].point == nextFresh && !fresh_res[fr].is_linearized && ((res_mask[i] >> fresh_res[fr].target) & 1u)
-                        && (c == 0 || fresh_res[fr - 1].target < fresh_res[fr].target), "ldso_ba_update_window: fresh residuals must be point-major, target-ascending and match res_mask");
-                    fr++;
-                }
-                nextFresh++;
-            }
-            REQ((res_mask[i] & ~fmask) == 0 && !((res_mask[i] >> host) & 1u), "ldso_ba_update_window: res_mask names a frame outside the window or the host itself");
-            REQ(i == 0 || newHost[i - 1] <= host, "ldso_ba_update_window: points must be ordered by host frame (EnergyFunctional::allPoints order)");
-            newHost[i] = host;
-            resBegin[i] = acc; acc += __builtin_popcount(res_mask[i]);
-        }
-        resBegin[P] = acc;
-        freshResBegin[n_fresh] = fr;
-        REQ(nextFresh == n_fresh && fr == n_fresh_res, "ldso_ba_update_window: unused fresh points / residuals");
-    }
-    const int R = resBegin[P];
     // ---- arena: [table | delta | image]; only table + delta cross PCIe ----
-    auto A16 = [](size_t b) { return (b + 15) & ~(size_t) 15; };
     const size_t tabBytes = A16(LD_XFER_MAX * sizeof(WinXfer));
-    const size_t deltaBytes = A16((size_t) F * 4) + 2 * A16((size_t) P * 4) + A16(((size_t) P + 1) * 4) + A16((size_t) n_fresh * sizeof(ldso_point_t)) + A16((size_t) n_fresh_res * sizeof(ldso_residual_t))
-                              + A16(((size_t) n_fresh + 1) * 4) + 2 * A16((size_t) n_fresh * 4);
-    const size_t need = tabBytes + deltaBytes + A16((size_t) P * sizeof(PtGeo)) + A16((size_t) P * 8 * sizeof(PtCw)) + A16((size_t) P * 4) + A16(PS * sizeof(SlotTab)) + A16(PS * sizeof(SlotRec))
-                        + 2 * A16((size_t) P * 4) + 64;
+    const size_t need = tabBytes + delta_bytes(J) + image_bytes(J) + 64;
     if (need > H->stageCap) {          // the arena only ever holds staging data: growing it loses nothing of the resident window
         CHK(hipStreamSynchronize(H->stream));
         if (H->h_stage) hipHostFree(H->h_stage);
@@ -433,61 +581,17 @@ int ldso_ba_update_window(ldso_ba_t *H, int F, const int32_t *image_slot, const 
     }
     if (H->stageBusy) { CHK(hipStreamSynchronize(H->stream)); H->stageBusy = false; }
     WinStage W{H->h_stage, H->stageCap, tabBytes, reinterpret_cast<WinXfer *>(H->h_stage), 0};
-    int32_t *hFrameFrom = W.raw<int32_t>(F), *hPointFrom = W.raw<int32_t>(P);
-    uint32_t *hMask = W.raw<uint32_t>(P);
-    int32_t *hResBegin = W.raw<int32_t>((size_t) P + 1);
-    ldso_point_t *hFresh = W.raw<ldso_point_t>(n_fresh);
-    ldso_residual_t *hFreshRes = W.raw<ldso_residual_t>(n_fresh_res);
-    int32_t *hFreshResBegin = W.raw<int32_t>((size_t) n_fresh + 1);
-    float *hMrb = W.raw<float>(n_fresh); int32_t *hNgr = W.raw<int32_t>(n_fresh);
-    REQ(hFrameFrom && hPointFrom && hMask && hResBegin && hFresh && hFreshRes && hFreshResBegin && hMrb && hNgr, "ldso_ba_update_window: staging arena too small (internal)");
-    const size_t upBytes = W.used;
-    memcpy(hFrameFrom, frame_from, (size_t) F * 4); memcpy(hPointFrom, point_from, (size_t) P * 4); memcpy(hMask, res_mask, (size_t) P * 4);
-    memcpy(hResBegin, resBegin.data(), ((size_t) P + 1) * 4); memcpy(hFreshResBegin, freshResBegin.data(), ((size_t) n_fresh + 1) * 4);
-    if (n_fresh) { memcpy(hFresh, fresh, (size_t) n_fresh * sizeof(ldso_point_t)); memcpy(hMrb, fresh_mrb, (size_t) n_fresh * 4); memcpy(hNgr, fresh_ngr, (size_t) n_fresh * 4); }
-    if (n_fresh_res) memcpy(hFreshRes, fresh_res, (size_t) n_fresh_res * sizeof(ldso_residual_t));
-    BaPtrs &B = H->B;
-    // the image region: same destinations, same order, same zero fills as ldso_ba_set_window
-    PtGeo *geo = W.put(B.pgeo, P);
-    PtCw *pcw = W.put(B.pcw, (size_t) P * 8);
-    int32_t *phost = W.put(B.phost, P);
-    SlotTab *tab = W.put(B.rtab, PS);
-    SlotRec *sr = W.put(H->sets[0].slot, PS);
-    REQ(geo && pcw && phost && tab && sr, "ldso_ba_update_window: staging arena too small (internal)");
-    float *mrb = W.raw<float>(P); int32_t *ngr = W.raw<int32_t>(P);
-    REQ(mrb && ngr, "ldso_ba_update_window: staging arena too small (internal)");
-    auto dev = [&](const void *hp) { return H->d_stage + (reinterpret_cast<const char *>(hp) - H->h_stage); };
     WinDelta Wd;
-    const ResSet &So = H->sets[H->cur];
-    Wd.oGeo = B.pgeo; Wd.oPcw = B.pcw; Wd.oHost = B.phost; Wd.oTab = B.rtab; Wd.oSlot = So.slot; Wd.oPt = So.pt; Wd.oF = oD.F; Wd.oFS = oD.FS; Wd.oP = oD.P;
-    Wd.frameFrom = (const int32_t *) dev(hFrameFrom); Wd.pointFrom = (const int32_t *) dev(hPointFrom); Wd.resMask = (const uint32_t *) dev(hMask); Wd.resBegin = (const int32_t *) dev(hResBegin);
-    Wd.fresh = (const ldso_point_t *) dev(hFresh); Wd.freshRes = (const ldso_residual_t *) dev(hFreshRes); Wd.freshResBegin = (const int32_t *) dev(hFreshResBegin);
-    Wd.freshMrb = (const float *) dev(hMrb); Wd.freshNgr = (const int32_t *) dev(hNgr);
-    Wd.F = F; Wd.FS = FS; Wd.P = P;
-    Wd.geo = (PtGeo *) dev(geo); Wd.pcw = (PtCw *) dev(pcw); Wd.phost = (int32_t *) dev(phost); Wd.tab = (SlotTab *) dev(tab); Wd.sr = (SlotRec *) dev(sr); Wd.mrb = (float *) dev(mrb); Wd.ngr = (int32_t *) dev(ngr);
+    delta_resident(H, Wd);
+    REQ(stage_delta(W, J, Pl, H->d_stage, Wd), "ldso_ba_update_window: staging arena too small (internal)");
+    const size_t upBytes = W.used;
     // from here on the handle describes the new window (a failure leaves it without one, as in ldso_ba_set_window)
-    struct WinGuard { ldso_ba *H; bool ok; ~WinGuard() { if (!ok) { H->D.P = 0; H->D.R = 0; H->R = 0; H->appliedValid = false; H->itemValid = false; } } } guard{H, false};
-    BaDims &D = H->D;
-    D.F = F; D.FS = FS; D.P = P; D.R = R; D.n = 8 * F + 4; D.GS = 8 * D.FS + LD_GEXTRA; D.w = H->w; D.h = H->h; D.nsg = D.FS / 8; D.ks = H->reduceSplits;
-    D.pBegin = 0; D.pEnd = P; D.wM3G = (float) (H->w - 3); D.hM3G = (float) (H->h - 3); D.nL = 0;
-    H->GSP = (D.GS + 15) / 16 * 16;
-    H->R = R;
-    H->imageSlot.assign(image_slot, image_slot + F);
-    for (int f = 0; f < F; f++) B.img[f] = H->imgSlots[image_slot[f]];
-    H->h_phost.assign(newHost.begin(), newHost.end());
-    H->flat2slot.assign(R, -1);
-    for (int i = 0; i < P; i++) { int k = resBegin[i]; for (int t = 0; t < F; t++) if ((res_mask[i] >> t) & 1u) H->flat2slot[k++] = (int32_t) ((size_t) i * FS + t); }
-    H->hasL = false; H->cur = 0; H->pendingApply = false; H->appliedValid = false; H->itemValid = false;
-    bool okT = W.again(H->sets[1].slot, sr, PS);
-    for (int s_ = 0; s_ < 2; s_++) {
-        ResSet &S = H->sets[s_];
-        okT = okT && W.zero(S.pt, (size_t) P) && W.zero(S.acc, (size_t) P) && W.zero(S.G, (size_t) P * D.GS);
-    }
-    okT = okT && W.zero(B.HM, (size_t) D.n * D.n) && W.zero(B.bM, (size_t) D.n) && W.zero(B.scalars, (size_t) 16) && W.zero(B.scPart, (size_t) LD_SC_SPLITS * H->GSP * H->GSP);
-    REQ(okT, "ldso_ba_update_window: upload table overflow (internal)");
-    H->hasPrior = false;
+    WinGuard guard{H, false};
+    adopt_window(H, J, Pl);
+    // the image region: same destinations, same order, same zero fills as ldso_ba_set_window
+    REQ(stage_image(H, W, H->d_stage, Wd), "ldso_ba_update_window: staging arena too small or upload table overflow (internal)");
     CHK(hipMemcpyAsync(H->d_stage, H->h_stage, upBytes, hipMemcpyHostToDevice, H->stream));
-    hipLaunchKernelGGL(k_win_rebuild, dim3((unsigned) ((PS + 255) / 256)), dim3(256), 0, H->stream, Wd);
+    hipLaunchKernelGGL(k_win_rebuild, dim3((unsigned) (((size_t) Wd.P * Wd.FS + 255) / 256)), dim3(256), 0, H->stream, Wd);
     CHK(hipGetLastError());
     hipLaunchKernelGGL(k_win_scatter, dim3(256), dim3(256), 0, H->stream, (const char *) H->d_stage, W.n);
     CHK(hipGetLastError());
@@ -497,6 +601,174 @@ int ldso_ba_update_window(ldso_ba_t *H, int F, const int32_t *image_slot, const 
     const int rc_ = build_chunks(H);
     guard.ok = (rc_ == LDSO_OK);
     return rc_;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// The same step for every window of a batch (include/ldso_hip.h: ldso_ba_batch_update_windows): the pieces above per window - check_window_delta for ALL windows
+// first, then stage_delta / adopt_window / stage_image into ONE arena (the batch's, batch_stage) laid out [transfer table | work units | n WinDelta | every
+// window's delta | every window's chunk tables || every window's image]: what stands in front of || goes up in one copy, the images are written by
+// k_win_rebuild_batch and distributed, with the chunk tables and the zero fills, by k_win_scatter_batch.  In between the batch re-runs its chunk policy on the new
+// point counts (batch_chunk_policy, as ldso_ba_batch_create): the participating windows hold no applied linearisation, so cutting them is host work (plan_chunks)
+// whose tables ride in the same upload; a window that sits out is re-cut by rechunk.
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+#define LD_BATCH_XFER_PER_WIN 24          // transfer-table entries of one window: 5 image parts, 1 copy for the second set, 10 zero fills, 5 chunk tables (+ slack)
+static_assert(sizeof(ldso_win_job_t) == 96 && sizeof(ldso_frames_job_t) == 32, "the job records of the batched entries as the Python binding declares them");
+// the work units of a finished transfer table (k_win_scatter_batch) -> unit0[0 .. n]; returns the grid
+static int xfer_units(const WinStage &W, int32_t *unit0) {
+    int u = 0;
+    for (int e = 0; e < W.n; e++) { unit0[e] = u; u += (int) ((W.tab[e].words + LD_XFER_UNIT - 1) / LD_XFER_UNIT); }
+    unit0[W.n] = u;
+    return u;
+}
+struct BatchWinGuard {
+    ldso_ba_batch *Bt; std::vector<ldso_ba *> taking; bool ok;
+    ~BatchWinGuard() { if (!ok) { for (ldso_ba *H : taking) { WinGuard g{H, false}; } Bt->lost = true; } }
+};
+int ldso_ba_batch_update_windows(ldso_ba_batch_t *Bt, const ldso_win_job_t *jobs) {
+    REQ(Bt, "ldso_ba_batch_update_windows: null batch");
+    REQ(jobs, "ldso_ba_batch_update_windows: null job array");
+    REQ(!Bt->lost, "ldso_ba_batch_update_windows: an earlier call left windows of the batch unset: destroy and re-create the batch");
+    ldso_ba *H0 = Bt->h[0];
+    const int n = (int) Bt->h.size();
+    // ---- validation of every participating window before anything is written ----
+    std::vector<WinPlan> plans((size_t) n);
+    std::vector<int> part;
+    for (int i = 0; i < n; i++) {
+        if (jobs[i].frame_from == nullptr) continue;
+        RUN(check_window_delta(Bt->h[(size_t) i], "ldso_ba_batch_update_windows", jobs[i], plans[(size_t) i]));
+        REQ((jobs[i].F + 7) / 8 * 8 == Bt->FS, "ldso_ba_batch_update_windows: the new window's slot-table width differs from the batch's (all F <= 8 or all 9 <= F <= 16)");
+        part.push_back(i);
+    }
+    REQ(!part.empty(), "ldso_ba_batch_update_windows: no window takes part (every frame_from is NULL)");
+    const int nPart = (int) part.size();
+    CHK(hipSetDevice(H0->device));
+    // ---- the arena ----
+    const int maxEntries = nPart * LD_BATCH_XFER_PER_WIN;
+    const size_t headBytes = A16((size_t) maxEntries * sizeof(WinXfer)) + A16(((size_t) maxEntries + 1) * 4) + A16((size_t) nPart * sizeof(WinDelta));
+    size_t up = headBytes, img = 64;
+    for (int i : part) {
+        const ldso_ba *H = Bt->h[(size_t) i];
+        up += delta_bytes(jobs[i]) + 3 * A16((size_t) H->maxChunks * 4) + A16(((size_t) jobs[i].F + 1) * 4) + A16((size_t) H->maxChunks * sizeof(BatchBlock));
+        img += image_bytes(jobs[i]);
+    }
+    RUN(batch_stage(Bt, up, img));          // (may wait for the stream and replace the arena: nothing of the windows lives there)
+    WinStage W{Bt->h_marg, Bt->margCap, 0, reinterpret_cast<WinXfer *>(Bt->h_marg), 0, maxEntries};
+    W.used = A16((size_t) maxEntries * sizeof(WinXfer));
+    int32_t *unit0 = W.raw<int32_t>((size_t) maxEntries + 1);
+    WinDelta *hWd = W.raw<WinDelta>((size_t) nPart);
+    REQ(unit0 && hWd, "ldso_ba_batch_update_windows: staging arena too small (internal)");
+    std::vector<WinDelta> Wd((size_t) nPart);
+    for (int k = 0; k < nPart; k++) {
+        delta_resident(Bt->h[(size_t) part[(size_t) k]], Wd[(size_t) k]);
+        REQ(stage_delta(W, jobs[part[(size_t) k]], plans[(size_t) part[(size_t) k]], Bt->d_marg, Wd[(size_t) k]), "ldso_ba_batch_update_windows: staging arena too small (internal)");
+    }
+    // ---- from here on the participating handles describe their new windows: a failure leaves them without one and the batch fit for ldso_ba_batch_destroy only ----
+    BatchWinGuard guard{Bt, {}, false};
+    for (int i : part) guard.taking.push_back(Bt->h[(size_t) i]);
+    for (int i : part) adopt_window(Bt->h[(size_t) i], jobs[i], plans[(size_t) i]);
+    // the batch re-cuts itself: the policy of ldso_ba_batch_create on the new point counts (the cuts the batch gave its windows are its own to replace)
+    if (Bt->balanced) for (ldso_ba *H : Bt->h) H->chunkCuts.clear();
+    BatchCuts C;
+    batch_chunk_policy(Bt->h.data(), n, C);
+    for (int i : part) {
+        ldso_ba *H = Bt->h[(size_t) i];
+        ChunkPlan Cp;
+        RUN(batch_cut_window(H, i, C, true, [&](ldso_ba *Hc) { return plan_chunks(Hc, Cp); }));
+        adopt_chunks(H, Cp);
+        int32_t *p0 = W.put(H->B.chunk_p0, Cp.p0.size()), *cn = W.put(H->B.chunk_n, Cp.cn.size()), *ch = W.put(H->B.chunk_host, Cp.ch.size()), *cs = W.put(H->d_chunkStart, Cp.cs.size());
+        BatchBlock *bl = W.put(H->d_blocks, H->h_blocks.size());
+        REQ(p0 && cn && ch && cs && bl, "ldso_ba_batch_update_windows: staging arena too small or upload table overflow (internal)");
+        memcpy(p0, Cp.p0.data(), Cp.p0.size() * 4); memcpy(cn, Cp.cn.data(), Cp.cn.size() * 4); memcpy(ch, Cp.ch.data(), Cp.ch.size() * 4); memcpy(cs, Cp.cs.data(), Cp.cs.size() * 4);
+        memcpy(bl, H->h_blocks.data(), H->h_blocks.size() * sizeof(BatchBlock));
+    }
+    size_t upBytes = W.used;
+    size_t maxPS = 0, maxP = 0;
+    for (int k = 0; k < nPart; k++) {
+        REQ(stage_image(Bt->h[(size_t) part[(size_t) k]], W, Bt->d_marg, Wd[(size_t) k]), "ldso_ba_batch_update_windows: staging arena too small or upload table overflow (internal)");
+        maxPS = std::max(maxPS, (size_t) Wd[(size_t) k].P * Wd[(size_t) k].FS); maxP = std::max(maxP, (size_t) Wd[(size_t) k].P);
+    }
+    REQ(upBytes <= up && W.used <= Bt->margCap, "ldso_ba_batch_update_windows: staging arena too small (internal)");
+    memcpy(hWd, Wd.data(), (size_t) nPart * sizeof(WinDelta));
+    const int units = xfer_units(W, unit0);
+    auto dev = [&](const void *hp) { return Bt->d_marg + (reinterpret_cast<const char *>(hp) - Bt->h_marg); };
+    hipStream_t st = H0->stream;
+    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, upBytes, hipMemcpyHostToDevice, st));
+    // the order of the single-window path: the rebuild reads the resident windows that the scatter overwrites
+    hipLaunchKernelGGL(k_win_rebuild_batch, dim3((unsigned) ((maxPS + 255) / 256), (unsigned) nPart), dim3(256), 0, st, (const WinDelta *) dev(hWd));
+    CHK(hipGetLastError());
+    hipLaunchKernelGGL(k_win_scatter_batch, dim3((unsigned) units), dim3(256), 0, st, (const char *) Bt->d_marg, (const WinXfer *) Bt->d_marg, (const int32_t *) dev(unit0), W.n);
+    CHK(hipGetLastError());
+    hipLaunchKernelGGL(k_point_stats_batch, dim3((unsigned) ((maxP + 255) / 256), (unsigned) nPart), dim3(256), 0, st, (const WinDelta *) dev(hWd));
+    CHK(hipGetLastError());
+    // the cost of sitting out: the window keeps its bytes and its applied state, re-formed under the batch's new chunks (one linearisation launch, the parity flips)
+    for (int i = 0; i < n; i++) if (jobs[i].frame_from == nullptr) RUN(batch_cut_window(Bt->h[(size_t) i], i, C, true, rechunk));
+    Bt->balanced = C.balanced;
+    for (int u = 0; u < 3; u++) Bt->wg[u] = C.wg[u];
+    Bt->chunkPoints = batch_chunk_points(Bt->h.data(), n, C);
+    Bt->Dmax = H0->D;
+    for (ldso_ba *H : Bt->h) if (H->D.F > Bt->Dmax.F) Bt->Dmax = H->D;
+    RUN(batch_refresh(Bt));
+    CHK(hipStreamSynchronize(st));          // the arena is handed back to the next batched call
+    guard.ok = true;
+    return LDSO_OK;
+}
+
+// ldso_ba_set_frames + ldso_ba_set_prior for every window of the batch that brings frames: the records of all of them in one upload, distributed (and the absent
+// priors zero-filled) by k_win_scatter_batch, then the adjoints and the precalc values of all windows in one k_solve_batch over a table of the participating
+// windows' descriptors that rides in the same upload (SK_ADJ | SK_PRECALC read neither the residual sets nor the scalars the kernel picks its set by).
+int ldso_ba_batch_set_frames(ldso_ba_batch_t *Bt, const ldso_frames_job_t *jobs) {
+    REQ(Bt, "ldso_ba_batch_set_frames: null batch");
+    REQ(jobs, "ldso_ba_batch_set_frames: null job array");
+    REQ(!Bt->lost, "ldso_ba_batch_set_frames: an earlier ldso_ba_batch_update_windows left windows of the batch unset: destroy and re-create the batch");
+    ldso_ba *H0 = Bt->h[0];
+    const int n = (int) Bt->h.size();
+    std::vector<int> part;
+    size_t up = 0;
+    for (int i = 0; i < n; i++) {
+        if (jobs[i].frames == nullptr) continue;
+        const ldso_ba *H = Bt->h[(size_t) i];
+        REQ(jobs[i].calib && H->D.P > 0 && H->D.F > 0, "ldso_ba_batch_set_frames: a window that takes part needs its calibration and a resident window");
+        part.push_back(i);
+        up += A16((size_t) H->D.F * sizeof(DevFrame)) + A16(sizeof(DevCalib)) + A16((size_t) H->D.n * H->D.n * 8) + A16((size_t) H->D.n * 8);
+    }
+    if (part.empty()) return LDSO_OK;
+    const int nPart = (int) part.size(), maxEntries = 4 * nPart;
+    up += A16((size_t) maxEntries * sizeof(WinXfer)) + A16(((size_t) maxEntries + 1) * 4) + A16((size_t) nPart * sizeof(BatchItem)) + 64;
+    CHK(hipSetDevice(H0->device));
+    RUN(batch_stage(Bt, up, 0));
+    WinStage W{Bt->h_marg, Bt->margCap, 0, reinterpret_cast<WinXfer *>(Bt->h_marg), 0, maxEntries};
+    W.used = A16((size_t) maxEntries * sizeof(WinXfer));
+    int32_t *unit0 = W.raw<int32_t>((size_t) maxEntries + 1);
+    BatchItem *hItems = W.raw<BatchItem>((size_t) nPart);
+    REQ(unit0 && hItems, "ldso_ba_batch_set_frames: staging arena too small (internal)");
+    for (int k = 0; k < nPart; k++) {
+        ldso_ba *H = Bt->h[(size_t) part[(size_t) k]];
+        const ldso_frames_job_t &J = jobs[part[(size_t) k]];
+        const size_t nn = (size_t) H->D.n;
+        DevFrame *df = W.put(H->B.frames, (size_t) H->D.F);
+        DevCalib *dc = W.put(H->B.calib, 1);
+        REQ(df && dc, "ldso_ba_batch_set_frames: staging arena too small (internal)");
+        fill_dev_frames(H, J.frames, J.calib, df, dc);
+        bool ok = true;
+        if (J.HM) { double *q = W.put(H->B.HM, nn * nn); ok = ok && q; if (q) memcpy(q, J.HM, nn * nn * 8); } else ok = ok && W.zero(H->B.HM, nn * nn);
+        if (J.bM) { double *q = W.put(H->B.bM, nn); ok = ok && q; if (q) memcpy(q, J.bM, nn * 8); } else ok = ok && W.zero(H->B.bM, nn);
+        REQ(ok, "ldso_ba_batch_set_frames: staging arena too small (internal)");
+        H->hasPrior = (J.HM != nullptr) || (J.bM != nullptr);
+        // the window's descriptors as batch_refresh writes them
+        BatchItem &it = hItems[k];
+        memset(&it, 0, sizeof(it));
+        it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[H->cur]; it.set[1] = H->sets[H->cur ^ 1]; it.cs = H->chunkStarts;
+        it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.outSlot = (int32_t) part[(size_t) k];
+    }
+    const int units = xfer_units(W, unit0);
+    auto dev = [&](const void *hp) { return Bt->d_marg + (reinterpret_cast<const char *>(hp) - Bt->h_marg); };
+    hipStream_t st = H0->stream;
+    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, W.used, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_win_scatter_batch, dim3((unsigned) units), dim3(256), 0, st, (const char *) Bt->d_marg, (const WinXfer *) Bt->d_marg, (const int32_t *) dev(unit0), W.n);
+    CHK(hipGetLastError());
+    CHK(ba_launch_solve_batch((const BatchItem *) dev(hItems), nPart, Bt->Dmax, H0->settings, SK_ADJ | SK_PRECALC, 0, nullptr, st));
+    CHK(hipStreamSynchronize(st));
+    return LDSO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
