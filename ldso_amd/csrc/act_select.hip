@@ -513,7 +513,7 @@ int batch_select_run(ldso_ba_batch *Bt, const char *who, const char *solo, ldso_
         CHK(hipDeviceGetAttribute(&perBlock, hipDeviceAttributeMaxSharedMemoryPerBlock, H0->device));
         Bt->selLdsLimit = std::max(0, std::min(perBlock, SEL_LDS_MAX) - (int) fa.sharedSizeBytes);
     }
-    char *hs = Bt->h_marg, *d = Bt->d_marg, *dIn = d + oIn, *dOut = d + up, *dScr = d + up + down;
+    char *hs = Bt->h_stage, *d = Bt->d_stage, *dIn = d + oIn, *dOut = d + up, *dScr = d + up + down;
     SelArgs *tab = (SelArgs *) (hs + oTab);
     ActWin *act = (ActWin *) (hs + oAct);
     int32_t *wave = (int32_t *) (hs + oWave);
@@ -600,7 +600,7 @@ int ldso_ba_batch_activate_points(ldso_ba_batch_t *Bt, const int *n_pts, const l
     RUN(batch_refresh(Bt));
     const size_t oWave = up16((size_t) nTab * sizeof(ActWin)), oPts = oWave + up16(((size_t) nTab + 1) * 4), up = oPts + total * sizeof(ldso_immature_t), down = total * sizeof(ldso_activation_t);
     RUN(batch_stage(Bt, up, down));
-    char *hs = Bt->h_marg, *d = Bt->d_marg;
+    char *hs = Bt->h_stage, *d = Bt->d_stage;
     ActWin *tab = (ActWin *) hs;
     int32_t *wave = (int32_t *) (hs + oWave);
     size_t at = 0;

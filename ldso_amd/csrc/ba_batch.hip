@@ -10,6 +10,17 @@
 // pieces with; the chunk policy it re-runs is batch_chunk_policy here.
 #include "ba_host.h"
 
+// a device table of the batch (d_blocks, d_wg) with room for `n` elements: one that is too small is replaced once both streams, whose launches read it, have drained
+template <class T> static int grow_table(ldso_ba_batch *Bt, T *&d, size_t &cap, size_t n) {
+    if (n <= cap) return LDSO_OK;
+    CHK(hipStreamSynchronize(Bt->h[0]->stream));
+    if (Bt->aux) CHK(hipStreamSynchronize(Bt->aux));
+    if (d) (void) hipFree(d);
+    d = nullptr; cap = 0;
+    CHK(hipMalloc((void **) &d, n * sizeof(T)));
+    cap = n;
+    return LDSO_OK;
+}
 int batch_refresh(ldso_ba_batch *Bt) {
     REQ(!Bt->lost, "ldso_ba_batch: a ldso_ba_batch_update_windows that failed behind its validation left windows of the batch unset: destroy and re-create the batch");
     ldso_ba *H0 = Bt->h[0];
@@ -22,8 +33,8 @@ int batch_refresh(ldso_ba_batch *Bt) {
             if (pass == 1 && (int) i == Bt->n0) { Bt->halfChunks[0] = lin; Bt->halfReduce[0] = red; lin = 0; red = 0; }
             if (H->B.acc != H->ownAcc) H->B.acc = H->ownAcc;
             // the per-window parity: set[0] = the window's applied set, so the launches name the sets relative to it and windows at different parities share them
-            it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[H->cur]; it.set[1] = H->sets[H->cur ^ 1]; it.cs = H->chunkStarts;
-            it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.linBlock0 = lin; it.redBlock0 = red; it.outSlot = (int32_t) i;
+            fill_item(it, H, Bt->ks, true, (int) i);
+            it.linBlock0 = lin; it.redBlock0 = red;
             lin += H->D.nChunks;
             red += reduce_grid(H->D.F, 0, Bt->ks, H->GSP).total;
         }
@@ -36,15 +47,7 @@ int batch_refresh(ldso_ba_batch *Bt) {
     Bt->blocks.clear();
     for (size_t i = 0; i < n; i++) for (const BatchBlock &b : Bt->h[i]->h_blocks) Bt->blocks.push_back(BatchBlock{(int32_t) i, b.p0, b.np, b.host_chunk});
     for (size_t i = 0; i < n; i++) { const int32_t w = (int) i < Bt->n0 ? (int32_t) i : (int32_t) i - Bt->n0; for (const BatchBlock &b : Bt->h[i]->h_blocks) Bt->blocks.push_back(BatchBlock{w, b.p0, b.np, b.host_chunk}); }
-    if (Bt->blocks.size() > Bt->blocksCap) {
-        CHK(hipStreamSynchronize(H0->stream));
-        if (Bt->aux) CHK(hipStreamSynchronize(Bt->aux));
-        if (Bt->d_blocks) hipFree(Bt->d_blocks);
-        Bt->d_blocks = nullptr; Bt->blocksCap = 0;
-        void *q = nullptr;
-        CHK(hipMalloc(&q, Bt->blocks.size() * sizeof(BatchBlock)));
-        Bt->d_blocks = (BatchBlock *) q; Bt->blocksCap = Bt->blocks.size();
-    }
+    RUN(grow_table(Bt, Bt->d_blocks, Bt->blocksCap, Bt->blocks.size()));
     CHK(hipMemcpyAsync(Bt->d_blocks, Bt->blocks.data(), Bt->blocks.size() * sizeof(BatchBlock), hipMemcpyHostToDevice, H0->stream));
     if (Bt->balanced) {
         // the per-workgroup block ranges of the three launches (whole batch | half A | half B), valid while the windows keep the chunks ldso_ba_batch_create cut
@@ -52,15 +55,7 @@ int batch_refresh(ldso_ba_batch *Bt) {
         REQ(ok, "ldso_ba_batch: the windows of the batch were re-chunked behind its back (ldso_ba_set_window / ldso_ba_set_chunk_points on a member): destroy and re-create the batch");
         std::vector<int32_t> all;
         for (int u = 0; u < 3; u++) { Bt->wgOff[u] = all.size(); Bt->nWG[u] = Bt->wg[u].empty() ? 0 : (int) Bt->wg[u].size() - 1; all.insert(all.end(), Bt->wg[u].begin(), Bt->wg[u].end()); }
-        if (all.size() > Bt->wgCap) {
-            CHK(hipStreamSynchronize(H0->stream));
-            if (Bt->aux) CHK(hipStreamSynchronize(Bt->aux));
-            if (Bt->d_wg) hipFree(Bt->d_wg);
-            Bt->d_wg = nullptr; Bt->wgCap = 0;
-            void *q = nullptr;
-            CHK(hipMalloc(&q, all.size() * sizeof(int32_t)));
-            Bt->d_wg = (int32_t *) q; Bt->wgCap = all.size();
-        }
+        RUN(grow_table(Bt, Bt->d_wg, Bt->wgCap, all.size()));
         Bt->wgHost.swap(all);
         CHK(hipMemcpyAsync(Bt->d_wg, Bt->wgHost.data(), Bt->wgHost.size() * sizeof(int32_t), hipMemcpyHostToDevice, H0->stream));
     }
@@ -274,8 +269,8 @@ int ldso_ba_batch_destroy(ldso_ba_batch_t *Bt) {
     if (Bt->h_scalars) hipHostFree(Bt->h_scalars);
     if (Bt->d_blocks) hipFree(Bt->d_blocks);
     if (Bt->d_wg) hipFree(Bt->d_wg);
-    if (Bt->d_marg) hipFree(Bt->d_marg);
-    if (Bt->h_marg) hipHostFree(Bt->h_marg);
+    if (Bt->d_stage) hipFree(Bt->d_stage);
+    if (Bt->h_stage) hipHostFree(Bt->h_stage);
     // back to the single-window chunking (handles that were re-chunked by ldso_ba_batch_create)
     if (Bt->balanced) { for (ldso_ba *H : Bt->h) { H->chunkCuts.clear(); if (H->D.P > 0) rechunk(H); } }
     else if (Bt->chunkPoints > 0) for (ldso_ba *H : Bt->h) if (H->chunkPoints == 0 && H->D.P > 0) rechunk(H);
@@ -390,23 +385,11 @@ int ldso_ba_batch_optimize(ldso_ba_batch_t *Bt, int mnumOptIts, int force_all_it
 
 }  // extern "C"
 
-// The staging arena of the batched marginalisations and activations: `up` bytes go up (the marginalisations: [n MargWin | flags]), `down` bytes come down behind
-// them.  Grown on demand; both streams are idle when it is replaced (every user of the arena ends with a wait on the batch's stream).
+// The staging arena of the batched key-frame steps (marginalisations, activations, window update, frames): `up` bytes go up (the marginalisations:
+// [n MargWin | flags]), `down` bytes come down, or are written on the device, behind them.  Grown on demand with half as much again; both streams are idle when it
+// is replaced (every user of the arena ends with a wait on the batch's stream).
 int batch_stage(ldso_ba_batch *Bt, size_t up, size_t down) {
-    const size_t need = up + down;
-    if (need <= Bt->margCap) return LDSO_OK;
-    CHK(hipStreamSynchronize(Bt->h[0]->stream));
-    if (Bt->d_marg) (void) hipFree(Bt->d_marg);
-    if (Bt->h_marg) (void) hipHostFree(Bt->h_marg);
-    Bt->d_marg = nullptr; Bt->h_marg = nullptr; Bt->margCap = 0;
-    const size_t cap = need + need / 2;
-    void *q = nullptr;
-    CHK(hipMalloc(&q, cap));
-    Bt->d_marg = (char *) q;
-    CHK(hipHostMalloc(&q, cap, hipHostMallocDefault));
-    Bt->h_marg = (char *) q;
-    Bt->margCap = cap;
-    return LDSO_OK;
+    return grow_arena(Bt->h_stage, Bt->d_stage, Bt->stageCap, up + down, 2, Bt->h[0]->stream);
 }
 // what both entries refuse, worded like ldso_ba_batch_optimize; `solo`: the single-window entry the message points to, `part(i)`: does window i take part
 template <class Part> static int marg_checks(ldso_ba_batch *Bt, const char *who, const char *solo, Part part) {
@@ -453,20 +436,20 @@ int ldso_ba_batch_marginalize_points(ldso_ba_batch_t *Bt, const int32_t *const *
     if (taking == 0) return LDSO_OK;
     const size_t up = (n * sizeof(MargWin) + nFlags * sizeof(int32_t) + 7) & ~(size_t) 7, down = nOut * sizeof(double);
     RUN(batch_stage(Bt, up, down));
-    memcpy(Bt->h_marg, tab.data(), n * sizeof(MargWin));
-    int32_t *h_flags = (int32_t *) (Bt->h_marg + n * sizeof(MargWin));
+    memcpy(Bt->h_stage, tab.data(), n * sizeof(MargWin));
+    int32_t *h_flags = (int32_t *) (Bt->h_stage + n * sizeof(MargWin));
     for (int i = 0; i < n; i++) if (tab[(size_t) i].active) memcpy(h_flags + tab[(size_t) i].flagOff, flags[i], (size_t) Bt->h[i]->D.P * sizeof(int32_t));
-    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, up, hipMemcpyHostToDevice, H0->stream));
-    const MargWin *d_mw = (const MargWin *) Bt->d_marg;
-    const int32_t *d_flags = (const int32_t *) (Bt->d_marg + n * sizeof(MargWin));
-    double *d_out = (double *) (Bt->d_marg + up);
+    CHK(hipMemcpyAsync(Bt->d_stage, Bt->h_stage, up, hipMemcpyHostToDevice, H0->stream));
+    const MargWin *d_mw = (const MargWin *) Bt->d_stage;
+    const int32_t *d_flags = (const int32_t *) (Bt->d_stage + n * sizeof(MargWin));
+    double *d_out = (double *) (Bt->d_stage + up);
     CHK(ba_launch_linearize_batch_marg(Bt->d_items, Bt->d_blocks, Bt->totalChunks, Bt->balanced ? Bt->d_wg + Bt->wgOff[0] : nullptr, Bt->nWG[0], d_mw, d_flags, H0->settings, H0->stream));
     CHK(ba_launch_reduce_batch_marg(Bt->d_items, d_mw, n, red, maxGSP, H0->stream));
     CHK(ba_launch_marg_gather_update_batch(Bt->d_items, d_mw, n, maxN, (double) H0->settings.margWeightFac, d_out, H0->stream));
     for (int i = 0; i < n; i++) if (tab[(size_t) i].active) Bt->h[i]->hasPrior = true;          // the next batch_refresh / refresh_item hands it to the iteration kernels
-    CHK(hipMemcpyAsync(Bt->h_marg + up, d_out, down, hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipMemcpyAsync(Bt->h_stage + up, d_out, down, hipMemcpyDeviceToHost, H0->stream));
     CHK(hipStreamSynchronize(H0->stream));
-    const double *h_out = (const double *) (Bt->h_marg + up);
+    const double *h_out = (const double *) (Bt->h_stage + up);
     for (int i = 0; i < n; i++) {
         const MargWin &m = tab[(size_t) i];
         if (!m.active) continue;
@@ -506,13 +489,13 @@ int ldso_ba_batch_marginalize_frame(ldso_ba_batch_t *Bt, const int32_t *frame_id
     RUN(batch_refresh(Bt));
     const size_t up = (n * sizeof(MargWin) + 7) & ~(size_t) 7, down = nOut * sizeof(double);
     RUN(batch_stage(Bt, up, down));
-    memcpy(Bt->h_marg, tab.data(), n * sizeof(MargWin));
-    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, up, hipMemcpyHostToDevice, H0->stream));
-    double *d_out = (double *) (Bt->d_marg + up);
-    CHK(ba_launch_marg_frame_batch(Bt->d_items, n, (const MargWin *) Bt->d_marg, d_out, H0->stream));
-    CHK(hipMemcpyAsync(Bt->h_marg + up, d_out, down, hipMemcpyDeviceToHost, H0->stream));
+    memcpy(Bt->h_stage, tab.data(), n * sizeof(MargWin));
+    CHK(hipMemcpyAsync(Bt->d_stage, Bt->h_stage, up, hipMemcpyHostToDevice, H0->stream));
+    double *d_out = (double *) (Bt->d_stage + up);
+    CHK(ba_launch_marg_frame_batch(Bt->d_items, n, (const MargWin *) Bt->d_stage, d_out, H0->stream));
+    CHK(hipMemcpyAsync(Bt->h_stage + up, d_out, down, hipMemcpyDeviceToHost, H0->stream));
     CHK(hipStreamSynchronize(H0->stream));
-    const double *h_out = (const double *) (Bt->h_marg + up);
+    const double *h_out = (const double *) (Bt->h_stage + up);
     for (int i = 0; i < n; i++) {
         const MargWin &m = tab[(size_t) i];
         if (!m.active) continue;

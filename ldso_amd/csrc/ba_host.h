@@ -175,11 +175,12 @@ struct ldso_ba_batch {
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evEnd = nullptr;
     BaDims Dmax;
     double *d_scalars = nullptr, *h_scalars = nullptr;      // [n][16]: every window's scalars after ldso_ba_batch_optimize (device block, pinned host copy)
-    // The staging arena of the batched key-frame steps (batch_stage): one pinned arena and its device twin, grown on demand.  ldso_ba_batch_marginalize_points /
+    // The staging arena of the batched key-frame steps (batch_stage): one pinned arena and its device twin, grown on demand (grow_arena).  ldso_ba_batch_marginalize_points /
     // _frame: [n MargWin | the flags of all windows | pad to 8] go up in one copy, [the windows' (H_M | b_M) in doubles] come down in one; the batched activation
-    // entries (act_select.hip): [tables | every window's inputs] up, [every window's results] down, the selection's scratch behind them on the device
-    char *h_marg = nullptr, *d_marg = nullptr;
-    size_t margCap = 0;
+    // entries (act_select.hip): [tables | every window's inputs] up, [every window's results] down, the selection's scratch behind them on the device; the batched
+    // window update and ldso_ba_batch_set_frames (ba_window.hip): [transfer table | tables | every window's delta or records] up, the images behind them on the device
+    char *h_stage = nullptr, *d_stage = nullptr;
+    size_t stageCap = 0;
     int selLdsLimit = -1, selLdsSet = 0; // dynamic LDS k_act_select_batch may have on this device (-1: not asked yet), and what its attribute was last raised to
     bool lost = false;                 // a ldso_ba_batch_update_windows failed behind its validation: members hold no window, batch_refresh refuses, ldso_ba_batch_destroy cleans up
 };
@@ -249,6 +250,20 @@ inline int swap_stream(hipStream_t &stream, bool &ownStream, void *s) {
     else if (!ownStream) { CHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); ownStream = true; }
     return LDSO_OK;
 }
+// A pinned arena and its device twin (the handle's h_stage / d_stage, the batch's) with room for `need` bytes.  A pair that is too small is replaced by one of
+// need + need / slackDiv bytes once `st`, the stream whose work may still read the old pair, has drained.
+inline int grow_arena(char *&h, char *&d, size_t &cap, size_t need, size_t slackDiv, hipStream_t st) {
+    if (need <= cap) return LDSO_OK;
+    CHK(hipStreamSynchronize(st));
+    if (h) (void) hipHostFree(h);
+    if (d) (void) hipFree(d);
+    h = nullptr; d = nullptr; cap = 0;
+    const size_t room = need + need / slackDiv;
+    CHK(hipHostMalloc((void **) &h, room));
+    CHK(hipMalloc((void **) &d, room));
+    cap = room;
+    return LDSO_OK;
+}
 // A resident pyramid handed to a consumer `what` (named in the message): it holds an image and matches in device, size and levels; then `st` waits for its build.
 inline int pyramid_wait(const ldso_pyramid *pyr, int device, int w, int h, int minLevels, hipStream_t st, const char *who, const char *what) {
     REQ(pyr->built && pyr->device == device && pyr->w == w && pyr->h == h && pyr->levels >= minLevels, std::string(who) + ": pyramid does not match " + what + " or holds no image");
@@ -300,6 +315,9 @@ int launch_gather(ldso_ba *H, const ResSet &S, double lambda, int mode, double *
 int launch_solve(ldso_ba *H, const ResSet &S, unsigned flags, int iteration = 0, double lambda = 0, int logIdx = -1, double *rout = nullptr, const double *rin = nullptr);
 int launch_pstep(ldso_ba *H, const ResSet &S, int mode);
 int refresh_item(ldso_ba *H);
+// the descriptors of H's window as the kernels read them: `ks` K-splits per Schur tile; the residual sets as the handle numbers them, or (`relative`, the batch's
+// order) set[0] = the applied one; linBlock0 / redBlock0 stay 0 (batch_refresh adds the offsets it computes)
+void fill_item(BatchItem &it, const ldso_ba *H, int ks, bool relative, int outSlot);
 int read_scalars(ldso_ba *H, double *sc);
 SolveArgs solve_args(const ldso_ba *H, unsigned flags);
 struct Damping { double lam, l1, il; };

@@ -27,11 +27,15 @@ int launch_solve(ldso_ba *H, const ResSet &S, unsigned flags, int iteration, dou
     return LDSO_OK;
 }
 // the handle's BatchItem in device memory, uploaded when it changed (window, image slots, accumulator lent to an all-reduce buffer, prior)
+void fill_item(BatchItem &it, const ldso_ba *H, int ks, bool relative, int outSlot) {
+    const int applied = relative ? H->cur : 0;
+    memset(&it, 0, sizeof(it));
+    it.B = H->B; it.D = H->D; it.D.ks = ks; it.set[0] = H->sets[applied]; it.set[1] = H->sets[applied ^ 1]; it.cs = H->chunkStarts;
+    it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.outSlot = (int32_t) outSlot;
+}
 int refresh_item(ldso_ba *H) {
     BatchItem it;
-    memset(&it, 0, sizeof(it));
-    it.B = H->B; it.D = H->D; it.set[0] = H->sets[0]; it.set[1] = H->sets[1]; it.cs = H->chunkStarts;
-    it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.linBlock0 = 0; it.redBlock0 = 0;
+    fill_item(it, H, H->D.ks, false, 0);
     if (H->itemValid && memcmp(&it, &H->itemShadow, sizeof(it)) == 0) return LDSO_OK;
     CHK(hipStreamSynchronize(H->stream));            // the pinned copy may still be in flight (rare: the descriptors change per key frame)
     memcpy(H->h_item, &it, sizeof(it));

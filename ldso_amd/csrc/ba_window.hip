@@ -145,10 +145,13 @@ __global__ __launch_bounds__(256) void k_point_stats_batch(const WinDelta *__res
     point_stats_one(W.pt0, W.pt1, W.mrb, W.ngr, i);
 }
 
+static inline size_t A16(size_t b) { return (b + 15) & ~(size_t) 15; }
 // host side of the arena: reserve (16-byte aligned) room, remember where it goes
 struct WinStage {
-    char *base; size_t cap, used; WinXfer *tab; int n;
-    int maxN = LD_XFER_MAX;          // entries `tab` has room for (a batch brings a table of its own size)
+    char *base, *devBase; size_t cap, used; WinXfer *tab; int n, maxN;
+    // over a pinned arena and its device twin, with the transfer table (room for maxN entries; a batch brings a size of its own) at its head
+    WinStage(char *h, char *d, size_t cap_, int maxN_ = LD_XFER_MAX) : base(h), devBase(d), cap(cap_), used(A16((size_t) maxN_ * sizeof(WinXfer))), tab(reinterpret_cast<WinXfer *>(h)), n(0), maxN(maxN_) {}
+    template <class T> T *dev(T *hp) const { return reinterpret_cast<T *>(devBase + (reinterpret_cast<const char *>(hp) - base)); }          // where staged data lies on the device
     template <class T> T *put(T *dst, size_t count) {          // room for `count` elements that will land at dst; returns where to write them
         const size_t bytes = (count * sizeof(T) + 15) & ~(size_t) 15;
         if (n >= maxN || used + bytes > cap) return nullptr;
@@ -272,8 +275,14 @@ int rechunk(ldso_ba *H) {
     return LDSO_OK;
 }
 
-// ---- the pieces of ldso_ba_update_window, shared with ldso_ba_batch_update_windows (one window's delta is a ldso_win_job_t in both) ----
-static inline size_t A16(size_t b) { return (b + 15) & ~(size_t) 15; }
+// ---- the pieces of a window upload, shared by ldso_ba_set_window, ldso_ba_update_window and ldso_ba_batch_update_windows (one window's delta is a ldso_win_job_t in the last two) ----
+// The handle's arena with room for `need` bytes, free for the caller to fill: a copy out of it that may still be in flight (stageBusy) has landed.  The arena only
+// ever holds staging data: growing it loses nothing of the resident window
+static int handle_stage(ldso_ba *H, size_t need) {
+    RUN(grow_arena(H->h_stage, H->d_stage, H->stageCap, need, 4, H->stream));
+    if (H->stageBusy) { CHK(hipStreamSynchronize(H->stream)); H->stageBusy = false; }          // (after a growth the stream has drained already: the wait returns at once)
+    return LDSO_OK;
+}
 // what the validation derives on the way: the flat residual index of every point's first residual, of every fresh point's first record, the new host of every point
 struct WinPlan { std::vector<int32_t> resBegin, freshResBegin, newHost; int R = 0; };
 // The checks of a delta against the resident window of H (indices only; nothing of the resident data is read back, nothing is written).  `who` names the entry.
@@ -349,8 +358,8 @@ static size_t delta_bytes(const ldso_win_job_t &J) {
     const size_t F = (size_t) J.F, P = (size_t) J.P, nf = (size_t) J.n_fresh, nr = (size_t) J.n_fresh_res;
     return A16(F * 4) + 2 * A16(P * 4) + A16((P + 1) * 4) + A16(nf * sizeof(ldso_point_t)) + A16(nr * sizeof(ldso_residual_t)) + A16((nf + 1) * 4) + 2 * A16(nf * 4);
 }
-static size_t image_bytes(const ldso_win_job_t &J) {
-    const size_t P = (size_t) J.P, PS = P * (size_t) ((J.F + 7) / 8 * 8);
+static size_t image_bytes(int F, int P_) {
+    const size_t P = (size_t) P_, PS = P * (size_t) ((F + 7) / 8 * 8);
     return A16(P * sizeof(PtGeo)) + A16(P * 8 * sizeof(PtCw)) + A16(P * 4) + A16(PS * sizeof(SlotTab)) + A16(PS * sizeof(SlotRec)) + 2 * A16(P * 4);
 }
 // what k_win_rebuild reads of the resident window: taken BEFORE the handle adopts the new one
@@ -359,8 +368,8 @@ static void delta_resident(const ldso_ba *H, WinDelta &Wd) {
     const ResSet &So = H->sets[H->cur];
     Wd.oGeo = B.pgeo; Wd.oPcw = B.pcw; Wd.oHost = B.phost; Wd.oTab = B.rtab; Wd.oSlot = So.slot; Wd.oPt = So.pt; Wd.oF = H->D.F; Wd.oFS = H->D.FS; Wd.oP = H->D.P;
 }
-// room for the delta behind what the arena holds, filled; Wd receives its device addresses (`devBase` = the arena's device twin).  false: arena too small
-static bool stage_delta(WinStage &W, const ldso_win_job_t &J, const WinPlan &Pl, const char *devBase, WinDelta &Wd) {
+// room for the delta behind what the arena holds, filled; Wd receives its device addresses.  false: arena too small
+static bool stage_delta(WinStage &W, const ldso_win_job_t &J, const WinPlan &Pl, WinDelta &Wd) {
     const int F = J.F, P = J.P, n_fresh = J.n_fresh, n_fresh_res = J.n_fresh_res;
     int32_t *hFrameFrom = W.raw<int32_t>(F), *hPointFrom = W.raw<int32_t>(P);
     uint32_t *hMask = W.raw<uint32_t>(P);
@@ -374,53 +383,72 @@ static bool stage_delta(WinStage &W, const ldso_win_job_t &J, const WinPlan &Pl,
     memcpy(hResBegin, Pl.resBegin.data(), ((size_t) P + 1) * 4); memcpy(hFreshResBegin, Pl.freshResBegin.data(), ((size_t) n_fresh + 1) * 4);
     if (n_fresh) { memcpy(hFresh, J.fresh, (size_t) n_fresh * sizeof(ldso_point_t)); memcpy(hMrb, J.fresh_mrb, (size_t) n_fresh * 4); memcpy(hNgr, J.fresh_ngr, (size_t) n_fresh * 4); }
     if (n_fresh_res) memcpy(hFreshRes, J.fresh_res, (size_t) n_fresh_res * sizeof(ldso_residual_t));
-    auto dev = [&](const void *hp) { return devBase + (reinterpret_cast<const char *>(hp) - W.base); };
-    Wd.frameFrom = (const int32_t *) dev(hFrameFrom); Wd.pointFrom = (const int32_t *) dev(hPointFrom); Wd.resMask = (const uint32_t *) dev(hMask); Wd.resBegin = (const int32_t *) dev(hResBegin);
-    Wd.fresh = (const ldso_point_t *) dev(hFresh); Wd.freshRes = (const ldso_residual_t *) dev(hFreshRes); Wd.freshResBegin = (const int32_t *) dev(hFreshResBegin);
-    Wd.freshMrb = (const float *) dev(hMrb); Wd.freshNgr = (const int32_t *) dev(hNgr);
+    Wd.frameFrom = W.dev(hFrameFrom); Wd.pointFrom = W.dev(hPointFrom); Wd.resMask = W.dev(hMask); Wd.resBegin = W.dev(hResBegin);
+    Wd.fresh = W.dev(hFresh); Wd.freshRes = W.dev(hFreshRes); Wd.freshResBegin = W.dev(hFreshResBegin);
+    Wd.freshMrb = W.dev(hMrb); Wd.freshNgr = W.dev(hNgr);
     Wd.F = F; Wd.FS = (F + 7) / 8 * 8; Wd.P = P;
     return true;
 }
-// the handle describes the new window: dimensions, image slots, host-side tables; no applied linearisation, no prior (the caller holds a WinGuard)
-static void adopt_window(ldso_ba *H, const ldso_win_job_t &J, const WinPlan &Pl) {
-    const int F = J.F, P = J.P, R = Pl.R, FS = (F + 7) / 8 * 8;
+// The handle's dimensions for a window of F frames on the image slots `image_slot`, P points, R residuals (the caller holds a WinGuard: a slot without an image leaves the
+// handle without a window).  What the callers set differently stays theirs: D.nL / hasL, cur, pendingApply, appliedValid, hasPrior, itemValid, h_phost, flat2slot
+static int adopt_dims(ldso_ba *H, const std::string &who, int F, const int32_t *image_slot, int P, int R) {
     BaDims &D = H->D;
-    D.F = F; D.FS = FS; D.P = P; D.R = R; D.n = 8 * F + 4; D.GS = 8 * D.FS + LD_GEXTRA; D.w = H->w; D.h = H->h; D.nsg = D.FS / 8; D.ks = H->reduceSplits;
-    D.pBegin = 0; D.pEnd = P; D.wM3G = (float) (H->w - 3); D.hM3G = (float) (H->h - 3); D.nL = 0;
+    D.F = F; D.FS = (F + 7) / 8 * 8; D.P = P; D.R = R; D.n = 8 * F + 4; D.GS = 8 * D.FS + LD_GEXTRA; D.w = H->w; D.h = H->h; D.nsg = D.FS / 8; D.ks = H->reduceSplits;
+    D.pBegin = 0; D.pEnd = P; D.wM3G = (float) (H->w - 3); D.hM3G = (float) (H->h - 3);
     H->GSP = (D.GS + 15) / 16 * 16;
     H->R = R;
-    H->imageSlot.assign(J.image_slot, J.image_slot + F);
-    for (int f = 0; f < F; f++) H->B.img[f] = H->imgSlots[J.image_slot[f]];
+    H->imageSlot.assign(image_slot, image_slot + F);
+    for (int f = 0; f < F; f++) {
+        REQ(image_slot[f] >= 0 && image_slot[f] < H->maxF && H->imgSlots[image_slot[f]] != nullptr, who + ": image slot not set");
+        H->B.img[f] = H->imgSlots[image_slot[f]];
+    }
+    return LDSO_OK;
+}
+// the handle describes the new window of a checked delta: dimensions, image slots, host-side tables; no applied linearisation, no prior (the caller holds a WinGuard)
+static int adopt_window(ldso_ba *H, const char *who, const ldso_win_job_t &J, const WinPlan &Pl) {
+    const int F = J.F, P = J.P, R = Pl.R;
+    RUN(adopt_dims(H, who, F, J.image_slot, P, R));
+    const int FS = H->D.FS;
+    H->D.nL = 0;
     H->h_phost.assign(Pl.newHost.begin(), Pl.newHost.end());
     H->flat2slot.assign(R, -1);
     for (int i = 0; i < P; i++) { int k = Pl.resBegin[i]; for (int t = 0; t < F; t++) if ((J.res_mask[i] >> t) & 1u) H->flat2slot[k++] = (int32_t) ((size_t) i * FS + t); }
     H->hasL = false; H->cur = 0; H->pendingApply = false; H->appliedValid = false; H->itemValid = false;
     H->hasPrior = false;
+    return LDSO_OK;
 }
-// the image region of the window H has adopted: same destinations, same order, same zero fills as ldso_ba_set_window.  false: arena or table too small
-static bool stage_image(ldso_ba *H, WinStage &W, const char *devBase, WinDelta &Wd) {
+// The image of the window H has adopted, the ONE list of its destinations and zero fills: room in the arena for the five parts that are copied to the window's buffers
+// (both residual sets take the same slot records), zero for everything else a new window starts from - the point records and accumulators of both sets, the
+// marginalisation prior (a new window has a new dimension 8F+4; ldso_ba_set_prior follows when there is one), the scalars, the Schur partials.  16 table entries.
+// `stats`: room for maxRelBaseline / numGoodResiduals behind the parts (no destination: k_point_stats reads them where they lie).  false: arena or table too small
+struct WinImage { PtGeo *geo; PtCw *pcw; int32_t *phost; SlotTab *tab; SlotRec *sr; float *mrb; int32_t *ngr; };          // host pointers into the arena
+static bool stage_image(ldso_ba *H, WinStage &W, bool stats, WinImage &I) {
     BaPtrs &B = H->B;
     const BaDims &D = H->D;
     const size_t P = (size_t) D.P, PS = P * (size_t) D.FS;
-    PtGeo *geo = W.put(B.pgeo, P);
-    PtCw *pcw = W.put(B.pcw, P * 8);
-    int32_t *phost = W.put(B.phost, P);
-    SlotTab *tab = W.put(B.rtab, PS);
-    SlotRec *sr = W.put(H->sets[0].slot, PS);
-    if (!(geo && pcw && phost && tab && sr)) return false;
-    float *mrb = W.raw<float>(P); int32_t *ngr = W.raw<int32_t>(P);
-    if (!(mrb && ngr)) return false;
-    auto dev = [&](const void *hp) { return const_cast<char *>(devBase) + (reinterpret_cast<const char *>(hp) - W.base); };
-    Wd.geo = (PtGeo *) dev(geo); Wd.pcw = (PtCw *) dev(pcw); Wd.phost = (int32_t *) dev(phost); Wd.tab = (SlotTab *) dev(tab); Wd.sr = (SlotRec *) dev(sr); Wd.mrb = (float *) dev(mrb); Wd.ngr = (int32_t *) dev(ngr);
-    Wd.pt0 = H->sets[0].pt; Wd.pt1 = H->sets[1].pt;
-    bool okT = W.again(H->sets[1].slot, sr, PS);
+    I.geo = W.put(B.pgeo, P);
+    I.pcw = W.put(B.pcw, P * 8);
+    I.phost = W.put(B.phost, P);
+    I.tab = W.put(B.rtab, PS);
+    I.sr = W.put(H->sets[0].slot, PS);
+    if (!(I.geo && I.pcw && I.phost && I.tab && I.sr)) return false;
+    I.mrb = stats ? W.raw<float>(P) : nullptr; I.ngr = stats ? W.raw<int32_t>(P) : nullptr;
+    if (stats && !(I.mrb && I.ngr)) return false;
+    bool okT = W.again(H->sets[1].slot, I.sr, PS);
     for (int s_ = 0; s_ < 2; s_++) {
         ResSet &S = H->sets[s_];
         okT = okT && W.zero(S.pt, P) && W.zero(S.acc, P) && W.zero(S.G, P * D.GS);
     }
-    // a new window has a new dimension 8F+4: the marginalisation prior starts at zero
     okT = okT && W.zero(B.HM, (size_t) D.n * D.n) && W.zero(B.bM, (size_t) D.n) && W.zero(B.scalars, (size_t) 16) && W.zero(B.scPart, (size_t) LD_SC_SPLITS * H->GSP * H->GSP);
     return okT;
+}
+// the image as k_win_rebuild writes it and k_point_stats reads it: the device addresses of its parts
+static bool stage_delta_image(ldso_ba *H, WinStage &W, WinDelta &Wd) {
+    WinImage I;
+    if (!stage_image(H, W, true, I)) return false;
+    Wd.geo = W.dev(I.geo); Wd.pcw = W.dev(I.pcw); Wd.phost = W.dev(I.phost); Wd.tab = W.dev(I.tab); Wd.sr = W.dev(I.sr); Wd.mrb = W.dev(I.mrb); Wd.ngr = W.dev(I.ngr);
+    Wd.pt0 = H->sets[0].pt; Wd.pt1 = H->sets[1].pt;
+    return true;
 }
 
 extern "C" {
@@ -433,45 +461,22 @@ int ldso_ba_set_window(ldso_ba_t *H, int F, const int32_t *image_slot, int P, co
     BaDims &D = H->D;
     BaPtrs &B = H->B;
     WinGuard guard{H, false};          // a failure from here on leaves the handle without a window (ba_host.h)
-    D.F = F; D.FS = (F + 7) / 8 * 8; D.P = P; D.R = R; D.n = 8 * F + 4; D.GS = 8 * D.FS + LD_GEXTRA; D.w = H->w; D.h = H->h; D.nsg = D.FS / 8; D.ks = H->reduceSplits;
-    D.pBegin = 0; D.pEnd = P; D.wM3G = (float) (H->w - 3); D.hM3G = (float) (H->h - 3);
-    H->GSP = (D.GS + 15) / 16 * 16;
-    H->R = R;
-    H->imageSlot.assign(image_slot, image_slot + F);
-    for (int f = 0; f < F; f++) {
-        REQ(image_slot[f] >= 0 && image_slot[f] < H->maxF && H->imgSlots[image_slot[f]] != nullptr, "ldso_ba_set_window: image slot not set");
-        B.img[f] = H->imgSlots[image_slot[f]];
-    }
+    RUN(adopt_dims(H, "ldso_ba_set_window", F, image_slot, P, R));
     const int FS = D.FS;
     const size_t PS = (size_t) P * FS;
     // ---- staging arena: everything the window needs goes over PCIe in ONE copy and is distributed (or zero-filled) by ONE kernel ----
     size_t nLin = 0;
     for (int i = 0; i < R; i++) nLin += res[i].is_linearized ? 1 : 0;
     REQ(nLin == 0 || (linJ && lin_rtz), "ldso_ba_set_window: linearised residual without linJ / lin_res_toZeroF");
-    auto A16 = [](size_t b) { return (b + 15) & ~(size_t) 15; };
-    const size_t tabBytes = A16(LD_XFER_MAX * sizeof(WinXfer));
-    const size_t need = tabBytes + A16((size_t) P * sizeof(PtGeo)) + A16((size_t) P * 8 * sizeof(PtCw)) + A16((size_t) P * 4) + A16(PS * sizeof(SlotTab)) + A16(nLin * sizeof(ldso_rawjac_t)) + A16(nLin * 32)
-                      + A16(PS * sizeof(SlotRec)) + 64;
-    if (need > H->stageCap) {
-        CHK(hipStreamSynchronize(H->stream));
-        if (H->h_stage) hipHostFree(H->h_stage);
-        if (H->d_stage) hipFree(H->d_stage);
-        H->h_stage = nullptr; H->d_stage = nullptr; H->stageCap = 0;
-        const size_t cap = need + need / 4;
-        CHK(hipHostMalloc((void **) &H->h_stage, cap));
-        CHK(hipMalloc((void **) &H->d_stage, cap));
-        H->stageCap = cap;
-    }
-    if (H->stageBusy) { CHK(hipStreamSynchronize(H->stream)); H->stageBusy = false; }
-    WinStage W{H->h_stage, H->stageCap, tabBytes, reinterpret_cast<WinXfer *>(H->h_stage), 0};
-    PtGeo *geo = W.put(B.pgeo, P);
-    PtCw *pcw = W.put(B.pcw, (size_t) P * 8);
-    int32_t *phost = W.put(B.phost, P);
-    SlotTab *tab = W.put(B.rtab, PS);
+    RUN(handle_stage(H, A16(LD_XFER_MAX * sizeof(WinXfer)) + image_bytes(F, P) + A16(nLin * sizeof(ldso_rawjac_t)) + A16(nLin * 32) + 64));
+    WinStage W(H->h_stage, H->d_stage, H->stageCap);
+    WinImage I;
+    REQ(stage_image(H, W, false, I), "ldso_ba_set_window: staging arena too small or upload table overflow (internal)");
+    // the image's parts are filled from the caller's records; behind them what only this entry brings: the linearised residuals' Jacobians and res_toZeroF
+    PtGeo *geo = I.geo; PtCw *pcw = I.pcw; int32_t *phost = I.phost; SlotTab *tab = I.tab; SlotRec *sr = I.sr;
     ldso_rawjac_t *Jl = W.put(B.Jlin, nLin);
     float *rtz = W.put(B.rtz, nLin * 8);
-    SlotRec *sr = W.put(H->sets[0].slot, PS);
-    REQ(geo && pcw && phost && tab && Jl && rtz && sr, "ldso_ba_set_window: staging arena too small (internal)");
+    REQ(Jl && rtz, "ldso_ba_set_window: staging arena too small (internal)");
     H->h_phost.resize(P);
     for (int i = 0; i < P; i++) {
         PtGeo g_;
@@ -510,15 +515,6 @@ int ldso_ba_set_window(ldso_ba_t *H, int F, const int32_t *image_slot, int P, co
     D.nL = (int) nLin;
     H->hasL = D.nL > 0;
     H->cur = 0; H->pendingApply = false; H->appliedValid = false;
-    bool okT = W.again(H->sets[1].slot, sr, PS);
-    for (int s_ = 0; s_ < 2; s_++) {
-        ResSet &S = H->sets[s_];
-        okT = okT && W.zero(S.pt, (size_t) P) && W.zero(S.acc, (size_t) P) && W.zero(S.G, (size_t) P * D.GS);
-    }
-    // a new window has a new dimension 8F+4: the marginalisation prior starts at zero (ldso_ba_set_prior follows when there is one)
-    okT = okT && W.zero(B.HM, (size_t) D.n * D.n) && W.zero(B.bM, (size_t) D.n) && W.zero(B.scalars, (size_t) 16)
-              && W.zero(B.scPart, (size_t) LD_SC_SPLITS * H->GSP * H->GSP);
-    REQ(okT, "ldso_ba_set_window: upload table overflow (internal)");
     H->hasPrior = false;
     CHK(hipMemcpyAsync(H->d_stage, H->h_stage, W.used, hipMemcpyHostToDevice, H->stream));
     hipLaunchKernelGGL(k_win_scatter, dim3(256), dim3(256), 0, H->stream, (const char *) H->d_stage, W.n);
@@ -567,29 +563,16 @@ int ldso_ba_update_window(ldso_ba_t *H, int F, const int32_t *image_slot, const 
     RUN(check_window_delta(H, "ldso_ba_update_window", J, Pl));
     CHK(hipSetDevice(H->device));
     // ---- arena: [table | delta | image]; only table + delta cross PCIe ----
-    const size_t tabBytes = A16(LD_XFER_MAX * sizeof(WinXfer));
-    const size_t need = tabBytes + delta_bytes(J) + image_bytes(J) + 64;
-    if (need > H->stageCap) {          // the arena only ever holds staging data: growing it loses nothing of the resident window
-        CHK(hipStreamSynchronize(H->stream));
-        if (H->h_stage) hipHostFree(H->h_stage);
-        if (H->d_stage) hipFree(H->d_stage);
-        H->h_stage = nullptr; H->d_stage = nullptr; H->stageCap = 0; H->stageBusy = false;
-        const size_t cap = need + need / 4;
-        CHK(hipHostMalloc((void **) &H->h_stage, cap));
-        CHK(hipMalloc((void **) &H->d_stage, cap));
-        H->stageCap = cap;
-    }
-    if (H->stageBusy) { CHK(hipStreamSynchronize(H->stream)); H->stageBusy = false; }
-    WinStage W{H->h_stage, H->stageCap, tabBytes, reinterpret_cast<WinXfer *>(H->h_stage), 0};
+    RUN(handle_stage(H, A16(LD_XFER_MAX * sizeof(WinXfer)) + delta_bytes(J) + image_bytes(F, P) + 64));
+    WinStage W(H->h_stage, H->d_stage, H->stageCap);
     WinDelta Wd;
     delta_resident(H, Wd);
-    REQ(stage_delta(W, J, Pl, H->d_stage, Wd), "ldso_ba_update_window: staging arena too small (internal)");
+    REQ(stage_delta(W, J, Pl, Wd), "ldso_ba_update_window: staging arena too small (internal)");
     const size_t upBytes = W.used;
     // from here on the handle describes the new window (a failure leaves it without one, as in ldso_ba_set_window)
     WinGuard guard{H, false};
-    adopt_window(H, J, Pl);
-    // the image region: same destinations, same order, same zero fills as ldso_ba_set_window
-    REQ(stage_image(H, W, H->d_stage, Wd), "ldso_ba_update_window: staging arena too small or upload table overflow (internal)");
+    RUN(adopt_window(H, "ldso_ba_update_window", J, Pl));
+    REQ(stage_delta_image(H, W, Wd), "ldso_ba_update_window: staging arena too small or upload table overflow (internal)");
     CHK(hipMemcpyAsync(H->d_stage, H->h_stage, upBytes, hipMemcpyHostToDevice, H->stream));
     hipLaunchKernelGGL(k_win_rebuild, dim3((unsigned) (((size_t) Wd.P * Wd.FS + 255) / 256)), dim3(256), 0, H->stream, Wd);
     CHK(hipGetLastError());
@@ -605,7 +588,7 @@ int ldso_ba_update_window(ldso_ba_t *H, int F, const int32_t *image_slot, const 
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 // The same step for every window of a batch (include/ldso_hip.h: ldso_ba_batch_update_windows): the pieces above per window - check_window_delta for ALL windows
-// first, then stage_delta / adopt_window / stage_image into ONE arena (the batch's, batch_stage) laid out [transfer table | work units | n WinDelta | every
+// first, then stage_delta / adopt_window / stage_delta_image into ONE arena (the batch's, batch_stage) laid out [transfer table | work units | n WinDelta | every
 // window's delta | every window's chunk tables || every window's image]: what stands in front of || goes up in one copy, the images are written by
 // k_win_rebuild_batch and distributed, with the chunk tables and the zero fills, by k_win_scatter_batch.  In between the batch re-runs its chunk policy on the new
 // point counts (batch_chunk_policy, as ldso_ba_batch_create): the participating windows hold no applied linearisation, so cutting them is host work (plan_chunks)
@@ -649,23 +632,22 @@ int ldso_ba_batch_update_windows(ldso_ba_batch_t *Bt, const ldso_win_job_t *jobs
     for (int i : part) {
         const ldso_ba *H = Bt->h[(size_t) i];
         up += delta_bytes(jobs[i]) + 3 * A16((size_t) H->maxChunks * 4) + A16(((size_t) jobs[i].F + 1) * 4) + A16((size_t) H->maxChunks * sizeof(BatchBlock));
-        img += image_bytes(jobs[i]);
+        img += image_bytes(jobs[i].F, jobs[i].P);
     }
     RUN(batch_stage(Bt, up, img));          // (may wait for the stream and replace the arena: nothing of the windows lives there)
-    WinStage W{Bt->h_marg, Bt->margCap, 0, reinterpret_cast<WinXfer *>(Bt->h_marg), 0, maxEntries};
-    W.used = A16((size_t) maxEntries * sizeof(WinXfer));
+    WinStage W(Bt->h_stage, Bt->d_stage, Bt->stageCap, maxEntries);
     int32_t *unit0 = W.raw<int32_t>((size_t) maxEntries + 1);
     WinDelta *hWd = W.raw<WinDelta>((size_t) nPart);
     REQ(unit0 && hWd, "ldso_ba_batch_update_windows: staging arena too small (internal)");
     std::vector<WinDelta> Wd((size_t) nPart);
     for (int k = 0; k < nPart; k++) {
         delta_resident(Bt->h[(size_t) part[(size_t) k]], Wd[(size_t) k]);
-        REQ(stage_delta(W, jobs[part[(size_t) k]], plans[(size_t) part[(size_t) k]], Bt->d_marg, Wd[(size_t) k]), "ldso_ba_batch_update_windows: staging arena too small (internal)");
+        REQ(stage_delta(W, jobs[part[(size_t) k]], plans[(size_t) part[(size_t) k]], Wd[(size_t) k]), "ldso_ba_batch_update_windows: staging arena too small (internal)");
     }
     // ---- from here on the participating handles describe their new windows: a failure leaves them without one and the batch fit for ldso_ba_batch_destroy only ----
     BatchWinGuard guard{Bt, {}, false};
     for (int i : part) guard.taking.push_back(Bt->h[(size_t) i]);
-    for (int i : part) adopt_window(Bt->h[(size_t) i], jobs[i], plans[(size_t) i]);
+    for (int i : part) RUN(adopt_window(Bt->h[(size_t) i], "ldso_ba_batch_update_windows", jobs[i], plans[(size_t) i]));
     // the batch re-cuts itself: the policy of ldso_ba_batch_create on the new point counts (the cuts the batch gave its windows are its own to replace)
     if (Bt->balanced) for (ldso_ba *H : Bt->h) H->chunkCuts.clear();
     BatchCuts C;
@@ -684,21 +666,20 @@ int ldso_ba_batch_update_windows(ldso_ba_batch_t *Bt, const ldso_win_job_t *jobs
     size_t upBytes = W.used;
     size_t maxPS = 0, maxP = 0;
     for (int k = 0; k < nPart; k++) {
-        REQ(stage_image(Bt->h[(size_t) part[(size_t) k]], W, Bt->d_marg, Wd[(size_t) k]), "ldso_ba_batch_update_windows: staging arena too small or upload table overflow (internal)");
+        REQ(stage_delta_image(Bt->h[(size_t) part[(size_t) k]], W, Wd[(size_t) k]), "ldso_ba_batch_update_windows: staging arena too small or upload table overflow (internal)");
         maxPS = std::max(maxPS, (size_t) Wd[(size_t) k].P * Wd[(size_t) k].FS); maxP = std::max(maxP, (size_t) Wd[(size_t) k].P);
     }
-    REQ(upBytes <= up && W.used <= Bt->margCap, "ldso_ba_batch_update_windows: staging arena too small (internal)");
+    REQ(upBytes <= up && W.used <= Bt->stageCap, "ldso_ba_batch_update_windows: staging arena too small (internal)");
     memcpy(hWd, Wd.data(), (size_t) nPart * sizeof(WinDelta));
     const int units = xfer_units(W, unit0);
-    auto dev = [&](const void *hp) { return Bt->d_marg + (reinterpret_cast<const char *>(hp) - Bt->h_marg); };
     hipStream_t st = H0->stream;
-    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, upBytes, hipMemcpyHostToDevice, st));
+    CHK(hipMemcpyAsync(Bt->d_stage, Bt->h_stage, upBytes, hipMemcpyHostToDevice, st));
     // the order of the single-window path: the rebuild reads the resident windows that the scatter overwrites
-    hipLaunchKernelGGL(k_win_rebuild_batch, dim3((unsigned) ((maxPS + 255) / 256), (unsigned) nPart), dim3(256), 0, st, (const WinDelta *) dev(hWd));
+    hipLaunchKernelGGL(k_win_rebuild_batch, dim3((unsigned) ((maxPS + 255) / 256), (unsigned) nPart), dim3(256), 0, st, (const WinDelta *) W.dev(hWd));
     CHK(hipGetLastError());
-    hipLaunchKernelGGL(k_win_scatter_batch, dim3((unsigned) units), dim3(256), 0, st, (const char *) Bt->d_marg, (const WinXfer *) Bt->d_marg, (const int32_t *) dev(unit0), W.n);
+    hipLaunchKernelGGL(k_win_scatter_batch, dim3((unsigned) units), dim3(256), 0, st, (const char *) Bt->d_stage, (const WinXfer *) Bt->d_stage, (const int32_t *) W.dev(unit0), W.n);
     CHK(hipGetLastError());
-    hipLaunchKernelGGL(k_point_stats_batch, dim3((unsigned) ((maxP + 255) / 256), (unsigned) nPart), dim3(256), 0, st, (const WinDelta *) dev(hWd));
+    hipLaunchKernelGGL(k_point_stats_batch, dim3((unsigned) ((maxP + 255) / 256), (unsigned) nPart), dim3(256), 0, st, (const WinDelta *) W.dev(hWd));
     CHK(hipGetLastError());
     // the cost of sitting out: the window keeps its bytes and its applied state, re-formed under the batch's new chunks (one linearisation launch, the parity flips)
     for (int i = 0; i < n; i++) if (jobs[i].frame_from == nullptr) RUN(batch_cut_window(Bt->h[(size_t) i], i, C, true, rechunk));
@@ -736,8 +717,7 @@ int ldso_ba_batch_set_frames(ldso_ba_batch_t *Bt, const ldso_frames_job_t *jobs)
     up += A16((size_t) maxEntries * sizeof(WinXfer)) + A16(((size_t) maxEntries + 1) * 4) + A16((size_t) nPart * sizeof(BatchItem)) + 64;
     CHK(hipSetDevice(H0->device));
     RUN(batch_stage(Bt, up, 0));
-    WinStage W{Bt->h_marg, Bt->margCap, 0, reinterpret_cast<WinXfer *>(Bt->h_marg), 0, maxEntries};
-    W.used = A16((size_t) maxEntries * sizeof(WinXfer));
+    WinStage W(Bt->h_stage, Bt->d_stage, Bt->stageCap, maxEntries);
     int32_t *unit0 = W.raw<int32_t>((size_t) maxEntries + 1);
     BatchItem *hItems = W.raw<BatchItem>((size_t) nPart);
     REQ(unit0 && hItems, "ldso_ba_batch_set_frames: staging arena too small (internal)");
@@ -754,19 +734,14 @@ int ldso_ba_batch_set_frames(ldso_ba_batch_t *Bt, const ldso_frames_job_t *jobs)
         if (J.bM) { double *q = W.put(H->B.bM, nn); ok = ok && q; if (q) memcpy(q, J.bM, nn * 8); } else ok = ok && W.zero(H->B.bM, nn);
         REQ(ok, "ldso_ba_batch_set_frames: staging arena too small (internal)");
         H->hasPrior = (J.HM != nullptr) || (J.bM != nullptr);
-        // the window's descriptors as batch_refresh writes them
-        BatchItem &it = hItems[k];
-        memset(&it, 0, sizeof(it));
-        it.B = H->B; it.D = H->D; it.D.ks = Bt->ks; it.set[0] = H->sets[H->cur]; it.set[1] = H->sets[H->cur ^ 1]; it.cs = H->chunkStarts;
-        it.hasPrior = H->hasPrior ? 1 : 0; it.GSP = H->GSP; it.outSlot = (int32_t) part[(size_t) k];
+        fill_item(hItems[k], H, Bt->ks, true, part[(size_t) k]);          // the window's descriptors as batch_refresh writes them
     }
     const int units = xfer_units(W, unit0);
-    auto dev = [&](const void *hp) { return Bt->d_marg + (reinterpret_cast<const char *>(hp) - Bt->h_marg); };
     hipStream_t st = H0->stream;
-    CHK(hipMemcpyAsync(Bt->d_marg, Bt->h_marg, W.used, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_win_scatter_batch, dim3((unsigned) units), dim3(256), 0, st, (const char *) Bt->d_marg, (const WinXfer *) Bt->d_marg, (const int32_t *) dev(unit0), W.n);
+    CHK(hipMemcpyAsync(Bt->d_stage, Bt->h_stage, W.used, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_win_scatter_batch, dim3((unsigned) units), dim3(256), 0, st, (const char *) Bt->d_stage, (const WinXfer *) Bt->d_stage, (const int32_t *) W.dev(unit0), W.n);
     CHK(hipGetLastError());
-    CHK(ba_launch_solve_batch((const BatchItem *) dev(hItems), nPart, Bt->Dmax, H0->settings, SK_ADJ | SK_PRECALC, 0, nullptr, st));
+    CHK(ba_launch_solve_batch((const BatchItem *) W.dev(hItems), nPart, Bt->Dmax, H0->settings, SK_ADJ | SK_PRECALC, 0, nullptr, st));
     CHK(hipStreamSynchronize(st));
     return LDSO_OK;
 }
