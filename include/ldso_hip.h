@@ -490,6 +490,33 @@ int ldso_tr_track_new_coarse(ldso_tracker_t *t, const double sprelast_w2c[12], c
                              double new_frame_w2c[12], float aff_out[2], int *tries_consumed, int *good);
 int ldso_tr_get_pc(ldso_tracker_t *t, int lvl, float *u, float *v, float *idepth, float *color, int *n);
 
+/* ------------------------------------------------------------------------------------------------
+ * A group of trackers: the per-frame leg of many sequences on one card.  CoarseTracker::trackNewestCoarse (CoarseTracker.cc:61-217) runs on
+ * every frame of every sequence; one track alone is latency bound and occupies 16 of the CUs, so the tracks of a group share launches.
+ * All arrays are member-major (member i of ldso_tr_group_create at row i).
+ * ---------------------------------------------------------------------------------------------- */
+/* The launch shape of a track: *G = how many workgroups share each of `count` concurrent tracks on a device with num_cu CUs
+ * (16 / 12 / 8 / 4 while count * G <= num_cu: all workgroups of a cooperative launch must be resident; else 1).  Pure host function. */
+int ldso_tr_coop_width(int count, int num_cu, int *G);
+typedef struct ldso_tr_group ldso_tr_group_t;
+/* 1 <= n <= 128 trackers on one device and one stream (ldso_tr_set_stream); image size, level count, settings and point counts may differ.  A tracker
+ * belongs to at most one group and stays usable on its own between group calls (ldso_tr_set_ref*, ldso_tr_set_new_frame*, ldso_tr_track): the group
+ * reads every member's current frames and settings at each call.  ldso_tr_destroy of a member is refused while the group lives. */
+int ldso_tr_group_create(ldso_tracker_t *const *trackers, int n, ldso_tr_group_t **out);
+int ldso_tr_group_destroy(ldso_tr_group_t *g);
+/* what a launch of n_jobs tracks uses on the group's device (ldso_tr_coop_width with its CU count) */
+int ldso_tr_group_coop_width(ldso_tr_group_t *g, int n_jobs, int *G);
+/* CoarseTracker::trackNewestCoarse (CoarseTracker.cc:61-217) = ldso_tr_track for every member with active[i] != 0 (active == NULL: all), in ONE launch with
+ * one upload, one download and one wait.  Rows of inactive members are left untouched.  minResForAbort: n x 5 or NULL (never abort). */
+int ldso_tr_group_track(ldso_tr_group_t *g, const uint8_t *active /* n or NULL = all */, double *T_ref2new_inout /* n*12 */, float *aff_inout /* n*2 */,
+                        const int *coarsestLvl /* n */, const double *minResForAbort /* n*5 or NULL */, double *lastResiduals_out /* n*5 */,
+                        double *lastFlowIndicators_out /* n*3 */, int *ok_out /* n */, int *iterations_out /* n */);
+/* Vec4 FullSystem::trackNewCoarse(fh) (FullSystem.cc:179-386) = ldso_tr_track_new_coarse for every active member, in two launches for the whole group:
+ * try 0 of every member, then the remaining tries of all members whose loop goes on (:355 not met) in one. */
+int ldso_tr_group_track_new_coarse(ldso_tr_group_t *g, const uint8_t *active, const double *sprelast_w2c /* n*12 */, const double *slast_w2c, const double *lastF_w2c,
+                                   const int *poses_valid /* n */, const float *aff_last /* n*2 */, double *lastCoarseRMSE_inout /* n*5 */, const double *reTrackThreshold /* n */,
+                                   double *result4 /* n*4 */, double *new_frame_w2c /* n*12 */, float *aff_out /* n*2 */, int *tries_consumed /* n */, int *good /* n */);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Immature-point tracing: FullSystem::traceNewCoarse (FullSystem.cc:1012-1050) = ImmaturePoint::traceOn
  * (src/internal/ImmaturePoint.cc:47-310) for every immature point of the window against a new frame, one launch.

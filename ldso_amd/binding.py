@@ -988,7 +988,7 @@ class Tracker:
 
     def close(self):
         if self.h:
-            self.L.ldso_tr_destroy(self.h)
+            _chk(self.L.ldso_tr_destroy(self.h))          # refused while the tracker is a member of a live TrackerGroup: the handle stays
             self.h = None
 
     def __del__(self):
@@ -996,6 +996,10 @@ class Tracker:
             self.close()
         except Exception:
             pass
+
+    def set_stream(self, stream_ptr):
+        """the caller's HIP stream (an integer handle) instead of the tracker's own; None / 0: an own one again"""
+        _chk(self.L.ldso_tr_set_stream(self.h, C.c_void_p(stream_ptr or None)))
 
     def _pyr(self, pyr):
         keep = [np.ascontiguousarray(pyr[l], np.float32) for l in range(self.levels)]
@@ -1101,6 +1105,84 @@ class Tracker:
         it = np.zeros(n, np.int32)
         _chk(self.L.ldso_tr_track_batch(self.h, C.c_int(n), _p(T), _p(ab), C.c_int(coarsest), _p(mr), _p(lr), _p(fl), _p(ok), _p(it)))
         return dict(ok=ok.astype(bool), T=T, a=ab[:, 0].copy(), b=ab[:, 1].copy(), lastResiduals=lr, flow=fl, iterations=it)
+
+
+def coop_width(count, num_cu) -> int:
+    """ldso_tr_coop_width: workgroups that share each of `count` concurrent tracks on a device with num_cu CUs"""
+    G = C.c_int()
+    _chk(lib().ldso_tr_coop_width(C.c_int(count), C.c_int(num_cu), C.byref(G)))
+    return G.value
+
+
+class TrackerGroup:
+    """ldso_tr_group_*: the tracks of several trackers (independent sequences on one device and one stream) in one launch.  Arguments and results are per member,
+    in the order of `trackers`; the members stay usable on their own between group calls."""
+
+    def __init__(self, trackers):
+        self.L = lib()
+        self.trackers = list(trackers)          # kept alive: the group dereferences its members
+        arr = (C.c_void_p * len(self.trackers))(*[t.h for t in self.trackers])
+        self.h = C.c_void_p()
+        _chk(self.L.ldso_tr_group_create(arr, C.c_int(len(self.trackers)), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.ldso_tr_group_destroy(self.h)          # unchecked, unlike Tracker.close: a group's destroy has nothing that refuses it
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def coop_width(self, n_jobs) -> int:
+        G = C.c_int()
+        _chk(self.L.ldso_tr_group_coop_width(self.h, C.c_int(n_jobs), C.byref(G)))
+        return G.value
+
+    def _active(self, active):
+        n = len(self.trackers)
+        if active is None:
+            return None, list(range(n))
+        act = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
+        assert act.shape == (n,)
+        return act, [i for i in range(n) if act[i]]
+
+    def track(self, Ts, affs, coarsest, min_res=None, active=None):
+        """ldso_tr_group_track -> per member the dict of Tracker.track (None for an inactive member).  Ts: n poses (4x4 or 3x4), affs: n (a, b) pairs, coarsest: n levels
+        (or one for all), min_res: None, one row of 5 for all, or n rows (a row of NaN never aborts)."""
+        n = len(self.trackers)
+        T = np.ascontiguousarray(np.stack([np.asarray(t, np.float64)[:3, :4] for t in Ts]), np.float64).copy()
+        ab = np.ascontiguousarray(np.asarray(affs, np.float32).reshape(n, 2)).copy()
+        co = np.ascontiguousarray(np.broadcast_to(np.asarray(coarsest, np.int32), (n,)), np.int32)
+        mr = None if min_res is None else np.ascontiguousarray(np.broadcast_to(np.asarray(min_res, np.float64), (n, 5)), np.float64)
+        lr = np.zeros((n, 5)); fl = np.zeros((n, 3)); ok = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
+        act, idx = self._active(active)
+        _chk(self.L.ldso_tr_group_track(self.h, _p(act), _p(T), _p(ab), _p(co), _p(mr), _p(lr), _p(fl), _p(ok), _p(it)))
+        out = [None] * n
+        for i in idx:
+            out[i] = dict(ok=bool(ok[i]), T=T[i].copy(), a=ab[i, 0], b=ab[i, 1], lastResiduals=lr[i].copy(), flow=fl[i].copy(), iterations=it[i])
+        return out
+
+    def track_new_coarse(self, sprelast, slast, lastF, aff_last, last_rmse, retrack_threshold=1.5, poses_valid=True, active=None):
+        """ldso_tr_group_track_new_coarse -> per member the dict of Tracker.track_new_coarse (None for an inactive member).  sprelast / slast / lastF: n worldToCam poses
+        each, aff_last: n pairs, last_rmse: n rows of 5; retrack_threshold and poses_valid: one value for all or n."""
+        n = len(self.trackers)
+        P = [np.ascontiguousarray(np.stack([np.asarray(m, np.float64)[:3, :4] for m in ms]), np.float64) for ms in (sprelast, slast, lastF)]
+        aff = np.ascontiguousarray(np.asarray(aff_last, np.float32).reshape(n, 2))
+        rmse = np.ascontiguousarray(np.asarray(last_rmse, np.float64).reshape(n, 5)).copy()
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(retrack_threshold, np.float64), (n,)), np.float64)
+        pv = np.ascontiguousarray(np.broadcast_to(np.asarray(poses_valid).astype(np.int32), (n,)), np.int32)
+        res4 = np.zeros((n, 4)); w2c = np.zeros((n, 3, 4)); aff_out = np.zeros((n, 2), np.float32)
+        tries = np.full(n, -1, np.int32); good = np.full(n, -1, np.int32)
+        act, idx = self._active(active)
+        _chk(self.L.ldso_tr_group_track_new_coarse(self.h, _p(act), _p(P[0]), _p(P[1]), _p(P[2]), _p(pv), _p(aff), _p(rmse), _p(thr), _p(res4), _p(w2c), _p(aff_out),
+                                                   _p(tries), _p(good)))
+        out = [None] * n
+        for i in idx:
+            out[i] = dict(result=res4[i].copy(), w2c=w2c[i].copy(), aff=aff_out[i].copy(), lastCoarseRMSE=rmse[i].copy(), tries=int(tries[i]), good=int(good[i]))
+        return out
 
 
 class Tracer:

@@ -188,7 +188,9 @@ __device__ __forceinline__ void tr_eval(const TrParams &P, int lvl, const float 
             }
         }
         pass(pc.id, pc.x, pc.y, pc.col, lo + tid, nU);
-        for (int ib = lo + tid + nth * TR_U; ib < hi; ib += nth * TR_U) {
+        // the trip count is the WAVE's (its first lane decides): the matrix instructions of pass() take the operands of all 64 lanes whatever the execution mask, so a
+        // lane that left the loop early would feed them whatever its operand registers hold; a lane past `hi` stages zeros like the lanes past `hi` of the first pass
+        for (int ib = lo + tid + nth * TR_U; ib - lane < hi; ib += nth * TR_U) {
             float id[TR_U], x[TR_U], y[TR_U], col[TR_U];
 #pragma unroll
             for (int u_ = 0; u_ < TR_U; u_++) {
@@ -486,9 +488,11 @@ __device__ void tr_helper_loop(const TrParams &P, TrCoop *co, int g, int seq, do
 // ---------------------------------------------------------------------------------------------------------
 // trackNewestCoarse: G workgroups per hypothesis (G = 1: one workgroup runs everything)
 // ---------------------------------------------------------------------------------------------------------
+// The track of one hypothesis `hy` under the parameters P by the G workgroups that share the hand-over record `co` (nullptr for G = 1); this workgroup is
+// number g of them (0: the leader).  Inlined into its kernels: k_tr_track (one TrParams for the whole grid) and k_tr_track_group (one job per G workgroups).
+// P carries no __restrict__ here: on the inlined body it lets the compiler hoist loads of P over the whole LM loop (+28..+78 registers per lane, spills in the group kernel).
 template <int G>
-__global__ __launch_bounds__(TR_NT) void k_tr_track(const TrParams *__restrict__ Pp, TrHyp *hyps, TrCoop *coop, int seq0) {
-    const TrParams &P = *Pp;      // device memory, not a by-value argument: a dynamically indexed kernel argument would be copied to scratch memory
+__device__ __forceinline__ void tr_track_body(const TrParams &P, TrHyp &hy, TrCoop *co, int g, int seq0) {
     __shared__ double sAcc[TR_NACC];
     __shared__ __attribute__((aligned(16))) float sRed[TR_LDS_FLOATS];
     __shared__ float sRt[12];
@@ -507,11 +511,9 @@ __global__ __launch_bounds__(TR_NT) void k_tr_track(const TrParams *__restrict__
     __shared__ int sEv[5];
     __shared__ float sCoF[4];
     if (threadIdx.x < 5) sEv[threadIdx.x] = 0;
-    TrHyp &hy = hyps[blockIdx.x / G];
-    TrCoop *co = (G > 1) ? coop + blockIdx.x / G : nullptr;
     const int tid = threadIdx.x;
     int coSeq = seq0;
-    if (G > 1 && (blockIdx.x % G) != 0) { tr_helper_loop<G>(P, co, (int) (blockIdx.x % G), seq0, sAcc, sRed, sRt, sCoF, sCtl); return; }
+    if (G > 1 && g != 0) { tr_helper_loop<G>(P, co, g, seq0, sAcc, sRed, sRt, sCoF, sCtl); return; }
     TrPts pc; pc.lvl = -1;
     if (tid < 12) sT[tid] = hy.T[tid];
     if (tid == 0) { sAff[0] = hy.a; sAff[1] = hy.b; sCtl[3] = 0; sCtl[2] = 0; sCtl[4] = 0; for (int i = 0; i < 5; i++) hy.lastResiduals[i] = NAN; for (int i = 0; i < 3; i++) hy.flow[i] = 1000; }
@@ -660,6 +662,22 @@ __global__ __launch_bounds__(TR_NT) void k_tr_track(const TrParams *__restrict__
     }
 }
 
+template <int G>
+__global__ __launch_bounds__(TR_NT) void k_tr_track(const TrParams *__restrict__ Pp, TrHyp *hyps, TrCoop *coop, int seq0) {
+    // *Pp: device memory, not a by-value argument: a dynamically indexed kernel argument would be copied to scratch memory
+    tr_track_body<G>(*Pp, hyps[blockIdx.x / G], (G > 1) ? coop + blockIdx.x / G : nullptr, (int) (blockIdx.x % G), seq0);
+}
+
+// The tracks of a group of trackers in one launch (ldso_tr_group_*, tracker_group.hip): workgroup b serves job b / G in role b % G.  The job index is wave-uniform
+// (readfirstlane), so the job's three pointers are fetched with scalar loads and stay in scalar registers; every job brings its own TrParams (device memory, as above),
+// its own record and its own hand-over slot - the jobs of a launch share nothing but the sequence number seq0.
+template <int G>
+__global__ __launch_bounds__(TR_NT) void k_tr_track_group(const TrJob *__restrict__ jobs, int seq0) {
+    const int j = __builtin_amdgcn_readfirstlane((int) (blockIdx.x / G));
+    const TrJob &J = jobs[j];
+    tr_track_body<G>(*J.P, *J.hyp, (G > 1) ? J.coop : nullptr, (int) (blockIdx.x % G), seq0);
+}
+
 // stand-alone calcRes / calcGSSSE for the step-wise API (one workgroup)
 __global__ __launch_bounds__(TR_NT) void k_tr_calc(const TrParams *__restrict__ Pp, int lvl, const double *Tdev, float a, float b, float cutoffTH, double *outAcc) {
     const TrParams &P = *Pp;
@@ -697,6 +715,14 @@ hipError_t tr_launch_track(int G, int nhyp, const TrParams *d_P, TrHyp *d_hyp, T
     else if (G == 8) hipLaunchKernelGGL(k_tr_track<8>, dim3(nhyp * 8), dim3(TR_NT), 0, st, d_P, d_hyp, d_coop, seq0);
     else if (G == 4) hipLaunchKernelGGL(k_tr_track<4>, dim3(nhyp * 4), dim3(TR_NT), 0, st, d_P, d_hyp, d_coop, seq0);
     else hipLaunchKernelGGL(k_tr_track<1>, dim3(nhyp), dim3(TR_NT), 0, st, d_P, d_hyp, (TrCoop *) nullptr, 0);
+    return hipGetLastError();
+}
+hipError_t tr_launch_track_group(int G, int njobs, const TrJob *d_jobs, int seq0, hipStream_t st) {
+    if (G == 16) hipLaunchKernelGGL(k_tr_track_group<16>, dim3(njobs * 16), dim3(TR_NT), 0, st, d_jobs, seq0);
+    else if (G == 12) hipLaunchKernelGGL(k_tr_track_group<12>, dim3(njobs * 12), dim3(TR_NT), 0, st, d_jobs, seq0);
+    else if (G == 8) hipLaunchKernelGGL(k_tr_track_group<8>, dim3(njobs * 8), dim3(TR_NT), 0, st, d_jobs, seq0);
+    else if (G == 4) hipLaunchKernelGGL(k_tr_track_group<4>, dim3(njobs * 4), dim3(TR_NT), 0, st, d_jobs, seq0);
+    else hipLaunchKernelGGL(k_tr_track_group<1>, dim3(njobs), dim3(TR_NT), 0, st, d_jobs, 0);
     return hipGetLastError();
 }
 hipError_t tr_launch_calc(const TrParams *d_P, int lvl, const double *d_T, float a, float b, float cutoffTH, double *d_acc, hipStream_t st) {

@@ -25,6 +25,70 @@ static int tr_upload_levels(ldso_tracker *H, const float *const *src, float *con
     return LDSO_OK;
 }
 
+// Cooperative launches (G > 1) spin-wait across workgroups: forward progress needs every workgroup of the launch resident.  One launch
+// alone is (nhyp * G <= #CUs, one 256-thread workgroup per CU whatever else runs: other kernels finish and free their CUs); two such
+// launches from different handles could each hold CUs with spinning leaders while the other's helpers wait for a CU.  Within a process
+// they are therefore chained per device through an event; across processes (or under a CU mask) the bounded spins of the kernel turn a
+// would-be hang into LDSO_E_HIP.
+static std::mutex g_coopMutex;
+static hipEvent_t g_coopLast[64] = {nullptr};
+int tr_coop_begin(int device, hipStream_t st, TrCoop *d_coop, int &coopSeq, std::unique_lock<std::mutex> &lk) {
+    lk = std::unique_lock<std::mutex>(g_coopMutex);
+    if (device >= 0 && device < 64) {
+        hipEvent_t &e = g_coopLast[device];
+        if (!e) CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        else CHK(hipStreamWaitEvent(st, e, 0));
+    }
+    if (coopSeq > (1 << 30)) { CHK(hipMemsetAsync(d_coop, 0, TR_COOP_SLOTS * sizeof(TrCoop), st)); coopSeq = 1; }
+    return LDSO_OK;
+}
+int tr_coop_end(int device, hipStream_t st, int &coopSeq) {
+    coopSeq += 1024;           // more than the evaluations of one track (5 levels x (50 iterations + 7 cut-off repeats) + 1)
+    if (device >= 0 && device < 64) CHK(hipEventRecord(g_coopLast[device], st));
+    return LDSO_OK;
+}
+
+// FullSystem::trackNewCoarse (FullSystem.cc:179-386) around its tracks, in three pieces (ldso_tr_track_new_coarse runs them on one tracker, ldso_tr_group_track_new_coarse
+// on every member of a group).  Before: the hypothesis list (:189-309), every try starts from the last frame's affine pair.
+int tr_new_coarse_before(TrNewCoarse &S, int levels, const double sprelast[12], const double slast[12], const double lastF[12], int poses_valid, const float aff_last[2]) {
+    S.T0.assign(83 * 12, 0.0); S.lr.assign(83 * 5, 0.0); S.flow.assign(83 * 3, 0.0); S.aff.assign(83 * 2, 0.f); S.ok.assign(83, 0);
+    S.n = 0;
+    RUN(ldso_tr_motion_hypotheses(sprelast, slast, lastF, poses_valid, S.T0.data(), &S.n));
+    S.T = S.T0;
+    for (int i = 0; i < S.n; i++) { S.aff[2 * i] = aff_last[0]; S.aff[2 * i + 1] = aff_last[1]; }
+    S.coarsest = levels - 1;
+    S.best = -1; S.used = 0; S.done = false;
+    return LDSO_OK;
+}
+// Between: try 0 has run alone; the loop ends there when it is good enough (:355), else ALL remaining tries run (S.done stays false and S.n > 1)
+int tr_new_coarse_between(TrNewCoarse &S, const double lastCoarseRMSE[5], double reTrackThreshold) {
+    RUN(ldso_tr_select_hypothesis(1, S.coarsest, S.lr.data(), S.ok.data(), lastCoarseRMSE[0], reTrackThreshold, &S.best, &S.used, S.achieved));
+    S.done = S.best == 0 && S.achieved[0] < lastCoarseRMSE[0] * reTrackThreshold;
+    return LDSO_OK;
+}
+// After: with the remaining tries run (ranRest), the sequential accept / abort / early-exit decisions replayed on all of them; then the hand-over (:359-378)
+int tr_new_coarse_after(TrNewCoarse &S, bool ranRest, const double lastF[12], const float aff_last[2], double lastCoarseRMSE[5], double reTrackThreshold,
+                        double result4[4], double new_w2c[12], float aff_out[2], int *tries_consumed, int *good) {
+    if (ranRest) RUN(ldso_tr_select_hypothesis(S.n, S.coarsest, S.lr.data(), S.ok.data(), lastCoarseRMSE[0], reTrackThreshold, &S.best, &S.used, S.achieved));
+    double lastF_2_fh[12];
+    if (S.best >= 0) {
+        memcpy(lastF_2_fh, S.T.data() + 12 * S.best, 96);
+        aff_out[0] = S.aff[2 * S.best]; aff_out[1] = S.aff[2 * S.best + 1];
+        for (int i = 0; i < 3; i++) result4[1 + i] = S.flow[3 * S.best + i];
+    } else {
+        memcpy(lastF_2_fh, S.T0.data(), 96);
+        aff_out[0] = aff_last[0]; aff_out[1] = aff_last[1];
+        result4[1] = result4[2] = result4[3] = 0;
+    }
+    result4[0] = S.achieved[0];
+    for (int l = 0; l < 5; l++) lastCoarseRMSE[l] = S.achieved[l];
+    // camToWorld = lastF^-1 * lastF_2_fh^-1, the frame's pose is its inverse (:376-377) = lastF_2_fh * lastF
+    ld::se3_mul(lastF_2_fh, lastF, new_w2c);
+    if (tries_consumed) *tries_consumed = S.used;
+    if (good) *good = S.best >= 0 ? 1 : 0;
+    return LDSO_OK;
+}
+
 extern "C" {
 
 static int tr_create_body(ldso_tracker *H, int device, int w, int h, int levels) {
@@ -64,6 +128,7 @@ int ldso_tr_create(int device, int w, int h, int levels, ldso_tracker_t **out) {
 
 int ldso_tr_destroy(ldso_tracker_t *H) {
     if (!H) return LDSO_OK;
+    REQ(H->inGroup == nullptr, "ldso_tr_destroy: the tracker is a member of a live group (ldso_tr_group_destroy first: the group dereferences its members)");
     hipSetDevice(H->device);
     hipDeviceSynchronize();
     for (void *p : H->allocs) hipFree(p);
@@ -209,21 +274,6 @@ int ldso_tr_calc_gs(ldso_tracker_t *H, int lvl, const double T[12], float a, flo
     return LDSO_OK;
 }
 
-// Cooperative launches (G > 1) spin-wait across workgroups: forward progress needs every workgroup of the launch resident.  One launch
-// alone is (nhyp * G <= #CUs, one 256-thread workgroup per CU whatever else runs: other kernels finish and free their CUs); two such
-// launches from different handles could each hold CUs with spinning leaders while the other's helpers wait for a CU.  Within a process
-// they are therefore chained per device through an event; across processes (or under a CU mask) the bounded spins of the kernel turn a
-// would-be hang into LDSO_E_HIP.
-static std::mutex g_coopMutex;
-static hipEvent_t g_coopLast[64] = {nullptr};
-static int tr_coop_chain_begin(ldso_tracker_t *H) {
-    if (H->device < 0 || H->device >= 64) return LDSO_OK;
-    hipEvent_t &e = g_coopLast[H->device];
-    if (!e) CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    else CHK(hipStreamWaitEvent(H->stream, e, 0));
-    return LDSO_OK;
-}
-
 int ldso_tr_track_batch(ldso_tracker_t *H, int nhyp, double *T_inout /*nhyp*12*/, float *aff_inout /*nhyp*2*/, int coarsestLvl, const double minRes[5],
                         double *lastResiduals /*nhyp*5*/, double *flow /*nhyp*3*/, int *ok /*nhyp*/, int *iterations /*nhyp*/) {
     REQ(H && nhyp >= 1 && nhyp <= 128 && T_inout && aff_inout && coarsestLvl >= 0 && coarsestLvl < 5 && coarsestLvl < H->levels, "ldso_tr_track: bad arguments");
@@ -239,14 +289,12 @@ int ldso_tr_track_batch(ldso_tracker_t *H, int nhyp, double *T_inout /*nhyp*12*/
     // few hypotheses: TR_GMAX workgroups share each of them on the large levels (all workgroups resident: nhyp * G <= CUs);
     // many hypotheses fill the chip by themselves
     RUN(tr_sync_params(H));
-    const int G = getenv("LDSO_TR_NO_COOP") ? 1 : nhyp * 16 <= H->numCU ? 16 : nhyp * 12 <= H->numCU ? 12 : nhyp * 8 <= H->numCU ? 8 : nhyp * 4 <= H->numCU ? 4 : 1;
+    const int G = tr_coop_width(nhyp, H->numCU);
     if (G > 1) {
-        std::lock_guard<std::mutex> lk(g_coopMutex);
-        RUN(tr_coop_chain_begin(H));
-        if (H->coopSeq > (1 << 30)) { CHK(hipMemsetAsync(H->d_coop, 0, TR_COOP_SLOTS * sizeof(TrCoop), H->stream)); H->coopSeq = 1; }
+        std::unique_lock<std::mutex> lk;
+        RUN(tr_coop_begin(H->device, H->stream, H->d_coop, H->coopSeq, lk));
         CHK(tr_launch_track(G, nhyp, H->d_P, H->d_hyp, H->d_coop, H->coopSeq, H->stream));
-        H->coopSeq += 1024;           // more than the evaluations of one track (5 levels x (50 iterations + 7 cut-off repeats) + 1)
-        if (H->device >= 0 && H->device < 64) CHK(hipEventRecord(g_coopLast[H->device], H->stream));
+        RUN(tr_coop_end(H->device, H->stream, H->coopSeq));
     } else {
         CHK(tr_launch_track(1, nhyp, H->d_P, H->d_hyp, nullptr, 0, H->stream));
     }
@@ -283,40 +331,13 @@ int ldso_tr_track_batch(ldso_tracker_t *H, int nhyp, double *T_inout /*nhyp*12*/
 int ldso_tr_track_new_coarse(ldso_tracker_t *H, const double sprelast[12], const double slast[12], const double lastF[12], int poses_valid, const float aff_last[2],
                              double lastCoarseRMSE[5], double reTrackThreshold, double result4[4], double new_w2c[12], float aff_out[2], int *tries_consumed, int *good) {
     REQ(H && aff_last && lastCoarseRMSE && result4 && new_w2c && aff_out, "ldso_tr_track_new_coarse: null argument");
-    std::vector<double> T(83 * 12), T0(83 * 12), lr(83 * 5), flow(83 * 3);
-    std::vector<float> aff(83 * 2);
-    std::vector<int> ok(83);
-    int n = 0;
-    RUN(ldso_tr_motion_hypotheses(sprelast, slast, lastF, poses_valid, T0.data(), &n));
-    T = T0;
-    for (int i = 0; i < n; i++) { aff[2 * i] = aff_last[0]; aff[2 * i + 1] = aff_last[1]; }
-    const int coarsest = H->levels - 1;
-    int best = -1, used = 0;
-    double achieved[5];
-    RUN(ldso_tr_track_batch(H, 1, T.data(), aff.data(), coarsest, nullptr, lr.data(), flow.data(), ok.data(), nullptr));
-    RUN(ldso_tr_select_hypothesis(1, coarsest, lr.data(), ok.data(), lastCoarseRMSE[0], reTrackThreshold, &best, &used, achieved));
-    const bool done = best == 0 && achieved[0] < lastCoarseRMSE[0] * reTrackThreshold;
-    if (!done && n > 1) {
-        RUN(ldso_tr_track_batch(H, n - 1, T.data() + 12, aff.data() + 2, coarsest, nullptr, lr.data() + 5, flow.data() + 3, ok.data() + 1, nullptr));
-        RUN(ldso_tr_select_hypothesis(n, coarsest, lr.data(), ok.data(), lastCoarseRMSE[0], reTrackThreshold, &best, &used, achieved));
-    }
-    double lastF_2_fh[12];
-    if (best >= 0) {
-        memcpy(lastF_2_fh, T.data() + 12 * best, 96);
-        aff_out[0] = aff[2 * best]; aff_out[1] = aff[2 * best + 1];
-        for (int i = 0; i < 3; i++) result4[1 + i] = flow[3 * best + i];
-    } else {
-        memcpy(lastF_2_fh, T0.data(), 96);
-        aff_out[0] = aff_last[0]; aff_out[1] = aff_last[1];
-        result4[1] = result4[2] = result4[3] = 0;
-    }
-    result4[0] = achieved[0];
-    for (int l = 0; l < 5; l++) lastCoarseRMSE[l] = achieved[l];
-    // camToWorld = lastF^-1 * lastF_2_fh^-1, the frame's pose is its inverse (:376-377) = lastF_2_fh * lastF
-    ld::se3_mul(lastF_2_fh, lastF, new_w2c);
-    if (tries_consumed) *tries_consumed = used;
-    if (good) *good = best >= 0 ? 1 : 0;
-    return LDSO_OK;
+    TrNewCoarse S;
+    RUN(tr_new_coarse_before(S, H->levels, sprelast, slast, lastF, poses_valid, aff_last));
+    RUN(ldso_tr_track_batch(H, 1, S.T.data(), S.aff.data(), S.coarsest, nullptr, S.lr.data(), S.flow.data(), S.ok.data(), nullptr));
+    RUN(tr_new_coarse_between(S, lastCoarseRMSE, reTrackThreshold));
+    const bool rest = !S.done && S.n > 1;
+    if (rest) RUN(ldso_tr_track_batch(H, S.n - 1, S.T.data() + 12, S.aff.data() + 2, S.coarsest, nullptr, S.lr.data() + 5, S.flow.data() + 3, S.ok.data() + 1, nullptr));
+    return tr_new_coarse_after(S, rest, lastF, aff_last, lastCoarseRMSE, reTrackThreshold, result4, new_w2c, aff_out, tries_consumed, good);
 }
 
 // calcRes evaluations per level of the last ldso_tr_track / hypothesis 0 of the last batch, and the reference point counts pc_n:
@@ -350,6 +371,13 @@ int ldso_tr_debug_solve8(const double H[64], const double b[8], double diag_scal
 
 int ldso_tr_track(ldso_tracker_t *H, double T[12], float aff[2], int coarsestLvl, const double minRes[5], double lastResiduals[5], double flow[3], int *ok, int *iterations) {
     return ldso_tr_track_batch(H, 1, T, aff, coarsestLvl, minRes, lastResiduals, flow, ok, iterations);
+}
+
+// the launch-shape rule of a track by itself (tracker.h: tr_coop_width): pure host function
+int ldso_tr_coop_width(int count, int num_cu, int *G) {
+    REQ(G && count >= 1 && num_cu >= 1, "ldso_tr_coop_width: bad arguments");
+    *G = tr_coop_width(count, num_cu);
+    return LDSO_OK;
 }
 
 int ldso_tr_get_pc(ldso_tracker_t *H, int lvl, float *u, float *v, float *idepth, float *color, int *n) {
