@@ -12,8 +12,14 @@
 // Float projections in the reference's operation order, no contraction, IEEE division, int conversion by truncation after + 0.5f (as trace.hip, ba_activate.hip).
 // For a batch of windows (ldso_ba_batch_select_candidates / _select_activate_points / _activate_points, at the end of the file) the same body runs as one workgroup per
 // window in one launch, k_act_select_batch, each window with its own sizes and map placement.
+//
+// The host side, behind the kernels: all seven entries of point activation (ldso_ba_activate_points, the three single-window selections, the three batched calls).  What
+// can be said of a selection without a device - the job, its checks, the layout of its arenas, packing and unpacking - is act_stage.h, once for both paths; this file
+// adds the device: sel_args (regions -> pointers), sel_arena (growth of ldso_ba::d_sel), sel_lds_rule (the map in LDS or not), act_preconditions, then sel_run for one window
+// and batch_select_run for a batch, each: check every job, lay out, stage, fill SelArgs, launch, download, unpack.
 #include <hip/hip_runtime.h>
 #include "ba_host.h"
+#include "act_stage.h"
 
 namespace {
 
@@ -221,122 +227,88 @@ __global__ __launch_bounds__(SEL_THREADS) void k_act_select_batch(const SelArgs 
     else act_select_body<false>(A, sel_lds);
 }
 
-struct SelBuffers {                // the carve-up of ldso_ba::d_sel for one call
-    char *in = nullptr; size_t inBytes = 0;                       // [points | seeds | my_type | KRKi | Kt | flagged]: one upload
-    char *out = nullptr; size_t outBytes = 0;                     // [n_selected (16 B) | decision | selected | activation records]: one download
-    ldso_immature_t *pts = nullptr; ldso_act_seed_t *seeds = nullptr; float *myType = nullptr, *KRKi = nullptr, *Kt = nullptr; int32_t *flagged = nullptr;
-    int32_t *nSelected = nullptr, *decision = nullptr, *selected = nullptr; ldso_activation_t *act = nullptr;
-    int32_t *cell = nullptr; float *frac = nullptr, *thr = nullptr; unsigned char *gmap = nullptr;
-};
+// ---- the host side.  What a job is, its checks, where its bytes lie and the two host copies: act_stage.h, for the single-window entries and the batch alike; here: what
+// needs the device ----
 
-static size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+// the kernel's view of job J: its regions on the device addresses of the three arenas, its map at gmap
+SelArgs sel_args(const ActJob &J, const ActRegions &R, char *dUp, char *dDown, char *dScr, unsigned char *gmap, float minQuality) {
+    SelArgs A;
+    memset(&A, 0, sizeof(A));
+    A.seeds = (const ldso_act_seed_t *) (dUp + R.seeds); A.pts = (const ldso_immature_t *) (dUp + R.pts); A.myType = (const float *) (dUp + R.type);
+    A.KRKi = (const float *) (dUp + R.KRKi); A.Kt = (const float *) (dUp + R.Kt); A.flagged = (const int32_t *) (dUp + R.flag);
+    A.nSeeds = J.nSeeds; A.n = J.n; A.nHosts = J.nHosts; A.w1 = J.w1; A.h1 = J.h1; A.minDist = J.minDist; A.minQuality = minQuality; A.newestHost = -1; A.gmap = gmap;
+    A.nSelected = (int32_t *) (dDown + R.nSel); A.decision = (int32_t *) (dDown + R.dec); A.selected = (int32_t *) (dDown + R.sel);
+    A.cell = (int32_t *) (dScr + R.cell); A.frac = (float *) (dScr + R.frac); A.thr = (float *) (dScr + R.thr);
+    return A;
+}
+
+// H's device arena with at least `need` bytes; one that is too small is replaced by one of `room`, and the map the last selection left in it is gone with it
+int sel_arena(ldso_ba *H, size_t need, size_t room) {
+    if (need <= H->selCap) return LDSO_OK;
+    if (H->d_sel) hipFree(H->d_sel);
+    H->d_sel = nullptr; H->selCap = 0; H->selW1 = 0; H->selH1 = 0;
+    CHK(hipMalloc(&H->d_sel, room));
+    H->selCap = room;
+    return LDSO_OK;
+}
+
+// A map of mapBytes lies in LDS (ldsMap) where a workgroup of `kernel` can have that much beside the frontier lists and the kernel's own static bytes, in global memory
+// otherwise.  ldsBytes: the launch's dynamic LDS, raised to hold the map; limit / set: what the owner of the kernel's attribute remembers (-1: not asked yet; raised to).
+int sel_lds_rule(const void *kernel, int device, int &limit, int &set, size_t mapBytes, size_t &ldsBytes, int &ldsMap) {
+    if (limit < 0) {
+        hipFuncAttributes fa; int perBlock = 0;
+        CHK(hipFuncGetAttributes(&fa, kernel));
+        CHK(hipDeviceGetAttribute(&perBlock, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+        limit = std::max(0, std::min(perBlock, SEL_LDS_MAX) - (int) fa.sharedSizeBytes);
+    }
+    ldsMap = SEL_LIST_BYTES + mapBytes <= (size_t) limit ? 1 : 0;
+    if (ldsMap) ldsBytes = std::max(ldsBytes, SEL_LIST_BYTES + mapBytes);
+    if (ldsMap && (int) ldsBytes > set) { CHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes)); set = (int) ldsBytes; }
+    return LDSO_OK;
+}
+
+// what point activation needs of the resident window; n_hosts: the frames the caller brought poses for
+int act_preconditions(const ldso_ba *H, const std::string &who, int n_hosts, bool images = true) {
+    REQ(H->D.F >= 2, who + ": set the window and the frames first");
+    REQ(n_hosts == H->D.F, who + ": one KRKi / Kt / flag per frame of the resident window");
+    for (int f = 0; images && f < H->D.F; f++) REQ(H->B.img[f] != nullptr, who + ": a key-frame image is missing");
+    return LDSO_OK;
+}
+
+struct SelCall { ActRegions R; ActBases total; SelArgs A; char *dDown = nullptr; };          // an enqueued single-window selection: its regions, arena sizes and device view
+
+// One window alone: the arena is H->d_sel, [upload | download | scratch | map], staged through H->selHost.  Selection, k_activate on the selected list where the selection
+// kernel left it if the job wants records, and the download, all enqueued; the caller waits and unpacks.  T: the tracer of a resident job.
+int sel_run(ldso_ba *H, const char *who, const ActJob &J, const ldso_tracer *T, float minQuality, int min_obs, float min_idepth_hessian, int gn_iterations, SelCall &C) {
+    RUN(act_job_check(J, who, ACT_MISSING_SOLO));
+    CHK(hipSetDevice(H->device));
+    C.R = act_layout(J, C.total);
+    const ActBases &t = C.total;
+    const size_t oMap = t.up + t.down + t.scratch, total = oMap + C.R.mapBytes;
+    RUN(sel_arena(H, total, total + total / 2));
+    char *d = (char *) H->d_sel, *hs;
+    C.dDown = d + t.up;
+    H->selHost.resize(std::max(t.up, t.down));
+    hs = H->selHost.data();
+    memset(hs, 0, t.up);
+    act_pack(J, C.R, hs);
+    CHK(hipMemcpyAsync(d, hs, t.up, hipMemcpyHostToDevice, H->stream));
+    SelArgs &A = C.A;
+    A = sel_args(J, C.R, d, C.dDown, C.dDown + t.down, (unsigned char *) d + oMap, minQuality);
+    // the seeds straight from the resident window: every point whose host is not the newest frame
+    if (J.resident) { A.pts = T->d_pts; A.myType = T->d_type; A.pgeo = H->B.pgeo; A.phost = H->B.phost; A.nWin = H->D.P; A.newestHost = J.nHosts - 1; }
+    size_t ldsBytes = SEL_LIST_BYTES;
+    RUN(sel_lds_rule((const void *) k_act_select<true>, H->device, H->selLdsLimit, H->selLdsSet, C.R.mapBytes, ldsBytes, A.ldsMap));
+    if (A.ldsMap) hipLaunchKernelGGL(k_act_select<true>, dim3(1), dim3(SEL_THREADS), ldsBytes, H->stream, A);
+    else hipLaunchKernelGGL(k_act_select<false>, dim3(1), dim3(SEL_THREADS), ldsBytes, H->stream, A);
+    CHK(hipGetLastError());
+    H->selW1 = J.w1; H->selH1 = J.h1; H->selMapOffset = oMap;
+    if (J.records) CHK(ba_launch_activate(H->B, H->D, H->settings, act_win(A.pts, (ldso_activation_t *) (C.dDown + C.R.act), J.n, min_obs, min_idepth_hessian, gn_iterations, A.selected, A.nSelected, 0).A, H->stream));
+    CHK(hipMemcpyAsync(hs, C.dDown, t.down, hipMemcpyDeviceToHost, H->stream));
+    return LDSO_OK;
+}
 
 }  // namespace
-
-// Where a selection takes its candidates and seeds from: flat host arrays (uploaded with the poses), or device memory - the records and types of a tracer's
-// resident set and the points of the handle's resident window - of which nothing is uploaded.
-struct SelSource {
-    int nSeeds = 0; const ldso_act_seed_t *seeds = nullptr;                          // host
-    int n = 0; const ldso_immature_t *points = nullptr; const float *myType = nullptr;      // host
-    const ldso_immature_t *d_points = nullptr; const float *d_myType = nullptr;      // device (then points / myType / seeds are null)
-    bool windowSeeds = false;
-    int newestHost = -1;
-};
-
-static int sel_enqueue(ldso_ba *H, const char *who, const SelSource &I, int n_hosts, const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist,
-                       float minTraceQuality, SelBuffers &S) {
-    const int n = I.n, n_seeds = I.nSeeds;
-    const bool onDevice = I.d_points != nullptr || I.windowSeeds;
-    REQ(H && n_seeds >= 0 && n >= 0 && n_hosts >= 1 && n_hosts <= LDSO_MAX_FRAMES && KRKi && Kt && host_flagged && (n_seeds == 0 || I.seeds)
-        && (n == 0 || (I.points && I.myType) || (I.d_points && I.d_myType)), std::string(who) + ": bad arguments");
-    const int w1 = H->w >> 1, h1 = H->h >> 1;
-    REQ(w1 >= 3 && h1 >= 3 && w1 < 65536 && h1 < 65536, std::string(who) + ": image size out of range");
-    // device data cannot be range-checked here: the kernel drops a candidate and skips a seed whose host is not a frame of the window
-    for (int i = 0; !onDevice && i < n; i++) REQ(I.points[i].host >= 0 && I.points[i].host < n_hosts, std::string(who) + ": a candidate's host is not a frame of the window");
-    for (int i = 0; i < n_seeds; i++) REQ(I.seeds[i].host >= 0 && I.seeds[i].host < n_hosts, std::string(who) + ": a seed's host is not a frame of the window");
-    CHK(hipSetDevice(H->device));
-    const size_t wh = (size_t) w1 * h1, nn = (size_t) n, nUp = I.points ? nn : 0;
-    const size_t oPts = 0, oSeeds = oPts + nUp * sizeof(ldso_immature_t), oType = oSeeds + up16((size_t) n_seeds * sizeof(ldso_act_seed_t)), oKRKi = oType + up16(nUp * 4),
-                 oKt = oKRKi + up16((size_t) n_hosts * 36), oFlag = oKt + up16((size_t) n_hosts * 12), inBytes = oFlag + up16((size_t) n_hosts * 4);
-    const size_t oDec = 16, oSel = oDec + up16(nn * 4), oAct = oSel + up16(nn * 4), outBytes = oAct + nn * sizeof(ldso_activation_t);
-    const size_t oCell = inBytes + outBytes, oFrac = oCell + up16(nn * 4), oThr = oFrac + up16(nn * 4), oMap = oThr + up16(nn * 4), total = oMap + up16(wh);
-    if (total > H->selCap) {
-        if (H->d_sel) hipFree(H->d_sel);
-        H->d_sel = nullptr; H->selCap = 0;
-        CHK(hipMalloc(&H->d_sel, total + total / 2));
-        H->selCap = total + total / 2;
-    }
-    char *d = (char *) H->d_sel;
-    S.in = d; S.inBytes = inBytes; S.out = d + inBytes; S.outBytes = outBytes;
-    S.pts = (ldso_immature_t *) (d + oPts); S.seeds = (ldso_act_seed_t *) (d + oSeeds); S.myType = (float *) (d + oType); S.KRKi = (float *) (d + oKRKi); S.Kt = (float *) (d + oKt);
-    S.flagged = (int32_t *) (d + oFlag);
-    S.nSelected = (int32_t *) S.out; S.decision = (int32_t *) (S.out + oDec); S.selected = (int32_t *) (S.out + oSel); S.act = (ldso_activation_t *) (S.out + oAct);
-    S.cell = (int32_t *) (d + oCell); S.frac = (float *) (d + oFrac); S.thr = (float *) (d + oThr); S.gmap = (unsigned char *) (d + oMap);
-    H->selHost.resize(std::max(inBytes, outBytes));
-    char *hs = H->selHost.data();
-    memset(hs, 0, inBytes);
-    if (nUp) { memcpy(hs + oPts, I.points, nn * sizeof(ldso_immature_t)); memcpy(hs + oType, I.myType, nn * 4); }
-    if (n_seeds) memcpy(hs + oSeeds, I.seeds, (size_t) n_seeds * sizeof(ldso_act_seed_t));
-    memcpy(hs + oKRKi, KRKi, (size_t) n_hosts * 36); memcpy(hs + oKt, Kt, (size_t) n_hosts * 12); memcpy(hs + oFlag, host_flagged, (size_t) n_hosts * 4);
-    CHK(hipMemcpyAsync(S.in, hs, inBytes, hipMemcpyHostToDevice, H->stream));
-    SelArgs A;
-    A.seeds = S.seeds; A.pts = I.d_points ? I.d_points : S.pts; A.myType = I.d_points ? I.d_myType : S.myType; A.KRKi = S.KRKi; A.Kt = S.Kt; A.flagged = S.flagged;
-    A.nSeeds = n_seeds; A.n = n; A.nHosts = n_hosts; A.w1 = w1; A.h1 = h1; A.minDist = currentMinActDist; A.minQuality = minTraceQuality;
-    A.pgeo = I.windowSeeds ? H->B.pgeo : nullptr; A.phost = I.windowSeeds ? H->B.phost : nullptr; A.nWin = I.windowSeeds ? H->D.P : 0; A.newestHost = I.newestHost;
-    A.gmap = S.gmap; A.ldsMap = 0; A.decision = S.decision; A.selected = S.selected; A.nSelected = S.nSelected; A.cell = S.cell; A.frac = S.frac; A.thr = S.thr;
-    // the map in LDS where the workgroup can have that much (beside the kernel's own static bytes), in global memory otherwise
-    const size_t ldsBytes = SEL_LIST_BYTES + up16(wh);
-    if (H->selLdsLimit < 0) {
-        hipFuncAttributes fa; int perBlock = 0;
-        CHK(hipFuncGetAttributes(&fa, (const void *) k_act_select<true>));
-        CHK(hipDeviceGetAttribute(&perBlock, hipDeviceAttributeMaxSharedMemoryPerBlock, H->device));
-        H->selLdsLimit = std::max(0, std::min(perBlock, SEL_LDS_MAX) - (int) fa.sharedSizeBytes);
-    }
-    if (ldsBytes <= (size_t) H->selLdsLimit) {
-        if ((int) ldsBytes > H->selLdsSet) { CHK(hipFuncSetAttribute((const void *) k_act_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes)); H->selLdsSet = (int) ldsBytes; }
-        hipLaunchKernelGGL(k_act_select<true>, dim3(1), dim3(SEL_THREADS), ldsBytes, H->stream, A);
-    } else hipLaunchKernelGGL(k_act_select<false>, dim3(1), dim3(SEL_THREADS), SEL_LIST_BYTES, H->stream, A);
-    CHK(hipGetLastError());
-    H->selW1 = w1; H->selH1 = h1; H->selMapOffset = oMap;
-    return LDSO_OK;
-}
-
-static SelSource host_source(int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type) {
-    SelSource I;
-    I.nSeeds = n_seeds; I.seeds = seeds; I.n = n; I.points = points; I.myType = my_type;
-    return I;
-}
-
-// the preconditions of point activation on the resident window (ldso_ba_activate_points)
-static int act_preconditions(const ldso_ba *H, const char *who, int n_hosts) {
-    REQ(H->D.F >= 2, std::string(who) + ": set the window and the frames first");
-    REQ(n_hosts == H->D.F, std::string(who) + ": one KRKi / Kt / flag per frame of the resident window");
-    for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, std::string(who) + ": a key-frame image is missing");
-    return LDSO_OK;
-}
-
-// selection, then k_activate on the selected list where the selection kernel left it; the results come down with the caller's one synchronisation
-static int sel_activate_enqueue(ldso_ba *H, const char *who, const SelSource &I, int n_hosts, const float *KRKi, const float *Kt, const int32_t *host_flagged, float currentMinActDist,
-                                float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations, SelBuffers &S) {
-    RUN(sel_enqueue(H, who, I, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
-    CHK(ba_launch_activate_selected(H->B, H->D, H->settings, I.d_points ? I.d_points : S.pts, S.selected, S.nSelected, S.act, I.n, min_obs, min_idepth_hessian, gn_iterations, H->stream));
-    CHK(hipMemcpyAsync(H->selHost.data(), S.out, S.outBytes, hipMemcpyDeviceToHost, H->stream));
-    return LDSO_OK;
-}
-
-static void sel_unpack_activations(const ldso_ba *H, int n, int n_selected, ldso_activation_t *out) {
-    const size_t oAct = 16 + 2 * up16((size_t) n * 4);
-    if (n_selected > 0) memcpy(out, H->selHost.data() + oAct, (size_t) n_selected * sizeof(ldso_activation_t));
-}
-
-static void sel_unpack(const ldso_ba *H, int n, int32_t *decision_out, int32_t *selected_out, int *n_selected_out) {
-    const char *hs = H->selHost.data();
-    const int ns = *(const int32_t *) hs;
-    const size_t oDec = 16, oSel = oDec + up16((size_t) n * 4);
-    if (n) memcpy(decision_out, hs + oDec, (size_t) n * 4);
-    if (selected_out && ns > 0) memcpy(selected_out, hs + oSel, (size_t) ns * 4);
-    if (n_selected_out) *n_selected_out = ns;
-}
 
 extern "C" {
 
@@ -369,17 +341,40 @@ int ldso_act_update_min_dist(float current, int nPoints, float desiredDensity, f
     return LDSO_OK;
 }
 
+// FullSystem::optimizeImmaturePoint (FullSystem.cc:892-1010) for n immature points against the key frames of the window that is resident in the handle
+// (ldso_ba_set_image*, ldso_ba_set_window, ldso_ba_set_frames: images, calibration, current poses).  Its arena, d_act [n records | n results], stays its own: in d_sel
+// the call would overwrite, or with a larger n take away, the distance map ldso_ba_get_distance_map still reads.
+int ldso_ba_activate_points(ldso_ba_t *H, int n, const ldso_immature_t *pts, int min_obs, float min_idepth_hessian, int gn_iterations, ldso_activation_t *out) {
+    REQ(H && n >= 0 && (n == 0 || (pts && out)) && gn_iterations >= 0, "ldso_ba_activate_points: bad arguments");
+    RUN(act_preconditions(H, "ldso_ba_activate_points", H->D.F, n > 0));
+    if (n == 0) return LDSO_OK;
+    CHK(hipSetDevice(H->device));
+    if (n > H->actCap) {
+        if (H->d_act) hipFree(H->d_act);
+        H->d_act = nullptr; H->actCap = 0;
+        CHK(hipMalloc(&H->d_act, (size_t) n * (sizeof(ldso_immature_t) + sizeof(ldso_activation_t))));
+        H->actCap = n;
+    }
+    ldso_immature_t *dp = (ldso_immature_t *) H->d_act;
+    ldso_activation_t *dout = (ldso_activation_t *) ((char *) H->d_act + (size_t) H->actCap * sizeof(ldso_immature_t));
+    CHK(hipMemcpyAsync(dp, pts, (size_t) n * sizeof(ldso_immature_t), hipMemcpyHostToDevice, H->stream));
+    CHK(ba_launch_activate(H->B, H->D, H->settings, act_win(dp, dout, n, min_obs, min_idepth_hessian, gn_iterations, nullptr, nullptr, 0).A, H->stream));
+    CHK(hipMemcpyAsync(out, dout, (size_t) n * sizeof(ldso_activation_t), hipMemcpyDeviceToHost, H->stream));
+    CHK(hipStreamSynchronize(H->stream));
+    return LDSO_OK;
+}
+
 // makeDistanceMap + the selection loop of FullSystem::activatePointsMT (FullSystem.cc:1080-1152, CoarseTracker.cc:686-818)
 int ldso_ba_select_candidates(ldso_ba_t *H, int n_seeds, const ldso_act_seed_t *seeds, int n, const ldso_immature_t *points, const float *my_type, int n_hosts, const float *KRKi,
                               const float *Kt, const int32_t *host_flagged, float currentMinActDist, float minTraceQuality, int32_t *decision_out, int32_t *selected_out,
                               int *n_selected_out) {
     REQ(H && (n <= 0 || decision_out), "ldso_ba_select_candidates: bad arguments");
-    SelBuffers S;
-    RUN(sel_enqueue(H, "ldso_ba_select_candidates", host_source(n_seeds, seeds, n, points, my_type), n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, S));
-    const size_t bytes = 16 + 2 * up16((size_t) n * 4);
-    CHK(hipMemcpyAsync(H->selHost.data(), S.out, bytes, hipMemcpyDeviceToHost, H->stream));
+    const ActJob J = act_job(n_seeds, seeds, n, points, my_type, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, H->w, H->h, false, decision_out, selected_out, nullptr);
+    SelCall C;
+    RUN(sel_run(H, "ldso_ba_select_candidates", J, nullptr, minTraceQuality, 0, 0.0f, 0, C));
     CHK(hipStreamSynchronize(H->stream));
-    sel_unpack(H, n, decision_out, selected_out, n_selected_out);
+    const int ns = act_unpack(J, C.R, H->selHost.data());
+    if (n_selected_out) *n_selected_out = ns;
     return LDSO_OK;
 }
 
@@ -390,12 +385,11 @@ int ldso_ba_select_activate_points(ldso_ba_t *H, int n_seeds, const ldso_act_see
                                    float min_idepth_hessian, int gn_iterations, int32_t *decision_out, int32_t *selected_out, int *n_selected_out, ldso_activation_t *out) {
     REQ(H && gn_iterations >= 0 && n_selected_out && (n <= 0 || (decision_out && selected_out && out)), "ldso_ba_select_activate_points: bad arguments");
     RUN(act_preconditions(H, "ldso_ba_select_activate_points", n_hosts));
-    SelBuffers S;
-    RUN(sel_activate_enqueue(H, "ldso_ba_select_activate_points", host_source(n_seeds, seeds, n, points, my_type), n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality,
-                             min_obs, min_idepth_hessian, gn_iterations, S));
+    const ActJob J = act_job(n_seeds, seeds, n, points, my_type, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, H->w, H->h, true, decision_out, selected_out, out);
+    SelCall C;
+    RUN(sel_run(H, "ldso_ba_select_activate_points", J, nullptr, minTraceQuality, min_obs, min_idepth_hessian, gn_iterations, C));
     CHK(hipStreamSynchronize(H->stream));
-    sel_unpack(H, n, decision_out, selected_out, n_selected_out);
-    sel_unpack_activations(H, n, *n_selected_out, out);
+    *n_selected_out = act_unpack(J, C.R, H->selHost.data());
     return LDSO_OK;
 }
 
@@ -411,17 +405,15 @@ int ldso_ba_select_activate_tracer(ldso_ba_t *H, ldso_tracer_t *T, int n_hosts, 
     REQ(T->device == H->device, "ldso_ba_select_activate_tracer: the tracer and the window live on different devices");
     REQ_UNSHARDED("ldso_ba_select_activate_tracer");
     RUN(act_preconditions(H, "ldso_ba_select_activate_tracer", n_hosts));
-    SelSource I;
-    I.n = n; I.d_points = T->d_pts; I.d_myType = T->d_type; I.windowSeeds = true; I.newestHost = n_hosts - 1;
-    SelBuffers S;
-    RUN(sel_activate_enqueue(H, "ldso_ba_select_activate_tracer", I, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, minTraceQuality, min_obs, min_idepth_hessian,
-                             gn_iterations, S));
-    const int rcCompact = compact ? trace_compact_enqueue(T, nullptr, S.decision, LDSO_ACT_KEEP, n_hosts, false, H->stream) : LDSO_OK;
+    ActJob J = act_job(0, nullptr, n, nullptr, nullptr, n_hosts, KRKi, Kt, host_flagged, currentMinActDist, H->w, H->h, true, decision_out, selected_out, out);
+    J.resident = true;
+    SelCall C;
+    RUN(sel_run(H, "ldso_ba_select_activate_tracer", J, T, minTraceQuality, min_obs, min_idepth_hessian, gn_iterations, C));
+    const int rcCompact = compact ? trace_compact_enqueue(T, nullptr, C.A.decision, LDSO_ACT_KEEP, n_hosts, false, H->stream) : LDSO_OK;
     CHK(hipStreamSynchronize(H->stream));          // also where the compaction could not be enqueued: the copy into selHost is in flight
     if (rcCompact != LDSO_OK) return rcCompact;
     if (compact) trace_compact_finish(T);
-    sel_unpack(H, n, decision_out, selected_out, n_selected_out);
-    sel_unpack_activations(H, n, *n_selected_out, out);
+    *n_selected_out = act_unpack(J, C.R, H->selHost.data());
     if (n_left_out) *n_left_out = T->n;
     return LDSO_OK;
 }
@@ -431,141 +423,80 @@ int ldso_ba_select_activate_tracer(ldso_ba_t *H, ldso_tracer_t *T, int n_hosts, 
 // ---- the batch: activatePointsMT (FullSystem.cc:1052-1189) for every window of a ldso_ba_batch, one launch per kernel whatever the number of windows ----------------
 namespace {
 
-struct SelPlan {                   // a participating window's share of the call's arena; offsets in bytes into the upload, the download and the scratch region
-    int win = 0, w1 = 0, h1 = 0;
-    size_t oPts = 0, oSeeds = 0, oType = 0, oKRKi = 0, oKt = 0, oFlag = 0, oOut = 0, oDec = 0, oSel = 0, oAct = 0, oCell = 0, oFrac = 0, oThr = 0, mapBytes = 0;
-};
-
-// what every batched activation entry refuses: for the batch as a whole, and for a window that takes part (`images`: the entry reads the resident window); `solo`: the
-// single-window entry the message points to
+// what every batched activation entry refuses: for the batch as a whole (`solo`: the single-window entry the message points to), and for a window that takes part
+// (`window`: the entry reads the resident window, for n_hosts frames)
 int batch_act_checks(const ldso_ba_batch *Bt, const std::string &w, const char *solo) {
     REQ(Bt->FS == 8, w + ": windows of more than 8 key frames are not supported in a batched activation (every window needs F <= 8): run them with " + solo);
     return LDSO_OK;
 }
-int batch_act_window_checks(const ldso_ba *H, const std::string &w, bool images) {
+int batch_act_window_checks(const ldso_ba *H, const std::string &w, bool window, int n_hosts) {
     REQ(H->D.pBegin == 0 && H->D.pEnd == H->D.P, w + ": not available on a sharded handle (ldso_ba_set_shard)");
-    if (images) {
-        REQ(H->D.F >= 2, w + ": set the window and the frames first");
-        for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, w + ": a key-frame image is missing");
-    }
-    return LDSO_OK;
+    return window ? act_preconditions(H, w, n_hosts) : LDSO_OK;
 }
 
-// the map of window H for a batched selection: in the handle's own arena, where ldso_ba_get_distance_map looks for it
-int batch_sel_map(ldso_ba *H, size_t mapBytes, unsigned char **gmap) {
-    if (mapBytes > H->selCap) {
-        if (H->d_sel) hipFree(H->d_sel);
-        H->d_sel = nullptr; H->selCap = 0; H->selW1 = 0; H->selH1 = 0;
-        CHK(hipMalloc(&H->d_sel, mapBytes));
-        H->selCap = mapBytes;
-    }
-    *gmap = (unsigned char *) H->d_sel;
-    return LDSO_OK;
-}
+struct SelPart { int win; ActJob J; ActRegions R; };          // a participating window, its job and its share of the call's arenas
 
+// The arenas of a batched call lie in the batch's staging pair (batch_stage): [nPart SelArgs | nAct ActWin | nAct + 1 wavefront offsets | every window's upload] go up,
+// [every window's download] comes down, the scratch lies behind it on the device; a window's map lies in its own d_sel at offset 0, where ldso_ba_get_distance_map reads it.
 int batch_select_run(ldso_ba_batch *Bt, const char *who, const char *solo, ldso_act_job_t *jobs, float minTraceQuality, bool activate, int min_obs, float min_idepth_hessian,
                      int gn_iterations) {
     const std::string w(who);
     REQ(Bt, w + ": null batch");
     REQ(jobs && gn_iterations >= 0, w + ": bad arguments (null jobs)");
     RUN(batch_act_checks(Bt, w, solo));
-    const int n = (int) Bt->h.size();
     ldso_ba *H0 = Bt->h[0];
-    // ---- every refusal, before anything is enqueued or written; the regions of the arena on the way ----
-    std::vector<SelPlan> plan;
-    size_t in = 0, down = 0, scratch = 0, cands = 0;
+    // ---- every refusal, before anything is enqueued or written; the regions of the arenas on the way ----
+    std::vector<SelPart> part;
+    ActBases at;
+    size_t cands = 0;
     int nAct = 0;
-    for (int i = 0; i < n; i++) {
-        const ldso_act_job_t &J = jobs[i];
-        if (J.n_hosts == 0) continue;
-        const ldso_ba *H = Bt->h[i];
-        REQ(J.n_seeds >= 0 && J.n >= 0 && J.n_hosts >= 1 && J.n_hosts <= LDSO_MAX_FRAMES && J.KRKi && J.Kt && J.host_flagged && (J.n_seeds == 0 || J.seeds)
-            && (J.n == 0 || (J.points && J.my_type && J.decision_out)) && (!activate || J.n == 0 || (J.selected_out && J.out)),
-            w + ": a window that takes part needs its arrays (seeds, points, my_type, KRKi, Kt, host_flagged and the outputs)");
-        RUN(batch_act_window_checks(H, w, false));
-        if (activate) RUN(act_preconditions(H, who, J.n_hosts));
-        SelPlan p;
-        p.win = i; p.w1 = H->w >> 1; p.h1 = H->h >> 1;
-        REQ(p.w1 >= 3 && p.h1 >= 3 && p.w1 < 65536 && p.h1 < 65536, w + ": image size out of range");
-        for (int k = 0; k < J.n; k++) REQ(J.points[k].host >= 0 && J.points[k].host < J.n_hosts, w + ": a candidate's host is not a frame of the window");
-        for (int k = 0; k < J.n_seeds; k++) REQ(J.seeds[k].host >= 0 && J.seeds[k].host < J.n_hosts, w + ": a seed's host is not a frame of the window");
-        const size_t nn = (size_t) J.n;
-        p.oPts = in; p.oSeeds = p.oPts + nn * sizeof(ldso_immature_t); p.oType = p.oSeeds + up16((size_t) J.n_seeds * sizeof(ldso_act_seed_t)); p.oKRKi = p.oType + up16(nn * 4);
-        p.oKt = p.oKRKi + up16((size_t) J.n_hosts * 36); p.oFlag = p.oKt + up16((size_t) J.n_hosts * 12); in = p.oFlag + up16((size_t) J.n_hosts * 4);
-        p.oOut = down; p.oDec = p.oOut + 16; p.oSel = p.oDec + up16(nn * 4); p.oAct = p.oSel + up16(nn * 4); down = p.oAct + (activate ? nn * sizeof(ldso_activation_t) : 0);
-        p.oCell = scratch; p.oFrac = p.oCell + up16(nn * 4); p.oThr = p.oFrac + up16(nn * 4); scratch = p.oThr + up16(nn * 4);
-        p.mapBytes = up16((size_t) p.w1 * p.h1);
-        if (activate && J.n > 0) nAct++;
-        cands += nn;
-        plan.push_back(p);
+    for (int i = 0; i < (int) Bt->h.size(); i++) {
+        if (jobs[i].n_hosts == 0) continue;
+        const ldso_ba *H = Bt->h[(size_t) i];
+        SelPart p;
+        p.win = i; p.J = act_job(jobs[i], H->w, H->h, activate);
+        RUN(act_job_check(p.J, w, ACT_MISSING_BATCH));
+        RUN(batch_act_window_checks(H, w, activate, p.J.nHosts));
+        p.R = act_layout(p.J, at);
+        if (activate && p.J.n > 0) nAct++;
+        cands += (size_t) p.J.n;
+        part.push_back(p);
     }
     REQ(cands < (size_t) 1 << 30, w + ": too many candidates");
-    const int nPart = (int) plan.size();
+    const int nPart = (int) part.size();
     if (nPart == 0) return LDSO_OK;
     CHK(hipSetDevice(H0->device));
     if (activate) RUN(batch_refresh(Bt));
-    // the upload: [nPart SelArgs | nAct ActWin | nAct + 1 wavefront offsets | every window's inputs]
-    const size_t oTab = 0, oAct = oTab + up16((size_t) nPart * sizeof(SelArgs)), oWave = oAct + up16((size_t) nAct * sizeof(ActWin)), oIn = oWave + up16(((size_t) nAct + 1) * 4), up = oIn + in;
-    RUN(batch_stage(Bt, up, down + scratch));
-    if (Bt->selLdsLimit < 0) {
-        hipFuncAttributes fa; int perBlock = 0;
-        CHK(hipFuncGetAttributes(&fa, (const void *) k_act_select_batch));
-        CHK(hipDeviceGetAttribute(&perBlock, hipDeviceAttributeMaxSharedMemoryPerBlock, H0->device));
-        Bt->selLdsLimit = std::max(0, std::min(perBlock, SEL_LDS_MAX) - (int) fa.sharedSizeBytes);
-    }
-    char *hs = Bt->h_stage, *d = Bt->d_stage, *dIn = d + oIn, *dOut = d + up, *dScr = d + up + down;
+    const size_t oTab = 0, oAct = oTab + up16((size_t) nPart * sizeof(SelArgs)), oWave = oAct + up16((size_t) nAct * sizeof(ActWin)), oIn = oWave + up16(((size_t) nAct + 1) * 4), up = oIn + at.up;
+    RUN(batch_stage(Bt, up, at.down + at.scratch));
+    char *hs = Bt->h_stage, *d = Bt->d_stage, *dOut = d + up;
     SelArgs *tab = (SelArgs *) (hs + oTab);
     ActWin *act = (ActWin *) (hs + oAct);
     int32_t *wave = (int32_t *) (hs + oWave);
     size_t ldsBytes = SEL_LIST_BYTES;
     int waves = 0, ia = 0;
     for (int k = 0; k < nPart; k++) {
-        const SelPlan &p = plan[(size_t) k];
-        const ldso_act_job_t &J = jobs[p.win];
+        const SelPart &p = part[(size_t) k];
         ldso_ba *H = Bt->h[(size_t) p.win];
-        const size_t nn = (size_t) J.n;
-        char *hi = hs + oIn;
-        if (J.n) { memcpy(hi + p.oPts, J.points, nn * sizeof(ldso_immature_t)); memcpy(hi + p.oType, J.my_type, nn * 4); }
-        if (J.n_seeds) memcpy(hi + p.oSeeds, J.seeds, (size_t) J.n_seeds * sizeof(ldso_act_seed_t));
-        memcpy(hi + p.oKRKi, J.KRKi, (size_t) J.n_hosts * 36); memcpy(hi + p.oKt, J.Kt, (size_t) J.n_hosts * 12); memcpy(hi + p.oFlag, J.host_flagged, (size_t) J.n_hosts * 4);
+        act_pack(p.J, p.R, hs + oIn);
+        RUN(sel_arena(H, p.R.mapBytes, p.R.mapBytes));
         SelArgs &A = tab[k];
-        memset(&A, 0, sizeof(A));
-        A.seeds = (const ldso_act_seed_t *) (dIn + p.oSeeds); A.pts = (const ldso_immature_t *) (dIn + p.oPts); A.myType = (const float *) (dIn + p.oType);
-        A.KRKi = (const float *) (dIn + p.oKRKi); A.Kt = (const float *) (dIn + p.oKt); A.flagged = (const int32_t *) (dIn + p.oFlag);
-        A.nSeeds = J.n_seeds; A.n = J.n; A.nHosts = J.n_hosts; A.w1 = p.w1; A.h1 = p.h1; A.minDist = J.currentMinActDist; A.minQuality = minTraceQuality;
-        A.pgeo = nullptr; A.phost = nullptr; A.nWin = 0; A.newestHost = -1;
-        RUN(batch_sel_map(H, p.mapBytes, &A.gmap));
-        // the map in LDS where the workgroup can have that much, in global memory otherwise: the rule of the single-window entry, window by window
-        A.ldsMap = SEL_LIST_BYTES + p.mapBytes <= (size_t) Bt->selLdsLimit ? 1 : 0;
-        if (A.ldsMap) ldsBytes = std::max(ldsBytes, SEL_LIST_BYTES + p.mapBytes);
-        A.nSelected = (int32_t *) (dOut + p.oOut); A.decision = (int32_t *) (dOut + p.oDec); A.selected = (int32_t *) (dOut + p.oSel);
-        A.cell = (int32_t *) (dScr + p.oCell); A.frac = (float *) (dScr + p.oFrac); A.thr = (float *) (dScr + p.oThr);
-        if (activate && J.n > 0) {
-            ActWin &T = act[ia];
-            memset(&T, 0, sizeof(T));
-            T.A.pts = A.pts; T.A.out = (ldso_activation_t *) (dOut + p.oAct); T.A.n = J.n; T.A.minObs = min_obs; T.A.GNIts = gn_iterations; T.A.minIdepthH_act = min_idepth_hessian;
-            T.A.sel = A.selected; T.A.nSel = A.nSelected; T.item = p.win;
-            wave[ia++] = waves; waves += J.n;
+        A = sel_args(p.J, p.R, d + oIn, dOut, dOut + at.down, (unsigned char *) H->d_sel, minTraceQuality);
+        RUN(sel_lds_rule((const void *) k_act_select_batch, H0->device, Bt->selLdsLimit, Bt->selLdsSet, p.R.mapBytes, ldsBytes, A.ldsMap));
+        if (activate && p.J.n > 0) {
+            act[ia] = act_win(A.pts, (ldso_activation_t *) (dOut + p.R.act), p.J.n, min_obs, min_idepth_hessian, gn_iterations, A.selected, A.nSelected, p.win);
+            wave[ia++] = waves; waves += p.J.n;
         }
     }
     wave[ia] = waves;
     CHK(hipMemcpyAsync(d, hs, up, hipMemcpyHostToDevice, H0->stream));
-    if ((int) ldsBytes > Bt->selLdsSet) { CHK(hipFuncSetAttribute((const void *) k_act_select_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes)); Bt->selLdsSet = (int) ldsBytes; }
     hipLaunchKernelGGL(k_act_select_batch, dim3(nPart), dim3(SEL_THREADS), ldsBytes, H0->stream, (const SelArgs *) (d + oTab));
     CHK(hipGetLastError());
-    for (const SelPlan &p : plan) { ldso_ba *H = Bt->h[(size_t) p.win]; H->selW1 = p.w1; H->selH1 = p.h1; H->selMapOffset = 0; }
+    for (const SelPart &p : part) { ldso_ba *H = Bt->h[(size_t) p.win]; H->selW1 = p.J.w1; H->selH1 = p.J.h1; H->selMapOffset = 0; }
     if (activate) CHK(ba_launch_activate_batch(Bt->d_items, (const ActWin *) (d + oAct), (const int32_t *) (d + oWave), nAct, waves, Bt->Dmax.nsg, H0->settings, H0->stream));
-    CHK(hipMemcpyAsync(hs + up, dOut, down, hipMemcpyDeviceToHost, H0->stream));
+    CHK(hipMemcpyAsync(hs + up, dOut, at.down, hipMemcpyDeviceToHost, H0->stream));
     CHK(hipStreamSynchronize(H0->stream));
-    for (const SelPlan &p : plan) {
-        ldso_act_job_t &J = jobs[p.win];
-        const char *ho = hs + up;
-        const int ns = std::min(std::max(*(const int32_t *) (ho + p.oOut), 0), J.n);
-        if (J.n) memcpy(J.decision_out, ho + p.oDec, (size_t) J.n * 4);
-        if (J.selected_out && ns > 0) memcpy(J.selected_out, ho + p.oSel, (size_t) ns * 4);
-        if (activate && ns > 0) memcpy(J.out, ho + p.oAct, (size_t) ns * sizeof(ldso_activation_t));
-        J.n_selected = ns;
-    }
+    for (const SelPart &p : part) jobs[p.win].n_selected = act_unpack(p.J, p.R, hs + up);
     return LDSO_OK;
 }
 
@@ -589,7 +520,7 @@ int ldso_ba_batch_activate_points(ldso_ba_batch_t *Bt, const int *n_pts, const l
     for (int i = 0; i < n; i++) {
         if (n_pts[i] == 0 || points[i] == nullptr) continue;
         REQ(n_pts[i] > 0 && out[i], w + ": a window that takes part needs n[i] > 0 and its out[i]");
-        RUN(batch_act_window_checks(Bt->h[(size_t) i], w, true));
+        RUN(batch_act_window_checks(Bt->h[(size_t) i], w, true, Bt->h[(size_t) i]->D.F));
         part.push_back(i);
         total += (size_t) n_pts[i];
     }
@@ -606,11 +537,8 @@ int ldso_ba_batch_activate_points(ldso_ba_batch_t *Bt, const int *n_pts, const l
     size_t at = 0;
     for (int k = 0; k < nTab; k++) {
         const int i = part[(size_t) k];
-        ActWin &T = tab[k];
-        memset(&T, 0, sizeof(T));
         memcpy(hs + oPts + at * sizeof(ldso_immature_t), points[i], (size_t) n_pts[i] * sizeof(ldso_immature_t));
-        T.A.pts = (const ldso_immature_t *) (d + oPts) + at; T.A.out = (ldso_activation_t *) (d + up) + at; T.A.n = n_pts[i]; T.A.minObs = min_obs; T.A.GNIts = gn_iterations;
-        T.A.minIdepthH_act = min_idepth_hessian; T.A.sel = nullptr; T.A.nSel = nullptr; T.item = i;
+        tab[k] = act_win((const ldso_immature_t *) (d + oPts) + at, (ldso_activation_t *) (d + up) + at, n_pts[i], min_obs, min_idepth_hessian, gn_iterations, nullptr, nullptr, i);
         wave[k] = (int32_t) at;
         at += (size_t) n_pts[i];
     }
@@ -655,3 +583,4 @@ int ldso_ba_get_distance_map(ldso_ba_t *H, float *out) {
 }
 
 }  // extern "C"
+

@@ -183,22 +183,10 @@ __global__ __launch_bounds__(256) void k_activate_batch(const BatchItem *items, 
     activate_body<NSG>(it.B, it.D, S, T.A, w - waveOff[lo]);
 }
 
-hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs,
-                              float minIdepthH_act, int GNIts, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    ActArgs A; A.pts = d_pts; A.out = d_out; A.n = n; A.minObs = minObs; A.GNIts = GNIts; A.minIdepthH_act = minIdepthH_act; A.sel = nullptr; A.nSel = nullptr;
-    const int blocks = (n + 3) / 4;
-    if (D.nsg == 1) hipLaunchKernelGGL(k_activate<1>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
-    else hipLaunchKernelGGL(k_activate<2>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
-    return hipGetLastError();
-}
-
-// the same kernel over a selection that lives on the device: at most nMax wavefronts start, those beyond *d_nSel leave at once
-hipError_t ba_launch_activate_selected(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, const int32_t *d_sel, const int32_t *d_nSel,
-                                       ldso_activation_t *d_out, int nMax, int minObs, float minIdepthH_act, int GNIts, hipStream_t st) {
-    if (nMax <= 0) return hipSuccess;
-    ActArgs A; A.pts = d_pts; A.out = d_out; A.n = nMax; A.minObs = minObs; A.GNIts = GNIts; A.minIdepthH_act = minIdepthH_act; A.sel = d_sel; A.nSel = d_nSel;
-    const int blocks = (nMax + 3) / 4;
+// A.n wavefronts: one per point, or, over a selection that lives on the device (A.sel / A.nSel), at most that many, of which those beyond *A.nSel leave at once
+hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ActArgs &A, hipStream_t st) {
+    if (A.n <= 0) return hipSuccess;
+    const int blocks = (A.n + 3) / 4;
     if (D.nsg == 1) hipLaunchKernelGGL(k_activate<1>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
     else hipLaunchKernelGGL(k_activate<2>, dim3(blocks), dim3(256), 0, st, B, D, S, A);
     return hipGetLastError();

@@ -28,6 +28,13 @@ struct ActArgs {
     const int32_t *nSel;
 };
 struct ActWin { ActArgs A; int32_t item, pad_[3]; };
+// one window's activation: n wavefronts over d_pts -> d_out, or over the list d_sel of length *d_nSel (both null: every point); every byte set, the records cross PCIe in tables
+inline ActWin act_win(const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs, float minIdepthH_act, int GNIts, const int32_t *d_sel, const int32_t *d_nSel, int item) {
+    ActWin T;
+    memset(&T, 0, sizeof(T));
+    T.A.pts = d_pts; T.A.out = d_out; T.A.n = n; T.A.minObs = minObs; T.A.GNIts = GNIts; T.A.minIdepthH_act = minIdepthH_act; T.A.sel = d_sel; T.A.nSel = d_nSel; T.item = item;
+    return T;
+}
 
 // the launchers, defined beside their kernels (ba_linearize / ba_reduce / ba_solve / ba_activate .hip)
 hipError_t ba_launch_linearize(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, bool hasL, bool fix, int stepMode, const GnInit &gi, hipStream_t st);
@@ -40,8 +47,7 @@ hipError_t ba_launch_linearize_marg(const BaPtrs &B, const BaDims &D, const ResS
 hipError_t ba_launch_marg_frame(const BaPtrs &B, const BaDims &D, int idx, double *work, double *outH, double *outb, hipStream_t st);
 hipError_t ba_launch_acc_init(const BaPtrs &B, const BaDims &D, const GnInit &gi, hipStream_t st);
 hipError_t ba_launch_gn_export(const BaPtrs &B, const BaDims &D, const ResSet &S, double *tail, hipStream_t st);
-hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, ldso_activation_t *d_out, int n, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
-hipError_t ba_launch_activate_selected(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ldso_immature_t *d_pts, const int32_t *d_sel, const int32_t *d_nSel, ldso_activation_t *d_out, int nMax, int minObs, float minIdepthH_act, int GNIts, hipStream_t st);
+hipError_t ba_launch_activate(const BaPtrs &B, const BaDims &D, const ldso_settings_t &S, const ActArgs &A, hipStream_t st);
 hipError_t ba_launch_activate_batch(const BatchItem *d_items, const ActWin *d_tab, const int32_t *d_waveOff, int nTab, int totalWaves, int nsg, const ldso_settings_t &S, hipStream_t st);
 hipError_t ba_launch_linearize_batch(const BatchItem *d_items, const BatchBlock *d_blocks, int totalChunks, const int32_t *d_wgStart, int nWG, int FS, int cur, const ldso_settings_t &S, int stepMode, float calibPrior, hipStream_t st, int itCheck = -1);
 hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalBlocks, int cur, float calibPrior, double l1, double il, hipStream_t st, int itCheck = -1);

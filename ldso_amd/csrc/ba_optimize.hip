@@ -1,5 +1,5 @@
 // ba_optimize.hip — kernel sequencing of one window: the launch helpers, the step-wise LM entries, the GN iteration with its HIP-graph cache,
-// ldso_ba_optimize, both marginalisations, point activation.
+// ldso_ba_optimize, both marginalisations.  (Point activation, ldso_ba_activate_points, lies beside the other activation entries in act_select.hip.)
 //
 // Kernel sequences:
 //   fast path (ldso_ba_optimize, ldso_ba_enqueue_gn):  k_reduce(atomic) -> k_gn_solve -> k_linearize(point step fused)   per iteration
@@ -451,29 +451,6 @@ int ldso_ba_marginalize_frame(ldso_ba_t *H, int frame_idx, double *HM_out, doubl
     CHK(ba_launch_marg_frame(H->B, H->D, frame_idx, work, oH, ob, H->stream));
     CHK(hipMemcpyAsync(HM_out, oH, nd * nd * 8, hipMemcpyDeviceToHost, H->stream));
     CHK(hipMemcpyAsync(bM_out, ob, nd * 8, hipMemcpyDeviceToHost, H->stream));
-    CHK(hipStreamSynchronize(H->stream));
-    return LDSO_OK;
-}
-
-// FullSystem::optimizeImmaturePoint (FullSystem.cc:892-1010) for n immature points against the key frames of the window that is
-// resident in the handle (ldso_ba_set_image*, ldso_ba_set_window, ldso_ba_set_frames: images, calibration, current poses).
-int ldso_ba_activate_points(ldso_ba_t *H, int n, const ldso_immature_t *pts, int min_obs, float min_idepth_hessian, int gn_iterations, ldso_activation_t *out) {
-    REQ(H && n >= 0 && (n == 0 || (pts && out)) && gn_iterations >= 0, "ldso_ba_activate_points: bad arguments");
-    REQ(H->D.F >= 2, "ldso_ba_activate_points: set the window and the frames first");
-    if (n == 0) return LDSO_OK;
-    CHK(hipSetDevice(H->device));
-    for (int f = 0; f < H->D.F; f++) REQ(H->B.img[f] != nullptr, "ldso_ba_activate_points: a key-frame image is missing");
-    if (n > H->actCap) {
-        if (H->d_act) hipFree(H->d_act);
-        H->d_act = nullptr; H->actCap = 0;
-        CHK(hipMalloc(&H->d_act, (size_t) n * (sizeof(ldso_immature_t) + sizeof(ldso_activation_t))));
-        H->actCap = n;
-    }
-    ldso_immature_t *dp = (ldso_immature_t *) H->d_act;
-    ldso_activation_t *dout = (ldso_activation_t *) ((char *) H->d_act + (size_t) H->actCap * sizeof(ldso_immature_t));
-    CHK(hipMemcpyAsync(dp, pts, (size_t) n * sizeof(ldso_immature_t), hipMemcpyHostToDevice, H->stream));
-    CHK(ba_launch_activate(H->B, H->D, H->settings, dp, dout, n, min_obs, min_idepth_hessian, gn_iterations, H->stream));
-    CHK(hipMemcpyAsync(out, dout, (size_t) n * sizeof(ldso_activation_t), hipMemcpyDeviceToHost, H->stream));
     CHK(hipStreamSynchronize(H->stream));
     return LDSO_OK;
 }

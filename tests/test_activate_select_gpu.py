@@ -168,6 +168,43 @@ def test_fused_selection_and_activation(min_dist):
     ba.close()
 
 
+def test_small_large_small_on_one_handle():
+    """ldso_ba_select_activate_points with 5, then 600, then 5 candidates on ONE handle (a 320 x 240 `tiny` window): its arena grows between the first two calls and is
+    larger than the third needs.  Every call equals - decisions, selected list, records, distance map, byte for byte - the same call on a freshly created handle, and so
+    does an ldso_ba_activate_points on the same handle behind each of them.  The five: two candidates the large call selects and one it keeps (with fewer accepted
+    before them the first two are selected again), two the rules drop."""
+    import batch_activate_common as bac
+    win = synth.make_config("tiny", w=320, h=240, fx=200.0)
+    large = bac.make_job(win, 200, seed=61)
+    assert len(large["cand"]) == 600
+    min_dist = 1.0
+
+    def fused(ba, job):
+        dec, sel, rec = ba.select_activate_points(*bac.solo_args(job), min_dist)
+        return dec, sel, rec, ba.get_distance_map(), ba.activate_points(job["cand"][:8])
+
+    fresh = binding.BA.from_window(win)
+    dec = fused(fresh, large)[0]
+    fresh.close()
+    pick = np.sort(np.concatenate([np.nonzero(dec == synth.ACT_SELECTED)[0][[3, -3]], np.nonzero(dec == synth.ACT_KEEP)[0][:1], np.nonzero(dec == synth.ACT_DROP)[0][[0, -1]]]))
+    small = dict(large, cand=np.ascontiguousarray(large["cand"][pick]), my_type=np.ascontiguousarray(large["my_type"][pick]))
+    assert len(small["cand"]) == 5
+    ba = binding.BA.from_window(win)
+    for job in (small, large, small):
+        got = fused(ba, job)
+        fresh = binding.BA.from_window(win)
+        want = fused(fresh, job)
+        fresh.close()
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (len(job["cand"]), k)
+        n_sel, n_drop = len(got[1]), int((got[0] == synth.ACT_DROP).sum())
+        print("candidates", len(job["cand"]), "selected", n_sel, "dropped", n_drop, "ok", float(got[2]["ok"].mean()))
+        assert n_sel >= 1 and n_drop >= 1 and len(got[2]) == n_sel and (got[3] == 0).sum() >= n_sel
+        if job is small:
+            assert n_sel >= 2 and n_drop == 2
+    ba.close()
+
+
 def test_adapter_activate_points_mt_equals_reference_member():
     """GpuBackend::activatePointsMT(fs) against the reference's fs.activatePointsMT() on two identical object graphs, one step: every Feature::status and
     currentMinActDist exact, the new points as close as tests/test_adapter_gpu.py asks of activatePoints (verdicts exact, inverse depth to 1e-5)."""

@@ -191,6 +191,36 @@ def test_twice_on_the_same_batch_with_growing_counts():
     b.close()
 
 
+def test_counts_at_which_a_regions_rounding_changes():
+    """1, 3, 4 and 5 candidates (4 n bytes cross a 16-byte boundary between 4 and 5) with no seed and with one, on two 320 x 240 `tiny` windows: each count once as
+    the first window of the batched fused call, whose size moves the second window's regions, and once as the second.  The batch against the single-window entry on
+    its member, and the single-window entry against ldso_ba_activate_points on the candidates it selected.  The candidates are ones that reach the distance test, so
+    every call selects."""
+    import activation_select_common as asc
+    st = stream()
+    wins = [synth.make_config("tiny", w=320, h=240, fx=200.0, seed=71 + i) for i in range(2)]
+    batch, b = make_batch(wins, st)
+    pool = []
+    for i, w in enumerate(wins):
+        j = bac.with_distance(bac.make_job(w, 40, seed=75 + i), 1.0)
+        el = np.nonzero(asc.eligible_in_bounds(j, (120, 160)))[0]
+        assert len(el) >= 5
+        pool.append(dict(j, cand=np.ascontiguousarray(j["cand"][el]), my_type=np.ascontiguousarray(j["my_type"][el])))
+    for n_seeds in (0, 1):
+        for counts in ((1, 3), (3, 4), (4, 5), (5, 1)):
+            jobs = [dict(j, cand=j["cand"][:n].copy(), my_type=j["my_type"][:n].copy(), seeds=j["seeds"][:n_seeds].copy()) for j, n in zip(pool, counts)]
+            out = b.select_activate_points(jobs)
+            for i, (g, job) in enumerate(zip(batch, jobs)):
+                got_map = g.get_distance_map()
+                want = solo_fused(g, job)
+                assert_window_equal((n_seeds, counts, i), out[i], got_map, want[:-1], want[-1])
+                dec, sel, rec = want[:3]
+                assert len(dec) == counts[i] and 1 <= len(sel) <= counts[i] and len(rec) == len(sel), (n_seeds, counts, i)
+                assert rec.tobytes() == g.activate_points(job["cand"][sel]).tobytes(), (n_seeds, counts, i)
+                assert (got_map == 0).sum() >= len(sel)
+    b.close()
+
+
 SENTINEL = -7
 
 
