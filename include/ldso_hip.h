@@ -66,6 +66,21 @@ int ldso_pyr_make_images_device(ldso_pyramid_t *p, const void *irradiance_dev, v
 /* device pointer and size of a level ((w>>lvl)*(h>>lvl)*3 floats); ldso_pyr_get_level: test fetch to the host */
 int ldso_pyr_level(ldso_pyramid_t *p, int lvl, const void **dev_ptr, int *wl, int *hl);
 int ldso_pyr_get_level(ldso_pyramid_t *p, int lvl, float *out);
+/* A group of pyramids: FrameHessian::makeImages (FrameHessian.cc:44-113) of the new frames of many sequences on one card.  ldso_pyr_make_images is
+ * 2 x levels small launches per pyramid; a group call builds every active member in at most 2 x Lmax launches whatever n (Lmax = the largest level count
+ * among them), with the job tables of all levels in one upload.  Every level of every member holds the bytes ldso_pyr_make_images gives it.
+ * 1 <= n <= 128 pyramids of one device; sizes and level counts are free.  A pyramid belongs to at most one group and stays usable on its own between
+ * group calls; ldso_pyr_destroy of a member is refused while the group lives. */
+typedef struct ldso_pyr_group ldso_pyr_group_t;
+int ldso_pyr_group_create(ldso_pyramid_t *const *pyramids, int n, ldso_pyr_group_t **out);
+int ldso_pyr_group_destroy(ldso_pyr_group_t *g);
+/* irradiance: n host pointers (member i: w_i * h_i floats; entries of inactive members are not read), copied straight into the members' own staging
+ * images on hip_stream; active: n bytes or NULL = all.  Like the solo entries the call does not wait: every active member's event is recorded behind the
+ * last launch, and every consumer (ldso_tr_set_new_frame_pyramid, ldso_trace_set_frame_pyramid, ...) orders itself behind it.  The host images must stay
+ * valid until the stream has passed the copies.  LDSO_E_INVALID (a NULL image of an active member, no active member) before anything is enqueued. */
+int ldso_pyr_group_make_images(ldso_pyr_group_t *g, const uint8_t *active /* n or NULL */, const float *const *irradiance /* n host pointers */, void *hip_stream);
+/* the same from n device pointers */
+int ldso_pyr_group_make_images_device(ldso_pyr_group_t *g, const uint8_t *active /* n or NULL */, const void *const *irradiance_dev /* n device pointers */, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Windowed bundle adjustment (EnergyFunctional + the optimisation slice of FullSystem).
@@ -566,6 +581,33 @@ int ldso_trace_set_frame_pyramid(ldso_tracer_t *t, ldso_pyramid_t *pyr);
 /* per host key frame h < n_hosts (FullSystem.cc:1025-1032): KRKi[h] = K R K^-1 (row-major 3x3), Kt[h] = K t,
  * aff[h] = AffLight::fromToVecExposure(host, new).  counts_out[6] (optional): points per resulting LDSO_IPS_* status. */
 int ldso_trace_on(ldso_tracer_t *t, int n_hosts, const float *KRKi, const float *Kt, const float *aff, int *counts_out);
+/* The caller's stream instead of the tracer's own (NULL: an own one again).  The tracer holds no frame afterwards (the wait ldso_trace_set_frame_pyramid
+ * queued for the frame's build stands on the old stream): set the frame again before the next trace. */
+int ldso_trace_set_stream(ldso_tracer_t *t, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * A group of tracers: FullSystem::traceNewCoarse (FullSystem.cc:1012-1050) = ImmaturePoint::traceOn (src/internal/ImmaturePoint.cc:47-310) of the
+ * new frames of many sequences on one card.  One ldso_trace_on is a pose upload, a memset, a launch, a download and a wait; a group call traces the points of
+ * all active members in ONE launch (one wavefront per point, the members' points packed wavefront by wavefront) with one upload, one download and one wait.
+ * A member's records and counts are those of its own ldso_trace_on from the same input, byte for byte.  All arrays are member-major.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct ldso_trace_group ldso_trace_group_t;
+/* The member-lookup rule of a grouped launch: first[j] = the wavefronts in front of job j (first[0] = 0, non-decreasing), first[n_jobs] = all of them;
+ * *job_out = the job j with first[j] <= wave < first[j + 1] - jobs without wavefronts are skipped.  LDSO_E_INVALID for a wave outside
+ * [0, first[n_jobs]).  Pure host function; the kernel runs the same search. */
+int ldso_trace_group_member_of(const int *first, int n_jobs, int wave, int *job_out);
+/* 1 <= n <= 128 tracers on one device and one stream (ldso_trace_set_stream); image size, max_points, settings and point counts may differ.  A tracer belongs to
+ * at most one group and stays usable on its own between group calls (ldso_trace_set_points, ldso_trace_set_frame*, ldso_trace_on, ldso_trace_compact, ...): the
+ * group reads every member's current records, frame and settings at each call, and every call checks that the members still share their stream.
+ * ldso_trace_destroy of a member is refused while the group lives. */
+int ldso_trace_group_create(ldso_tracer_t *const *tracers, int n, ldso_trace_group_t **out);
+int ldso_trace_group_destroy(ldso_trace_group_t *g);
+/* ldso_trace_on for every member with active[i] != 0 (NULL: all).  Member i brings n_hosts[i] hosts: KRKi[i], Kt[i], aff[i] point to n_hosts[i] x 9, 3 and 2
+ * floats (entries of inactive members are not read).  counts_out: n x 6 or NULL; rows of inactive members are left untouched.  Everything is checked before
+ * anything is enqueued: a member without a frame or an n_hosts outside 1..LDSO_MAX_FRAMES gives LDSO_E_INVALID with the member's index in the message, and no
+ * record of any member changes. */
+int ldso_trace_group_on(ldso_trace_group_t *g, const uint8_t *active /* n or NULL = all */, const int *n_hosts /* n */, const float *const *KRKi /* n pointers */,
+                        const float *const *Kt /* n pointers */, const float *const *aff /* n pointers */, int *counts_out /* n*6 or NULL */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * New features of a key frame: FullSystem::makeNewTraces (FullSystem.cc:1272-1325) for setting_pointSelection == 1 (the default, Setting.cc:125) =

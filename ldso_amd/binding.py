@@ -1269,6 +1269,111 @@ class Tracer:
         _chk(self.L.ldso_trace_on(self.h, C.c_int(len(K1)), _p(K1), _p(K2), _p(A), _p(counts)))
         return counts
 
+    def set_stream(self, stream_ptr):
+        """the caller's stream (None: an own one again); the tracer holds no frame afterwards: set it again"""
+        _chk(self.L.ldso_trace_set_stream(self.h, C.c_void_p(stream_ptr)))
+
+
+def _active_mask(active, n):
+    """an active mask as the group entries take it: (None, all indices) or (n bytes, the indices set)"""
+    if active is None:
+        return None, list(range(n))
+    act = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
+    assert act.shape == (n,)
+    return act, [i for i in range(n) if act[i]]
+
+
+class TracerGroup:
+    """ldso_trace_group_*: the traces of several tracers (independent sequences on one device and one stream) in one launch.  Arguments and results are per member,
+    in the order of `tracers`; the members stay usable on their own between group calls."""
+
+    def __init__(self, tracers):
+        self.L = lib()
+        self.tracers = list(tracers)          # kept alive: the group dereferences its members
+        arr = (C.c_void_p * len(self.tracers))(*[t.h for t in self.tracers])
+        self.h = C.c_void_p()
+        _chk(self.L.ldso_trace_group_create(arr, C.c_int(len(self.tracers)), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.ldso_trace_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def trace_on(self, poses, active=None):
+        """ldso_trace_group_on -> counts (n, 6) int32; rows of inactive members stay zero.  poses: one (KRKi, Kt, aff) triple per member (None for an inactive one)."""
+        n = len(self.tracers)
+        assert len(poses) == n
+        act, idx = _active_mask(active, n)
+        keep = []
+        ptrs = [(C.c_void_p * n)() for _ in range(3)]
+        nh = np.zeros(n, np.int32)
+        for i in idx:
+            K = [np.ascontiguousarray(a, np.float32) for a in poses[i]]
+            nh[i] = len(K[0])
+            assert K[0].size == 9 * nh[i] and K[1].size == 3 * nh[i] and K[2].size == 2 * nh[i]
+            keep.append(K)
+            for q in range(3):
+                ptrs[q][i] = K[q].ctypes.data
+        counts = np.zeros((n, 6), np.int32)
+        _chk(self.L.ldso_trace_group_on(self.h, _p(act), _p(nh), ptrs[0], ptrs[1], ptrs[2], _p(counts)))
+        return counts
+
+
+class PyramidGroup:
+    """ldso_pyr_group_*: FrameHessian::makeImages of several pyramids (one device; sizes and level counts are free) in at most 2 x Lmax launches per call."""
+
+    def __init__(self, pyramids):
+        self.L = lib()
+        self.pyramids = list(pyramids)          # kept alive: the group dereferences its members
+        arr = (C.c_void_p * len(self.pyramids))(*[p.h for p in self.pyramids])
+        self.h = C.c_void_p()
+        _chk(self.L.ldso_pyr_group_create(arr, C.c_int(len(self.pyramids)), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.ldso_pyr_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def make_images(self, images, stream=None, active=None):
+        """ldso_pyr_group_make_images: images = one irradiance array per member (None for an inactive one), enqueued on `stream`; like Pyramid.make_images it does not wait.
+        The converted arrays are kept until the next call: the copies read them on the stream."""
+        n = len(self.pyramids)
+        assert len(images) == n
+        act, idx = _active_mask(active, n)
+        ptrs = (C.c_void_p * n)()
+        keep = []
+        for i in idx:
+            a = np.ascontiguousarray(images[i], np.float32)
+            assert a.size == self.pyramids[i].w * self.pyramids[i].hh
+            keep.append(a)
+            ptrs[i] = a.ctypes.data
+        _chk(self.L.ldso_pyr_group_make_images(self.h, _p(act), ptrs, C.c_void_p(stream)))
+        self._images = keep
+        return self
+
+    def make_images_device(self, image_ptrs, stream=None, active=None):
+        """ldso_pyr_group_make_images_device: one device pointer per member (None / 0 for an inactive one)"""
+        n = len(self.pyramids)
+        assert len(image_ptrs) == n
+        act, idx = _active_mask(active, n)
+        ptrs = (C.c_void_p * n)()
+        for i in idx:
+            ptrs[i] = image_ptrs[i]
+        _chk(self.L.ldso_pyr_group_make_images_device(self.h, _p(act), ptrs, C.c_void_p(stream)))
+        return self
+
 
 class Initializer:
     """Monocular initialiser handle: CoarseInitializer::setFirst / trackFrame on one GPU (include/ldso_hip.h)."""

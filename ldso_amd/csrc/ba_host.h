@@ -207,10 +207,26 @@ struct BatchCuts {
     std::vector<int32_t> wg[3];
 };
 
+// One trace as the kernels of trace.hip read it: the by-value argument of k_trace_on, one row of the job table of k_trace_group (device memory there, every pointer
+// a device pointer; the rows of a launch share nothing)
+struct TraceJob {
+    ldso_immature_t *pts;
+    int n;
+    const float *img;       // level-0 image of the new frame, 12-byte AoS (I, dx, dy)
+    int w, h;
+    const float *KRKi, *Kt, *aff;      // per host: 9, 3, 2 floats
+    int nHosts;
+    ldso_trace_settings_t s;
+    int *counts;            // [6] per resulting status (a row of 8 ints)
+};
+hipError_t trace_launch_group(const TraceJob *d_jobs, const int *d_first, int nJobs, int totalWaves, hipStream_t st);      // trace.hip: totalWaves = first[nJobs] > 0
+
 // the immature-point tracer (trace.hip)
 struct ldso_tracer {
     int device = 0, w = 0, h = 0, maxPoints = 0, n = 0;
     hipStream_t stream = nullptr;
+    bool ownStream = false;
+    const void *inGroup = nullptr;    // the ldso_trace_group this tracer belongs to (at most one; ldso_trace_destroy refuses while set: the group dereferences its members)
     ldso_trace_settings_t settings;
     ldso_immature_t *d_pts = nullptr, *d_alt = nullptr;     // the resident records; the buffer the next compaction writes (the two swap)
     float *d_type = nullptr, *d_typeAlt = nullptr;          // ImmaturePoint::my_type of every record (ImmaturePoint.h:114), beside d_pts / d_alt
@@ -221,6 +237,29 @@ struct ldso_tracer {
     const float *img = nullptr;       // the frame traced on: d_img, or level 0 of a shared ldso_pyramid_t
     int *d_counts = nullptr;
     bool haveFrame = false;
+};
+
+// a group of tracers whose traces share one launch (trace_group.hip)
+struct ldso_trace_group {
+    std::vector<ldso_tracer *> m;
+    int device = 0;
+    // one pinned arena and its device twin (grow_arena): [pose blocks of the active members | TraceJob table | first | count rows] go up in one copy, the count rows come down in one
+    char *h_stage = nullptr, *d_stage = nullptr;
+    size_t stageCap = 0;
+};
+
+// a group of pyramids whose builds share launches (images.hip)
+struct ldso_pyr_group {
+    std::vector<ldso_pyramid *> m;
+    int device = 0;
+    // one pinned arena and its device twin: the job tables and workgroup prefixes of every level go up in one copy per call.  A call does not wait on the host, so
+    // `uploaded` (recorded behind the copy) guards the pinned side against the next call's writes, and `done` (recorded behind the last launch) orders a call on
+    // another stream behind the kernels that still read the device side
+    char *h_stage = nullptr, *d_stage = nullptr;
+    size_t stageCap = 0;
+    hipEvent_t uploaded = nullptr, done = nullptr;
+    hipStream_t lastStream = nullptr;
+    bool used = false;
 };
 
 #pragma GCC visibility push(hidden)

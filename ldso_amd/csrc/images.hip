@@ -5,6 +5,7 @@
 // reference leaves them uninitialised and never samples them).  Pure streaming: 4 B in / 12 B out per pixel at level 0.
 // absSquaredGrad (pixel selector only) is not produced.
 #include "ba_host.h"
+#include "group_member.h"
 
 // channel 0 of a level (copy of the input or 2x2 mean of the level below), gradients zeroed
 __global__ __launch_bounds__(256) void k_img_intensity(const float *__restrict__ color, const float *__restrict__ below, float *__restrict__ dI, int wl, int hl, int wlm1) {
@@ -22,6 +23,48 @@ __global__ __launch_bounds__(256) void k_img_intensity(const float *__restrict__
 
 __global__ __launch_bounds__(256) void k_img_gradient(float *__restrict__ dI, int wl, int hl) {
     const int idx = wl + blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= wl * (hl - 1)) return;
+    float dx = 0.5f * (dI[3 * (size_t) (idx + 1)] - dI[3 * (size_t) (idx - 1)]);
+    float dy = 0.5f * (dI[3 * (size_t) (idx + wl)] - dI[3 * (size_t) (idx - wl)]);
+    if (!(fabsf(dx) <= 255.0f)) dx = 0;        // NaN or |.| > 255 (FrameHessian.cc:86-87)
+    if (!(fabsf(dy) <= 255.0f)) dy = 0;
+    dI[3 * (size_t) idx + 1] = dx;
+    dI[3 * (size_t) idx + 2] = dy;
+}
+
+// The same two kernels for one level of a group of pyramids (ldso_pyr_group_*): job j is one member that has this level, a workgroup belongs to one job -
+// wgFirst[j] workgroups lie in front of job j, wgFirst[nJobs] is the grid (group_member_of: a member whose level needs no workgroups is skipped).  Inside its job a
+// lane computes what the solo kernel computes for the same pixel, operation for operation.
+struct ImgJob {          // the pointers are typed as device memory (group_member.h: LD_GLOBAL)
+    LD_GLOBAL const float *color;     // level 0: the irradiance
+    LD_GLOBAL const float *below;     // level l >= 1: level l - 1 of the same member (color is null then)
+    LD_GLOBAL float *dI;
+    int wl, hl, wlm1, pad_;
+};
+
+__global__ __launch_bounds__(256) void k_img_intensity_group(const ImgJob *__restrict__ jobs, const int *__restrict__ wgFirst, int nJobs) {
+    const int j = group_member_of(wgFirst, nJobs, (int) blockIdx.x);
+    const ImgJob J = jobs[j];
+    const int wl = J.wl, hl = J.hl, wlm1 = J.wlm1;
+    const int i = ((int) blockIdx.x - wgFirst[j]) * blockDim.x + threadIdx.x;
+    if (i >= wl * hl) return;
+    float v;
+    if (J.below == nullptr) v = J.color[i];
+    else {
+        const int x = i % wl, y = i / wl;
+        const float *p = (const float *) J.below + 3 * (size_t) (2 * x + 2 * y * wlm1);
+        v = 0.25f * (((p[0] + p[3]) + p[3 * wlm1]) + p[3 * wlm1 + 3]);
+    }
+    float *dI = (float *) J.dI;
+    dI[3 * (size_t) i] = v; dI[3 * (size_t) i + 1] = 0.0f; dI[3 * (size_t) i + 2] = 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_img_gradient_group(const ImgJob *__restrict__ jobs, const int *__restrict__ wgFirst, int nJobs) {
+    const int j = group_member_of(wgFirst, nJobs, (int) blockIdx.x);
+    const ImgJob J = jobs[j];
+    const int wl = J.wl, hl = J.hl;
+    float *dI = (float *) J.dI;
+    const int idx = wl + ((int) blockIdx.x - wgFirst[j]) * blockDim.x + threadIdx.x;
     if (idx >= wl * (hl - 1)) return;
     float dx = 0.5f * (dI[3 * (size_t) (idx + 1)] - dI[3 * (size_t) (idx - 1)]);
     float dy = 0.5f * (dI[3 * (size_t) (idx + wl)] - dI[3 * (size_t) (idx - wl)]);
@@ -70,6 +113,7 @@ int ldso_pyr_create(int device, int w, int h, int levels, ldso_pyramid_t **out) 
 
 int ldso_pyr_destroy(ldso_pyramid_t *P) {
     if (!P) return LDSO_OK;
+    REQ(P->inGroup == nullptr, "ldso_pyr_destroy: the pyramid is a member of a live group (ldso_pyr_group_destroy first: the group dereferences its members)");
     hipSetDevice(P->device);
     hipDeviceSynchronize();          // consumers may still be reading the levels
     if (P->ready) hipEventDestroy(P->ready);
@@ -97,6 +141,139 @@ int ldso_pyr_make_images(ldso_pyramid_t *P, const float *irradiance, void *hip_s
     hipStream_t st = (hipStream_t) hip_stream;
     CHK(hipMemcpyAsync(P->d_color, irradiance, (size_t) P->w * P->h * sizeof(float), hipMemcpyHostToDevice, st));
     return ldso_pyr_make_images_device(P, P->d_color, hip_stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ldso_pyr_group_*: FrameHessian::makeImages (FrameHessian.cc:44-113) of the new frames of several sequences.  One ldso_pyr_make_images is 2 x levels small
+// launches; the group builds level l of every active member that has one in two launches (intensity, gradient), 2 x Lmax per call whatever n, with the job tables
+// of all levels in one upload.
+// ---------------------------------------------------------------------------------------------------------
+
+int ldso_pyr_group_create(ldso_pyramid_t *const *pyramids, int n, ldso_pyr_group_t **out) {
+    REQ(pyramids && out && n >= 1 && n <= 128, "ldso_pyr_group_create: bad arguments (1 <= n <= 128 pyramids)");
+    for (int i = 0; i < n; i++) {
+        REQ(pyramids[i], "ldso_pyr_group_create: null pyramid");
+        REQ(pyramids[i]->inGroup == nullptr, "ldso_pyr_group_create: a pyramid belongs to at most one group at a time");
+        for (int k = 0; k < i; k++) REQ(pyramids[k] != pyramids[i], "ldso_pyr_group_create: the same pyramid twice");
+        REQ(pyramids[i]->device == pyramids[0]->device, "ldso_pyr_group_create: the members of a group share one device");
+    }
+    CHK(hipSetDevice(pyramids[0]->device));
+    ldso_pyr_group *g = new ldso_pyr_group();
+    g->device = pyramids[0]->device;
+    auto body = [&]() -> int {
+        CHK(hipEventCreateWithFlags(&g->uploaded, hipEventDisableTiming));
+        CHK(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
+        return LDSO_OK;
+    };
+    RUN(finish_create(body(), g, out, ldso_pyr_group_destroy));
+    g->m.assign(pyramids, pyramids + n);
+    for (ldso_pyramid *P : g->m) P->inGroup = g;
+    return LDSO_OK;
+}
+
+int ldso_pyr_group_destroy(ldso_pyr_group_t *g) {
+    if (!g) return LDSO_OK;
+    hipSetDevice(g->device);
+    if (g->used) hipEventSynchronize(g->done);          // the last call's kernels read the device arena
+    for (ldso_pyramid *P : g->m) if (P->inGroup == g) P->inGroup = nullptr;
+    if (g->uploaded) hipEventDestroy(g->uploaded);
+    if (g->done) hipEventDestroy(g->done);
+    if (g->h_stage) hipHostFree(g->h_stage);
+    if (g->d_stage) hipFree(g->d_stage);
+    delete g;
+    return LDSO_OK;
+}
+
+// the build of every active member from src[i] (device memory: the member's own d_color behind an upload, or the caller's image)
+static int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const std::vector<const float *> &src, hipStream_t st) {
+    const size_t nm = members.size();
+    int Lmax = 0;
+    for (int i : members) Lmax = std::max(Lmax, g->m[(size_t) i]->levels);
+    // per level: [ImgJob of the nl members that have it | nl + 1 workgroup prefixes of the intensity launch | nl + 1 of the gradient launch]
+    struct LevelPlan { size_t offJ, offI, offG; int nl, gridI, gridG; };
+    std::vector<LevelPlan> plan((size_t) Lmax);
+    size_t total = 0;
+    for (int l = 0; l < Lmax; l++) {
+        int nl = 0;
+        for (int i : members) nl += g->m[(size_t) i]->levels > l;
+        LevelPlan &L = plan[(size_t) l];
+        L.nl = nl; L.offJ = total; L.offI = L.offJ + (size_t) nl * sizeof(ImgJob); L.offG = L.offI + (size_t) (nl + 1) * 4;
+        total = (L.offG + (size_t) (nl + 1) * 4 + 15) & ~(size_t) 15;
+    }
+    // the arena is reused without a host wait at the end of a call: the pinned side is free once the last upload has been read, the device side once the last
+    // call's kernels are through - in stream order on the same stream, behind `done` on another
+    if (g->used) CHK(hipEventSynchronize(g->uploaded));
+    if (g->used && (total > g->stageCap || st != g->lastStream)) CHK(hipStreamWaitEvent(st, g->done, 0));
+    if (g->used && total > g->stageCap) CHK(hipEventSynchronize(g->done));
+    RUN(grow_arena(g->h_stage, g->d_stage, g->stageCap, total, 2, st));
+    for (int l = 0; l < Lmax; l++) {
+        LevelPlan &L = plan[(size_t) l];
+        ImgJob *hJ = (ImgJob *) (g->h_stage + L.offJ);
+        int *hI = (int *) (g->h_stage + L.offI), *hG = (int *) (g->h_stage + L.offG);
+        int j = 0, wgI = 0, wgG = 0;
+        for (size_t k = 0; k < nm; k++) {
+            const ldso_pyramid *P = g->m[(size_t) members[k]];
+            if (P->levels <= l) continue;
+            const int wl = P->w >> l, hl = P->h >> l, nPix = wl * hl, nGrad = wl * (hl - 2);
+            ImgJob &J = hJ[j];
+            J.color = (LD_GLOBAL const float *) (l == 0 ? src[k] : nullptr); J.below = (LD_GLOBAL const float *) (l == 0 ? nullptr : P->lv[l - 1]); J.dI = (LD_GLOBAL float *) P->lv[l];
+            J.wl = wl; J.hl = hl; J.wlm1 = P->w >> (l > 0 ? l - 1 : 0); J.pad_ = 0;
+            hI[j] = wgI; hG[j] = wgG;
+            wgI += (nPix + 255) / 256;
+            wgG += nGrad > 0 ? (nGrad + 255) / 256 : 0;
+            j++;
+        }
+        hI[j] = wgI; hG[j] = wgG;
+        L.gridI = wgI; L.gridG = wgG;
+    }
+    CHK(hipMemcpyAsync(g->d_stage, g->h_stage, total, hipMemcpyHostToDevice, st));
+    CHK(hipEventRecord(g->uploaded, st));
+    for (int l = 0; l < Lmax; l++) {
+        const LevelPlan &L = plan[(size_t) l];
+        const ImgJob *dJ = (const ImgJob *) (g->d_stage + L.offJ);
+        hipLaunchKernelGGL(k_img_intensity_group, dim3(L.gridI), dim3(256), 0, st, dJ, (const int *) (g->d_stage + L.offI), L.nl);
+        if (L.gridG > 0) hipLaunchKernelGGL(k_img_gradient_group, dim3(L.gridG), dim3(256), 0, st, dJ, (const int *) (g->d_stage + L.offG), L.nl);
+    }
+    CHK(hipGetLastError());
+    CHK(hipEventRecord(g->done, st));
+    g->used = true; g->lastStream = st;
+    for (int i : members) { ldso_pyramid *P = g->m[(size_t) i]; CHK(hipEventRecord(P->ready, st)); P->built = true; }
+    return LDSO_OK;
+}
+
+static int pyr_group_members(ldso_pyr_group *g, const uint8_t *active, const void *const *images, const char *who, std::vector<int> &members) {
+    REQ(g && images, std::string(who) + ": null argument");
+    for (int i = 0; i < (int) g->m.size(); i++) {
+        if (active && !active[i]) continue;
+        REQ(images[i], std::string(who) + ": member " + std::to_string(i) + ": null image");
+        members.push_back(i);
+    }
+    REQ(!members.empty(), std::string(who) + ": no active member");
+    return LDSO_OK;
+}
+
+int ldso_pyr_group_make_images_device(ldso_pyr_group_t *g, const uint8_t *active, const void *const *irradiance_dev, void *hip_stream) {
+    std::vector<int> members;
+    RUN(pyr_group_members(g, active, irradiance_dev, "ldso_pyr_group_make_images_device", members));
+    CHK(hipSetDevice(g->device));
+    std::vector<const float *> src;
+    for (int i : members) src.push_back((const float *) irradiance_dev[i]);
+    return pyr_group_build(g, members, src, (hipStream_t) hip_stream);
+}
+
+// from host images: every image goes straight into its pyramid's own d_color on the stream (the bytes dominate: no second staging copy on the host)
+int ldso_pyr_group_make_images(ldso_pyr_group_t *g, const uint8_t *active, const float *const *irradiance, void *hip_stream) {
+    std::vector<int> members;
+    RUN(pyr_group_members(g, active, (const void *const *) irradiance, "ldso_pyr_group_make_images", members));
+    CHK(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t) hip_stream;
+    std::vector<const float *> src;
+    for (int i : members) {
+        ldso_pyramid *P = g->m[(size_t) i];
+        CHK(hipMemcpyAsync(P->d_color, irradiance[i], (size_t) P->w * P->h * sizeof(float), hipMemcpyHostToDevice, st));
+        src.push_back(P->d_color);
+    }
+    return pyr_group_build(g, members, src, st);
 }
 
 int ldso_pyr_level(ldso_pyramid_t *P, int lvl, const void **dev_ptr, int *wl, int *hl) {

@@ -10,6 +10,7 @@ struct ldso_pyramid {
     float *d_color = nullptr;              // staging of the raw irradiance (host uploads)
     hipEvent_t ready = nullptr;            // recorded after the last build: consumers wait on it with hipStreamWaitEvent
     bool built = false;
+    const void *inGroup = nullptr;         // the ldso_pyr_group this pyramid belongs to (at most one; ldso_pyr_destroy refuses while set: the group dereferences its members)
 };
 
 extern "C" hipError_t img_launch_make_images(const float *d_color, int w, int h, int levels, float *const *d_levels, hipStream_t st);

@@ -10,17 +10,7 @@
 // Memory: per point 128 B record in / out + 4-byte taps of the level-0 image along the epipolar line (L2 resident).
 #include "ba_host.h"
 #include "lane.h"
-
-struct TraceArgs {
-    ldso_immature_t *pts;
-    int n;
-    const float *img;       // level-0 image of the new frame, 12-byte AoS (I, dx, dy)
-    int w, h;
-    const float *KRKi, *Kt, *aff;      // per host: 9, 3, 2 floats
-    int nHosts;
-    ldso_trace_settings_t s;
-    int *counts;            // [6] per resulting status
-};
+#include "group_member.h"
 
 // getInterpolatedElement31 (GlobalFuncs.h:146-159)
 static __device__ __forceinline__ float interp31(const float *img, float x, float y, int w) {
@@ -39,9 +29,9 @@ static __device__ __forceinline__ void trace_fail(ldso_immature_t *p, int lane, 
     if (lane == 0) { p->lastTraceUV[0] = -1; p->lastTraceUV[1] = -1; p->lastTracePixelInterval = 0; p->lastTraceStatus = status; atomicAdd(&counts[status], 1); }
 }
 
-__global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int i = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+// ImmaturePoint::traceOn of point i of one job by one wavefront (`lane` = its lane; i is wave-uniform).  No LDS and no barrier: the wavefronts of a workgroup are
+// independent, which is what lets k_trace_group put wavefronts of different jobs into one workgroup.
+static __device__ __forceinline__ void trace_point(const TraceJob &A, int i, int lane) {
     if (i >= A.n) return;
     ldso_immature_t *P = A.pts + i;
     const int hst = P->host;
@@ -247,6 +237,48 @@ __global__ __launch_bounds__(256) void k_trace_on(TraceArgs A) {
     }
 }
 
+__global__ __launch_bounds__(256) void k_trace_on(TraceJob A) {
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    trace_point(A, i, lane);
+}
+
+// a row of the job table as the kernel reads it: TraceJob with its pointers typed as device memory (group_member.h: LD_GLOBAL)
+struct TraceJobDev {
+    LD_GLOBAL ldso_immature_t *pts;
+    int n;
+    LD_GLOBAL const float *img;
+    int w, h;
+    LD_GLOBAL const float *KRKi, *Kt, *aff;
+    int nHosts;
+    ldso_trace_settings_t s;
+    LD_GLOBAL int *counts;
+};
+static_assert(sizeof(TraceJobDev) == sizeof(TraceJob) && offsetof(TraceJobDev, counts) == offsetof(TraceJob, counts) && offsetof(TraceJobDev, s) == offsetof(TraceJob, s) &&
+              offsetof(TraceJobDev, aff) == offsetof(TraceJob, aff), "TraceJobDev is TraceJob");
+
+// The traces of a group of tracers in one launch (ldso_trace_group_*, trace_group.hip): one wavefront per point, the points of all jobs packed wave-granular, so a
+// workgroup may hold wavefronts of several jobs (trace_point has no LDS and no barrier).  first[j] = the wavefronts in front of job j, first[nJobs] = all of them; the
+// wavefront finds its job with group_member_of.  Wave index and job index are wave-uniform (readfirstlane), and the job is copied before the first store of the
+// kernel: its pointers and settings are fetched with scalar loads and stay in scalar registers, as the by-value argument of k_trace_on does.
+__global__ __launch_bounds__(256) void k_trace_group(const TraceJob *__restrict__ jobs, const int *__restrict__ first, int nJobs) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int) ((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (wave >= first[nJobs]) return;
+    const int j = __builtin_amdgcn_readfirstlane(group_member_of(first, nJobs, wave));
+    const int i = __builtin_amdgcn_readfirstlane(wave - first[j]);
+    const TraceJobDev D = ((const TraceJobDev *) jobs)[j];
+    TraceJob A;
+    A.pts = (ldso_immature_t *) D.pts; A.n = D.n; A.img = (const float *) D.img; A.w = D.w; A.h = D.h;
+    A.KRKi = (const float *) D.KRKi; A.Kt = (const float *) D.Kt; A.aff = (const float *) D.aff; A.nHosts = D.nHosts; A.s = D.s; A.counts = (int *) D.counts;
+    trace_point(A, i, lane);
+}
+
+hipError_t trace_launch_group(const TraceJob *d_jobs, const int *d_first, int nJobs, int totalWaves, hipStream_t st) {
+    hipLaunchKernelGGL(k_trace_group, dim3((totalWaves + 3) / 4), dim3(256), 0, st, d_jobs, d_first, nJobs);
+    return hipGetLastError();
+}
+
 
 // ---------------------------------------------------------------------------------------------------------
 // Stable compaction of the resident set (what leaves it: points the selection dropped or activated, FullSystem.cc:1105-1188; points of a marginalised host
@@ -362,6 +394,7 @@ static int trace_create_body(ldso_tracer *T, int device, int w, int h, int max_p
     T->device = device; T->w = w; T->h = h; T->maxPoints = max_points;
     ldso_trace_settings_default(&T->settings);
     CHK(hipStreamCreateWithFlags(&T->stream, hipStreamNonBlocking));
+    T->ownStream = true;
     CHK(hipMalloc(&T->d_pts, (size_t) max_points * sizeof(ldso_immature_t))); CHK(hipMalloc(&T->d_alt, (size_t) max_points * sizeof(ldso_immature_t)));
     CHK(hipMalloc(&T->d_type, (size_t) max_points * 4)); CHK(hipMalloc(&T->d_typeAlt, (size_t) max_points * 4));
     CHK(hipMalloc(&T->d_keep, (size_t) max_points)); CHK(hipMalloc(&T->d_flag, (size_t) max_points));
@@ -382,11 +415,22 @@ int ldso_trace_create(int device, int w, int h, int max_points, ldso_tracer_t **
 
 int ldso_trace_destroy(ldso_tracer_t *T) {
     if (!T) return LDSO_OK;
+    REQ(T->inGroup == nullptr, "ldso_trace_destroy: the tracer is a member of a live group (ldso_trace_group_destroy first: the group dereferences its members)");
     hipSetDevice(T->device);
     hipDeviceSynchronize();
     hipFree(T->d_pts); hipFree(T->d_alt); hipFree(T->d_type); hipFree(T->d_typeAlt); hipFree(T->d_keep); hipFree(T->d_flag); hipFree(T->d_cmp); hipFree(T->d_img); hipFree(T->d_color); hipFree(T->d_pose); hipFree(T->d_counts);
-    if (T->stream) hipStreamDestroy(T->stream);
+    if (T->stream && T->ownStream) hipStreamDestroy(T->stream);
     delete T;
+    return LDSO_OK;
+}
+
+// The caller's stream instead of the tracer's own (NULL: an own one again).  The wait that ldso_trace_set_frame_pyramid queued for the frame's build stands on the
+// OLD stream, so the tracer holds no frame afterwards: set it again.
+int ldso_trace_set_stream(ldso_tracer_t *T, void *s) {
+    REQ(T, "ldso_trace_set_stream: null handle");
+    CHK(hipSetDevice(T->device));
+    RUN(swap_stream(T->stream, T->ownStream, s));
+    T->haveFrame = false;
     return LDSO_OK;
 }
 
@@ -506,7 +550,7 @@ int ldso_trace_on(ldso_tracer_t *T, int n_hosts, const float *KRKi, const float 
     CHK(hipMemcpyAsync(T->d_pose, pose.data(), pose.size() * 4, hipMemcpyHostToDevice, T->stream));
     CHK(hipMemsetAsync(T->d_counts, 0, 8 * 4, T->stream));
     if (T->n > 0) {
-        TraceArgs A;
+        TraceJob A;
         A.pts = T->d_pts; A.n = T->n; A.img = T->img; A.w = T->w; A.h = T->h;
         A.KRKi = T->d_pose; A.Kt = T->d_pose + n_hosts * 9; A.aff = T->d_pose + n_hosts * 12; A.nHosts = n_hosts;
         A.s = T->settings; A.counts = T->d_counts;
