@@ -720,6 +720,28 @@ int ldso_undist_device(ldso_undistorter_t *u, const void **dev_ptr);
 /* enable != 0: ldso_undist_frame brackets its stages with HIP events; us_out[3] (optional) = microseconds of the last profiled frame: copy of the raw
  * frame, undistortion kernel, pyramid build (this call waits for that frame) */
 int ldso_undist_profile(ldso_undistorter_t *u, int enable, float us_out[3]);
+/* A group of undistorters: Undistort::undistort<T> (Undistort.cc:357-457) of the raw frames of many sequences on one card.  n ldso_undist_frame calls are n
+ * copies, n launches and n x 2 x levels pyramid launches; a group call stages the raw frames of all active members and its job table into one pinned arena,
+ * moves them in ONE copy (1 or 2 bytes per pixel), undistorts them in ONE launch and - into a pyramid group - builds the pyramids in at most 2 x Lmax more.
+ * Every member's irradiance and every pyramid level hold the bytes ldso_undist_frame gives them.  1 <= n <= 128 undistorters on one device and one stream
+ * (ldso_undist_set_stream; checked at create and at every call); sizes, tables, calibration and settings are free per member.  An undistorter belongs to at
+ * most one group and stays usable on its own between group calls; ldso_undist_destroy of a member is refused while the group lives. */
+typedef struct ldso_undist_group ldso_undist_group_t;
+int ldso_undist_group_create(ldso_undistorter_t *const *u, int n, ldso_undist_group_t **out);
+int ldso_undist_group_destroy(ldso_undist_group_t *g);
+/* ldso_undist_frame of every active member (active: n bytes or NULL = all; entries of inactive members are read in none of the arrays): raw[i] = wOrg_i * hOrg_i
+ * pixels of bytes_per_pixel[i] (1 | 2) bytes, copied to the group's pinned arena before the call returns (the caller may reuse them at once).  Copy, kernel and
+ * the pyramid builds are enqueued on the members' stream; no host synchronisation.  pyr_group_or_null == NULL: every member's irradiance stays in its own
+ * buffer.  Otherwise a pyramid group of exactly n members on the same device: pyramid i takes the frame of undistorter i (w x h of every active pair must
+ * match), and exactly the active members' pyramids are built and get their `ready` events, as by ldso_pyr_group_make_images_device.  exposure_out (n floats or
+ * NULL): ImageAndExposure::exposure_time per active member; entries of inactive members are not written.  Afterwards ldso_undist_get / ldso_undist_device
+ * answer per member.  LDSO_E_INVALID before anything is staged or enqueued, every member's last output untouched, the message naming the member at fault:
+ * a NULL array, no active member, a NULL raw frame, a bytes_per_pixel other than 1 or 2, a member without ldso_undist_set_remap, a 16-bit frame on a
+ * calibrated path with fewer than 65536 entries of G, members no longer on one stream, a pyramid group of another length, size or device. */
+int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active /* n or NULL */, const void *const *raw /* n */, const int *bytes_per_pixel /* n */,
+                             const float *exposure /* n */, const float *factor /* n */, ldso_pyr_group_t *pyr_group_or_null, float *exposure_out /* n or NULL */);
+/* as ldso_undist_profile, of the last profiled group call: the one copy, the undistortion kernel, the grouped pyramid build */
+int ldso_undist_group_profile(ldso_undist_group_t *g, int enable, float us_out[3]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Monocular initialiser: CoarseInitializer (src/frontend/CoarseInitializer.cc, include/frontend/CoarseInitializer.h).

@@ -1375,6 +1375,58 @@ class PyramidGroup:
         return self
 
 
+class UndistorterGroup:
+    """ldso_undist_group_*: the raw frames of several undistorters (independent sequences on one device and one stream) in one copy and one launch, optionally
+    straight into a PyramidGroup of as many members.  Arguments and results are per member, in the order of `undistorters`."""
+
+    def __init__(self, undistorters):
+        self.L = lib()
+        self.undistorters = list(undistorters)          # kept alive: the group dereferences its members
+        arr = (C.c_void_p * len(self.undistorters))(*[u.h for u in self.undistorters])
+        self.h = C.c_void_p()
+        _chk(self.L.ldso_undist_group_create(arr, C.c_int(len(self.undistorters)), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.ldso_undist_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def frames(self, raws, exposures, factors=None, pyr_group: "PyramidGroup" = None, active=None):
+        """ldso_undist_group_frames: raws = one uint8 or uint16 image of the original size per member (None for an inactive one) -> float32 (n,) of the exposures
+        the reference would return, NaN for inactive members.  The frames are staged before the call returns; it does not wait for the device."""
+        n = len(self.undistorters)
+        assert len(raws) == n and len(exposures) == n and (factors is None or len(factors) == n)
+        act, idx = _active_mask(active, n)
+        ptrs = (C.c_void_p * n)()
+        bpp = np.zeros(n, np.int32)
+        keep = []
+        for i in idx:
+            if raws[i] is None:          # refused by the library, with the member's index
+                continue
+            r = np.ascontiguousarray(raws[i])
+            assert r.dtype in (np.uint8, np.uint16) and r.size == self.undistorters[i].w_org * self.undistorters[i].h_org
+            keep.append(r)
+            ptrs[i] = r.ctypes.data
+            bpp[i] = r.dtype.itemsize
+        e = np.ascontiguousarray(exposures, np.float32)
+        f = np.ones(n, np.float32) if factors is None else np.ascontiguousarray(factors, np.float32)
+        out = np.full(n, np.nan, np.float32)
+        _chk(self.L.ldso_undist_group_frames(self.h, _p(act), ptrs, _p(bpp), _p(e), _p(f), pyr_group.h if pyr_group is not None else None, _p(out)))
+        return out
+
+    def profile(self, enable=True):
+        """microseconds of the last profiled call: the one copy, the undistortion kernel, the grouped pyramid build"""
+        us = np.zeros(3, np.float32)
+        _chk(self.L.ldso_undist_group_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
+        return us
+
+
 class Initializer:
     """Monocular initialiser handle: CoarseInitializer::setFirst / trackFrame on one GPU (include/ldso_hip.h)."""
 

@@ -324,6 +324,9 @@ inline int raw_to_images(float *&d_color, const float *irradiance, int w, int h,
     return LDSO_OK;
 }
 
+// images.hip: the grouped FrameHessian::makeImages of the members `members` of g (indices into g->m) from src[k] = the level-0 irradiance of members[k] in device
+// memory, enqueued on `st` without a host wait; records the members' `ready` events and `built` flags (ldso_pyr_group_make_images*, ldso_undist_group_frames)
+int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const std::vector<const float *> &src, hipStream_t st);
 // trace.hip: the compaction of the tracer's resident immature set with keep flags that lie in device memory (ldso_ba_select_activate_tracer, act_select.hip):
 // record i stays where d_keep8[i] != 0 / d_keep32[i] == keepValue (both null: everywhere) and its host is a frame of the window.  Enqueued on `st`;
 // trace_compact_finish swaps the buffers and takes the new count once the caller has synchronised `st`.

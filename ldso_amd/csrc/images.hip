@@ -184,8 +184,9 @@ int ldso_pyr_group_destroy(ldso_pyr_group_t *g) {
     return LDSO_OK;
 }
 
-// the build of every active member from src[i] (device memory: the member's own d_color behind an upload, or the caller's image)
-static int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const std::vector<const float *> &src, hipStream_t st) {
+// the build of every active member from src[i] (device memory: the member's own d_color behind an upload or behind ldso_undist_group_frames' kernel, or the
+// caller's image); declared in ba_host.h
+extern "C++" int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const std::vector<const float *> &src, hipStream_t st) {
     const size_t nm = members.size();
     int Lmax = 0;
     for (int i : members) Lmax = std::max(Lmax, g->m[(size_t) i]->levels);

@@ -6,11 +6,14 @@
 //   k_undist_frame   one lane per output pixel: its remap entry, four taps of the raw frame (a gather: about 32 bytes per pixel from tables that are L2
 //                    resident), the pixel rule of undistort_px.h.  The 256-entry response G is staged in LDS for 8-bit frames; the 65536-entry one of
 //                    16-bit frames is read from global memory.  Passthrough (rectification "none", :450-452): the photometric output of pixel idx.
+//   k_undist_group   the same per-pixel work (undist_workgroup, defined once) for the frames of a group of undistorters: a job table, one launch
+//                    (ldso_undist_group_*: the raw frames of many sequences in one copy).
 //
 // The result is bit for bit what the reference returns (float arithmetic in its operand order, -ffp-contract=off), with the one deliberate difference that
 // undistort_px.h states: a pixel whose four taps are not all inside the source image is 0 and nothing outside the raw buffer is read, where the reference
 // over-reads one row for the table entry xxi == 0 && yyi == hOrg - 1.  benchmark_varNoise / benchmark_varBlurNoise (:376-413, :468-555) are out of scope.
 #include "ba_host.h"
+#include "group_member.h"
 #include "undistort_px.h"
 
 struct UndistArgs {
@@ -22,21 +25,63 @@ struct UndistArgs {
     float factor;
 };
 
+// Workgroup `wg` (256 lanes) of one frame: the stage of the response, the bounds test, the pixel rule.  Gs: 256 floats of LDS (BPP 1; unused for BPP 2).
+// The one definition of the per-pixel work: k_undist_frame and k_undist_group both call it.
 template <int BPP>
-__global__ __launch_bounds__(256) void k_undist_frame(UndistArgs A) {
-    __shared__ float Gs[BPP == 1 ? 256 : 1];
+__device__ __forceinline__ void undist_workgroup(const UndistArgs &A, int wg, float *Gs) {
     const float *G = A.G;
     if (BPP == 1 && A.mode != UNDIST_PLAIN) {          // block-uniform
         Gs[threadIdx.x] = A.G[threadIdx.x];
         __syncthreads();
         G = Gs;
     }
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int idx = wg * 256 + threadIdx.x;
     if (idx >= A.w * A.h) return;
     float v;
     if (A.remapX == nullptr) v = undist_photo(A.raw, BPP, idx, G, A.vig, A.mode, A.factor);
     else v = undist_px(A.raw, BPP, G, A.vig, A.mode, A.factor, A.remapX[idx], A.remapY[idx], A.wOrg, A.hOrg);
     A.out[idx] = v;
+}
+
+template <int BPP>
+__global__ __launch_bounds__(256) void k_undist_frame(UndistArgs A) {
+    __shared__ float Gs[BPP == 1 ? 256 : 1];
+    undist_workgroup<BPP>(A, (int) blockIdx.x, Gs);
+}
+
+// The frames of a group of undistorters in one launch (ldso_undist_group_*): job j is one active member's frame, a workgroup belongs to one job - wgFirst[j]
+// workgroups lie in front of job j, wgFirst[nJobs] is the grid (group_member_of).  bpp and mode are the job's, hence uniform per workgroup: an 8-bit job on a
+// calibrated path stages its response in LDS, a 16-bit one reads it from global memory, exactly as k_undist_frame<1> / <2> do.
+struct UndistJob {          // one row of the job table: UndistArgs and the pixel width; every pointer a device pointer, `raw` inside the group's device arena
+    const void *raw;
+    const float *G, *vig, *remapX, *remapY;
+    float *out;
+    int w, h, wOrg, hOrg, mode, bpp;
+    float factor;
+    int pad_;
+};
+// a row as the kernel reads it: UndistJob with its pointers typed as device memory (group_member.h: LD_GLOBAL)
+struct UndistJobDev {
+    LD_GLOBAL const void *raw;
+    LD_GLOBAL const float *G, *vig, *remapX, *remapY;
+    LD_GLOBAL float *out;
+    int w, h, wOrg, hOrg, mode, bpp;
+    float factor;
+    int pad_;
+};
+static_assert(sizeof(UndistJobDev) == sizeof(UndistJob) && sizeof(UndistJob) % 16 == 0 && offsetof(UndistJobDev, out) == offsetof(UndistJob, out) &&
+              offsetof(UndistJobDev, factor) == offsetof(UndistJob, factor), "UndistJobDev is UndistJob");
+
+__global__ __launch_bounds__(256) void k_undist_group(const UndistJob *__restrict__ jobs, const int *__restrict__ wgFirst, int nJobs) {
+    __shared__ float Gs[256];
+    const int j = group_member_of(wgFirst, nJobs, (int) blockIdx.x);
+    const UndistJobDev D = ((const UndistJobDev *) jobs)[j];
+    UndistArgs A;
+    A.raw = (const void *) D.raw; A.G = (const float *) D.G; A.vig = (const float *) D.vig; A.remapX = (const float *) D.remapX; A.remapY = (const float *) D.remapY;
+    A.out = (float *) D.out; A.w = D.w; A.h = D.h; A.wOrg = D.wOrg; A.hOrg = D.hOrg; A.mode = D.mode; A.factor = D.factor;
+    const int wg = (int) blockIdx.x - wgFirst[j];
+    if (D.bpp == 1) undist_workgroup<1>(A, wg, Gs);
+    else undist_workgroup<2>(A, wg, Gs);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -57,12 +102,69 @@ struct ldso_undistorter {
     hipEvent_t done = nullptr;          // recorded behind the last frame's kernel
     hipEvent_t ev[4] = {};
     float us[3] = {0, 0, 0};
+    const void *inGroup = nullptr;      // the ldso_undist_group this undistorter belongs to (at most one; ldso_undist_destroy refuses while set: the group dereferences its members)
 };
+
+// a group of undistorters whose frames share one copy and one launch
+struct ldso_undist_group {
+    std::vector<ldso_undistorter *> m;
+    int device = 0;
+    // one pinned arena and its device twin: [UndistJob table | wgFirst | the raw frames of the active members] go up in one copy per call.  A call does not wait on
+    // the host, so `uploaded` (recorded behind the copy) guards the pinned side against the next call's writes, and `done` (recorded behind the last launch)
+    // orders a call on another stream behind the kernel that still reads the device side
+    char *h_stage = nullptr, *d_stage = nullptr;
+    size_t stageCap = 0;
+    hipEvent_t uploaded = nullptr, done = nullptr;
+    hipStream_t lastStream = nullptr;
+    bool used = false, profile = false, profPending = false;
+    hipEvent_t ev[4] = {};
+    float us[3] = {0, 0, 0};
+};
+
+namespace {
+
+// PhotometricUndistorter::processFrame for one frame of U: the path it takes (:197-198) and ImageAndExposure::exposure_time (:203, :220, :224-225)
+struct FrameRule { int mode; float exposureOut; };
+FrameRule frame_rule(const ldso_undistorter *U, float exposure) {
+    int mode = UNDIST_PLAIN;
+    if (U->hasG && exposure > 0 && U->photometricCalibration != 0) mode = U->photometricCalibration == 2 ? UNDIST_VIGNETTE : UNDIST_RESPONSE;
+    return {mode, U->useExposure ? exposure : 1.0f};
+}
+
+// the kernel's view of one frame of U: `raw` in device memory, the irradiance into `out`
+UndistArgs frame_args(const ldso_undistorter *U, const void *d_raw, float *out, int mode, float factor) {
+    UndistArgs A;
+    const size_t n = (size_t) U->w * U->h;
+    A.raw = d_raw; A.G = U->d_G; A.vig = U->d_vig;
+    A.remapX = U->hasRemap ? U->d_remap : nullptr; A.remapY = U->hasRemap ? U->d_remap + n : nullptr;
+    A.out = out;
+    A.w = U->w; A.h = U->h; A.wOrg = U->wOrg; A.hOrg = U->hOrg; A.mode = mode; A.factor = factor;
+    return A;
+}
+
+// microseconds between the four events of a profiled call (copy, undistortion kernel, pyramid build); waits for that call
+int read_profile(const hipEvent_t ev[4], float us[3]) {
+    CHK(hipEventSynchronize(ev[3]));
+    for (int i = 0; i < 3; i++) { float ms = 0; CHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); us[i] = ms * 1e3f; }
+    return LDSO_OK;
+}
+
+inline size_t up64(size_t x) { return (x + 63) & ~(size_t) 63; }
+
+// what create and every call check of a group: the members share one device and one stream
+int group_check(ldso_undistorter *const *m, size_t n, const char *who) {
+    for (size_t i = 0; i < n; i++)
+        REQ(m[i]->device == m[0]->device && m[i]->stream == m[0]->stream, std::string(who) + ": the members of a group share one device and one stream (ldso_undist_set_stream)");
+    return LDSO_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 int ldso_undist_destroy(ldso_undistorter_t *U) {
     if (!U) return LDSO_OK;
+    REQ(U->inGroup == nullptr, "ldso_undist_destroy: the undistorter is a member of a live group (ldso_undist_group_destroy first: the group dereferences its members)");
     hipSetDevice(U->device);
     hipDeviceSynchronize();
     hipFree(U->d_remap); hipFree(U->d_G); hipFree(U->d_vig); hipFree(U->d_out); hipFree(U->d_raw);
@@ -133,8 +235,7 @@ int ldso_undist_profile(ldso_undistorter_t *U, int enable, float us_out[3]) {
     REQ(U, "ldso_undist_profile: null handle");
     if (U->profPending) {
         CHK(hipSetDevice(U->device));
-        CHK(hipEventSynchronize(U->ev[3]));
-        for (int i = 0; i < 3; i++) { float ms = 0; CHK(hipEventElapsedTime(&ms, U->ev[i], U->ev[i + 1])); U->us[i] = ms * 1e3f; }
+        RUN(read_profile(U->ev, U->us));
         U->profPending = false;
     }
     U->profile = enable != 0;
@@ -146,9 +247,8 @@ int ldso_undist_frame(ldso_undistorter_t *U, const void *raw, int bytes_per_pixe
     REQ(U && raw && (bytes_per_pixel == 1 || bytes_per_pixel == 2), "ldso_undist_frame: bad arguments (bytes_per_pixel is 1 or 2)");
     REQ(U->remapSet, "ldso_undist_frame: ldso_undist_set_remap has not been called");
     REQ(!pyr || (pyr->device == U->device && pyr->w == U->w && pyr->h == U->h), "ldso_undist_frame: pyramid does not match the undistorter (device, size)");
-    // PhotometricUndistorter::processFrame :197-198
-    int mode = UNDIST_PLAIN;
-    if (U->hasG && exposure > 0 && U->photometricCalibration != 0) mode = U->photometricCalibration == 2 ? UNDIST_VIGNETTE : UNDIST_RESPONSE;
+    const FrameRule rule = frame_rule(U, exposure);
+    const int mode = rule.mode;
     REQ(mode == UNDIST_PLAIN || bytes_per_pixel == 1 || U->GDepth >= 65536, "ldso_undist_frame: a 16-bit frame needs a response of 65536 entries");
     CHK(hipSetDevice(U->device));
     hipStream_t st = U->stream;
@@ -162,12 +262,8 @@ int ldso_undist_frame(ldso_undistorter_t *U, const void *raw, int bytes_per_pixe
     CHK(hipMemcpyAsync(U->d_raw, U->h_raw[t], bytes, hipMemcpyHostToDevice, st));
     CHK(hipEventRecord(U->copied[t], st));
     if (prof) CHK(hipEventRecord(U->ev[1], st));
-    UndistArgs A;
+    const UndistArgs A = frame_args(U, U->d_raw, pyr ? pyr->d_color : U->d_out, mode, factor);
     const size_t n = (size_t) U->w * U->h;
-    A.raw = U->d_raw; A.G = U->d_G; A.vig = U->d_vig;
-    A.remapX = U->hasRemap ? U->d_remap : nullptr; A.remapY = U->hasRemap ? U->d_remap + n : nullptr;
-    A.out = pyr ? pyr->d_color : U->d_out;
-    A.w = U->w; A.h = U->h; A.wOrg = U->wOrg; A.hOrg = U->hOrg; A.mode = mode; A.factor = factor;
     const dim3 grid((unsigned) ((n + 255) / 256));
     if (bytes_per_pixel == 1) hipLaunchKernelGGL(k_undist_frame<1>, grid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL(k_undist_frame<2>, grid, dim3(256), 0, st, A);
@@ -181,7 +277,7 @@ int ldso_undist_frame(ldso_undistorter_t *U, const void *raw, int bytes_per_pixe
         pyr->built = true;
     }
     if (prof) { CHK(hipEventRecord(U->ev[3], st)); U->profPending = true; }
-    if (exposure_out) *exposure_out = U->useExposure ? exposure : 1.0f;          // :203, :220, :224-225
+    if (exposure_out) *exposure_out = rule.exposureOut;
     return LDSO_OK;
 }
 
@@ -196,6 +292,137 @@ int ldso_undist_get(ldso_undistorter_t *U, float *irradiance_out) {
 int ldso_undist_device(ldso_undistorter_t *U, const void **dev_ptr) {
     REQ(U && dev_ptr, "ldso_undist_device: bad arguments");
     *dev_ptr = U->last;
+    return LDSO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ldso_undist_group_*: Undistort::undistort<T> (Undistort.cc:357-457) of the raw frames of several sequences.  One ldso_undist_frame is a copy, a launch and - into
+// a pyramid - 2 x levels more; the group stages every active member's raw frame and the job table into one pinned arena, moves it in one copy, undistorts in one
+// launch (k_undist_group) and hands the members' pyramids to the grouped build (pyr_group_build, images.hip): 1 + 2 x Lmax launches and one copy whatever n.
+// ---------------------------------------------------------------------------------------------------------
+
+int ldso_undist_group_destroy(ldso_undist_group_t *g) {
+    if (!g) return LDSO_OK;
+    hipSetDevice(g->device);
+    if (g->used) hipEventSynchronize(g->done);          // the last call's kernel reads the device arena
+    for (ldso_undistorter *U : g->m) if (U->inGroup == g) U->inGroup = nullptr;
+    if (g->uploaded) hipEventDestroy(g->uploaded);
+    if (g->done) hipEventDestroy(g->done);
+    for (hipEvent_t e : g->ev) if (e) hipEventDestroy(e);
+    if (g->h_stage) hipHostFree(g->h_stage);
+    if (g->d_stage) hipFree(g->d_stage);
+    delete g;
+    return LDSO_OK;
+}
+
+int ldso_undist_group_create(ldso_undistorter_t *const *u, int n, ldso_undist_group_t **out) {
+    REQ(u && out && n >= 1 && n <= 128, "ldso_undist_group_create: bad arguments (1 <= n <= 128 undistorters)");
+    for (int i = 0; i < n; i++) {
+        REQ(u[i], "ldso_undist_group_create: null undistorter");
+        REQ(u[i]->inGroup == nullptr, "ldso_undist_group_create: an undistorter belongs to at most one group at a time");
+        for (int k = 0; k < i; k++) REQ(u[k] != u[i], "ldso_undist_group_create: the same undistorter twice");
+    }
+    RUN(group_check(u, (size_t) n, "ldso_undist_group_create"));
+    CHK(hipSetDevice(u[0]->device));
+    ldso_undist_group *g = new ldso_undist_group();
+    g->device = u[0]->device;
+    auto body = [&]() -> int {
+        CHK(hipEventCreateWithFlags(&g->uploaded, hipEventDisableTiming));
+        CHK(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
+        for (hipEvent_t &e : g->ev) CHK(hipEventCreate(&e));
+        return LDSO_OK;
+    };
+    RUN(finish_create(body(), g, out, ldso_undist_group_destroy));
+    g->m.assign(u, u + n);
+    for (ldso_undistorter *U : g->m) U->inGroup = g;
+    return LDSO_OK;
+}
+
+int ldso_undist_group_profile(ldso_undist_group_t *g, int enable, float us_out[3]) {
+    REQ(g, "ldso_undist_group_profile: null group");
+    if (g->profPending) {
+        CHK(hipSetDevice(g->device));
+        RUN(read_profile(g->ev, g->us));
+        g->profPending = false;
+    }
+    g->profile = enable != 0;
+    if (us_out) for (int i = 0; i < 3; i++) us_out[i] = g->us[i];
+    return LDSO_OK;
+}
+
+int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active, const void *const *raw, const int *bytes_per_pixel, const float *exposure, const float *factor,
+                             ldso_pyr_group_t *pg, float *exposure_out) {
+    static const char who[] = "ldso_undist_group_frames";
+    REQ(g && raw && bytes_per_pixel && exposure && factor, std::string(who) + ": null argument");
+    RUN(group_check(g->m.data(), g->m.size(), who));
+    const int n = (int) g->m.size();
+    REQ(!pg || ((int) pg->m.size() == n && pg->device == g->device), std::string(who) + ": the pyramid group does not match the undistorter group (device, number of members)");
+    // every refusal comes before anything is staged or enqueued; the arena is [UndistJob table | wgFirst | the frames of the active members]
+    struct Plan { int i, bpp; FrameRule rule; size_t off, bytes; };
+    std::vector<Plan> plan;
+    std::vector<int> members;
+    for (int i = 0; i < n; i++) {
+        if (active && !active[i]) continue;
+        const ldso_undistorter *U = g->m[(size_t) i];
+        const std::string mem = std::string(who) + ": member " + std::to_string(i);
+        REQ(raw[i], mem + ": null raw frame");
+        REQ(bytes_per_pixel[i] == 1 || bytes_per_pixel[i] == 2, mem + ": bytes_per_pixel is 1 or 2");
+        REQ(U->remapSet, mem + ": ldso_undist_set_remap has not been called");
+        const FrameRule rule = frame_rule(U, exposure[i]);
+        REQ(rule.mode == UNDIST_PLAIN || bytes_per_pixel[i] == 1 || U->GDepth >= 65536, mem + ": a 16-bit frame needs a response of 65536 entries");
+        REQ(!pg || (pg->m[(size_t) i]->w == U->w && pg->m[(size_t) i]->h == U->h), mem + ": pyramid does not match the undistorter (size)");
+        plan.push_back({i, bytes_per_pixel[i], rule, 0, (size_t) U->wOrg * U->hOrg * bytes_per_pixel[i]});
+        members.push_back(i);
+    }
+    REQ(!plan.empty(), std::string(who) + ": no active member");
+    const size_t nj = plan.size(), offF = nj * sizeof(UndistJob);
+    size_t total = up64(offF + (nj + 1) * 4);
+    for (Plan &p : plan) { p.off = total; total = up64(total + p.bytes); }          // every frame 64-byte aligned
+    CHK(hipSetDevice(g->device));
+    hipStream_t st = g->m[0]->stream;
+    // the arena is reused without a host wait at the end of a call: the pinned side is free once the last upload has been read, the device side once the last
+    // call's kernel is through - in stream order on the same stream, behind `done` on another (pyr_group_build's rule)
+    if (g->used) CHK(hipEventSynchronize(g->uploaded));
+    if (g->used && (total > g->stageCap || st != g->lastStream)) CHK(hipStreamWaitEvent(st, g->done, 0));
+    if (g->used && total > g->stageCap) CHK(hipEventSynchronize(g->done));
+    RUN(grow_arena(g->h_stage, g->d_stage, g->stageCap, total, 2, st));
+    UndistJob *hJ = (UndistJob *) g->h_stage;
+    int *hF = (int *) (g->h_stage + offF);
+    int wgs = 0;
+    for (size_t j = 0; j < nj; j++) {
+        const Plan &p = plan[j];
+        const ldso_undistorter *U = g->m[(size_t) p.i];
+        memcpy(g->h_stage + p.off, raw[p.i], p.bytes);
+        const UndistArgs A = frame_args(U, g->d_stage + p.off, pg ? pg->m[(size_t) p.i]->d_color : U->d_out, p.rule.mode, factor[p.i]);
+        UndistJob &J = hJ[j];
+        J.raw = A.raw; J.G = A.G; J.vig = A.vig; J.remapX = A.remapX; J.remapY = A.remapY; J.out = A.out;
+        J.w = A.w; J.h = A.h; J.wOrg = A.wOrg; J.hOrg = A.hOrg; J.mode = A.mode; J.bpp = p.bpp; J.factor = A.factor; J.pad_ = 0;
+        hF[j] = wgs;
+        wgs += (int) (((size_t) U->w * U->h + 255) / 256);
+    }
+    hF[nj] = wgs;
+    const bool prof = g->profile;
+    if (prof) CHK(hipEventRecord(g->ev[0], st));
+    CHK(hipMemcpyAsync(g->d_stage, g->h_stage, total, hipMemcpyHostToDevice, st));
+    CHK(hipEventRecord(g->uploaded, st));
+    if (prof) CHK(hipEventRecord(g->ev[1], st));
+    hipLaunchKernelGGL(k_undist_group, dim3((unsigned) wgs), dim3(256), 0, st, (const UndistJob *) g->d_stage, (const int *) (g->d_stage + offF), (int) nj);
+    CHK(hipGetLastError());
+    CHK(hipEventRecord(g->done, st));
+    g->used = true; g->lastStream = st;
+    if (prof) CHK(hipEventRecord(g->ev[2], st));
+    for (size_t j = 0; j < nj; j++) {
+        ldso_undistorter *U = g->m[(size_t) plan[j].i];
+        U->last = hJ[j].out;
+        CHK(hipEventRecord(U->done, st));
+    }
+    if (pg) {
+        std::vector<const float *> src;
+        for (int i : members) src.push_back(pg->m[(size_t) i]->d_color);
+        RUN(pyr_group_build(pg, members, src, st));
+    }
+    if (prof) { CHK(hipEventRecord(g->ev[3], st)); g->profPending = true; }
+    if (exposure_out) for (const Plan &p : plan) exposure_out[p.i] = p.rule.exposureOut;
     return LDSO_OK;
 }
 
