@@ -1114,20 +1114,30 @@ def coop_width(count, num_cu) -> int:
     return G.value
 
 
-class TrackerGroup:
-    """ldso_tr_group_*: the tracks of several trackers (independent sequences on one device and one stream) in one launch.  Arguments and results are per member,
-    in the order of `trackers`; the members stay usable on their own between group calls."""
+def _active_mask(active, n):
+    """an active mask as the group entries take it: (None, all indices) or (n bytes, the indices set)"""
+    if active is None:
+        return None, list(range(n))
+    act = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
+    assert act.shape == (n,)
+    return act, [i for i in range(n) if act[i]]
 
-    def __init__(self, trackers):
+
+class _Group:
+    """what the four groups share: the members are kept alive (the group dereferences them), the handle comes from the entry named by _create and goes back
+    through the one named by _destroy - unchecked, unlike a member's close: a group's destroy has nothing that refuses it"""
+    _create = _destroy = None
+
+    def __init__(self, members):
         self.L = lib()
-        self.trackers = list(trackers)          # kept alive: the group dereferences its members
-        arr = (C.c_void_p * len(self.trackers))(*[t.h for t in self.trackers])
+        self.members = list(members)
+        arr = (C.c_void_p * len(self.members))(*[m.h for m in self.members])
         self.h = C.c_void_p()
-        _chk(self.L.ldso_tr_group_create(arr, C.c_int(len(self.trackers)), C.byref(self.h)))
+        _chk(getattr(self.L, self._create)(arr, C.c_int(len(self.members)), C.byref(self.h)))
 
     def close(self):
         if self.h:
-            self.L.ldso_tr_group_destroy(self.h)          # unchecked, unlike Tracker.close: a group's destroy has nothing that refuses it
+            getattr(self.L, self._destroy)(self.h)
             self.h = None
 
     def __del__(self):
@@ -1136,18 +1146,21 @@ class TrackerGroup:
         except Exception:
             pass
 
+
+class TrackerGroup(_Group):
+    """ldso_tr_group_*: the tracks of several trackers (independent sequences on one device and one stream) in one launch.  Arguments and results are per member,
+    in the order of `trackers`; the members stay usable on their own between group calls."""
+
+    _create, _destroy = "ldso_tr_group_create", "ldso_tr_group_destroy"
+
+    def __init__(self, trackers):
+        super().__init__(trackers)
+        self.trackers = self.members
+
     def coop_width(self, n_jobs) -> int:
         G = C.c_int()
         _chk(self.L.ldso_tr_group_coop_width(self.h, C.c_int(n_jobs), C.byref(G)))
         return G.value
-
-    def _active(self, active):
-        n = len(self.trackers)
-        if active is None:
-            return None, list(range(n))
-        act = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
-        assert act.shape == (n,)
-        return act, [i for i in range(n) if act[i]]
 
     def track(self, Ts, affs, coarsest, min_res=None, active=None):
         """ldso_tr_group_track -> per member the dict of Tracker.track (None for an inactive member).  Ts: n poses (4x4 or 3x4), affs: n (a, b) pairs, coarsest: n levels
@@ -1158,7 +1171,7 @@ class TrackerGroup:
         co = np.ascontiguousarray(np.broadcast_to(np.asarray(coarsest, np.int32), (n,)), np.int32)
         mr = None if min_res is None else np.ascontiguousarray(np.broadcast_to(np.asarray(min_res, np.float64), (n, 5)), np.float64)
         lr = np.zeros((n, 5)); fl = np.zeros((n, 3)); ok = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
-        act, idx = self._active(active)
+        act, idx = _active_mask(active, n)
         _chk(self.L.ldso_tr_group_track(self.h, _p(act), _p(T), _p(ab), _p(co), _p(mr), _p(lr), _p(fl), _p(ok), _p(it)))
         out = [None] * n
         for i in idx:
@@ -1176,7 +1189,7 @@ class TrackerGroup:
         pv = np.ascontiguousarray(np.broadcast_to(np.asarray(poses_valid).astype(np.int32), (n,)), np.int32)
         res4 = np.zeros((n, 4)); w2c = np.zeros((n, 3, 4)); aff_out = np.zeros((n, 2), np.float32)
         tries = np.full(n, -1, np.int32); good = np.full(n, -1, np.int32)
-        act, idx = self._active(active)
+        act, idx = _active_mask(active, n)
         _chk(self.L.ldso_tr_group_track_new_coarse(self.h, _p(act), _p(P[0]), _p(P[1]), _p(P[2]), _p(pv), _p(aff), _p(rmse), _p(thr), _p(res4), _p(w2c), _p(aff_out),
                                                    _p(tries), _p(good)))
         out = [None] * n
@@ -1274,36 +1287,15 @@ class Tracer:
         _chk(self.L.ldso_trace_set_stream(self.h, C.c_void_p(stream_ptr)))
 
 
-def _active_mask(active, n):
-    """an active mask as the group entries take it: (None, all indices) or (n bytes, the indices set)"""
-    if active is None:
-        return None, list(range(n))
-    act = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
-    assert act.shape == (n,)
-    return act, [i for i in range(n) if act[i]]
-
-
-class TracerGroup:
+class TracerGroup(_Group):
     """ldso_trace_group_*: the traces of several tracers (independent sequences on one device and one stream) in one launch.  Arguments and results are per member,
     in the order of `tracers`; the members stay usable on their own between group calls."""
 
+    _create, _destroy = "ldso_trace_group_create", "ldso_trace_group_destroy"
+
     def __init__(self, tracers):
-        self.L = lib()
-        self.tracers = list(tracers)          # kept alive: the group dereferences its members
-        arr = (C.c_void_p * len(self.tracers))(*[t.h for t in self.tracers])
-        self.h = C.c_void_p()
-        _chk(self.L.ldso_trace_group_create(arr, C.c_int(len(self.tracers)), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.ldso_trace_group_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(tracers)
+        self.tracers = self.members
 
     def trace_on(self, poses, active=None):
         """ldso_trace_group_on -> counts (n, 6) int32; rows of inactive members stay zero.  poses: one (KRKi, Kt, aff) triple per member (None for an inactive one)."""
@@ -1325,26 +1317,14 @@ class TracerGroup:
         return counts
 
 
-class PyramidGroup:
+class PyramidGroup(_Group):
     """ldso_pyr_group_*: FrameHessian::makeImages of several pyramids (one device; sizes and level counts are free) in at most 2 x Lmax launches per call."""
 
+    _create, _destroy = "ldso_pyr_group_create", "ldso_pyr_group_destroy"
+
     def __init__(self, pyramids):
-        self.L = lib()
-        self.pyramids = list(pyramids)          # kept alive: the group dereferences its members
-        arr = (C.c_void_p * len(self.pyramids))(*[p.h for p in self.pyramids])
-        self.h = C.c_void_p()
-        _chk(self.L.ldso_pyr_group_create(arr, C.c_int(len(self.pyramids)), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.ldso_pyr_group_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(pyramids)
+        self.pyramids = self.members
 
     def make_images(self, images, stream=None, active=None):
         """ldso_pyr_group_make_images: images = one irradiance array per member (None for an inactive one), enqueued on `stream`; like Pyramid.make_images it does not wait.
@@ -1375,27 +1355,15 @@ class PyramidGroup:
         return self
 
 
-class UndistorterGroup:
+class UndistorterGroup(_Group):
     """ldso_undist_group_*: the raw frames of several undistorters (independent sequences on one device and one stream) in one copy and one launch, optionally
     straight into a PyramidGroup of as many members.  Arguments and results are per member, in the order of `undistorters`."""
 
+    _create, _destroy = "ldso_undist_group_create", "ldso_undist_group_destroy"
+
     def __init__(self, undistorters):
-        self.L = lib()
-        self.undistorters = list(undistorters)          # kept alive: the group dereferences its members
-        arr = (C.c_void_p * len(self.undistorters))(*[u.h for u in self.undistorters])
-        self.h = C.c_void_p()
-        _chk(self.L.ldso_undist_group_create(arr, C.c_int(len(self.undistorters)), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.L.ldso_undist_group_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(undistorters)
+        self.undistorters = self.members
 
     def frames(self, raws, exposures, factors=None, pyr_group: "PyramidGroup" = None, active=None):
         """ldso_undist_group_frames: raws = one uint8 or uint16 image of the original size per member (None for an inactive one) -> float32 (n,) of the exposures

@@ -2,9 +2,9 @@
 // inputs, results and scratch lie in the call's arenas, and the host side of the two copies.  The single-window entries and the batched ones share every line of it.
 // No HIP header: it compiles with a plain C++ compiler (tests/test_activation_stage_cpu.py runs it under the sanitizers).
 #pragma once
-#include "host_only.h"
+#include "group_stage.h"          // align_up
 
-inline size_t up16(size_t x) { return (x + 15) / 16 * 16; }
+inline size_t up16(size_t x) { return align_up(x, 16); }
 
 // One window's job.  resident: the candidates are a tracer's records where they lie on the device and the seeds the points of the resident window - nothing of either
 // is uploaded, `points` / `myType` / `seeds` stay null.  records: the activation follows, its records come down behind the selected list.

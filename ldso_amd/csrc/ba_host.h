@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "host_only.h"          // ldso_set_error, REQ, RUN
+#include "group_stage.h"        // align_up; membership, active list, prefix table and arena layouts of the grouped calls
 #include "ba_dev.h"
 #include "pyramid.h"
 #include "ba_solve.h"
@@ -239,27 +240,30 @@ struct ldso_tracer {
     bool haveFrame = false;
 };
 
+// The staging arena of a grouped call (group_stage.h: the layouts): one pinned arena and its device twin, grown on demand.  The tracker and tracer groups end every
+// call with a host wait, so the next call finds both sides free.
+struct GroupArena { char *h_stage = nullptr, *d_stage = nullptr; size_t stageCap = 0; };
+// The same for a group whose calls do NOT wait on the host (pyramid and undistorter groups).  The pinned side is free once the last upload has been read: `uploaded`,
+// recorded behind the copy, guards it against the next call's writes.  The device side is free once the last call's kernels are through: in stream order on the
+// same stream, behind `done` (recorded behind the last launch) on another.  A replacement of the pair waits for `done` on the host.
+struct AsyncArena : GroupArena {
+    hipEvent_t uploaded = nullptr, done = nullptr;
+    hipStream_t lastStream = nullptr;
+    bool used = false;
+};
+
 // a group of tracers whose traces share one launch (trace_group.hip)
 struct ldso_trace_group {
     std::vector<ldso_tracer *> m;
     int device = 0;
-    // one pinned arena and its device twin (grow_arena): [pose blocks of the active members | TraceJob table | first | count rows] go up in one copy, the count rows come down in one
-    char *h_stage = nullptr, *d_stage = nullptr;
-    size_t stageCap = 0;
+    GroupArena arena;
 };
 
 // a group of pyramids whose builds share launches (images.hip)
 struct ldso_pyr_group {
     std::vector<ldso_pyramid *> m;
     int device = 0;
-    // one pinned arena and its device twin: the job tables and workgroup prefixes of every level go up in one copy per call.  A call does not wait on the host, so
-    // `uploaded` (recorded behind the copy) guards the pinned side against the next call's writes, and `done` (recorded behind the last launch) orders a call on
-    // another stream behind the kernels that still read the device side
-    char *h_stage = nullptr, *d_stage = nullptr;
-    size_t stageCap = 0;
-    hipEvent_t uploaded = nullptr, done = nullptr;
-    hipStream_t lastStream = nullptr;
-    bool used = false;
+    AsyncArena arena;
 };
 
 #pragma GCC visibility push(hidden)
@@ -308,6 +312,36 @@ inline int grow_arena(char *&h, char *&d, size_t &cap, size_t need, size_t slack
     CHK(hipMalloc((void **) &d, room));
     cap = room;
     return LDSO_OK;
+}
+// the arena of a group with room for `need` bytes; `st` = the stream of the group's calls
+inline int group_arena_grow(GroupArena &A, size_t need, hipStream_t st) { return grow_arena(A.h_stage, A.d_stage, A.stageCap, need, 2, st); }
+inline void group_arena_free(GroupArena &A) {          // at destroy
+    if (A.h_stage) (void) hipHostFree(A.h_stage);
+    if (A.d_stage) (void) hipFree(A.d_stage);
+}
+inline int async_arena_create(AsyncArena &A) {
+    CHK(hipEventCreateWithFlags(&A.uploaded, hipEventDisableTiming));
+    CHK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
+    return LDSO_OK;
+}
+// both sides of the arena free for a call of `total` bytes on `st` (the rule beside AsyncArena), and large enough
+inline int async_arena_acquire(AsyncArena &A, size_t total, hipStream_t st) {
+    if (A.used) CHK(hipEventSynchronize(A.uploaded));
+    if (A.used && (total > A.stageCap || st != A.lastStream)) CHK(hipStreamWaitEvent(st, A.done, 0));
+    if (A.used && total > A.stageCap) CHK(hipEventSynchronize(A.done));
+    return group_arena_grow(A, total, st);
+}
+inline int async_arena_mark_uploaded(AsyncArena &A, hipStream_t st) { CHK(hipEventRecord(A.uploaded, st)); return LDSO_OK; }          // behind the call's one copy
+inline int async_arena_mark_done(AsyncArena &A, hipStream_t st) {          // behind the last launch that reads the device side
+    CHK(hipEventRecord(A.done, st));
+    A.used = true; A.lastStream = st;
+    return LDSO_OK;
+}
+inline void async_arena_release(AsyncArena &A) {          // at destroy
+    if (A.used) (void) hipEventSynchronize(A.done);          // the last call's kernels read the device side
+    if (A.uploaded) (void) hipEventDestroy(A.uploaded);
+    if (A.done) (void) hipEventDestroy(A.done);
+    group_arena_free(A);
 }
 // A resident pyramid handed to a consumer `what` (named in the message): it holds an image and matches in device, size and levels; then `st` waits for its build.
 inline int pyramid_wait(const ldso_pyramid *pyr, int device, int w, int h, int minLevels, hipStream_t st, const char *who, const char *what) {

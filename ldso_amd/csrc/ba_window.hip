@@ -145,15 +145,14 @@ __global__ __launch_bounds__(256) void k_point_stats_batch(const WinDelta *__res
     point_stats_one(W.pt0, W.pt1, W.mrb, W.ngr, i);
 }
 
-static inline size_t A16(size_t b) { return (b + 15) & ~(size_t) 15; }
 // host side of the arena: reserve (16-byte aligned) room, remember where it goes
 struct WinStage {
     char *base, *devBase; size_t cap, used; WinXfer *tab; int n, maxN;
     // over a pinned arena and its device twin, with the transfer table (room for maxN entries; a batch brings a size of its own) at its head
-    WinStage(char *h, char *d, size_t cap_, int maxN_ = LD_XFER_MAX) : base(h), devBase(d), cap(cap_), used(A16((size_t) maxN_ * sizeof(WinXfer))), tab(reinterpret_cast<WinXfer *>(h)), n(0), maxN(maxN_) {}
+    WinStage(char *h, char *d, size_t cap_, int maxN_ = LD_XFER_MAX) : base(h), devBase(d), cap(cap_), used(align_up((size_t) maxN_ * sizeof(WinXfer), 16)), tab(reinterpret_cast<WinXfer *>(h)), n(0), maxN(maxN_) {}
     template <class T> T *dev(T *hp) const { return reinterpret_cast<T *>(devBase + (reinterpret_cast<const char *>(hp) - base)); }          // where staged data lies on the device
     template <class T> T *put(T *dst, size_t count) {          // room for `count` elements that will land at dst; returns where to write them
-        const size_t bytes = (count * sizeof(T) + 15) & ~(size_t) 15;
+        const size_t bytes = align_up(count * sizeof(T), 16);
         if (n >= maxN || used + bytes > cap) return nullptr;
         T *p = reinterpret_cast<T *>(base + used);
         if (count) { tab[n].dst = dst; tab[n].src = used; tab[n].words = count * sizeof(T) / 4; n++; }
@@ -161,7 +160,7 @@ struct WinStage {
         return p;
     }
     template <class T> T *raw(size_t count) {          // room without a destination (operands of k_win_rebuild)
-        const size_t bytes = (count * sizeof(T) + 15) & ~(size_t) 15;
+        const size_t bytes = align_up(count * sizeof(T), 16);
         if (used + bytes > cap) return nullptr;
         T *p = reinterpret_cast<T *>(base + used);
         used += bytes;
@@ -356,11 +355,11 @@ static int check_window_delta(const ldso_ba *H, const char *who_, const ldso_win
 // arena bytes of one window: the delta (crosses PCIe) and the image (written on the device)
 static size_t delta_bytes(const ldso_win_job_t &J) {
     const size_t F = (size_t) J.F, P = (size_t) J.P, nf = (size_t) J.n_fresh, nr = (size_t) J.n_fresh_res;
-    return A16(F * 4) + 2 * A16(P * 4) + A16((P + 1) * 4) + A16(nf * sizeof(ldso_point_t)) + A16(nr * sizeof(ldso_residual_t)) + A16((nf + 1) * 4) + 2 * A16(nf * 4);
+    return align_up(F * 4, 16) + 2 * align_up(P * 4, 16) + align_up((P + 1) * 4, 16) + align_up(nf * sizeof(ldso_point_t), 16) + align_up(nr * sizeof(ldso_residual_t), 16) + align_up((nf + 1) * 4, 16) + 2 * align_up(nf * 4, 16);
 }
 static size_t image_bytes(int F, int P_) {
     const size_t P = (size_t) P_, PS = P * (size_t) ((F + 7) / 8 * 8);
-    return A16(P * sizeof(PtGeo)) + A16(P * 8 * sizeof(PtCw)) + A16(P * 4) + A16(PS * sizeof(SlotTab)) + A16(PS * sizeof(SlotRec)) + 2 * A16(P * 4);
+    return align_up(P * sizeof(PtGeo), 16) + align_up(P * 8 * sizeof(PtCw), 16) + align_up(P * 4, 16) + align_up(PS * sizeof(SlotTab), 16) + align_up(PS * sizeof(SlotRec), 16) + 2 * align_up(P * 4, 16);
 }
 // what k_win_rebuild reads of the resident window: taken BEFORE the handle adopts the new one
 static void delta_resident(const ldso_ba *H, WinDelta &Wd) {
@@ -468,7 +467,7 @@ int ldso_ba_set_window(ldso_ba_t *H, int F, const int32_t *image_slot, int P, co
     size_t nLin = 0;
     for (int i = 0; i < R; i++) nLin += res[i].is_linearized ? 1 : 0;
     REQ(nLin == 0 || (linJ && lin_rtz), "ldso_ba_set_window: linearised residual without linJ / lin_res_toZeroF");
-    RUN(handle_stage(H, A16(LD_XFER_MAX * sizeof(WinXfer)) + image_bytes(F, P) + A16(nLin * sizeof(ldso_rawjac_t)) + A16(nLin * 32) + 64));
+    RUN(handle_stage(H, align_up(LD_XFER_MAX * sizeof(WinXfer), 16) + image_bytes(F, P) + align_up(nLin * sizeof(ldso_rawjac_t), 16) + align_up(nLin * 32, 16) + 64));
     WinStage W(H->h_stage, H->d_stage, H->stageCap);
     WinImage I;
     REQ(stage_image(H, W, false, I), "ldso_ba_set_window: staging arena too small or upload table overflow (internal)");
@@ -563,7 +562,7 @@ int ldso_ba_update_window(ldso_ba_t *H, int F, const int32_t *image_slot, const 
     RUN(check_window_delta(H, "ldso_ba_update_window", J, Pl));
     CHK(hipSetDevice(H->device));
     // ---- arena: [table | delta | image]; only table + delta cross PCIe ----
-    RUN(handle_stage(H, A16(LD_XFER_MAX * sizeof(WinXfer)) + delta_bytes(J) + image_bytes(F, P) + 64));
+    RUN(handle_stage(H, align_up(LD_XFER_MAX * sizeof(WinXfer), 16) + delta_bytes(J) + image_bytes(F, P) + 64));
     WinStage W(H->h_stage, H->d_stage, H->stageCap);
     WinDelta Wd;
     delta_resident(H, Wd);
@@ -627,11 +626,11 @@ int ldso_ba_batch_update_windows(ldso_ba_batch_t *Bt, const ldso_win_job_t *jobs
     CHK(hipSetDevice(H0->device));
     // ---- the arena ----
     const int maxEntries = nPart * LD_BATCH_XFER_PER_WIN;
-    const size_t headBytes = A16((size_t) maxEntries * sizeof(WinXfer)) + A16(((size_t) maxEntries + 1) * 4) + A16((size_t) nPart * sizeof(WinDelta));
+    const size_t headBytes = align_up((size_t) maxEntries * sizeof(WinXfer), 16) + align_up(((size_t) maxEntries + 1) * 4, 16) + align_up((size_t) nPart * sizeof(WinDelta), 16);
     size_t up = headBytes, img = 64;
     for (int i : part) {
         const ldso_ba *H = Bt->h[(size_t) i];
-        up += delta_bytes(jobs[i]) + 3 * A16((size_t) H->maxChunks * 4) + A16(((size_t) jobs[i].F + 1) * 4) + A16((size_t) H->maxChunks * sizeof(BatchBlock));
+        up += delta_bytes(jobs[i]) + 3 * align_up((size_t) H->maxChunks * 4, 16) + align_up(((size_t) jobs[i].F + 1) * 4, 16) + align_up((size_t) H->maxChunks * sizeof(BatchBlock), 16);
         img += image_bytes(jobs[i].F, jobs[i].P);
     }
     RUN(batch_stage(Bt, up, img));          // (may wait for the stream and replace the arena: nothing of the windows lives there)
@@ -710,11 +709,11 @@ int ldso_ba_batch_set_frames(ldso_ba_batch_t *Bt, const ldso_frames_job_t *jobs)
         const ldso_ba *H = Bt->h[(size_t) i];
         REQ(jobs[i].calib && H->D.P > 0 && H->D.F > 0, "ldso_ba_batch_set_frames: a window that takes part needs its calibration and a resident window");
         part.push_back(i);
-        up += A16((size_t) H->D.F * sizeof(DevFrame)) + A16(sizeof(DevCalib)) + A16((size_t) H->D.n * H->D.n * 8) + A16((size_t) H->D.n * 8);
+        up += align_up((size_t) H->D.F * sizeof(DevFrame), 16) + align_up(sizeof(DevCalib), 16) + align_up((size_t) H->D.n * H->D.n * 8, 16) + align_up((size_t) H->D.n * 8, 16);
     }
     if (part.empty()) return LDSO_OK;
     const int nPart = (int) part.size(), maxEntries = 4 * nPart;
-    up += A16((size_t) maxEntries * sizeof(WinXfer)) + A16(((size_t) maxEntries + 1) * 4) + A16((size_t) nPart * sizeof(BatchItem)) + 64;
+    up += align_up((size_t) maxEntries * sizeof(WinXfer), 16) + align_up(((size_t) maxEntries + 1) * 4, 16) + align_up((size_t) nPart * sizeof(BatchItem), 16) + 64;
     CHK(hipSetDevice(H0->device));
     RUN(batch_stage(Bt, up, 0));
     WinStage W(Bt->h_stage, Bt->d_stage, Bt->stageCap, maxEntries);

@@ -149,37 +149,25 @@ int ldso_pyr_make_images(ldso_pyramid_t *P, const float *irradiance, void *hip_s
 // of all levels in one upload.
 // ---------------------------------------------------------------------------------------------------------
 
+static constexpr GroupRule PYR_RULE = {"a pyramid", nullptr, GROUP_MAX_MEMBERS};          // no stream of their own: it is an argument of each call
+static_assert(sizeof(ImgJob) == 40, "the row of pyr_group_layout as tests/test_group_stage_cpu.py sizes it");
+
 int ldso_pyr_group_create(ldso_pyramid_t *const *pyramids, int n, ldso_pyr_group_t **out) {
-    REQ(pyramids && out && n >= 1 && n <= 128, "ldso_pyr_group_create: bad arguments (1 <= n <= 128 pyramids)");
-    for (int i = 0; i < n; i++) {
-        REQ(pyramids[i], "ldso_pyr_group_create: null pyramid");
-        REQ(pyramids[i]->inGroup == nullptr, "ldso_pyr_group_create: a pyramid belongs to at most one group at a time");
-        for (int k = 0; k < i; k++) REQ(pyramids[k] != pyramids[i], "ldso_pyr_group_create: the same pyramid twice");
-        REQ(pyramids[i]->device == pyramids[0]->device, "ldso_pyr_group_create: the members of a group share one device");
-    }
+    RUN(group_admit(pyramids, n, out, "ldso_pyr_group_create", PYR_RULE));
     CHK(hipSetDevice(pyramids[0]->device));
     ldso_pyr_group *g = new ldso_pyr_group();
     g->device = pyramids[0]->device;
-    auto body = [&]() -> int {
-        CHK(hipEventCreateWithFlags(&g->uploaded, hipEventDisableTiming));
-        CHK(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
-        return LDSO_OK;
-    };
-    RUN(finish_create(body(), g, out, ldso_pyr_group_destroy));
+    RUN(finish_create(async_arena_create(g->arena), g, out, ldso_pyr_group_destroy));
     g->m.assign(pyramids, pyramids + n);
-    for (ldso_pyramid *P : g->m) P->inGroup = g;
+    group_join(g);
     return LDSO_OK;
 }
 
 int ldso_pyr_group_destroy(ldso_pyr_group_t *g) {
     if (!g) return LDSO_OK;
     hipSetDevice(g->device);
-    if (g->used) hipEventSynchronize(g->done);          // the last call's kernels read the device arena
-    for (ldso_pyramid *P : g->m) if (P->inGroup == g) P->inGroup = nullptr;
-    if (g->uploaded) hipEventDestroy(g->uploaded);
-    if (g->done) hipEventDestroy(g->done);
-    if (g->h_stage) hipHostFree(g->h_stage);
-    if (g->d_stage) hipFree(g->d_stage);
+    group_leave(g);
+    async_arena_release(g->arena);          // waits for the last call's kernels
     delete g;
     return LDSO_OK;
 }
@@ -190,67 +178,43 @@ extern "C++" int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &memb
     const size_t nm = members.size();
     int Lmax = 0;
     for (int i : members) Lmax = std::max(Lmax, g->m[(size_t) i]->levels);
-    // per level: [ImgJob of the nl members that have it | nl + 1 workgroup prefixes of the intensity launch | nl + 1 of the gradient launch]
-    struct LevelPlan { size_t offJ, offI, offG; int nl, gridI, gridG; };
-    std::vector<LevelPlan> plan((size_t) Lmax);
-    size_t total = 0;
+    const PyrGroupLayout plan = pyr_group_layout(Lmax, sizeof(ImgJob), [&](int l) { int nl = 0; for (int i : members) nl += g->m[(size_t) i]->levels > l; return nl; });
+    RUN(async_arena_acquire(g->arena, plan.total, st));
+    char *const h_stage = g->arena.h_stage, *const d_stage = g->arena.d_stage;
+    int gridI[LDSO_PYR_LEVELS], gridG[LDSO_PYR_LEVELS];
     for (int l = 0; l < Lmax; l++) {
-        int nl = 0;
-        for (int i : members) nl += g->m[(size_t) i]->levels > l;
-        LevelPlan &L = plan[(size_t) l];
-        L.nl = nl; L.offJ = total; L.offI = L.offJ + (size_t) nl * sizeof(ImgJob); L.offG = L.offI + (size_t) (nl + 1) * 4;
-        total = (L.offG + (size_t) (nl + 1) * 4 + 15) & ~(size_t) 15;
-    }
-    // the arena is reused without a host wait at the end of a call: the pinned side is free once the last upload has been read, the device side once the last
-    // call's kernels are through - in stream order on the same stream, behind `done` on another
-    if (g->used) CHK(hipEventSynchronize(g->uploaded));
-    if (g->used && (total > g->stageCap || st != g->lastStream)) CHK(hipStreamWaitEvent(st, g->done, 0));
-    if (g->used && total > g->stageCap) CHK(hipEventSynchronize(g->done));
-    RUN(grow_arena(g->h_stage, g->d_stage, g->stageCap, total, 2, st));
-    for (int l = 0; l < Lmax; l++) {
-        LevelPlan &L = plan[(size_t) l];
-        ImgJob *hJ = (ImgJob *) (g->h_stage + L.offJ);
-        int *hI = (int *) (g->h_stage + L.offI), *hG = (int *) (g->h_stage + L.offG);
-        int j = 0, wgI = 0, wgG = 0;
+        const PyrLevelLayout &L = plan.level[(size_t) l];
+        ImgJob *hJ = (ImgJob *) (h_stage + L.jobs);
+        int j = 0;
         for (size_t k = 0; k < nm; k++) {
             const ldso_pyramid *P = g->m[(size_t) members[k]];
             if (P->levels <= l) continue;
-            const int wl = P->w >> l, hl = P->h >> l, nPix = wl * hl, nGrad = wl * (hl - 2);
-            ImgJob &J = hJ[j];
+            const int wl = P->w >> l, hl = P->h >> l;
+            ImgJob &J = hJ[j++];
             J.color = (LD_GLOBAL const float *) (l == 0 ? src[k] : nullptr); J.below = (LD_GLOBAL const float *) (l == 0 ? nullptr : P->lv[l - 1]); J.dI = (LD_GLOBAL float *) P->lv[l];
             J.wl = wl; J.hl = hl; J.wlm1 = P->w >> (l > 0 ? l - 1 : 0); J.pad_ = 0;
-            hI[j] = wgI; hG[j] = wgG;
-            wgI += (nPix + 255) / 256;
-            wgG += nGrad > 0 ? (nGrad + 255) / 256 : 0;
-            j++;
         }
-        hI[j] = wgI; hG[j] = wgG;
-        L.gridI = wgI; L.gridG = wgG;
+        // the workgroups of the two launches: 256 pixels each; the gradient has the rows 1 .. hl - 2
+        gridI[l] = group_prefix(L.nl, (int *) (h_stage + L.firstI), [&](int q) { return (hJ[q].wl * hJ[q].hl + 255) / 256; });
+        gridG[l] = group_prefix(L.nl, (int *) (h_stage + L.firstG), [&](int q) { const int nGrad = hJ[q].wl * (hJ[q].hl - 2); return nGrad > 0 ? (nGrad + 255) / 256 : 0; });
     }
-    CHK(hipMemcpyAsync(g->d_stage, g->h_stage, total, hipMemcpyHostToDevice, st));
-    CHK(hipEventRecord(g->uploaded, st));
+    CHK(hipMemcpyAsync(d_stage, h_stage, plan.total, hipMemcpyHostToDevice, st));
+    RUN(async_arena_mark_uploaded(g->arena, st));
     for (int l = 0; l < Lmax; l++) {
-        const LevelPlan &L = plan[(size_t) l];
-        const ImgJob *dJ = (const ImgJob *) (g->d_stage + L.offJ);
-        hipLaunchKernelGGL(k_img_intensity_group, dim3(L.gridI), dim3(256), 0, st, dJ, (const int *) (g->d_stage + L.offI), L.nl);
-        if (L.gridG > 0) hipLaunchKernelGGL(k_img_gradient_group, dim3(L.gridG), dim3(256), 0, st, dJ, (const int *) (g->d_stage + L.offG), L.nl);
+        const PyrLevelLayout &L = plan.level[(size_t) l];
+        const ImgJob *dJ = (const ImgJob *) (d_stage + L.jobs);
+        hipLaunchKernelGGL(k_img_intensity_group, dim3(gridI[l]), dim3(256), 0, st, dJ, (const int *) (d_stage + L.firstI), L.nl);
+        if (gridG[l] > 0) hipLaunchKernelGGL(k_img_gradient_group, dim3(gridG[l]), dim3(256), 0, st, dJ, (const int *) (d_stage + L.firstG), L.nl);
     }
     CHK(hipGetLastError());
-    CHK(hipEventRecord(g->done, st));
-    g->used = true; g->lastStream = st;
+    RUN(async_arena_mark_done(g->arena, st));
     for (int i : members) { ldso_pyramid *P = g->m[(size_t) i]; CHK(hipEventRecord(P->ready, st)); P->built = true; }
     return LDSO_OK;
 }
 
 static int pyr_group_members(ldso_pyr_group *g, const uint8_t *active, const void *const *images, const char *who, std::vector<int> &members) {
     REQ(g && images, std::string(who) + ": null argument");
-    for (int i = 0; i < (int) g->m.size(); i++) {
-        if (active && !active[i]) continue;
-        REQ(images[i], std::string(who) + ": member " + std::to_string(i) + ": null image");
-        members.push_back(i);
-    }
-    REQ(!members.empty(), std::string(who) + ": no active member");
-    return LDSO_OK;
+    return group_active((int) g->m.size(), active, who, members, [&](int i) { return images[i] ? nullptr : "null image"; });
 }
 
 int ldso_pyr_group_make_images_device(ldso_pyr_group_t *g, const uint8_t *active, const void *const *irradiance_dev, void *hip_stream) {

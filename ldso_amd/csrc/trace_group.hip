@@ -7,13 +7,8 @@
 
 namespace {
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t) 15; }
-
-// what every call checks of its group before anything is enqueued: the members still share the stream the group was made on
-int group_check(const ldso_trace_group *g, const char *who) {
-    for (const ldso_tracer *T : g->m) REQ(T->stream == g->m[0]->stream && T->device == g->device, std::string(who) + ": the members of a group share one device and one stream (ldso_trace_set_stream)");
-    return LDSO_OK;
-}
+constexpr GroupRule RULE = {"a tracer", "ldso_trace_set_stream", GROUP_MAX_MEMBERS};
+static_assert(sizeof(TraceJob) == 112, "the row of trace_group_layout as tests/test_group_stage_cpu.py sizes it");
 
 }  // namespace
 
@@ -30,29 +25,22 @@ int ldso_trace_group_member_of(const int *first, int n_jobs, int wave, int *job_
 }
 
 int ldso_trace_group_create(ldso_tracer_t *const *tracers, int n, ldso_trace_group_t **out) {
-    REQ(tracers && out && n >= 1 && n <= 128, "ldso_trace_group_create: bad arguments (1 <= n <= 128 tracers)");
-    for (int i = 0; i < n; i++) {
-        REQ(tracers[i], "ldso_trace_group_create: null tracer");
-        REQ(tracers[i]->inGroup == nullptr, "ldso_trace_group_create: a tracer belongs to at most one group at a time");
-        for (int k = 0; k < i; k++) REQ(tracers[k] != tracers[i], "ldso_trace_group_create: the same tracer twice");
-        REQ(tracers[i]->device == tracers[0]->device && tracers[i]->stream == tracers[0]->stream,
-            "ldso_trace_group_create: the members of a group share one device and one stream (ldso_trace_set_stream)");
-    }
+    RUN(group_admit(tracers, n, out, "ldso_trace_group_create", RULE));
+    CHK(hipSetDevice(tracers[0]->device));
     ldso_trace_group *g = new ldso_trace_group();
     g->device = tracers[0]->device;
+    RUN(finish_create(LDSO_OK, g, out, ldso_trace_group_destroy));          // nothing of its own that could fail: the arena comes with the first call
     g->m.assign(tracers, tracers + n);
-    for (ldso_tracer *T : g->m) T->inGroup = g;
-    *out = g;
+    group_join(g);
     return LDSO_OK;
 }
 
 int ldso_trace_group_destroy(ldso_trace_group_t *g) {
     if (!g) return LDSO_OK;
     hipSetDevice(g->device);
-    if (g->h_stage && !g->m.empty()) hipStreamSynchronize(g->m[0]->stream);
-    for (ldso_tracer *T : g->m) if (T->inGroup == g) T->inGroup = nullptr;
-    if (g->h_stage) hipHostFree(g->h_stage);
-    if (g->d_stage) hipFree(g->d_stage);
+    if (g->arena.h_stage && !g->m.empty()) hipStreamSynchronize(g->m[0]->stream);
+    group_leave(g);
+    group_arena_free(g->arena);
     delete g;
     return LDSO_OK;
 }
@@ -60,51 +48,44 @@ int ldso_trace_group_destroy(ldso_trace_group_t *g) {
 // ldso_trace_on of every active member: ONE upload of [pose blocks | TraceJob table | first | zeroed count rows], one launch, ONE download of the count rows, one wait
 int ldso_trace_group_on(ldso_trace_group_t *g, const uint8_t *active, const int *n_hosts, const float *const *KRKi, const float *const *Kt, const float *const *aff, int *counts_out) {
     REQ(g && n_hosts && KRKi && Kt && aff, "ldso_trace_group_on: null argument");
-    RUN(group_check(g, "ldso_trace_group_on"));
-    const int n = (int) g->m.size();
+    RUN(group_check(g->m.data(), g->m.size(), "ldso_trace_group_on", RULE));
     std::vector<int> members;
+    RUN(group_active((int) g->m.size(), active, "ldso_trace_group_on", members, [&](int i) -> const char * {
+        if (!(n_hosts[i] >= 1 && n_hosts[i] <= LDSO_MAX_FRAMES)) return "n_hosts outside 1..LDSO_MAX_FRAMES";
+        if (!(KRKi[i] && Kt[i] && aff[i])) return "null pose array";
+        return g->m[(size_t) i]->haveFrame ? nullptr : "set the new frame first";
+    }));
     size_t poseFloats = 0;
-    for (int i = 0; i < n; i++) {
-        if (active && !active[i]) continue;
-        const std::string who = "ldso_trace_group_on: member " + std::to_string(i);
-        REQ(n_hosts[i] >= 1 && n_hosts[i] <= LDSO_MAX_FRAMES, who + ": n_hosts outside 1..LDSO_MAX_FRAMES");
-        REQ(KRKi[i] && Kt[i] && aff[i], who + ": null pose array");
-        REQ(g->m[(size_t) i]->haveFrame, who + ": set the new frame first");
-        members.push_back(i);
-        poseFloats += (size_t) n_hosts[i] * 14;
-    }
-    REQ(!members.empty(), "ldso_trace_group_on: no active member");
+    for (int i : members) poseFloats += (size_t) n_hosts[i] * 14;
     CHK(hipSetDevice(g->device));
     const size_t nj = members.size();
-    const size_t offJ = up16(poseFloats * 4), offF = up16(offJ + nj * sizeof(TraceJob)), offC = up16(offF + (nj + 1) * 4), total = offC + nj * 8 * 4;
+    const TraceGroupLayout L = trace_group_layout(poseFloats, nj, sizeof(TraceJob));
     hipStream_t st = g->m[0]->stream;
-    RUN(grow_arena(g->h_stage, g->d_stage, g->stageCap, total, 2, st));
-    float *hPose = (float *) g->h_stage;
-    TraceJob *hJ = (TraceJob *) (g->h_stage + offJ);
-    int *hF = (int *) (g->h_stage + offF), *hC = (int *) (g->h_stage + offC);
+    RUN(group_arena_grow(g->arena, L.total, st));
+    char *const h_stage = g->arena.h_stage, *const d_stage = g->arena.d_stage;
+    float *hPose = (float *) (h_stage + L.poses);
+    TraceJob *hJ = (TraceJob *) (h_stage + L.jobs);
+    int *hF = (int *) (h_stage + L.first), *hC = (int *) (h_stage + L.down);
     size_t po = 0;
-    int waves = 0;
     for (size_t j = 0; j < nj; j++) {
         const int i = members[j], nh = n_hosts[i];
         const ldso_tracer *T = g->m[(size_t) i];
         memcpy(hPose + po, KRKi[i], (size_t) nh * 9 * 4);
         memcpy(hPose + po + nh * 9, Kt[i], (size_t) nh * 3 * 4);
         memcpy(hPose + po + nh * 12, aff[i], (size_t) nh * 2 * 4);
-        const float *dPose = (const float *) g->d_stage + po;
+        const float *dPose = (const float *) (d_stage + L.poses) + po;
         TraceJob &A = hJ[j];
         memset(&A, 0, sizeof(A));
         A.pts = T->d_pts; A.n = T->n; A.img = T->img; A.w = T->w; A.h = T->h;
         A.KRKi = dPose; A.Kt = dPose + nh * 9; A.aff = dPose + nh * 12; A.nHosts = nh;
-        A.s = T->settings; A.counts = (int *) (g->d_stage + offC) + 8 * j;
-        hF[j] = waves;                       // one wavefront per point; a member without points: first[j] == first[j + 1]
-        waves += T->n;
+        A.s = T->settings; A.counts = (int *) (d_stage + L.down) + 8 * j;
         po += (size_t) nh * 14;
     }
-    hF[nj] = waves;
-    memset(hC, 0, nj * 8 * 4);
-    CHK(hipMemcpyAsync(g->d_stage, g->h_stage, total, hipMemcpyHostToDevice, st));
-    if (waves > 0) CHK(trace_launch_group((const TraceJob *) (g->d_stage + offJ), (const int *) (g->d_stage + offF), (int) nj, waves, st));
-    CHK(hipMemcpyAsync(hC, g->d_stage + offC, nj * 8 * 4, hipMemcpyDeviceToHost, st));
+    const int waves = group_prefix((int) nj, hF, [&](int j) { return g->m[(size_t) members[(size_t) j]]->n; });          // one wavefront per point; a member without points is skipped
+    memset(hC, 0, L.downBytes);
+    CHK(hipMemcpyAsync(d_stage, h_stage, L.total, hipMemcpyHostToDevice, st));
+    if (waves > 0) CHK(trace_launch_group((const TraceJob *) (d_stage + L.jobs), (const int *) (d_stage + L.first), (int) nj, waves, st));
+    CHK(hipMemcpyAsync(hC, d_stage + L.down, L.downBytes, hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
     if (counts_out) for (size_t j = 0; j < nj; j++) for (int k = 0; k < 6; k++) counts_out[6 * members[j] + k] = hC[8 * j + k];
     return LDSO_OK;

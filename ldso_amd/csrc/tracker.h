@@ -98,9 +98,7 @@ struct ldso_tr_group {
     int device = 0, numCU = 256;
     TrCoop *d_coop = nullptr;         // [TR_COOP_SLOTS] hand-over records, indexed by the job of a launch
     int coopSeq = 1;                  // sequence numbers already used by earlier launches on d_coop
-    // one pinned arena and its device twin (grow_arena): [TrParams of the members that take part | TrJob table | TrHyp records] go up in one copy, the records come down in one
-    char *h_stage = nullptr, *d_stage = nullptr;
-    size_t stageCap = 0;
+    GroupArena arena;                 // tr_group_layout
 };
 
 #pragma GCC visibility push(hidden)

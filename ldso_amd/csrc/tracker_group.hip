@@ -8,20 +8,22 @@ namespace {
 
 struct GroupJobIn { int p; const double *T; float a, b; int coarsest; const double *minRes; };      // p: index into the call's list of members that take part
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t) 15; }
+constexpr GroupRule RULE = {"a tracker", "ldso_tr_set_stream", TR_COOP_SLOTS};          // a hand-over slot per job: the bound is the slots'
+static_assert(sizeof(TrParams) == 904 && sizeof(TrJob) == 24 && sizeof(TrHyp) == 344, "the rows of tr_group_layout as tests/test_group_stage_cpu.py sizes them");
 
 // One launch for `jobs` (the jobs of a member are contiguous, in the order of `members`): ONE upload of [TrParams of the members | TrJob table | TrHyp records], the
 // kernel, ONE download of the records, one wait.  `out` = the records on the host (the group's pinned arena: valid until the next launch).  Every member's lastEvals /
 // lastPivotedSolves are written as ldso_tr_track_batch writes them for the same tries.
 int group_launch(ldso_tr_group *g, const std::vector<int> &members, const std::vector<GroupJobIn> &jobs, TrHyp *&out) {
     const size_t np = members.size(), nj = jobs.size();
-    const size_t offJ = up16(np * sizeof(TrParams)), offH = up16(offJ + nj * sizeof(TrJob)), total = offH + nj * sizeof(TrHyp);
+    const TrGroupLayout L = tr_group_layout(np, nj, sizeof(TrParams), sizeof(TrJob), sizeof(TrHyp));
     hipStream_t st = g->m[0]->stream;
-    RUN(grow_arena(g->h_stage, g->d_stage, g->stageCap, total, 2, st));
+    RUN(group_arena_grow(g->arena, L.total, st));
+    char *const h_stage = g->arena.h_stage, *const d_stage = g->arena.d_stage;
     const int G = tr_coop_width((int) nj, g->numCU);          // G > 1 only for nj <= TR_COOP_SLOTS: job j's hand-over record is d_coop[j]
-    TrParams *hP = (TrParams *) g->h_stage;
-    TrJob *hJ = (TrJob *) (g->h_stage + offJ);
-    TrHyp *hH = (TrHyp *) (g->h_stage + offH);
+    TrParams *hP = (TrParams *) (h_stage + L.params);
+    TrJob *hJ = (TrJob *) (h_stage + L.jobs);
+    TrHyp *hH = (TrHyp *) (h_stage + L.down);
     for (size_t i = 0; i < np; i++) hP[i] = g->m[(size_t) members[i]]->P;
     for (size_t j = 0; j < nj; j++) {
         const GroupJobIn &in = jobs[j];
@@ -30,12 +32,12 @@ int group_launch(ldso_tr_group *g, const std::vector<int> &members, const std::v
         memcpy(hy.T, in.T, 96);
         hy.a = in.a; hy.b = in.b; hy.coarsestLvl = in.coarsest;
         for (int k = 0; k < 5; k++) hy.minRes[k] = in.minRes ? in.minRes[k] : NAN;
-        hJ[j].P = (const TrParams *) g->d_stage + in.p;
-        hJ[j].hyp = (TrHyp *) (g->d_stage + offH) + j;
+        hJ[j].P = (const TrParams *) (d_stage + L.params) + in.p;
+        hJ[j].hyp = (TrHyp *) (d_stage + L.down) + j;
         hJ[j].coop = G > 1 ? g->d_coop + j : nullptr;
     }
-    CHK(hipMemcpyAsync(g->d_stage, g->h_stage, total, hipMemcpyHostToDevice, st));
-    const TrJob *dJ = (const TrJob *) (g->d_stage + offJ);
+    CHK(hipMemcpyAsync(d_stage, h_stage, L.total, hipMemcpyHostToDevice, st));
+    const TrJob *dJ = (const TrJob *) (d_stage + L.jobs);
     if (G > 1) {
         std::unique_lock<std::mutex> lk;
         RUN(tr_coop_begin(g->device, st, g->d_coop, g->coopSeq, lk));
@@ -44,7 +46,7 @@ int group_launch(ldso_tr_group *g, const std::vector<int> &members, const std::v
     } else {
         CHK(tr_launch_track_group(1, (int) nj, dJ, 0, st));
     }
-    CHK(hipMemcpyAsync(hH, g->d_stage + offH, nj * sizeof(TrHyp), hipMemcpyDeviceToHost, st));
+    CHK(hipMemcpyAsync(hH, d_stage + L.down, L.downBytes, hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
     for (size_t j = 0; j < nj; j++) if (hH[j].ok == -2) {
         ldso_set_error("ldso_tr_track: the cooperating workgroups of a hypothesis did not become co-resident (device shared with another process or CU-masked?); set LDSO_TR_NO_COOP=1");
@@ -59,37 +61,22 @@ int group_launch(ldso_tr_group *g, const std::vector<int> &members, const std::v
     return LDSO_OK;
 }
 
-// what every call checks of its group before anything is enqueued: the members still share the stream the group was made on
-int group_check(const ldso_tr_group *g, const char *who) {
-    for (const ldso_tracker *H : g->m) REQ(H->stream == g->m[0]->stream && H->device == g->device, std::string(who) + ": the members of a group share one device and one stream (ldso_tr_set_stream)");
-    return LDSO_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int ldso_tr_group_create(ldso_tracker_t *const *trackers, int n, ldso_tr_group_t **out) {
-    REQ(trackers && out && n >= 1 && n <= TR_COOP_SLOTS, "ldso_tr_group_create: bad arguments (1 <= n <= 128 trackers)");
-    for (int i = 0; i < n; i++) {
-        REQ(trackers[i], "ldso_tr_group_create: null tracker");
-        REQ(trackers[i]->inGroup == nullptr, "ldso_tr_group_create: a tracker belongs to at most one group at a time");
-        for (int k = 0; k < i; k++) REQ(trackers[k] != trackers[i], "ldso_tr_group_create: the same tracker twice");
-        REQ(trackers[i]->device == trackers[0]->device && trackers[i]->stream == trackers[0]->stream,
-            "ldso_tr_group_create: the members of a group share one device and one stream (ldso_tr_set_stream)");
-    }
+    RUN(group_admit(trackers, n, out, "ldso_tr_group_create", RULE));
     CHK(hipSetDevice(trackers[0]->device));
     ldso_tr_group *g = new ldso_tr_group();
     g->device = trackers[0]->device; g->numCU = trackers[0]->numCU;
-    g->m.assign(trackers, trackers + n);
     auto body = [&]() -> int {
         CHK(hipMalloc((void **) &g->d_coop, TR_COOP_SLOTS * sizeof(TrCoop)));
         return zero_fill(g->d_coop, TR_COOP_SLOTS * sizeof(TrCoop));
     };
-    const int r = body();
-    if (r != LDSO_OK) { const std::string keep = ldso_last_error(); g->m.clear(); ldso_tr_group_destroy(g); ldso_set_error(keep); return r; }
-    for (ldso_tracker *H : g->m) H->inGroup = g;
-    *out = g;
+    RUN(finish_create(body(), g, out, ldso_tr_group_destroy));
+    g->m.assign(trackers, trackers + n);
+    group_join(g);
     return LDSO_OK;
 }
 
@@ -97,10 +84,9 @@ int ldso_tr_group_destroy(ldso_tr_group_t *g) {
     if (!g) return LDSO_OK;
     hipSetDevice(g->device);
     if (!g->m.empty()) hipStreamSynchronize(g->m[0]->stream);
-    for (ldso_tracker *H : g->m) if (H->inGroup == g) H->inGroup = nullptr;
+    group_leave(g);
     if (g->d_coop) hipFree(g->d_coop);
-    if (g->h_stage) hipHostFree(g->h_stage);
-    if (g->d_stage) hipFree(g->d_stage);
+    group_arena_free(g->arena);
     delete g;
     return LDSO_OK;
 }
@@ -115,17 +101,16 @@ int ldso_tr_group_coop_width(ldso_tr_group_t *g, int n_jobs, int *G) {
 int ldso_tr_group_track(ldso_tr_group_t *g, const uint8_t *active, double *T_inout, float *aff_inout, const int *coarsestLvl, const double *minRes, double *lastResiduals,
                         double *flow, int *ok, int *iterations) {
     REQ(g && T_inout && aff_inout && coarsestLvl, "ldso_tr_group_track: null argument");
-    RUN(group_check(g, "ldso_tr_group_track"));
-    const int n = (int) g->m.size();
+    RUN(group_check(g->m.data(), g->m.size(), "ldso_tr_group_track", RULE));
     std::vector<int> members;
+    RUN(group_active((int) g->m.size(), active, "ldso_tr_group_track", members, [&](int i) -> const char * {
+        return coarsestLvl[i] >= 0 && coarsestLvl[i] < 5 && coarsestLvl[i] < g->m[(size_t) i]->levels ? nullptr : "coarsestLvl outside a member's pyramid levels";
+    }));
     std::vector<GroupJobIn> jobs;
-    for (int i = 0; i < n; i++) {
-        if (active && !active[i]) continue;
-        REQ(coarsestLvl[i] >= 0 && coarsestLvl[i] < 5 && coarsestLvl[i] < g->m[(size_t) i]->levels, "ldso_tr_group_track: coarsestLvl outside a member's pyramid levels");
-        jobs.push_back({(int) members.size(), T_inout + 12 * i, aff_inout[2 * i], aff_inout[2 * i + 1], coarsestLvl[i], minRes ? minRes + 5 * i : nullptr});
-        members.push_back(i);
+    for (size_t k = 0; k < members.size(); k++) {
+        const int i = members[k];
+        jobs.push_back({(int) k, T_inout + 12 * i, aff_inout[2 * i], aff_inout[2 * i + 1], coarsestLvl[i], minRes ? minRes + 5 * i : nullptr});
     }
-    REQ(!members.empty(), "ldso_tr_group_track: no active member");
     CHK(hipSetDevice(g->device));
     TrHyp *hy = nullptr;
     RUN(group_launch(g, members, jobs, hy));
@@ -148,14 +133,11 @@ int ldso_tr_group_track_new_coarse(ldso_tr_group_t *g, const uint8_t *active, co
                                    int *tries_consumed, int *good) {
     REQ(g && sprelast && slast && lastF && poses_valid && aff_last && lastCoarseRMSE && reTrackThreshold && result4 && new_w2c && aff_out,
         "ldso_tr_group_track_new_coarse: null argument");
-    RUN(group_check(g, "ldso_tr_group_track_new_coarse"));
-    const int n = (int) g->m.size();
+    RUN(group_check(g->m.data(), g->m.size(), "ldso_tr_group_track_new_coarse", RULE));
     std::vector<int> members;
-    for (int i = 0; i < n; i++) if (!active || active[i]) {
-        REQ(g->m[(size_t) i]->levels <= 5, "ldso_tr_group_track_new_coarse: a member has more than five pyramid levels");
-        members.push_back(i);
-    }
-    REQ(!members.empty(), "ldso_tr_group_track_new_coarse: no active member");
+    RUN(group_active((int) g->m.size(), active, "ldso_tr_group_track_new_coarse", members, [&](int i) -> const char * {
+        return g->m[(size_t) i]->levels <= 5 ? nullptr : "a member has more than five pyramid levels";
+    }));
     CHK(hipSetDevice(g->device));
     std::vector<TrNewCoarse> S(members.size());
     std::vector<GroupJobIn> jobs;

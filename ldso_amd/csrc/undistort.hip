@@ -109,14 +109,8 @@ struct ldso_undistorter {
 struct ldso_undist_group {
     std::vector<ldso_undistorter *> m;
     int device = 0;
-    // one pinned arena and its device twin: [UndistJob table | wgFirst | the raw frames of the active members] go up in one copy per call.  A call does not wait on
-    // the host, so `uploaded` (recorded behind the copy) guards the pinned side against the next call's writes, and `done` (recorded behind the last launch)
-    // orders a call on another stream behind the kernel that still reads the device side
-    char *h_stage = nullptr, *d_stage = nullptr;
-    size_t stageCap = 0;
-    hipEvent_t uploaded = nullptr, done = nullptr;
-    hipStream_t lastStream = nullptr;
-    bool used = false, profile = false, profPending = false;
+    AsyncArena arena;                   // undist_group_layout
+    bool profile = false, profPending = false;
     hipEvent_t ev[4] = {};
     float us[3] = {0, 0, 0};
 };
@@ -149,14 +143,8 @@ int read_profile(const hipEvent_t ev[4], float us[3]) {
     return LDSO_OK;
 }
 
-inline size_t up64(size_t x) { return (x + 63) & ~(size_t) 63; }
-
-// what create and every call check of a group: the members share one device and one stream
-int group_check(ldso_undistorter *const *m, size_t n, const char *who) {
-    for (size_t i = 0; i < n; i++)
-        REQ(m[i]->device == m[0]->device && m[i]->stream == m[0]->stream, std::string(who) + ": the members of a group share one device and one stream (ldso_undist_set_stream)");
-    return LDSO_OK;
-}
+constexpr GroupRule GROUP_RULE = {"an undistorter", "ldso_undist_set_stream", GROUP_MAX_MEMBERS};
+static_assert(sizeof(UndistJob) == 80, "the row of undist_group_layout as tests/test_group_stage_cpu.py sizes it");
 
 }  // namespace
 
@@ -304,37 +292,26 @@ int ldso_undist_device(ldso_undistorter_t *U, const void **dev_ptr) {
 int ldso_undist_group_destroy(ldso_undist_group_t *g) {
     if (!g) return LDSO_OK;
     hipSetDevice(g->device);
-    if (g->used) hipEventSynchronize(g->done);          // the last call's kernel reads the device arena
-    for (ldso_undistorter *U : g->m) if (U->inGroup == g) U->inGroup = nullptr;
-    if (g->uploaded) hipEventDestroy(g->uploaded);
-    if (g->done) hipEventDestroy(g->done);
+    group_leave(g);
+    async_arena_release(g->arena);          // waits for the last call's kernel
     for (hipEvent_t e : g->ev) if (e) hipEventDestroy(e);
-    if (g->h_stage) hipHostFree(g->h_stage);
-    if (g->d_stage) hipFree(g->d_stage);
     delete g;
     return LDSO_OK;
 }
 
 int ldso_undist_group_create(ldso_undistorter_t *const *u, int n, ldso_undist_group_t **out) {
-    REQ(u && out && n >= 1 && n <= 128, "ldso_undist_group_create: bad arguments (1 <= n <= 128 undistorters)");
-    for (int i = 0; i < n; i++) {
-        REQ(u[i], "ldso_undist_group_create: null undistorter");
-        REQ(u[i]->inGroup == nullptr, "ldso_undist_group_create: an undistorter belongs to at most one group at a time");
-        for (int k = 0; k < i; k++) REQ(u[k] != u[i], "ldso_undist_group_create: the same undistorter twice");
-    }
-    RUN(group_check(u, (size_t) n, "ldso_undist_group_create"));
+    RUN(group_admit(u, n, out, "ldso_undist_group_create", GROUP_RULE));
     CHK(hipSetDevice(u[0]->device));
     ldso_undist_group *g = new ldso_undist_group();
     g->device = u[0]->device;
     auto body = [&]() -> int {
-        CHK(hipEventCreateWithFlags(&g->uploaded, hipEventDisableTiming));
-        CHK(hipEventCreateWithFlags(&g->done, hipEventDisableTiming));
+        RUN(async_arena_create(g->arena));
         for (hipEvent_t &e : g->ev) CHK(hipEventCreate(&e));
         return LDSO_OK;
     };
     RUN(finish_create(body(), g, out, ldso_undist_group_destroy));
     g->m.assign(u, u + n);
-    for (ldso_undistorter *U : g->m) U->inGroup = g;
+    group_join(g);
     return LDSO_OK;
 }
 
@@ -354,65 +331,52 @@ int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active, cons
                              ldso_pyr_group_t *pg, float *exposure_out) {
     static const char who[] = "ldso_undist_group_frames";
     REQ(g && raw && bytes_per_pixel && exposure && factor, std::string(who) + ": null argument");
-    RUN(group_check(g->m.data(), g->m.size(), who));
+    RUN(group_check(g->m.data(), g->m.size(), who, GROUP_RULE));
     const int n = (int) g->m.size();
     REQ(!pg || ((int) pg->m.size() == n && pg->device == g->device), std::string(who) + ": the pyramid group does not match the undistorter group (device, number of members)");
-    // every refusal comes before anything is staged or enqueued; the arena is [UndistJob table | wgFirst | the frames of the active members]
-    struct Plan { int i, bpp; FrameRule rule; size_t off, bytes; };
-    std::vector<Plan> plan;
+    // every refusal comes before anything is staged or enqueued
     std::vector<int> members;
-    for (int i = 0; i < n; i++) {
-        if (active && !active[i]) continue;
+    RUN(group_active(n, active, who, members, [&](int i) -> const char * {
         const ldso_undistorter *U = g->m[(size_t) i];
-        const std::string mem = std::string(who) + ": member " + std::to_string(i);
-        REQ(raw[i], mem + ": null raw frame");
-        REQ(bytes_per_pixel[i] == 1 || bytes_per_pixel[i] == 2, mem + ": bytes_per_pixel is 1 or 2");
-        REQ(U->remapSet, mem + ": ldso_undist_set_remap has not been called");
+        if (!raw[i]) return "null raw frame";
+        if (bytes_per_pixel[i] != 1 && bytes_per_pixel[i] != 2) return "bytes_per_pixel is 1 or 2";
+        if (!U->remapSet) return "ldso_undist_set_remap has not been called";
         const FrameRule rule = frame_rule(U, exposure[i]);
-        REQ(rule.mode == UNDIST_PLAIN || bytes_per_pixel[i] == 1 || U->GDepth >= 65536, mem + ": a 16-bit frame needs a response of 65536 entries");
-        REQ(!pg || (pg->m[(size_t) i]->w == U->w && pg->m[(size_t) i]->h == U->h), mem + ": pyramid does not match the undistorter (size)");
-        plan.push_back({i, bytes_per_pixel[i], rule, 0, (size_t) U->wOrg * U->hOrg * bytes_per_pixel[i]});
-        members.push_back(i);
-    }
-    REQ(!plan.empty(), std::string(who) + ": no active member");
-    const size_t nj = plan.size(), offF = nj * sizeof(UndistJob);
-    size_t total = up64(offF + (nj + 1) * 4);
-    for (Plan &p : plan) { p.off = total; total = up64(total + p.bytes); }          // every frame 64-byte aligned
+        if (!(rule.mode == UNDIST_PLAIN || bytes_per_pixel[i] == 1 || U->GDepth >= 65536)) return "a 16-bit frame needs a response of 65536 entries";
+        if (pg && !(pg->m[(size_t) i]->w == U->w && pg->m[(size_t) i]->h == U->h)) return "pyramid does not match the undistorter (size)";
+        return nullptr;
+    }));
+    const size_t nj = members.size();
+    auto frame_bytes = [&](size_t j) { const int i = members[j]; return (size_t) g->m[(size_t) i]->wOrg * g->m[(size_t) i]->hOrg * bytes_per_pixel[i]; };
+    const UndistGroupLayout L = undist_group_layout(nj, sizeof(UndistJob), frame_bytes);
     CHK(hipSetDevice(g->device));
     hipStream_t st = g->m[0]->stream;
-    // the arena is reused without a host wait at the end of a call: the pinned side is free once the last upload has been read, the device side once the last
-    // call's kernel is through - in stream order on the same stream, behind `done` on another (pyr_group_build's rule)
-    if (g->used) CHK(hipEventSynchronize(g->uploaded));
-    if (g->used && (total > g->stageCap || st != g->lastStream)) CHK(hipStreamWaitEvent(st, g->done, 0));
-    if (g->used && total > g->stageCap) CHK(hipEventSynchronize(g->done));
-    RUN(grow_arena(g->h_stage, g->d_stage, g->stageCap, total, 2, st));
-    UndistJob *hJ = (UndistJob *) g->h_stage;
-    int *hF = (int *) (g->h_stage + offF);
-    int wgs = 0;
+    RUN(async_arena_acquire(g->arena, L.total, st));
+    char *const h_stage = g->arena.h_stage, *const d_stage = g->arena.d_stage;
+    UndistJob *hJ = (UndistJob *) (h_stage + L.jobs);
+    std::vector<FrameRule> rule(nj);
     for (size_t j = 0; j < nj; j++) {
-        const Plan &p = plan[j];
-        const ldso_undistorter *U = g->m[(size_t) p.i];
-        memcpy(g->h_stage + p.off, raw[p.i], p.bytes);
-        const UndistArgs A = frame_args(U, g->d_stage + p.off, pg ? pg->m[(size_t) p.i]->d_color : U->d_out, p.rule.mode, factor[p.i]);
+        const int i = members[j];
+        const ldso_undistorter *U = g->m[(size_t) i];
+        rule[j] = frame_rule(U, exposure[i]);
+        memcpy(h_stage + L.frame[j], raw[i], frame_bytes(j));
+        const UndistArgs A = frame_args(U, d_stage + L.frame[j], pg ? pg->m[(size_t) i]->d_color : U->d_out, rule[j].mode, factor[i]);
         UndistJob &J = hJ[j];
         J.raw = A.raw; J.G = A.G; J.vig = A.vig; J.remapX = A.remapX; J.remapY = A.remapY; J.out = A.out;
-        J.w = A.w; J.h = A.h; J.wOrg = A.wOrg; J.hOrg = A.hOrg; J.mode = A.mode; J.bpp = p.bpp; J.factor = A.factor; J.pad_ = 0;
-        hF[j] = wgs;
-        wgs += (int) (((size_t) U->w * U->h + 255) / 256);
+        J.w = A.w; J.h = A.h; J.wOrg = A.wOrg; J.hOrg = A.hOrg; J.mode = A.mode; J.bpp = bytes_per_pixel[i]; J.factor = A.factor; J.pad_ = 0;
     }
-    hF[nj] = wgs;
+    const int wgs = group_prefix((int) nj, (int *) (h_stage + L.first), [&](int j) { return (int) (((size_t) hJ[j].w * hJ[j].h + 255) / 256); });          // 256 pixels per workgroup
     const bool prof = g->profile;
     if (prof) CHK(hipEventRecord(g->ev[0], st));
-    CHK(hipMemcpyAsync(g->d_stage, g->h_stage, total, hipMemcpyHostToDevice, st));
-    CHK(hipEventRecord(g->uploaded, st));
+    CHK(hipMemcpyAsync(d_stage, h_stage, L.total, hipMemcpyHostToDevice, st));
+    RUN(async_arena_mark_uploaded(g->arena, st));
     if (prof) CHK(hipEventRecord(g->ev[1], st));
-    hipLaunchKernelGGL(k_undist_group, dim3((unsigned) wgs), dim3(256), 0, st, (const UndistJob *) g->d_stage, (const int *) (g->d_stage + offF), (int) nj);
+    hipLaunchKernelGGL(k_undist_group, dim3((unsigned) wgs), dim3(256), 0, st, (const UndistJob *) (d_stage + L.jobs), (const int *) (d_stage + L.first), (int) nj);
     CHK(hipGetLastError());
-    CHK(hipEventRecord(g->done, st));
-    g->used = true; g->lastStream = st;
+    RUN(async_arena_mark_done(g->arena, st));
     if (prof) CHK(hipEventRecord(g->ev[2], st));
     for (size_t j = 0; j < nj; j++) {
-        ldso_undistorter *U = g->m[(size_t) plan[j].i];
+        ldso_undistorter *U = g->m[(size_t) members[j]];
         U->last = hJ[j].out;
         CHK(hipEventRecord(U->done, st));
     }
@@ -422,7 +386,7 @@ int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active, cons
         RUN(pyr_group_build(pg, members, src, st));
     }
     if (prof) { CHK(hipEventRecord(g->ev[3], st)); g->profPending = true; }
-    if (exposure_out) for (const Plan &p : plan) exposure_out[p.i] = p.rule.exposureOut;
+    if (exposure_out) for (size_t j = 0; j < nj; j++) exposure_out[members[j]] = rule[j].exposureOut;
     return LDSO_OK;
 }
 

@@ -122,6 +122,29 @@ def test_active_mask_overwrite_and_the_device_pointer_entry():
     close_all(grp, pyr)
 
 
+@pytest.mark.parametrize("fetch_between", (True, False))
+def test_arena_grows_while_in_use_and_the_next_call_moves_to_another_stream(fetch_between):
+    """the arena's reuse rule on one group of three members with two levels: call 1 has one active member, call 2 all three (128 -> 320 bytes of tables: the arena
+    is replaced while it is in use), call 3 runs on another stream (ordered behind call 2, whose kernels may still read what call 3 restages).  With the levels
+    fetched after every call each call's bytes are checked; without, the three calls are enqueued back to back and nothing waits on the host between them."""
+    import torch
+    st = stream()
+    other = torch.cuda.Stream()
+    want = {seed: [solo_levels(seed)[i][:2] for i in range(3)] for seed in (1, 2)}          # levels 0 and 1 do not depend on how many lie above them
+    pyr = [binding.Pyramid(w, h, 2) for w, h, _ in SHAPES[:3]]
+    grp = binding.PyramidGroup(pyr)
+    grp.make_images([None, images(2)[1], None], stream=st, active=[False, True, False])
+    if fetch_between:
+        assert_levels("first call", pyr[1], want[2][1])
+    grp.make_images(images(1)[:3], stream=st)
+    for i, p in enumerate(pyr if fetch_between else []):
+        assert_levels((i, "second call"), p, want[1][i])
+    grp.make_images(images(2)[:3], stream=other.cuda_stream)
+    for i, p in enumerate(pyr):
+        assert_levels((i, "third call"), p, want[2][i])
+    close_all(grp, pyr)
+
+
 def test_refusals():
     L = binding.lib()
     pyr, grp = make_group()

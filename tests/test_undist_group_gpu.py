@@ -286,6 +286,48 @@ def test_back_to_back_calls_without_a_host_wait():
         p.close()
 
 
+@pytest.mark.parametrize("fetch_between", (True, False))
+def test_arena_grows_while_in_use_and_the_next_call_moves_to_another_stream(fetch_between):
+    """the reuse rule of both arenas (the undistorters' and the pyramids') on one pair of groups: three members, 8-bit frames, two pyramid levels.  Call 1 has one
+    active member, call 2 all three (the arenas are replaced while in use), call 3 runs with every member moved to another stream (ordered behind call 2, whose
+    kernels may still read what call 3 restages).  The members are configured once, so nothing but the calls touches their streams.  With the results fetched after
+    every call each call's bytes are checked; without, the three calls are enqueued back to back and nothing waits on the host between them."""
+    import torch
+    names, shapes = ("odd", "up", "A"), ((33, 29, 2), (96, 64, 2), (104, 72, 2))
+    calls = [tuple(Spec(8, 2, True, uc.EXPOSURE, 1.0, v) if on else None for on in mask) for v, mask in enumerate(((0, 1, 0), (1, 1, 1), (1, 1, 1)))]
+    for specs in calls:                               # the solo references first
+        for n, s, (_, _, lv) in zip(names, specs, shapes):
+            if s is not None:
+                solo(n, s), restated(n, s), solo_levels(n, s, lv)
+    other = torch.cuda.Stream()
+    G = Group(names)
+    pyr, pg = pyramids(shapes)
+    for u, n in zip(G.U, names):
+        configure(u, n, calls[1][names.index(n)])
+
+    def call(specs):
+        raws = [None if s is None else frame_of(n, s) for n, s in zip(names, specs)]
+        return G.g.frames(raws, [uc.EXPOSURE] * 3, pyr_group=pg, active=[s is not None for s in specs])
+
+    def check(specs, e):
+        G.check(specs, e)
+        for n, s, (_, _, lv), p in zip(names, specs, shapes, pyr):
+            if s is not None:
+                assert [x.tobytes() for x in levels_of(p)] == solo_levels(n, s, lv), n
+
+    for k, specs in enumerate(calls):
+        if k == 2:
+            for u in G.U:
+                u.set_stream(other.cuda_stream)
+        e = call(specs)
+        if fetch_between or k == 2:
+            check(specs, e)
+    G.close()
+    pg.close()
+    for p in pyr:
+        p.close()
+
+
 def test_raw_frames_may_be_overwritten_when_the_call_returns():
     G = Group()
     specs = CALLS[0][0]
