@@ -526,12 +526,12 @@ struct SolveIO {
 static __host__ __device__ constexpr int solve_cols(int NB) { return (NB == 7) ? LD_C7 : 4; }          // columns per round of solve_core<NB>
 #define LD_XFP (8 * LD_MAXF + 8)          // gn_tail: floats of one copy of x (or of the new deltas)
 // solve_core, offsets in doubles from the base.  sTail aliases the panel buffers (free after the factorisation): gn_tail's float copies of x and of the deltas,
-// 3 x 2 x LD_XFP floats.  slack: the launchers have always counted 46 M doubles (NB == 4) or 30 M (three panels of up to 8 columns at pitch 10) for sFp .. sPn and
-// 16 more behind sNs; the panels take 44 M and 3 CP M, no region uses the difference
+// 3 x 2 x LD_XFP floats.  slack: the launchers count 14 M doubles (NB == 4) or 30 M (three panels of up to 8 columns at pitch 10) for sFp .. sPn and
+// 16 more behind sNs; the panels take 12 M (NB == 4: two buffers, the matrix cores' operands stay in registers) and 3 CP M, no region uses the difference
 static __host__ __device__ constexpr size_t core_lds_end(int NB, int n) {          // CoreLds::end by itself, for the bodies: they lay their regions out behind it at run time
     size_t M = 16 * NB;
     size_t L = (NB == 4) ? M * (M + 2) : M * (M + 1) / 2;
-    return L + 2 * (M + 8) /*D,Y*/ + ((NB == 4) ? 46 : 30) * M /*F,G,panel + slack*/ + 2 * M /*scale,x*/ + 7 * (size_t) n + 16;
+    return L + 2 * (M + 8) /*D,Y*/ + ((NB == 4) ? 14 : 30) * M /*F,G,panel + slack*/ + 2 * M /*scale,x*/ + 7 * (size_t) n + 16;
 }
 struct CoreLds { size_t sL, sD, sY, sFp, sGp, sPn, sSc, sx, sNs, sTail, slack, end; };
 static __host__ __device__ constexpr CoreLds core_lds(int NB, int n) {
@@ -542,8 +542,8 @@ static __host__ __device__ constexpr CoreLds core_lds(int NB, int n) {
     o.sY = o.sD + M + 8;                                            // [M + 8]
     o.sFp = o.sTail = o.sY + M + 8;                                 // [M][CP]        (NB == 4: panel buffer A)
     o.sGp = o.sFp + CP * M;                                         // [M][CP]        (NB == 4: panel buffer B)
-    o.sPn = o.sGp + CP * M;                                         // [M][CP]        (NB == 4: per-wave copies of F, then of G: 2 x 4 x [M][4])
-    o.sSc = o.sPn + ((NB == 4) ? 2 * 4 * M * 4 : CP * M);           // [M]
+    o.sPn = o.sGp + CP * M;                                         // [M][CP]        (NB == 4: empty, the two buffers above alternate)
+    o.sSc = o.sPn + ((NB == 4) ? 0 : CP * M);                       // [M]
     o.sx = o.sSc + M;                                               // [M]
     o.sNs = o.sx + M;                                               // [7][n], the last region
     o.end = core_lds_end(NB, n);
@@ -623,6 +623,25 @@ static constexpr bool lds_layouts_ok() {
 }
 static_assert(lds_layouts_ok(), "solve kernels: an offset lost its alignment, an alias outgrew what it lies over, or a smaller window needs more LDS than a larger one");
 typedef double __attribute__((ext_vector_type(4))) ld_d4;
+
+// 4 x 4 transpose of (16-lane row group R = lane >> 4) x (register index q) over four doubles per lane, in registers: afterwards t[q] of lane (R, c) is what t[R] of
+// lane (q, c) was.  Per dword plane, v_permlane32_swap on the register pairs (0,2), (1,3) exchanges the off-diagonal 2 x 2 blocks (lanes 32..63 of vdst <-> lanes 0..31
+// of src), then v_permlane16_swap on (0,1), (2,3) transposes inside every block (odd row groups of vdst <-> even row groups of src): 16 swaps, no LDS, no wait.
+// vdst is the LOWER register of each pair; the other way round yields a wrong but finite matrix (NEXT.md, section 6).
+static __device__ __forceinline__ void transpose_rowgroups(double (&t)[4]) {
+    unsigned w[2][4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { w[0][q] = (unsigned) __double2loint(t[q]); w[1][q] = (unsigned) __double2hiint(t[q]); }
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+#pragma unroll
+        for (int q = 0; q < 2; q++) { const auto r = __builtin_amdgcn_permlane32_swap(w[p][q], w[p][q + 2], false, false); w[p][q] = r[0]; w[p][q + 2] = r[1]; }
+#pragma unroll
+        for (int q = 0; q < 4; q += 2) { const auto r = __builtin_amdgcn_permlane16_swap(w[p][q], w[p][q + 1], false, false); w[p][q] = r[0]; w[p][q + 1] = r[1]; }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) t[q] = __hiloint2double((int) w[1][q], (int) w[0][q]);
+}
 
 template <int NB, int C, bool GN, bool WAIT = false, bool MF = false>
 static __device__ __forceinline__ void solve_core(const BaPtrs &B, const BaDims &D, const ResSet &S, const ldso_settings_t &St, int iteration, double *sm, SolveIO &io) {
@@ -803,6 +822,7 @@ _Pragma("unroll") \
         // x -= (product of already known values) * inv_q, so that pivot d_{q+1} is ONE fma behind the reciprocal of d_q.
         // MF: every wavefront replays phase 1 for all 64 rows (lane = row) - the four copies run side by side on the four SIMDs and
         // spare the hand-over of F / G through a workgroup barrier; the panel buffers alternate (one barrier per round)
+        double Ta[4], Tb[4];          // MF: the matrix cores' operands of this round (see phase 2)
         if (MF || tid < M) {
             const double *sPr = MF ? (((k >> 2) & 1) ? sGp : sFp) : sPn;
             double c[C][C], inv[C];
@@ -856,12 +876,11 @@ _Pragma("unroll") \
                 const bool below = (i >= k + C);
                 const bool rowOn = below && (i <= n), colOn = below && (i < n);
                 if constexpr (MF) {
-                    double *Fw = sPn + wv * (M * 4), *Gw = sPn + 4 * M * 4 + wv * (M * 4);       // this wave's own copies: [M rows][4]
+                    // the masked -F and G of this lane's row, transposed in registers into MFMA operand order: afterwards Ta[t] / Tb[t] of lane l are
+                    // -F / G [16 t + (l & 15)][l >> 4], the A / B operand of every tile in tile row / tile column t
 #pragma unroll
-                    for (int q2 = 0; q2 < C; q2 += 2) {
-                        st2(&Fw[i * 4 + q2], rowOn ? f[rr][q2] : 0.0, rowOn ? f[rr][q2 + 1] : 0.0);
-                        st2(&Gw[i * 4 + q2], colOn ? g[rr][q2] : 0.0, colOn ? g[rr][q2 + 1] : 0.0);
-                    }
+                    for (int q = 0; q < C; q++) { Ta[q] = -(rowOn ? f[rr][q] : 0.0); Tb[q] = colOn ? g[rr][q] : 0.0; }
+                    transpose_rowgroups(Ta); transpose_rowgroups(Tb);
                 } else {
 #pragma unroll
                     for (int q2 = 0; q2 < C; q2 += 2) {
@@ -888,25 +907,26 @@ _Pragma("unroll") \
         }
         if constexpr (MF) {
             // ---------------- phase 2 on the matrix cores: one v_mfma_f64_16x16x4_f64 per live tile (D -= F_rows G_cols^T) -------------
-            // A operand: lane l supplies F[16 ta + (l & 15)][l >> 4], B operand: G[16 tb + (l & 15)][l >> 4] - read back from this
-            // wave's own LDS copies (same wave wrote them: no barrier).  Tile columns left of the next panel are finished.
-            RCYC(2, true);          // F, G, L, y, D stored
+            // A operand: lane l supplies -F[16 ta + (l & 15)][l >> 4], B operand: G[16 tb + (l & 15)][l >> 4] - Ta[ta] and Tb[tb], which phase 1 left in
+            // this wave's registers (no LDS copy, no wait between phase 1 and the matrix cores).  Tile columns left of the next panel are finished.
+            RCYC(2, true);          // L, y, D stored, operands transposed
             const int bDone = (k + C) >> 4, c0 = (k + C) & 15;
-            const double *Fw = sPn + wv * (M * 4), *Gw = sPn + 4 * M * 4 + wv * (M * 4);
             double *sPw = ((k >> 2) & 1) ? sFp : sGp;
+            // Ta[mta[s]] / Tb[mtb[s]] by wave-uniform selects, written out by what the tile tables hold: mta = wv | wv + 1 | min(wv + 2, 3), mtb = 0 | 1 | 2, 2, 3
+            // (14 v_cndmask a round; one case per wave with constant indices moved the accumulators between the cases and took 9 more registers)
+            const double aop[NS] = {(wv == 0) ? Ta[0] : (wv == 1) ? Ta[1] : (wv == 2) ? Ta[2] : Ta[3], (wv == 0) ? Ta[1] : (wv == 1) ? Ta[2] : Ta[3], (wv == 0) ? Ta[2] : Ta[3]};
+            const double bop[NS] = {Tb[0], Tb[1], (wv == 2) ? Tb[3] : Tb[2]};
 #pragma unroll
             for (int s_ = 0; s_ < NS; s_++) {
                 if (mta[s_] >= NB || mtb[s_] < bDone) continue;          // uniform per wave
-                const double aop = -Fw[(16 * mta[s_] + (lane & 15)) * 4 + (lane >> 4)];
-                const double bop = Gw[(16 * mtb[s_] + (lane & 15)) * 4 + (lane >> 4)];
-                Dv[s_] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bop, Dv[s_], 0, 0, 0);
+                Dv[s_] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[s_], bop[s_], Dv[s_], 0, 0, 0);
                 // owners of columns k+C .. k+2C-1 publish them as the next panel
                 if (mtb[s_] == bDone && (lane & 15) >= c0 && (lane & 15) < c0 + C) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) sPw[(16 * mta[s_] + (lane >> 4) + 4 * r) * CP + (lane & 15) - c0] = Dv[s_][r];
                 }
             }
-            RCYC(3, true);          // operands read back, matrix cores, next panel published
+            RCYC(3, true);          // operands selected, matrix cores, next panel published
             __syncthreads();
             RCYC(4, false);         // barrier
             continue;
