@@ -769,6 +769,14 @@ int ldso_init_set_points(ldso_initializer_t *t, int lvl, const ldso_init_point_t
  * as it stands.  H,Hsc 8x8 row-major, b,bsc 8, res = (E.A, alphaEnergy, E.num), ec = calcEC(lvl). */
 int ldso_init_calc_res_and_gs(ldso_initializer_t *t, int lvl, const double refToNew[12], double aff_a, double aff_b,
                               float *H, float *b, float *Hsc, float *bsc, float *res, float *ec);
+/* debug entries for the tests of the evaluation kernel (tests/test_init_stage_gpu.py); neither is part of trackFrame.
+ * get_jb: JbBuffer_new [n][10] of level lvl as the last evaluation wrote it (rows of points that are not good after it are not written).
+ * eval_step: one evaluation as trackFrame runs it, outside of it: the lazily applied applyStep of an accepted step (apply_pending), then resetPoints'
+ *   per-point part (mode 0) or doStep with inc[8] and lambda on the JbBuffer the previous evaluation wrote (mode 1), then calcResAndGS and calcEC at the
+ *   resulting idepth_new.  Outputs as ldso_init_calc_res_and_gs.  No step is pending afterwards; the next ldso_init_track_frame starts as after any other call. */
+int ldso_init_debug_get_jb(ldso_initializer_t *t, int lvl, float *jb_out);
+int ldso_init_debug_eval_step(ldso_initializer_t *t, int lvl, int mode, int apply_pending, const float inc[8], float lambda, const double refToNew[12],
+                              double aff_a, double aff_b, float *H, float *b, float *Hsc, float *bsc, float *res, float *ec);
 int ldso_init_set_new_frame(ldso_initializer_t *t, const float *irradiance, float ab_exposure);
 /* Launch schedule of ldso_init_track_frame (tuning / debugging; the results do not depend on it, bit for bit: tests/test_init_gpu.py).
  * first_steps: control steps (evaluation + control launch) enqueued before the state is read back for the first time; the rest of the

@@ -1479,6 +1479,24 @@ class Initializer:
         _chk(self.L.ldso_init_calc_res_and_gs(self.h, C.c_int(lvl), _p(T), C.c_double(a), C.c_double(b), _p(H), _p(bo), _p(Hsc), _p(bsc), _p(res), _p(ec)))
         return H, bo, Hsc, bsc, res, ec
 
+    def jb(self, lvl):
+        """JbBuffer_new [n, 10] of the last evaluation of the level (ldso_init_debug_get_jb); rows of points that are not good after it are not written"""
+        out = np.zeros((self.n[lvl], 10), np.float32)
+        _chk(self.L.ldso_init_debug_get_jb(self.h, C.c_int(lvl), _p(out)))
+        return out
+
+    def eval_step(self, lvl, mode, apply_pending, inc, lam, T, a, b):
+        """One evaluation as trackFrame runs it (ldso_init_debug_eval_step): applyStep if apply_pending, resetPoints' per-point part (mode 0) or doStep
+        (mode 1) with inc and lambda, then calcResAndGS and calcEC.  Returns what calc_res_and_gs returns."""
+        T = np.ascontiguousarray(np.asarray(T, dtype=np.float64)[:3, :4])
+        inc = np.ascontiguousarray(inc, np.float32)
+        assert inc.shape == (8,)
+        H = np.zeros((8, 8), np.float32); bo = np.zeros(8, np.float32); Hsc = np.zeros((8, 8), np.float32); bsc = np.zeros(8, np.float32)
+        res = np.zeros(3, np.float32); ec = np.zeros(3, np.float32)
+        _chk(self.L.ldso_init_debug_eval_step(self.h, C.c_int(lvl), C.c_int(mode), C.c_int(1 if apply_pending else 0), _p(inc), C.c_float(lam), _p(T),
+                                              C.c_double(a), C.c_double(b), _p(H), _p(bo), _p(Hsc), _p(bsc), _p(res), _p(ec)))
+        return H, bo, Hsc, bsc, res, ec
+
     # ---- setFirst from a resident pyramid (ldso_amd/csrc/init_first.hip) --------------------------------------------------------------------------
     @property
     def sparsity(self):

@@ -343,18 +343,11 @@ int ldso_init_set_points(ldso_initializer_t *H, int l, const ldso_init_point_t *
     return ini_put_points(H, l, pts);
 }
 
-int ldso_init_calc_res_and_gs(ldso_initializer_t *H, int lvl, const double refToNew[12], double aff_a, double aff_b,
-                              float *Hm, float *b, float *Hsc, float *bsc, float *res, float *ec) {
-    REQ(H && refToNew && lvl >= 0 && lvl < H->levels, "ldso_init_calc_res_and_gs: bad argument");
-    REQ(H->haveFirst && H->haveNew, "ldso_init_calc_res_and_gs: frames missing");
-    CHK(hipSetDevice(H->device));
-    CHK(hipStreamSynchronize(H->stream));
-    IniCtl c;
-    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
-    memcpy(c.Tnew, refToNew, sizeof(c.Tnew));
-    c.aNew = (float) aff_a; c.bNew = (float) aff_b; c.lvl = lvl;
+// One evaluation outside trackFrame: the control record c goes up, k_ini_eval (stage: calcResAndGS alone; otherwise as a step of trackFrame) and the
+// summing part of the control step run, and what they leave in the record is handed out.
+static int ini_stage_eval(ldso_initializer *H, IniCtl &c, int stage, float *Hm, float *b, float *Hsc, float *bsc, float *res, float *ec) {
     CHK(hipMemcpy(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
-    ini_launch_eval(H->P, 1, H->stream);
+    ini_launch_eval(H->P, stage, H->stream);
     ini_launch_ctl(H->P, INI_STAGE, H->ldsBytes, H->stream);
     CHK(hipGetLastError());
     CHK(hipStreamSynchronize(H->stream));
@@ -365,6 +358,49 @@ int ldso_init_calc_res_and_gs(ldso_initializer_t *H, int lvl, const double refTo
     if (bsc) memcpy(bsc, c.bscn, sizeof(c.bscn));
     if (res) memcpy(res, c.resNew, sizeof(c.resNew));
     if (ec) memcpy(ec, c.ec, sizeof(c.ec));
+    return LDSO_OK;
+}
+
+int ldso_init_calc_res_and_gs(ldso_initializer_t *H, int lvl, const double refToNew[12], double aff_a, double aff_b,
+                              float *Hm, float *b, float *Hsc, float *bsc, float *res, float *ec) {
+    REQ(H && refToNew && lvl >= 0 && lvl < H->levels, "ldso_init_calc_res_and_gs: bad argument");
+    REQ(H->haveFirst && H->haveNew, "ldso_init_calc_res_and_gs: frames missing");
+    CHK(hipSetDevice(H->device));
+    CHK(hipStreamSynchronize(H->stream));
+    IniCtl c;
+    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
+    memcpy(c.Tnew, refToNew, sizeof(c.Tnew));
+    c.aNew = (float) aff_a; c.bNew = (float) aff_b; c.lvl = lvl;
+    return ini_stage_eval(H, c, 1, Hm, b, Hsc, bsc, res, ec);
+}
+
+int ldso_init_debug_eval_step(ldso_initializer_t *H, int lvl, int mode, int apply_pending, const float inc[8], float lambda, const double refToNew[12],
+                              double aff_a, double aff_b, float *Hm, float *b, float *Hsc, float *bsc, float *res, float *ec) {
+    REQ(H && inc && refToNew && lvl >= 0 && lvl < H->levels && (mode == 0 || mode == 1), "ldso_init_debug_eval_step: bad argument");
+    REQ(H->haveFirst && H->haveNew, "ldso_init_debug_eval_step: frames missing");
+    CHK(hipSetDevice(H->device));
+    CHK(hipStreamSynchronize(H->stream));
+    IniCtl c;
+    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
+    memcpy(c.Tnew, refToNew, sizeof(c.Tnew));
+    c.aNew = (float) aff_a; c.bNew = (float) aff_b; c.lvl = lvl;
+    c.mode = mode; c.applyPending = apply_pending ? 1 : 0; c.lambda = lambda; c.done = 0; c.sweepDue = 0;
+    memcpy(c.inc, inc, sizeof(c.inc));
+    c.jbSel ^= 1;                                                           // as an accepted step does: what the previous evaluation wrote is JbBuffer now
+    RUN(ini_stage_eval(H, c, 0, Hm, b, Hsc, bsc, res, ec));
+    c.applyPending = 0;                                                     // the step is applied; ldso_init_get_points takes the handle again
+    CHK(hipMemcpy(H->P.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
+    return LDSO_OK;
+}
+
+int ldso_init_debug_get_jb(ldso_initializer_t *H, int lvl, float *out) {
+    REQ(H && out && lvl >= 0 && lvl < H->levels, "ldso_init_debug_get_jb: bad argument");
+    REQ(H->haveFirst, "ldso_init_debug_get_jb: no first frame");
+    CHK(hipSetDevice(H->device));
+    CHK(hipStreamSynchronize(H->stream));
+    IniCtl c;
+    CHK(hipMemcpy(&c, H->P.ctl, sizeof(c), hipMemcpyDeviceToHost));
+    if (H->n[lvl]) CHK(hipMemcpy(out, H->P.L[lvl].jb[c.jbSel ^ 1], (size_t) H->n[lvl] * 10 * sizeof(float), hipMemcpyDeviceToHost));
     return LDSO_OK;
 }
 

@@ -628,10 +628,9 @@ def select_init_points(pyr, densities=INIT_DENSITIES, grad_th=8.0, outlier_th=12
     """Stand-in for the pixel selection of CoarseInitializer::setFirst (PixelSelector::makeMaps / makePixelStatus, not on the
     path) plus an exact restatement of the point records (:567-603) and of makeNN (:717-783; k-d tree queries by scipy).
     pyr: list of float32 [h,w,3] (I,dx,dy).  Returns one INIT_POINT_DTYPE array per level, points in raster order."""
-    from scipy.spatial import cKDTree
     levels = len(pyr)
     h0, w0 = pyr[0].shape[:2]
-    out = []
+    pixels = []
     for lvl in range(levels):
         hl, wl = pyr[lvl].shape[:2]
         g2 = pyr[lvl][..., 1] ** 2 + pyr[lvl][..., 2] ** 2
@@ -652,6 +651,18 @@ def select_init_points(pyr, densities=INIT_DENSITIES, grad_th=8.0, outlier_th=12
         xx = x0 + bx * bs + am[by, bx] % bs
         sel[yy, xx] = True
         ys, xs = np.nonzero(sel)                            # raster order
+        pixels.append((xs, ys))
+    return init_point_records(pixels, outlier_th)
+
+
+def init_point_records(pixels, outlier_th=12.0 * 12.0):
+    """The point records of setFirst (:567-603) and makeNN (:717-783; k-d tree queries by scipy) for given pixels: pixels[lvl] = (xs, ys), integer
+    pixel coordinates of the level's points in the order the records are to have.  Returns one INIT_POINT_DTYPE array per level."""
+    from scipy.spatial import cKDTree
+    levels = len(pixels)
+    out = []
+    for xs, ys in pixels:
+        xs, ys = np.asarray(xs), np.asarray(ys)
         pts = np.zeros(len(xs), INIT_POINT_DTYPE)
         pts["u"] = (xs + 0.1).astype(np.float32)
         pts["v"] = (ys + 0.1).astype(np.float32)
