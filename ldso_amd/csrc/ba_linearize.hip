@@ -1281,7 +1281,7 @@ __global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch(const BatchIt
 }
 
 // linearizeAll(true) at the end of a batched optimize() (ldso_ba_batch_optimize), one slot group per point: every window reads ITS applied set, which the parity
-// of its own last executed iteration names (scalars[LD_SC_STOP], see k_solve_batch in ba_solve.hip), and writes the other one.
+// of its own last executed iteration names (scalars[LD_SC_STOP], see k_solve_batch in ba_solve_batch.hip), and writes the other one.
 __global__ __launch_bounds__(64 * LD_WAVES) void k_linearize_batch_fix(const BatchItem *__restrict__ items, const BatchBlock *__restrict__ blocks, const int32_t *__restrict__ wgStart,
                                                                        ldso_settings_t S, float calibPrior) {
     int b0 = (int) blockIdx.x, b1 = b0 + 1;

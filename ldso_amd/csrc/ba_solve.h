@@ -1,4 +1,4 @@
-// ba_solve.h — launch arguments of the control kernel (see ba_solve.hip)
+// ba_solve.h — launch arguments of the control kernels (see ba_solve.hip, ba_solve_body.h)
 #pragma once
 #include <stdint.h>
 

@@ -147,3 +147,13 @@ LD_HD void frame_nullspaces(const double *evalPT, double state_zero_a, float ab_
 }
 
 }  // namespace ld
+
+#if defined(__HIPCC__)
+// AffLight::fromToVecExposure in float: the brightness transfer (a, b) from a frame with exposure expF and affine (aF, bF) to one with expT, (aT, bT).
+// Device code only, outside the namespace: the bundle adjustment's pair records and the tracker call it by this name.
+static __device__ __forceinline__ void aff_from_to(float expF, float expT, float aF, float bF, float aT, float bT, float &a, float &b) {
+    if (expF == 0 || expT == 0) { expT = expF = 1; }
+    a = expf(aT - aF) * expT / expF;
+    b = bT - a * bF;
+}
+#endif

@@ -21,12 +21,6 @@
 // ---------------------------------------------------------------------------------------------------------
 #define TR_U 4            // points per thread and pass of tr_eval
 
-__device__ __forceinline__ void aff_from_to_f(float expF, float expT, float aF, float bF, float aT, float bT, float &a, float &b) {
-    if (expF == 0 || expT == 0) { expT = expF = 1; }
-    a = expf(aT - aF) * expT / expF;
-    b = bT - a * bF;
-}
-
 // A workgroup's share of a level: nAct workgroups split the n points into contiguous chunks (multiples of 64); a workgroup
 // works with only as many wavefronts as its share needs (TR_U points per lane), so the small levels pay the 52-value reduction
 // on few wavefronts.  The points of the first pass stay in registers across the evaluations of a level (they do not depend on the
@@ -68,7 +62,7 @@ __device__ __forceinline__ void tr_eval(const TrParams &P, int lvl, const float 
     for (int r = 0; r < 3; r++) t[r] = Rt[9 + r];
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) RKi[r * 3 + c] = (Rt[r * 3 + 0] * L.Ki[0 * 3 + c] + Rt[r * 3 + 1] * L.Ki[1 * 3 + c]) + Rt[r * 3 + 2] * L.Ki[2 * 3 + c];
     float affA, affB;
-    aff_from_to_f(P.ref_exposure, P.new_exposure, P.ref_a, P.ref_b, aff_a, aff_b, affA, affB);
+    aff_from_to(P.ref_exposure, P.new_exposure, P.ref_a, P.ref_b, aff_a, aff_b, affA, affB);
     const float maxEnergy = 2 * P.huberTH * cutoffTH - P.huberTH * P.huberTH;
     const float b0 = P.ref_b;
 
@@ -653,7 +647,7 @@ __device__ __forceinline__ void tr_track_body(const TrParams &P, TrHyp &hy, TrCo
             bool ok = true;
             if ((P.affineOptModeA != 0 && (fabsf(a) > 1.2)) || (P.affineOptModeB != 0 && (fabsf(b) > 200))) ok = false;
             float ra, rb;
-            aff_from_to_f(P.ref_exposure, P.new_exposure, P.ref_a, P.ref_b, a, b, ra, rb);
+            aff_from_to(P.ref_exposure, P.new_exposure, P.ref_a, P.ref_b, a, b, ra, rb);
             if ((P.affineOptModeA == 0 && (fabsf(logf(ra)) > 1.5)) || (P.affineOptModeB == 0 && (fabsf(rb) > 200))) ok = false;
             if (ok) { if (P.affineOptModeA < 0) a = 0; if (P.affineOptModeB < 0) b = 0; }
             hy.a = a; hy.b = b;

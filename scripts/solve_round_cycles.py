@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the control workgroup of k_reduce_solve spends its time, as JSON (stamps build: scripts/build_variant.sh stamps ba_solve.hip -DLDSO_STAMPS, then
+"""Where the control workgroup of k_reduce_solve spends its time, as JSON (stamps build of the unit that holds k_reduce_solve: scripts/build_variant.sh stamps ba_solve.hip -DLDSO_STAMPS, then
 LDSO_HIP_LIB=ldso_amd/libldso_hip_stamps.so python scripts/solve_round_cycles.py [config] [out.json]).  Medians over 12 launches of one iteration:
 cycles per round of the 4-column LDL^T on wave 0 (solve_core's RCYC counters) and the split of the control step in us (100 MHz wall clock stamps)."""
 import ctypes as C

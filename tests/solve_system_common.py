@@ -1,4 +1,4 @@
-"""Supplied-system tests of solve_core (ba_solve.hip): case generation, references and harnesses shared by tests/test_solve64_operands_gpu.py (NB = 4, the 64 x 64
+"""Supplied-system tests of solve_core (ba_ldlt.h): case generation, references and harnesses shared by tests/test_solve64_operands_gpu.py (NB = 4, the 64 x 64
 system on the matrix cores), tests/test_solve_large_cpu.py and tests/test_solve_large_gpu.py (NB = 7 / 9, the 112- and 144-row VALU variants).
 
 References of one operation - x = S (S H S)^+ S b with S = (diag H + 10)^-1/2, rows / columns that are exactly zero give x = 0, then (iteration >= 2) x -= U U^T x
@@ -17,7 +17,7 @@ import functools
 import numpy as np
 
 TINY = 2.2250738585072014e-308          # solve_core: |d| <= TINY -> inv = 0
-RCP_REL = 2.2e-15                       # fast_rcp (ba_solve.hip): documented relative error of the pivot reciprocal
+RCP_REL = 2.2e-15                       # fast_rcp (ba_ldlt.h): documented relative error of the pivot reciprocal
 E_MODEL_DRAWS = 4
 MARGIN = 3.0                            # the kernel against e_model
 

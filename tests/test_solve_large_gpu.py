@@ -1,4 +1,4 @@
-"""The 112- and 144-row LDL^T of solve_core<7> / <9> (n + 1 = 69 .. 133: windows of 8 .. 16 key frames, VALU) on systems the test supplies, against the long-double
+"""The 112- and 144-row LDL^T of solve_core<7> / <9> (ba_ldlt.h; n + 1 = 69 .. 133: windows of 8 .. 16 key frames, VALU) on systems the test supplies, against the long-double
 solution of the same operation - the test the 64 x 64 variant has in tests/test_solve64_operands_gpu.py, for the code that is specific to the large variants: the
 |d| <= TINY -> inv = 0 pivot, a negative pivot, the packed LIX storage of L, the two- and three-segment back substitution (lane l owns rows l, l + 64, l + 128; x_k is
 broadcast across the 64 | 128 boundaries), the right-hand-side row n at row 4 or 12 of tiles 4 .. 8, the padding rows n + 1 .. M - 1, the gauge projection with up to
