@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libldso_hip.so")
-SOURCES = ["ba_linearize.hip", "ba_reduce.hip", "ba_solve.hip", "ba_solve_batch.hip", "ba_step.hip", "ba_api.hip", "ba_window.hip", "ba_optimize.hip", "ba_batch.hip", "ba_dist.hip", "tracker.hip", "tracker_ref.hip", "tracker_api.hip", "tracker_group.hip", "tracker_hyp.cpp",
+SOURCES = ["ba_linearize.hip", "ba_linearize_batch.hip", "ba_reduce.hip", "ba_solve.hip", "ba_solve_batch.hip", "ba_step.hip", "ba_api.hip", "ba_window.hip", "ba_optimize.hip", "ba_batch.hip", "ba_dist.hip", "tracker.hip", "tracker_ref.hip", "tracker_api.hip", "tracker_group.hip", "tracker_hyp.cpp",
            "images.hip", "trace.hip", "trace_group.hip", "ba_activate.hip", "act_select.hip", "initializer.hip", "initializer_api.hip", "initializer_sched.cpp", "init_first.hip", "init_nn_tree.cpp", "features.hip", "pixel_select.hip", "undistort.hip"]
 # -ffp-contract=off: elementwise arithmetic is IEEE and follows the reference's operation order (bit-identical
 # energies / residual states); fused multiply-adds are spelled explicitly where they are wanted.

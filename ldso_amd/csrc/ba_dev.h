@@ -84,7 +84,7 @@ struct alignas(64) PtGeo {
 };
 static_assert(sizeof(PtGeo) == 64, "PtGeo is one 64-byte line");
 struct PtCw { float color, weight; };
-// the lane <-> dword maps the kernels rely on (ba_linearize.hip: load_point, the slot / point stores)
+// the lane <-> dword maps the kernels rely on (ba_lin_load.h: load_point; ba_linearize_body.h: the slot / point stores)
 #include <stddef.h>
 static_assert(offsetof(SlotRec, e[3].m) == 8 * 3 + 4 && offsetof(SlotRec, e[7].jp) == 56, "SlotRec: lane k owns dwords 2k (JpJdF[k]) and 2k+1 (scalar k)");
 static_assert(sizeof(SlotTab) == 16 && offsetof(SlotTab, rlin) == 4 && offsetof(SlotTab, rnew) == 8 && offsetof(SlotTab, rlidx) == 12, "SlotTab: x = rflat, y = rlin, z = rnew, w = rlidx");
@@ -98,8 +98,8 @@ static_assert(sizeof(PtCw) == 8, "PtCw: one dwordx2");
 
 // One of the two ping-pong sets (see header comment).
 struct ResSet {
-    // Field ORDER matters: the batched linearisation kernel fetches these pointers just in time with one s_load_dwordx16 (ba_linearize.hip:
-    // LDG16): the first eight pointers are one group (64 bytes).
+    // Field ORDER matters: the batched linearisation kernel fetches these pointers just in time with one s_load_dwordx16 (ba_lin_load.h:
+    // ldg16): the first eight pointers are one group (64 bytes).
     SlotRec *slot;         // [P*FS]
     PtRec *pt;             // [P]
     PtAcc *acc;            // [P]
@@ -130,7 +130,7 @@ struct BaPtrs {
     float *adHostF, *adTargetF;
     double *nsProj;                  // n*n projector onto the gauge nullspaces (reference ordering)
     double *HM, *bM;
-    // points and residual slots: ONE group of eight consecutive pointers (ba_linearize.hip: LDG16) - everything a wave reads / writes of a point
+    // points and residual slots: ONE group of eight consecutive pointers (ba_lin_load.h: ldg16) - everything a wave reads / writes of a point
     PtGeo *pgeo;                     // [P]     geometry + inverse depth + the scalars of the last solve, 64 bytes per point          ---- group B0
     PtCw *pcw;                       // [P*8]   (colour, weight) of the 8 pattern pixels
     SlotTab *rtab;                   // [P*FS]  residual slots: flat residual index (-1: none), linearised?, new?, index into Jlin / rtz

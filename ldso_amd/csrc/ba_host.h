@@ -37,7 +37,7 @@ inline ActWin act_win(const ldso_immature_t *d_pts, ldso_activation_t *d_out, in
     return T;
 }
 
-// the launchers, defined beside their kernels (ba_linearize / ba_reduce / ba_solve / ba_solve_batch / ba_step / ba_activate .hip)
+// the launchers, defined beside their kernels (ba_linearize / ba_linearize_batch / ba_reduce / ba_solve / ba_solve_batch / ba_step / ba_activate .hip)
 hipError_t ba_launch_linearize(const BaPtrs &B, const BaDims &D, const ResSet &cur, const ResSet &nxt, const ldso_settings_t &S, bool hasL, bool fix, int stepMode, const GnInit &gi, hipStream_t st);
 hipError_t ba_launch_reduce(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, bool hasL, int GSP, int atomicMode, bool hasPrior, float calibPrior, double l1, double il, int itCheck, hipStream_t st);
 hipError_t ba_launch_gather(const BaPtrs &B, const BaDims &D, const ResSet &S, bool hasL, bool hasPrior, int GSP, double lambda, const ldso_settings_t &St, int mode, double *rbuf, hipStream_t st);

@@ -1,6 +1,7 @@
 """Device wall-clock stamps (10 ns ticks since the workgroup started) of one mid-launch workgroup of the batched k_linearize (window 20 of 32,
 its chunk 0, wave 0): 1 operands staged, 2 first point starts, 3 its taps about to be issued, 4 taps back, 5 its slot loop done, 6 all points
-of the wave done, 7 block reduction barrier passed.  Needs a library built with -DLDSO_STAMPS for ba_linearize.hip (scripts/build_variant.sh)."""
+of the wave done, 7 block reduction barrier passed.  Needs a library built with -DLDSO_STAMPS for ba_linearize_batch.hip, the unit of the batched kernels
+(scripts/build_variant.sh stamps ba_linearize_batch.hip -DLDSO_STAMPS)."""
 import sys, ctypes as C
 sys.path.insert(0, '.')
 import numpy as np, torch
