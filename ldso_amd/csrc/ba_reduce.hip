@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void k_reduce(BaPtrs B, BaDims D, ResSet S, Ch
                                                 int hasPrior, float calibPrior, double l1, double il, int itCheck) {
     static_assert(sizeof(BaPtrs) + sizeof(BaDims) + sizeof(ResSet) + sizeof(ChunkStarts) >= 8 * 64 - 60, "k_reduce: ld_touch_kernarg<8> must stay inside the arguments");
     ld_touch_kernarg<8>();           // 620 bytes of arguments: the first 512 into the scalar cache with one wait (ba_dev.h): 9.24 -> 9.03 us at C3
-    reduce_body(B, D, S, chunkStart, hasL, GSP, atomicMode, hasPrior, calibPrior, l1, il, itCheck, (int) blockIdx.x);
+    reduce_body<RT_DIRECT>(B, D, S, chunkStart, hasL, GSP, atomicMode, hasPrior, calibPrior, l1, il, itCheck, (int) blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -157,7 +157,7 @@ hipError_t ba_launch_gather(const BaPtrs &B, const BaDims &D, const ResSet &S, b
 hipError_t ba_launch_reduce(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, bool hasL, int GSP, int atomicMode, bool hasPrior,
                             float calibPrior, double l1, double il, int itCheck, hipStream_t st) {
     const int nb = atomicMode ? reduce_grid(D.F, hasL, D.ks, GSP).total : reduce_pairs(D.F, hasL) + LD_SC_SPLITS;
-    const size_t lds = atomicMode ? reduce_atomic_lds_bytes() : (size_t) (SC_SLAB * GSP) * sizeof(float);
+    const size_t lds = atomicMode ? reduce_atomic_lds_bytes(RT_DIRECT) : (size_t) (SC_SLAB * GSP) * sizeof(float);
     return launch_lds(k_reduce, dim3(nb), dim3(256), lds, st, B, D, S, chunkStart, hasL ? 1 : 0, GSP, atomicMode, hasPrior ? 1 : 0, calibPrior, l1, il, itCheck);
 }
 
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_reduce_batch_marg(const BatchItem *__re
     const MargWin m = mw[w];
     if (!m.active) return;
     const BatchItem &it = items[w];
-    reduce_body(it.B, it.D, it.set[1], it.cs, 0, it.GSP, 0, 0, 0.0f, 1.0, 1.0, -1, (int) blockIdx.x - m.redBlock0);
+    reduce_body<RT_STAGED>(it.B, it.D, it.set[1], it.cs, 0, it.GSP, 0, 0, 0.0f, 1.0, 1.0, -1, (int) blockIdx.x - m.redBlock0);          // (no atomic mode here: no tile workgroups)
 }
 
 hipError_t ba_launch_reduce_batch_marg(const BatchItem *d_items, const MargWin *d_mw, int nWin, int totalBlocks, int maxGSP, hipStream_t st) {

@@ -9,12 +9,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define PA_SLICES 2     // Part A: interleaved slices of a pair's chunk range (2 x 91 threads)
 #define PA_UNROLL 24    // Part A: partial loads in flight per thread
 #define SCT_KS LD_SCT_KS // atomic mode: K-splits per Schur tile
-#define SCT_SLAB 512    // atomic mode: points staged per LDS slab of a tile block
+#define SCT_SLAB 512    // atomic mode, staged tiles: points staged per LDS slab of a tile block
+#define SCT_BATCH 256   // atomic mode, direct tiles: rows whose operands a tile block has in flight at once (16 k-steps per wavefront)
 #define SC_MAXT 12      // tiles per wave: GSP=144 (FS=16) -> 45 upper tiles / 4 waves
 
+// How a tile workgroup of the atomic mode gets its matrix-core operands (reduce_body<TILES>); the partial tiles are the same to the bit.
+//   RT_STAGED  through an LDS slab filled with 16-byte loads: fewest instructions and registers - the batched kernels, bound by throughput
+//   RT_DIRECT  every lane loads its own operands from G, all loads of a batch issued before the first wait: no slab, no barrier in front of the
+//              matrix cores - the kernels of a lone window (k_reduce_solve, k_reduce), where the workgroup's latency is the iteration's
+enum ReduceTiles { RT_STAGED, RT_DIRECT };
+
 __host__ __device__ constexpr int tri13r(int r, int c) { return r * 13 - (r * (r - 1)) / 2 + (c - r); }
-// dynamic LDS of a workgroup in atomic mode: the slab of a tile workgroup, two 16-column blocks of SCT_SLAB G rows and their weights (reduce_body: sAc, sBc, sWc)
-__host__ __device__ constexpr size_t reduce_atomic_lds_bytes() { return (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB) * sizeof(float); }
+// dynamic LDS of a workgroup in atomic mode.  Staged: the slab of a tile workgroup, two 16-column blocks of SCT_SLAB G rows and their weights (reduce_body: sAc,
+// sBc, sWc); direct: only the four waves' partial tiles (sR), which the slab holds as well
+__host__ __device__ constexpr size_t reduce_atomic_lds_bytes(ReduceTiles tiles) {
+    return (tiles == RT_DIRECT ? (size_t) 4 * 256 : (size_t) (2 * SCT_SLAB * 16 + SCT_SLAB)) * sizeof(float);
+}
 
 // chunkStart[h]..chunkStart[h+1]: chunks of host h (chunks are host-major)
 // atomicMode (GN fast path): instead of pairC / scPart the results are added (fp64 atomics) straight into the lower triangle of
@@ -22,9 +32,15 @@ __host__ __device__ constexpr size_t reduce_atomic_lds_bytes() { return (size_t)
 //   HFinal = (H_A + H_L + priors + H_M) with diag * (1+lambda) - H_sc / (1+lambda)   ->  top terms are scaled by l1 = 1+lambda on the
 //   diagonal, Schur terms by -il = -1/(1+lambda);  bFinal = b_A + b_L + (prior delta + b_M + H_M delta) - b_sc.
 static __device__ __forceinline__ void acc_add(double *p, double v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// one float through a raw buffer descriptor (stride 0, range in bytes): a byte offset outside the range reads 0.0f and touches no memory
+#define LD_BUFFER_RAW_DWORDS 0x00020000          // word 3 of the descriptor on gfx9: 32-bit data format, nothing else
+static __device__ __forceinline__ float buffer_float(__amdgpu_buffer_rsrc_t rsrc, unsigned byteOffset) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int) byteOffset, 0, 0));
+}
 
 template <int NT, int W> static __device__ __forceinline__ void schur_wave(const float *sG, int GSP, int cnt, int wcol, int li, int lk, f32x4 *acc);
 
+template <ReduceTiles TILES>
 static __device__ __forceinline__ void reduce_body(const BaPtrs &B, const BaDims &D, const ResSet &S, const ChunkStarts &chunkStart, int hasL, int GSP, int atomicMode,
                                    int hasPrior, float calibPrior, double l1, double il, int itCheck, const int bid) {
     if (LD_ITER_SKIPPED(B, itCheck)) return;
@@ -137,8 +153,8 @@ static __device__ __forceinline__ void reduce_body(const BaPtrs &B, const BaDims
         // The block stages the two 16-column blocks of its G rows (and the weights HdiF) in LDS with 16-byte loads, its four
         // waves interleave the k-steps of v_mfma_f32_16x16x4_f32, the four partial tiles are summed through LDS and each
         // thread adds ONE element (scaled by -1/(1+lambda)) into HFinal / bFinal: KS-way contention per address.
+        // RT_DIRECT: no slab - see below; which k-step goes into which accumulator, and in which order, is the same in both.
         extern __shared__ __attribute__((aligned(16))) float sT_[];
-        float *sAc = sT_, *sBc = sAc + SCT_SLAB * 16, *sWc = sBc + SCT_SLAB * 16;      // [SLAB][16], [SLAB][16], [SLAB]
         const int bb = bid - nSplitBase, tile = bb / KS, ks = bb % KS;
         const int nT = GSP / 16, GS = D.GS, n = D.n;
         int ti = 0, rem = tile;
@@ -149,49 +165,91 @@ static __device__ __forceinline__ void reduce_body(const BaPtrs &B, const BaDims
         const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
         const int wcol = 8 * FS + 5;
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f}, acc2 = acc;
-        for (int base = pa; base < pb; base += SCT_SLAB) {
-            const int cnt = min(SCT_SLAB, pb - base), rows = (cnt + 3) & ~3;
-            __syncthreads();
-            {
-                // float4 e of the slab: row r = e / 8, half = (e / 4) & 1 (A or B column block), c4 = e & 3
-                float4 q[16];
-                float wq[2];
+        if constexpr (TILES == RT_DIRECT) {
+            // Lane (lk, li) of the k-step at row k0 needs G[k0 + lk][16 ti + li] (times the row's weight) and G[k0 + lk][16 tj + li]: four 64-byte
+            // segments per wavefront load.  A wavefront issues the loads of all its 16 k-steps of a batch of SCT_BATCH rows - straight-line, no branch
+            // at the cold start of the kernel - and only then waits, once; nothing goes through LDS, so no barrier either.  The loads are buffer loads
+            // against a descriptor that spans exactly the batch's rows: the hardware checks the range, a row behind the split (or a padding column,
+            // whose lanes carry an offset far outside) comes back as 0.0f without touching memory - the slab's clamped addresses and masked values.
+            // The k-steps at k0 = 4 wave + 32 j go into acc and those at k0 + 16 into acc2, j ascending, batch after batch; a k-step behind the rows
+            // of a short split is left out, and where only the one at k0 + 16 is, it runs with a zero A operand and the B operand of row k0: all as
+            // the staged loop has it, so the partial tiles are the same to the bit.
+            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            const int colA = ti * 16 + li, colB = tj * 16 + li;
+            constexpr unsigned OUTSIDE = 0x80000000u;          // beyond every descriptor: a batch spans SCT_BATCH * 4 GS bytes
+            const unsigned rowB = 4u * (unsigned) GS, oA = colA < GS ? 4u * (unsigned) colA : OUTSIDE, oB = colB < GS ? 4u * (unsigned) colB : OUTSIDE, oW = 4u * (unsigned) wcol;
+            const unsigned r0 = (unsigned) (4 * wv + lk) * rowB;
+            for (int base = pa; base < pb; base += SCT_BATCH) {
+                const int cnt = min(SCT_BATCH, pb - base), rows = (cnt + 3) & ~3;
+                const __amdgpu_buffer_rsrc_t rowsG = __builtin_amdgcn_make_buffer_rsrc((void *) (S.G + (size_t) base * GS), (short) 0, cnt * (int) rowB, LD_BUFFER_RAW_DWORDS);
+                float aq[16], bq[16], wq[16];
 #pragma unroll
-                for (int u = 0; u < 16; u++) {
-                    const int e = tid + u * 256, r = e >> 3, half = (e >> 2) & 1, c4 = e & 3;
-                    const int col = (half ? tj : ti) * 16 + c4 * 4;
-                    // branch-free (clamped address, masked value): straight-line code keeps the instruction prefetch going at the
-                    // cold start of the kernel
-                    const float4 v = *(const float4 *) (S.G + (unsigned) ((base + min(r, cnt - 1)) * GS + min(col, GS - 4)));
-                    const bool in = r < cnt && col < GS;
-                    q[u] = make_float4(in ? v.x : 0.f, in ? v.y : 0.f, in ? v.z : 0.f, in ? v.w : 0.f);
+                for (int s = 0; s < 16; s++) {          // s = 2 j: rows k0 + lk;  s = 2 j + 1: rows k0 + 16 + lk
+                    const unsigned ro = r0 + (unsigned) (16 * s) * rowB;
+                    aq[s] = buffer_float(rowsG, ro + oA); bq[s] = buffer_float(rowsG, ro + oB); wq[s] = buffer_float(rowsG, ro + oW);
                 }
+                // the one wait: the empty statements take the loaded values as operands and stay where they are, so no load moves down behind a branch
 #pragma unroll
-                for (int u = 0; u < 2; u++) { const int r = tid + u * 256; const float v = S.G[(unsigned) ((base + min(r, cnt - 1)) * GS + wcol)]; wq[u] = (r < cnt) ? v : 0.f; }
+                for (int s = 0; s < 16; s++) asm volatile("" : "+v"(aq[s]), "+v"(bq[s]), "+v"(wq[s]));
+                if (bb == 0 && base == pa) RSTAMP(25);
 #pragma unroll
-                for (int u = 0; u < 16; u++) {
-                    const int e = tid + u * 256, r = e >> 3, half = (e >> 2) & 1, c4 = e & 3;
-                    if (r < rows) *(float4 *) ((half ? sBc : sAc) + r * 16 + c4 * 4) = q[u];
+                for (int j = 0; j < 8; j++) {
+                    const int k0 = 4 * wv + 32 * j;
+                    if (k0 < rows) {
+                        const bool in1 = k0 + 16 < rows;
+                        const float a0 = aq[2 * j] * wq[2 * j], b0 = bq[2 * j];
+                        const float a1 = in1 ? aq[2 * j + 1] * wq[2 * j + 1] : 0.f, b1 = in1 ? bq[2 * j + 1] : bq[2 * j];
+                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc, 0, 0, 0);
+                        acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc2, 0, 0, 0);
+                    }
                 }
-#pragma unroll
-                for (int u = 0; u < 2; u++) { const int r = tid + u * 256; if (r < rows) sWc[r] = wq[u]; }
             }
-            __syncthreads();
-            if (bb == 0) RSTAMP(25);
-            // two independent accumulation chains per wave (an MFMA depends on the previous one through its accumulator)
+        } else {
+            float *sAc = sT_, *sBc = sAc + SCT_SLAB * 16, *sWc = sBc + SCT_SLAB * 16;      // [SLAB][16], [SLAB][16], [SLAB]
+            for (int base = pa; base < pb; base += SCT_SLAB) {
+                const int cnt = min(SCT_SLAB, pb - base), rows = (cnt + 3) & ~3;
+                __syncthreads();
+                {
+                    // float4 e of the slab: row r = e / 8, half = (e / 4) & 1 (A or B column block), c4 = e & 3
+                    float4 q[16];
+                    float wq[2];
+#pragma unroll
+                    for (int u = 0; u < 16; u++) {
+                        const int e = tid + u * 256, r = e >> 3, half = (e >> 2) & 1, c4 = e & 3;
+                        const int col = (half ? tj : ti) * 16 + c4 * 4;
+                        // branch-free (clamped address, masked value): straight-line code keeps the instruction prefetch going at the
+                        // cold start of the kernel
+                        const float4 v = *(const float4 *) (S.G + (unsigned) ((base + min(r, cnt - 1)) * GS + min(col, GS - 4)));
+                        const bool in = r < cnt && col < GS;
+                        q[u] = make_float4(in ? v.x : 0.f, in ? v.y : 0.f, in ? v.z : 0.f, in ? v.w : 0.f);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 2; u++) { const int r = tid + u * 256; const float v = S.G[(unsigned) ((base + min(r, cnt - 1)) * GS + wcol)]; wq[u] = (r < cnt) ? v : 0.f; }
+#pragma unroll
+                    for (int u = 0; u < 16; u++) {
+                        const int e = tid + u * 256, r = e >> 3, half = (e >> 2) & 1, c4 = e & 3;
+                        if (r < rows) *(float4 *) ((half ? sBc : sAc) + r * 16 + c4 * 4) = q[u];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 2; u++) { const int r = tid + u * 256; if (r < rows) sWc[r] = wq[u]; }
+                }
+                __syncthreads();
+                if (bb == 0) RSTAMP(25);
+                // two independent accumulation chains per wave (an MFMA depends on the previous one through its accumulator)
 #pragma unroll 4
-            for (int k0 = wave * 4; k0 < rows; k0 += 32) {
-                const int k1 = k0 + 16;
-                const float a0 = sAc[(k0 + lk) * 16 + li] * sWc[k0 + lk], b0 = sBc[(k0 + lk) * 16 + li];
-                const bool in1 = k1 < rows;
-                const int k1c = in1 ? k1 : k0;
-                const float a1 = in1 ? sAc[(k1c + lk) * 16 + li] * sWc[k1c + lk] : 0.f, b1 = sBc[(k1c + lk) * 16 + li];
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc2, 0, 0, 0);
+                for (int k0 = wave * 4; k0 < rows; k0 += 32) {
+                    const int k1 = k0 + 16;
+                    const float a0 = sAc[(k0 + lk) * 16 + li] * sWc[k0 + lk], b0 = sBc[(k0 + lk) * 16 + li];
+                    const bool in1 = k1 < rows;
+                    const int k1c = in1 ? k1 : k0;
+                    const float a1 = in1 ? sAc[(k1c + lk) * 16 + li] * sWc[k1c + lk] : 0.f, b1 = sBc[(k1c + lk) * 16 + li];
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc2, 0, 0, 0);
+                }
             }
+            __syncthreads();          // the partial tiles below take the slab's place
         }
-        __syncthreads();
-        if (bb == 0) RSTAMP(26);
+        if (bb == 0 && (TILES == RT_STAGED || acc[0] + acc2[0] != 12345.678f)) RSTAMP(26);      // (stamps builds, direct tiles) the comparison makes the stamp wait for the matrix cores
         float *sR = sT_;      // [4 waves][256]
 #pragma unroll
         for (int r = 0; r < 4; r++) sR[wave * 256 + (lk * 4 + r) * 16 + li] = acc[r] + acc2[r];

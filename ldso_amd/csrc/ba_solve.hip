@@ -56,7 +56,7 @@ __global__ __launch_bounds__(NT) void k_reduce_solve(BaPtrs B, BaDims D, ResSet 
         const ReduceGrid rg = reduce_grid(D.F, A.hasL, D.ks, A.GSP);
         const int q = (int) blockIdx.x - LD_FUSED_CTL;
         const int bid = (q < rg.nTile) ? rg.nPair + q : (q < rg.nTile + rg.nPair) ? q - rg.nTile : q;
-        reduce_body(B, D, S, chunkStart, A.hasL, A.GSP, atomicMode, A.hasPrior, calibPrior, l1, il, -1, bid);
+        reduce_body<RT_DIRECT>(B, D, S, chunkStart, A.hasL, A.GSP, atomicMode, A.hasPrior, calibPrior, l1, il, -1, bid);
         // Everything a reduce workgroup hands to the control workgroup went through device-scope atomics (performed at the memory
         // side): waiting for their acknowledgement is enough - a release FENCE would also write the whole L2 back (the outputs of
         // the previous k_linearize are still dirty there), which costs more than the kernel boundary this fusion removes.
@@ -85,6 +85,6 @@ hipError_t ba_launch_reduce_solve(const BaPtrs &B, const BaDims &D, const ResSet
     const ReduceGrid rg = reduce_grid(D.F, A.hasL, D.ks, A.GSP);
     SolveArgs A2 = A;
     A2.waitTarget = rg.total;
-    return launch_lds(k_reduce_solve, dim3(rg.total + LD_FUSED_CTL), dim3(NT), std::max(gn_lds_bytes(D.F, D.n), reduce_atomic_lds_bytes()), st,
+    return launch_lds(k_reduce_solve, dim3(rg.total + LD_FUSED_CTL), dim3(NT), std::max(gn_lds_bytes(D.F, D.n), reduce_atomic_lds_bytes(RT_DIRECT)), st,
                       B, D, S, St, A2, chunkStart, atomicMode, calibPrior, l1, il);
 }

@@ -24,7 +24,7 @@ static __device__ __forceinline__ void reduce_batch_body(const BatchItem *__rest
     int w = 0;
     for (int i = 1; i < nWin; i++) if ((int) blockIdx.x >= items[i].redBlock0) w = i;
     const BatchItem &it = items[w];
-    reduce_body(it.B, it.D, it.set[cur], it.cs, 0, it.GSP, 1, it.hasPrior, calibPrior, l1, il, itCheck, (int) blockIdx.x - it.redBlock0);
+    reduce_body<RT_STAGED>(it.B, it.D, it.set[cur], it.cs, 0, it.GSP, 1, it.hasPrior, calibPrior, l1, il, itCheck, (int) blockIdx.x - it.redBlock0);
 }
 __global__ __launch_bounds__(NT) void k_reduce_batch(const BatchItem *__restrict__ items, int nWin, int cur, float calibPrior, double l1, double il, int itCheck) {
     reduce_batch_body(items, nWin, cur, calibPrior, l1, il, itCheck);
@@ -72,7 +72,7 @@ hipError_t ba_launch_reduce_batch(const BatchItem *d_items, int nWin, int totalB
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (numCU[dev] == 0) { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256; numCU[dev] = cu; }
-    return launch_lds(totalBlocks >= LD_REDB_DENSE_PER_CU * numCU[dev] ? k_reduce_batch_dense : k_reduce_batch, dim3(totalBlocks), dim3(NT), reduce_atomic_lds_bytes(), st,
+    return launch_lds(totalBlocks >= LD_REDB_DENSE_PER_CU * numCU[dev] ? k_reduce_batch_dense : k_reduce_batch, dim3(totalBlocks), dim3(NT), reduce_atomic_lds_bytes(RT_STAGED), st,
                       d_items, nWin, cur, calibPrior, l1, il, itCheck);
 }
 
