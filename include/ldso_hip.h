@@ -429,6 +429,20 @@ int ldso_ba_get_pair_rt(ldso_ba_t *h, float *out);
 int ldso_ba_get_counts(ldso_ba_t *h, int *resInA, int *resInL);
 /* energies of the linearizeAll calls inside the last ldso_ba_optimize (<= cap values), returns count */
 int ldso_ba_get_energy_log(ldso_ba_t *h, double *out, int cap);
+/* The hand-over inside the fused reduce + control-step launch of a forced iteration (k_reduce_solve): its reduce workgroups arrive on a fixed number of words,
+ * workgroup q (dispatch index behind the control workgroups) on word ldso_ba_arrival_shard(q), and the control workgroup waits on every word for its share of
+ * the launch's `total` arrivers.  Host logic without a device, by the functions the kernel compiles (tests/test_reduce_arrival_cpu.py):
+ * ldso_ba_arrival_targets fills that share for every word and returns the number of words (at most 64). */
+int ldso_ba_arrival_targets(int total, int *targets);
+int ldso_ba_arrival_shard(int q);
+/* Debug / test: the arrival words of the handle behind a stream synchronisation - all zero between launches (the control workgroup re-arms them).  Returns the
+ * number of words, or LDSO_E_NONFINITE (words filled all the same) when the iteration's non-finite status is set, which is also where a wait of the control
+ * workgroup that ran out of polls ends; ldso_ba_enqueue_gn has no status of its own. */
+int ldso_ba_get_arrival_words(ldso_ba_t *h, int *words);
+/* -DLDSO_STAMPS builds of k_reduce_solve (scripts/reduce_chain_stamps.py): the records of the last fused launch, three wall-clock values per reduce workgroup in
+ * dispatch order - started | data atomics acknowledged | arrival atomic returned.  Copies the first `cap` doubles of the buffer that holds them (the pair
+ * contributions of the step-wise path, which a product build leaves there), returns how many. */
+int ldso_ba_get_reduce_stamps(ldso_ba_t *h, double *out, int cap);
 /* bench.py roofline: average duration (us) of `reps` back-to-back launches of the dominant kernel (k_linearize, applied state
  * -> scratch set, nothing applied) between one pair of HIP events on the handle's stream. */
 int ldso_ba_time_linearize(ldso_ba_t *h, int reps, double *avg_us);

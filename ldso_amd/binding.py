@@ -67,6 +67,23 @@ def default_settings() -> np.ndarray:
     return s
 
 
+def arrival_targets(total) -> np.ndarray:
+    """how many of `total` reduce workgroups of a fused reduce + control-step launch arrive on each arrival word (ldso_ba_arrival_targets)"""
+    t = np.full(64, -1, np.int32)
+    n = lib().ldso_ba_arrival_targets(C.c_int(int(total)), _p(t))
+    if n < 0:
+        _chk(n)
+    return t[:n].copy()
+
+
+def arrival_shard(q) -> int:
+    """the arrival word of reduce workgroup q (dispatch index behind the control workgroups; ldso_ba_arrival_shard)"""
+    s = lib().ldso_ba_arrival_shard(C.c_int(int(q)))
+    if s < 0:
+        _chk(s)
+    return s
+
+
 def act_update_min_dist(current, n_points, desired_density) -> float:
     """the density controller of FullSystem::activatePointsMT (FullSystem.cc:1054-1073) on currentMinActDist"""
     out = C.c_float()
@@ -721,6 +738,15 @@ class BA:
 
     def set_debug_split_launch(self, enable=True):
         _chk(self.L.ldso_ba_set_debug_split_launch(self.h, C.c_int(1 if enable else 0)))
+
+    def get_arrival_words(self):
+        """the arrival words of the fused reduce + control-step launch behind a synchronisation (all zero between launches); raises LdsoError (E_NONFINITE)
+        when the non-finite status of the iteration is set - also the end of a control-workgroup wait that ran out of polls"""
+        words = np.full(64, -1, np.int32)
+        n = self.L.ldso_ba_get_arrival_words(self.h, _p(words))
+        if n < 0:
+            _chk(n)
+        return words[:n].copy()
 
     def get_precalc(self):
         out = np.zeros((self.F, self.F, 27), np.float32)

@@ -137,7 +137,7 @@ static int create_body(ldso_ba *H, int device, int w, int h, int max_frames, int
     DALLOC(H->allocs, B.Jlin, P * FS); DALLOC(H->allocs, B.rtz, P * FS * 8);
     DALLOC(H->allocs, B.chunk_p0, H->maxChunks); DALLOC(H->allocs, B.chunk_n, H->maxChunks); DALLOC(H->allocs, B.chunk_host, H->maxChunks);
     DALLOC(H->allocs, H->d_chunkStart, F + 2);
-    DALLOC(H->allocs, H->d_waitCtr, 4);
+    DALLOC(H->allocs, H->d_waitCtr, LD_ARRIVE_SHARDS * LD_ARRIVE_STRIDE);          // hipMalloc aligns to 256 bytes and more: every arrival word on a line of its own
     DALLOC(H->allocs, H->d_margFlags, P);
     DALLOC(H->allocs, B.pairC, 2 * F * F * LD_PAIRC);
     const size_t GSPmax = (8 * FS + LD_GEXTRA + 15) / 16 * 16;
@@ -575,6 +575,35 @@ int ldso_ba_get_energy_log(ldso_ba_t *H, double *out, int cap) {
     int n = H->lastIterations + 2;
     if (cap >= 64) { for (int i = 0; i < 64; i++) out[i] = e[i]; return n; }
     for (int i = 0; i < std::min(n, cap); i++) out[i] = e[i];
+    return n;
+}
+
+// the share of `total` arrivers on every arrival word of k_reduce_solve, by the functions the kernel compiles (ba_dev.h) - host logic without a device
+int ldso_ba_arrival_targets(int total, int *targets) {
+    REQ(total >= 0 && targets, "ldso_ba_arrival_targets: bad arguments");
+    for (int s = 0; s < LD_ARRIVE_SHARDS; s++) targets[s] = arrive_target(s, total);
+    return LD_ARRIVE_SHARDS;
+}
+int ldso_ba_arrival_shard(int q) { return (q >= 0) ? arrive_shard(q) : LDSO_E_INVALID; }
+
+int ldso_ba_get_arrival_words(ldso_ba_t *H, int *words) {
+    REQ(H && words, "ldso_ba_get_arrival_words: bad arguments");
+    std::vector<int> w;
+    D2H(w, H->d_waitCtr, (size_t) LD_ARRIVE_SHARDS * LD_ARRIVE_STRIDE);
+    double sc[16];
+    RUN(read_scalars(H, sc));          // synchronises the stream
+    for (int s = 0; s < LD_ARRIVE_SHARDS; s++) words[s] = w[(size_t) s * LD_ARRIVE_STRIDE];
+    if (sc[4] != 0.0) return LDSO_E_NONFINITE;
+    return LD_ARRIVE_SHARDS;
+}
+
+int ldso_ba_get_reduce_stamps(ldso_ba_t *H, double *out, int cap) {
+    REQ(H && out && cap >= 0, "bad arguments");
+    const int n = std::min(cap, 2 * H->maxF * H->maxF * LD_PAIRC);
+    std::vector<double> e;
+    D2H(e, H->B.pairC, (size_t) n);
+    CHK(hipStreamSynchronize(H->stream));
+    for (int i = 0; i < n; i++) out[i] = e[i];
     return n;
 }
 

@@ -225,6 +225,19 @@ __host__ __device__ inline ReduceGrid reduce_grid(int F, int hasL, int ks, int G
     return ReduceGrid{nPair, nTile, 1, nPair + nTile + 1};
 }
 #define LD_FUSED_CTL 2      // k_reduce_solve: workgroups 0 and 1 are the control step and the statistics, the reduce workgroups follow them
+// The arrival words of k_reduce_solve's hand-over.  One word takes about 88 device-scope atomics per microsecond and the 120 tile workgroups of a 7-frame
+// launch alone arrive at ~95 per microsecond: on a single word a queue built up that still held the last arrival back by ~0.4 us (profiles/r09_arrival_*.txt).
+// So the workgroups arrive on LD_ARRIVE_SHARDS words, each on a 256-byte line of its own.  arrive_shard: the word of reduce workgroup q (its dispatch index
+// behind the control workgroups, q = blockIdx.x - LD_FUSED_CTL: neighbours in time hit different words); arrive_target: how many of `total` arrivers that
+// puts on word s - what the control workgroup waits for there (0: nobody, the word passes at once).  8, 16 and 32 words measured the same (r09_arrival_shards.log).
+#ifndef LD_ARRIVE_SHARDS
+#define LD_ARRIVE_SHARDS 16
+#endif
+#define LD_ARRIVE_STRIDE 64          // ints from one word to the next
+#define LD_ARRIVE_BYTES ((size_t) LD_ARRIVE_SHARDS * LD_ARRIVE_STRIDE * sizeof(int))          // every word: what the host allocates and clears
+static_assert(LD_ARRIVE_SHARDS >= 1 && LD_ARRIVE_SHARDS <= 64, "the shards are polled by the lanes of one wavefront");
+__host__ __device__ inline int arrive_shard(int q) { return q % LD_ARRIVE_SHARDS; }
+__host__ __device__ inline int arrive_target(int s, int total) { return total / LD_ARRIVE_SHARDS + (s < total % LD_ARRIVE_SHARDS ? 1 : 0); }
 // iteration cap of optimize() (FullSystem.cc:735-736; both tests apply, as there: a window under 3 key frames ends at 15)
 __host__ __device__ inline int optimize_iteration_cap(int F, int mnumOptIts, int forceAll) {
     if (!forceAll) { if (F < 3) mnumOptIts = 20; if (F < 4) mnumOptIts = 15; }

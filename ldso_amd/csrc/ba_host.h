@@ -85,7 +85,7 @@ struct ldso_ba {
     float *imgSlots[LD_MAXF] = {nullptr};
     bool imgOwned[LD_MAXF] = {false};
     int32_t *d_chunkStart = nullptr;
-    int *d_waitCtr = nullptr;          // k_reduce_solve: producer counter (zero between launches)
+    int *d_waitCtr = nullptr;          // k_reduce_solve: the arrival words of the reduce workgroups, LD_ARRIVE_BYTES (ba_dev.h; zero between launches)
     int32_t *d_margFlags = nullptr;
     float *d_color = nullptr;          // irradiance staging of ldso_ba_set_image_raw
     void *d_act = nullptr;             // staging of ldso_ba_activate_points: n immature records + n results

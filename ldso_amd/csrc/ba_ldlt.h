@@ -68,8 +68,8 @@ struct SolveIO {
     const double *redScalars;  // GN, multi-GPU: all-reduced scalar sums (see k_gn_export), nullptr on one GPU
     const double *sx;          // out (GN): the solution in LDS (steps are its negative)
     float *sTail;              // out (GN): LDS scratch for gn_tail, 3 x 2 x LD_XFP floats (the panel buffers, free after the factorisation)
-    int *waitCtr;              // GN, fused kernel: HFinal / bFinal are complete when *waitCtr reaches waitTarget (nullptr: already complete)
-    int waitTarget;
+    int *waitCtr;              // GN, fused kernel: HFinal / bFinal are complete when the arrival words (ba_dev.h: arrive_shard) hold waitTarget arrivals in all,
+    int waitTarget;            //                   every word its arrive_target
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -315,9 +315,17 @@ _Pragma("unroll") \
     }
     if constexpr (waitH) {
         if (LD_STAMP_ON && tid == 0) B.energyLog[47] = (double) wall_clock64();
-        if (tid == 0) {
-            while (__hip_atomic_load(io.waitCtr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < io.waitTarget) __builtin_amdgcn_s_sleep(1);
-            __hip_atomic_store(io.waitCtr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // every producer has incremented: re-arm for the next launch
+        if (wv == 0) {
+            // the producers arrive on LD_ARRIVE_SHARDS words (ba_dev.h: arrive_shard): lane s polls word s until its share of the launch's arrivers is there.
+            // Bounded like gn_tail's flag wait: a target that is never met ends in the non-finite status of the iteration instead of a hung kernel
+            const bool mine = lane < LD_ARRIVE_SHARDS;
+            int *const word = io.waitCtr + (mine ? lane : 0) * LD_ARRIVE_STRIDE;
+            const int target = mine ? arrive_target(lane, io.waitTarget) : 0;
+            int spins = 0;
+            while (__builtin_amdgcn_ballot_w64(target > 0 && __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) != 0 && ++spins < (1 << 22))
+                __builtin_amdgcn_s_sleep(1);
+            if (spins >= (1 << 22) && lane == 0) B.scalars[4] = 1.0;
+            if (mine) __hip_atomic_store(word, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // every producer has arrived: re-arm for the next launch
         }
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");

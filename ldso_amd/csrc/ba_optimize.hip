@@ -241,7 +241,7 @@ static void gn_key(const ldso_ba *H, int first_iteration, int iters, std::vector
 // ... and their 64-bit hash (pre-selection only: a hit is confirmed on the bytes)
 static unsigned long long gn_signature(const std::vector<unsigned char> &key) { return fnv1a(1469598103934665603ull, key.data(), key.size()); }
 static int enqueue_gn_plain(ldso_ba *H, int first_iteration, int iters) {
-    CHK(hipMemsetAsync(H->d_waitCtr, 0, 4 * sizeof(int), H->stream));      // an aborted launch must not leave the producer counter armed
+    CHK(hipMemsetAsync(H->d_waitCtr, 0, LD_ARRIVE_BYTES, H->stream));      // an aborted launch must not leave an arrival word armed
     for (int i = 0; i < iters; i++) RUN(enqueue_iteration(H, first_iteration + i, 1e-1, -1));
     return LDSO_OK;
 }
@@ -357,7 +357,7 @@ int ldso_ba_optimize(ldso_ba_t *H, int mnumOptIts, int force_all, float *rmse_ou
     REQ(H && H->D.P > 0, "no window");
     REQ_UNSHARDED("ldso_ba_optimize");
     CHK(hipSetDevice(H->device));
-    CHK(hipMemsetAsync(H->d_waitCtr, 0, 4 * sizeof(int), H->stream));      // an aborted launch must not leave the producer counter armed
+    CHK(hipMemsetAsync(H->d_waitCtr, 0, LD_ARRIVE_BYTES, H->stream));      // an aborted launch must not leave an arrival word armed
     if (!H->settings.forceAcceptStep) return optimize_lm(H, mnumOptIts, force_all, rmse_out, iters_out);
     const int F = H->D.F;
     if (F < 2) { if (rmse_out) *rmse_out = 0; return LDSO_OK; }

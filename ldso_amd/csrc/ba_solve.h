@@ -24,8 +24,8 @@ struct SolveArgs {          // every field starts neutral: the callers set what 
     double *reduceOut = nullptr;          // multi-GPU: rank-local sums are exported here (SK_GATHER)
     const double *reduceIn = nullptr;     // multi-GPU: all-reduced sums are read from here (SK_FROMREDUCED)
     int itCheck = -1;           // k_gn_solve: >= 0 = un-forced optimize(): iteration index for the device-side `canbreak` early exit
-    int *waitCtr = nullptr;     // k_reduce_solve: counter the reduce workgroups of the same launch increment when their sums are in B.acc
-    int waitTarget = 0;         //                 ... and its value when all of them are done (0 / nullptr: no wait)
+    int *waitCtr = nullptr;     // k_reduce_solve: the arrival words (ba_dev.h: arrive_shard) the reduce workgroups of the same launch add to when their sums are in B.acc
+    int waitTarget = 0;         //                 ... and how many of them arrive in all; the kernel derives every word's share (arrive_target)
     int *hostStop = nullptr;    // un-forced optimize(): host-mapped word that receives the index of the iteration that ended the loop (canbreak, or the
     int lastIt = -1;            //                       last enqueued iteration lastIt) as soon as the device knows it - no stream synchronisation
 };

@@ -39,8 +39,10 @@ __global__ __launch_bounds__(NT) void k_gn_solve(BaPtrs B, BaDims D, ResSet S, l
 // k_reduce_solve — k_reduce and k_gn_solve of one GN iteration in ONE launch (single-GPU fast path): workgroup 0 is the control
 // step, workgroup 1 the statistics, workgroups 2.. the reduce workgroups.  The control workgroup stages everything that does not
 // depend on the system (frames, calibration, adjoints, nullspace projector, LDS set-up) while the reduce workgroups run, waits
-// until all of them have signalled (increment of a device counter once their atomics are acknowledged; acquire fence on the other side)
-// and only then loads HFinal / bFinal.  This removes one kernel boundary and hides the launch-to-first-data latency of the control
+// until all of them have arrived and only then loads HFinal / bFinal.  An arrival is one atomic increment once the workgroup's data atomics are acknowledged, on
+// one of LD_ARRIVE_SHARDS words chosen by dispatch index (ba_dev.h: arrive_shard - the tile workgroups of a 7-frame launch arrive faster than a single word takes
+// atomics); lane s of the control workgroup's first wavefront polls word s for its share of the arrivers (arrive_target), re-arms it, and an acquire fence
+// follows the workgroup barrier.  This removes one kernel boundary and hides the launch-to-first-data latency of the control
 // step (about 5 us of a 50 us iteration).  All workgroups of the launch are resident at once (F*F + 4*tiles + 3 <= 256 CUs), and the
 // waiting workgroup has the lowest index, so it never keeps a producer from being scheduled.
 // ---------------------------------------------------------------------------------------------------------
@@ -63,8 +65,15 @@ __global__ __launch_bounds__(NT) void k_reduce_solve(BaPtrs B, BaDims D, ResSet 
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
         if (threadIdx.x == 0) {
-            const int prev = __hip_atomic_fetch_add(A.waitCtr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (LD_STAMP_ON && prev == A.waitTarget - 1) { B.energyLog[29] = (double) wall_clock64(); B.energyLog[30] = (double) bid; B.energyLog[31] = (double) tStart_; }      // who was last, and when
+            // stamps builds: one record per reduce workgroup in B.pairC (idle in atomic mode) - started | data atomics acknowledged (every wave's wait, behind the
+            // barrier) | arrival atomic returned; the comparison makes the last stamp wait for the returned value (scripts/reduce_chain_stamps.py)
+            double *rec = B.pairC + 3 * q;
+            const bool recOk = LD_STAMP_ON && 3 * q + 2 < 2 * D.F * D.F * LD_PAIRC;
+            if (recOk) { rec[0] = (double) tStart_; rec[1] = (double) wall_clock64(); }
+            // the arrival: one of LD_ARRIVE_SHARDS words by dispatch index, so that workgroups that finish together do not queue on one word (ba_dev.h);
+            // nobody reads the returned value outside stamps builds
+            const int prev = __hip_atomic_fetch_add(A.waitCtr + arrive_shard(q) * LD_ARRIVE_STRIDE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (recOk && prev >= 0) rec[2] = (double) wall_clock64();
         }
         return;
     }
