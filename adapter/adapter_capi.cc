@@ -5,30 +5,8 @@
 #include <memory>
 #include <vector>
 #include <cmath>
-// test plumbing reaches into FullSystem's private members exactly as the adapter's translation unit does (see ldso_gpu_adapter.h)
-#include <deque>
-#include <list>
-#include <map>
-#include <mutex>
-#include <queue>
-#include <set>
-#include <string>
-#include <thread>
-#include <Eigen/Core>
-#include <glog/logging.h>
-#define private public
-#define protected public
-#include "frontend/CoarseTracker.h"
-#include "frontend/FullSystem.h"
-#undef private
-#undef protected
-#include "ldso_gpu_adapter.h"
-#include "internal/PointHessian.h"
-#include "internal/Residuals.h"
-#include "internal/ImmaturePoint.h"
-#include "internal/GlobalCalib.h"
-#include "internal/OptimizationBackend/EnergyFunctional.h"
-#include <chrono>
+// test plumbing reaches into FullSystem's private members exactly as the adapter's units do: through the same private header (see ldso_gpu_adapter.h)
+#include "adapter_internal.h"
 
 using namespace ldso;
 using namespace ldso::internal;
@@ -226,6 +204,19 @@ int adp_set_resident_immature(void *b, int on) { if (!b) return LDSO_E_INVALID; 
 int adp_sync_immature(void *b, void *fs) { if (!b || !fs) return LDSO_E_INVALID; GUARD(((GpuBackend *) b)->syncImmaturePoints(*(FullSystem *) fs)) }
 // how the reconcile steps of this backend went: [rows unchanged, one compaction, full upload]
 int adp_immature_reconcile_counts(void *b, int *out3) { if (!b || !out3) return LDSO_E_INVALID; for (int i = 0; i < 3; i++) out3[i] = ((GpuBackend *) b)->immatureReconcile[i]; return 0; }
+// the decision of GpuBackend::reconcileImmature (adp::planReconcile) on plain data, no backend and no device: integer ids stand for the ImmaturePoints.  Rows
+// (id, host index the device record carries) against the graph's current list (id, host index now).  Returns 0 same / 1 compact / 2 re-upload, or
+// LDSO_E_INVALID; keep[nRows] and hostMap[LDSO_MAX_FRAMES] (-1: unset) are written for outcome 1 only.
+int adp_reconcile_plan(int nRows, const int *rowId, const int *rowHost, int nCur, const int *curId, const int *curHost, int haveTracer, unsigned char *keep, int *hostMap) {
+    if (nRows < 0 || nCur < 0 || (nRows && (!rowId || !rowHost)) || (nCur && (!curId || !curHost)) || !keep || !hostMap) return LDSO_E_INVALID;
+    const std::vector<int> rows(rowId, rowId + nRows), rHost(rowHost, rowHost + nRows), cur(curId, curId + nCur), cHost(curHost, curHost + nCur);
+    const adp::ReconcilePlan plan = adp::planReconcile(cur, cHost, rows, rHost, haveTracer != 0);
+    if (plan.outcome == adp::ReconcilePlan::Compact) {
+        for (int i = 0; i < nRows; i++) keep[i] = plan.keep[i];
+        for (int f = 0; f < LDSO_MAX_FRAMES; f++) hostMap[f] = plan.hostMap[f];
+    }
+    return (int) plan.outcome;
+}
 
 // a new tracer of this backend holds at least n records (GpuBackend::tracerMinCapacity): a small value lets a test reach the path on which the tracer has to grow
 int adp_set_tracer_min_capacity(void *b, int n) { if (!b || n < 1) return LDSO_E_INVALID; ((GpuBackend *) b)->tracerMinCapacity = n; return 0; }

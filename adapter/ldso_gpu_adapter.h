@@ -20,7 +20,7 @@
 //
 // The functions reach into private members of FullSystem / CoarseTracker (frames, ef, activeResiduals, allFrameHistory, lastCoarseRMSE,
 // shellPoseMutex ...): a maintainer makes them member functions or adds `friend class ldso::GpuBackend;` to the two classes.  The reference tree
-// is read-only in this repository, so ldso_gpu_adapter.cc opens the access specifiers for its own inclusion of the two headers instead
+// is read-only in this repository, so adapter_internal.h opens the access specifiers for the adapter's own inclusion of the two headers instead
 // (LDSO_ADAPTER_OPEN_PRIVATE) - the class layout is unchanged, the object files link against the reference's own.
 #pragma once
 #include <map>
@@ -28,6 +28,7 @@
 #include <chrono>
 #include <deque>
 #include <mutex>
+#include <set>
 #include <vector>
 
 #include "frontend/CoarseTracker.h"
@@ -60,7 +61,7 @@ public:
     // FullSystem::makeKeyFrame :429-640).  Residual counts are checked per point and a point whose residual list changed in another way is re-read in full;
     // invalidateWindow() (or residentWindow = false) forces the next optimize() to upload everything.
     bool residentWindow = true;
-    void invalidateWindow() { residentValid_ = false; }
+    void invalidateWindow() { window_.valid = false; }
     bool lastUploadWasDelta = false;
     int uploadsDelta = 0, uploadsFresh = 0;          // how the windows of this backend's lifetime went over
     int uploadsFreshBecauseLinearized = 0;           // ... of the full uploads: windows that held linearised residuals (ldso_ba_update_window does not carry them)
@@ -185,81 +186,157 @@ public:
     const char *lastError() const;
 
 private:
-    ldso_undistorter_t *undist_ = nullptr;
-    ldso_ba_t *ba_ = nullptr;
-    static shared_ptr<PointHessian> makePoint(FullSystem &fs, const shared_ptr<internal::ImmaturePoint> &point, const ldso_activation_t &out);
-    ldso_tracer_t *tracer_ = nullptr;
-    int tracerCap_ = 0;
-    // resident mode: the ImmaturePoint of every tracer row in order (held: a released point's address must not come back as a new one's), and the host index
-    // the device record carries
-    std::vector<shared_ptr<internal::ImmaturePoint>> who_;
-    std::vector<int> whoHost_;
-    void reconcileImmature(FullSystem &fs, bool setIdxInImmaturePoints);
-    void ensureTracer(int capacity);
-    void downloadImmature(const std::vector<char> *alive);
-    ldso_features_t *features_ = nullptr;
-    int featuresCap_ = 0;
-    const int *featuresPattern_ = nullptr;
-    ldso_pixsel_t *pixsel_ = nullptr;                    // setting_pointSelection == 0: created at the first call with fs.pixelSelector's randomPattern
-    const unsigned char *pixselPattern_ = nullptr;      // ... which it is recreated for when another PixelSelector or image size comes along
-    int pixselW_ = 0, pixselH_ = 0;
-    void makeNewTracesPixelSelector(FullSystem &fs, shared_ptr<FrameHessian> newFrame);
-    void appendFreshRecords(const std::vector<ldso_immature_t> &rec, const void *immDev, const void *typeDev, const std::vector<shared_ptr<ImmaturePoint>> &fresh, int hostIdx);
-    std::map<CoarseTracker *, ldso_tracker_t *> trackers_;          // the reference double-buffers two CoarseTrackers (FullSystem.h:296-297)
-    std::map<unsigned long, int> slotOf_;                            // key frame (Frame::id: addresses get reused) -> image slot of the BA handle
-    std::vector<long> slotOwner_;                                    // slot -> Frame::id, -1 = free
-    std::vector<shared_ptr<PointHessian>> lastPoints_;               // the points of the window optimize() left on the device, in its order
-    // One device pyramid per frame (Frame::id), REFERENCE-COUNTED: the map below holds one reference, every consumer that names the pyramid on the device
-    // holds another (the BA image slot, the tracer, a tracker's reference frame / new frame).  releasePyramids() only drops the MAP's reference of frames that
-    // left the window and that nobody else holds; the device memory goes when the last holder lets go - no guessing which tracker may still read it, no
-    // reading of another thread's state (the keep-set was built from an unsynchronised read of the trackers' maps and of lastRef).
+    // The private state, grouped by the invariant that spans it; every group is a small nested type that owns what its invariant needs and offers the
+    // operations that keep it.  WHICH THREAD TOUCHES WHAT: only the pyramid registry and the tracker handles are shared between the tracking thread
+    // (undistortFrame, trackNewCoarse, trackNewestCoarse on coarseTracker) and the mapping thread (everything else; coarseTracker_forNewKF under
+    // coarseTrackerSwapMutex) - each has its mutex, taken by its own operations and by no other code.  Everything else belongs to the mapping thread, but for
+    // undist_, which setUndistortion sets before the first frame.  DESTRUCTION ORDER: the pyramids go after every handle that names one on the device (BA image
+    // slots, tracer, trackers): ~GpuBackend destroys the BA, tracker and selector handles in its body, the tracer goes with its row set, and the registry is declared before every
+    // consumer's reference (tracerPyr_ before the row set).
+    int device_, maxFrames_, maxPoints_;
+
+    // ---- the pyramid registry (adapter_pyramids.cc): one device pyramid per frame (Frame::id), REFERENCE-COUNTED.  The registry holds one reference, every
+    // consumer that names the pyramid on the device holds another (the BA image slot, the tracer, a tracker's reference frame / new frame).  release() only drops
+    // the REGISTRY's reference of frames that left the window and that nobody else holds; the device memory goes when the last holder lets go - no guessing which
+    // tracker may still read it, no reading of another thread's state.
     struct PyrHolder {
         ldso_pyramid_t *p = nullptr;
         std::vector<float> irradiance;                               // the host copy of channel 0 the build read from
         ~PyrHolder();
     };
     typedef std::shared_ptr<PyrHolder> PyrRef;
-    std::map<unsigned long, PyrRef> pyr_;                            // Frame::id -> pyramid
-    std::mutex pyrMutex_;                                            // tracking thread (new frame / reference) and mapping thread (window, tracer) share the map
-    // Frames undistortFrame registered that no consumer has asked for yet (guarded by pyrMutex_): such a frame is in no window and no consumer holds its
-    // pyramid, so releasePyramids() - the mapping thread may run it between the tracking thread's undistortFrame(id) and its trackNewCoarse(fh) - would
-    // take the map's reference for the last one.  It spares these ids; pyramidOf() takes an id off the list when it hands the pyramid out.  At most
-    // kMaxPending ids: a frame that never reaches a consumer loses the protection when kMaxPending newer frames have been registered, and is released then.
-    static constexpr size_t kMaxPending = 8;
-    std::deque<unsigned long> pendingPyr_;
-    std::vector<PyrRef> slotPyr_;                                    // BA image slot -> the pyramid it aliases (mapping thread only)
-    PyrRef tracerPyr_;                                               // the frame the tracer currently reads (mapping thread only)
-    struct TrackerPyr { PyrRef ref, newFrame; };
-    std::map<ldso_tracker_t *, TrackerPyr> trackerPyr_;              // guarded by handlesMutex_
-    PyrRef pyramidOf(const shared_ptr<FrameHessian> &fh);
+    class PyramidRegistry {
+    public:
+        // the frame's pyramid, built from fh->dIp[0] if the frame has none yet (`built` counts the builds); the caller holds it from here on
+        PyrRef getOrBuild(const shared_ptr<FrameHessian> &fh, int device, int &built);
+        // a pyramid undistortFrame filled, under its Frame::id: pending until the first consumer asks for it
+        void registerUndistorted(unsigned long frameId, const PyrRef &e, int &built);
+        // drops the registry's reference of every frame that is not in `keep`, not pending, and held by nobody else
+        void release(const std::set<unsigned long> &keep);
+    private:
+        std::map<unsigned long, PyrRef> pyr_;                        // Frame::id -> pyramid
+        std::mutex mutex_;                                           // tracking thread (new frame / reference) and mapping thread (window, tracer) share the map
+        // Frames registerUndistorted took that no consumer has asked for yet: such a frame is in no window and no consumer holds its pyramid, so release() -
+        // the mapping thread may run it between the tracking thread's undistortFrame(id) and its trackNewCoarse(fh) - would take the registry's reference
+        // for the last one.  It spares these ids; getOrBuild() takes an id off the list when it hands the pyramid out.  At most kMaxPending ids: a frame that
+        // never reaches a consumer loses the protection when kMaxPending newer frames have been registered, and is released then.
+        static constexpr size_t kMaxPending = 8;
+        std::deque<unsigned long> pending_;
+    };
+    PyramidRegistry pyramids_;                                       // declared before every consumer's PyrRef below: destroyed after them
+    PyrRef pyramidOf(const shared_ptr<FrameHessian> &fh) { return pyramids_.getOrBuild(fh, device_, pyramidsBuilt); }
     void releasePyramids(FullSystem &fs);
-    std::vector<int32_t> resBegin_;                                  // last upload: the residuals of point k are flat_[resBegin_[k] .. resBegin_[k + 1])
-    // the resident window as the host sees it: one row per point in device order, its residual objects by window column (= target frame index)
-    static constexpr int kMaxCols = 16;
-    static_assert(kMaxCols >= LDSO_MAX_FRAMES, "a row of the resident window holds one residual pointer per window column");
-    struct Row { PointHessian *ph; Feature *feat; uint32_t mask; int host; PointFrameResidual *res[kMaxCols]; };
-    std::vector<Row> rows_;
+    ldso_undistorter_t *undist_ = nullptr;
+
+    // ---- the BA handle and its image slots (mapping thread) ----
+    ldso_ba_t *ba_ = nullptr;
+    std::map<unsigned long, int> slotOf_;                            // key frame (Frame::id: addresses get reused) -> image slot of the BA handle
+    std::vector<long> slotOwner_;                                    // slot -> Frame::id, -1 = free
+    std::vector<PyrRef> slotPyr_;                                    // slot -> the pyramid it aliases
+    void syncImageSlots(FullSystem &fs, std::vector<int32_t> &slots);
+
+    // ---- the resident window as the host sees it (adapter_window.cc): one row per point in device order, its residual objects by window column (= target
+    // frame index).  rows, flat and resBegin describe the same residuals: flat / resBegin are rebuilt from the rows, a residual leaves through dropResidual.
+    struct ResidentWindow {
+        static constexpr int kMaxCols = 16;
+        static_assert(kMaxCols >= LDSO_MAX_FRAMES, "a row of the resident window holds one residual pointer per window column");
+        struct Row {
+            PointHessian *ph; Feature *feat; uint32_t mask; int host; PointFrameResidual *res[kMaxCols];
+            static Row empty(PointHessian *ph, Feature *feat, int host) { Row r; r.ph = ph; r.feat = feat; r.mask = 0; r.host = host; for (int c = 0; c < kMaxCols; c++) r.res[c] = nullptr; return r; }
+        };
+        std::vector<Row> rows;
+        std::vector<PointFrameResidual *> flat;                      // the residual objects in the device's flat order (point-major, target-ascending)
+        std::vector<int32_t> resBegin;                               // the residuals of point k are flat[resBegin[k] .. resBegin[k + 1])
+        std::vector<shared_ptr<Frame>> frames;                       // the frame of every column (held: the rows point into their features)
+        std::vector<shared_ptr<PointHessian>> points;                // the points of the window optimize() left on the device, in its order (held for the rows)
+        bool valid = false;
+        // The row of one point from its residual list: mask and one pointer per column.  Where a residual's column comes from: Stored = its targetIDX as
+        // makeIDX left it, FromTarget = its target frame's idx (one weak_ptr::lock); both write hostIDX / targetIDX into the residual, as a full upload
+        // does.  FromTargetNotLinearized = the target frame's idx, nothing written, a linearised residual refused (the delta path).  false: a residual names
+        // a frame outside the window, the host, or a target twice, or is refused (the row is not to be used then)
+        enum class Columns { Stored, FromTarget, FromTargetNotLinearized };
+        static bool buildRow(Row &row, PointHessian &ph, Feature *feat, int host, int F, Columns how);
+        void rebuildFlat(int F);
+        // one residual of a row leaves the graph (lastResiduals, EnergyFunctional::dropResidual) and the row (pointer and mask bit: the next delta says so
+        // through the cleared bit); nothing happens when the point's list does not hold it
+        static void dropResidual(Row &row, const PointFrameResidual *res, internal::EnergyFunctional &ef);
+    };
+    ResidentWindow window_;
+    bool uploadDelta(FullSystem &fs, const std::vector<int32_t> &slots, std::vector<shared_ptr<PointHessian>> &allPoints);
+    void uploadFresh(FullSystem &fs, const std::vector<int32_t> &slots, std::vector<shared_ptr<PointHessian>> &allPoints, bool trustIndices);
+    int uploadWindow(FullSystem &fs, std::vector<shared_ptr<PointHessian>> &allPoints, bool trustIndices = false);
     // optimize()'s write-back: where ldso_ba_get_results lands (kept across calls)
     std::vector<ldso_res_out_t> wbRes_; std::vector<int32_t> wbState_, wbActive_, wbRemove_;
     std::vector<ldso_point_out_t> wbPoints_; std::vector<ldso_frame_t> wbFrames_; std::vector<double> wbStep_;
-    std::vector<shared_ptr<Frame>> rowFrames_;                       // the frame of every column of the resident window (held: the rows point into their features)
-    std::vector<PointFrameResidual *> flat_;                         // the residual objects in the device's flat order (point-major, target-ascending)
-    bool residentValid_ = false;
     std::chrono::steady_clock::time_point lapT_;
     double lapSince() { const auto n = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double>(n - lapT_).count(); lapT_ = n; return d; }
-    bool uploadDelta(FullSystem &fs, const std::vector<int32_t> &slots, std::vector<shared_ptr<PointHessian>> &allPoints);
-    void uploadFresh(FullSystem &fs, const std::vector<int32_t> &slots, std::vector<shared_ptr<PointHessian>> &allPoints, bool trustIndices);
-    int device_, maxFrames_, maxPoints_;
-    // whose pyramid a tracker handle currently holds as "new frame": keyed by Frame::id, not by address (LDSO releases the FrameHessian of a
-    // non-key frame after tracking, the allocator may hand the same address to the next frame)
-    std::map<ldso_tracker_t *, unsigned long> trackerNewFrameId_;
-    // trackerOf / newFrameResident run on the tracking thread (coarseTracker) AND on the mapping thread (coarseTracker_forNewKF under
-    // coarseTrackerSwapMutex, FullSystem.cc makeKeyFrame): the two maps above are shared between them
-    std::mutex handlesMutex_;
-    bool newFrameResident(ldso_tracker_t *t, const shared_ptr<FrameHessian> &fh);
-    ldso_tracker_t *trackerOf(CoarseTracker &tr);
-    int uploadWindow(FullSystem &fs, std::vector<shared_ptr<PointHessian>> &allPoints, bool trustIndices = false);
-    void syncImageSlots(FullSystem &fs, std::vector<int32_t> &slots);
+    // the host hand-over of activatePointsMT (:1105-1149, :1166-1188): the deleted candidates, then the selected ones
+    void handOverSelection(FullSystem &fs, const std::vector<shared_ptr<internal::ImmaturePoint>> &who, const std::vector<int32_t> &decision, const std::vector<int32_t> &selected, int nSel,
+                           const std::vector<ldso_activation_t> &out);
+    static shared_ptr<PointHessian> makePoint(FullSystem &fs, const shared_ptr<internal::ImmaturePoint> &point, const ldso_activation_t &out);
+
+    // ---- the immature row set (adapter_immature.cc): the tracer and, in resident mode, the ImmaturePoint of every tracer row in order (held: a released
+    // point's address must not come back as a new one's) with the host index the device record carries.  THE RULE: the row list and the tracer's count move
+    // together; whatever fails in between forgets the rows, and the next reconcile uploads the set anew.  The list changes through the operations below only.
+    class ImmatureRows {
+    public:
+        ~ImmatureRows();                                 // the tracer goes with its rows
+        ldso_tracer_t *tracer = nullptr;
+        const std::vector<shared_ptr<internal::ImmaturePoint>> &who() const { return who_; }
+        const std::vector<int> &host() const { return host_; }
+        size_t size() const { return who_.size(); }
+        int capacity() const { return cap_; }
+        // a tracer that holds `need` records (created with twice that, or minCapacity); a new one starts with no rows
+        void ensure(int device, int need, int minCapacity);
+        void forget();
+        void adopt(std::vector<shared_ptr<internal::ImmaturePoint>> &cur, std::vector<int> &curHost);          // the rows are now these (taken by swap)
+        void append(const std::vector<shared_ptr<internal::ImmaturePoint>> &fresh, int hostIdx);
+        void compact(const std::vector<uint8_t> &keep);                                                         // the rows with keep[row] != 0 stay, in order
+        // a device call that changes the tracer's count: the rows are forgotten when it throws
+        template <class Call> void guarded(Call &&call) { try { call(); } catch (...) { forget(); throw; } }
+    private:
+        int cap_ = 0;
+        std::vector<shared_ptr<internal::ImmaturePoint>> who_;
+        std::vector<int> host_;
+    };
+    PyrRef tracerPyr_;                                               // the frame the tracer currently reads (declared before the tracer: released after it)
+    ImmatureRows imm_;
+    void reconcileImmature(FullSystem &fs, bool setIdxInImmaturePoints);
+    void downloadImmature(const std::vector<char> *alive);
+    // makeNewTraces: the detector (setting_pointSelection == 1) and the pixel selector (== 0) with what each is recreated for
+    ldso_features_t *features_ = nullptr;
+    int featuresCap_ = 0;
+    const int *featuresPattern_ = nullptr;
+    ldso_pixsel_t *pixsel_ = nullptr;                    // created at the first call with fs.pixelSelector's randomPattern
+    const unsigned char *pixselPattern_ = nullptr;      // ... which it is recreated for when another PixelSelector or image size comes along
+    int pixselW_ = 0, pixselH_ = 0;
+    struct NewTraces;                                    // what either mode reports: records, types, features
+    bool detectCorners(FullSystem &fs, const shared_ptr<FrameHessian> &newFrame, int hostIdx, NewTraces &out);
+    void selectPixels(FullSystem &fs, const shared_ptr<FrameHessian> &newFrame, int hostIdx, NewTraces &out);
+    void appendFreshRecords(const NewTraces &nt, const void *immDev, const void *typeDev, int nDev, const std::vector<shared_ptr<ImmaturePoint>> &fresh, int hostIdx);
+
+    // ---- the tracker handles (adapter_tracker.cc): the reference double-buffers two CoarseTrackers (FullSystem.h:296-297); of() / newFrameResident() / hold*()
+    // run on the tracking thread (coarseTracker) AND on the mapping thread (coarseTracker_forNewKF, FullSystem.cc makeKeyFrame)
+    class TrackerHandles {
+    public:
+        ldso_tracker_t *of(CoarseTracker &tr, int device);
+        // true when handle t already holds this frame's pyramid as its new frame; otherwise records that it is about to
+        bool newFrameResident(ldso_tracker_t *t, const shared_ptr<FrameHessian> &fh);
+        void holdRef(ldso_tracker_t *t, const PyrRef &pr);
+        void holdNewFrame(ldso_tracker_t *t, const PyrRef &pr);
+        void destroyAll();
+    private:
+        struct Held { PyrRef ref, newFrame; };
+        std::map<CoarseTracker *, ldso_tracker_t *> trackers_;
+        std::map<ldso_tracker_t *, Held> pyr_;
+        // whose pyramid a handle currently holds as "new frame": keyed by Frame::id, not by address (LDSO releases the FrameHessian of a non-key frame
+        // after tracking, the allocator may hand the same address to the next frame)
+        std::map<ldso_tracker_t *, unsigned long> newFrameId_;
+        std::mutex mutex_;
+    };
+    TrackerHandles trackers_;
+    ldso_tracker_t *trackerOf(CoarseTracker &tr) { return trackers_.of(tr, device_); }
+    void handNewFrame(ldso_tracker_t *t, const shared_ptr<FrameHessian> &fh);
 };
 
 }  // namespace ldso
