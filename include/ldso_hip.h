@@ -334,6 +334,26 @@ int ldso_ba_batch_activate_points(ldso_ba_batch_t *b, const int *n /*n_win*/, co
 int ldso_ba_batch_select_candidates(ldso_ba_batch_t *b, ldso_act_job_t *jobs /*n_win*/, float minTraceQuality);
 int ldso_ba_batch_select_activate_points(ldso_ba_batch_t *b, ldso_act_job_t *jobs /*n_win*/, float minTraceQuality, int min_obs, float min_idepth_hessian,
                                          int gn_iterations);
+/* ldso_ba_batch_select_activate_tracers: activatePointsMT (FullSystem.cc:1052-1189) with every window's immature set where it lives - per window exactly what
+ * ldso_ba_select_activate_tracer(handle_i, jobs[i].tracer, ...) gives on that handle alone: the candidates are the tracer's records and types, in their order, the
+ * seeds every point of the resident window i whose host is not the newest frame, at its current inverse depth; decisions, selected list, activation records and the
+ * distance map (ldso_ba_get_distance_map(handle_i)) byte for byte, and with compact != 0 the tracer's records, types and count afterwards (everything the loop did
+ * not KEEP leaves its set, :1105-1188; the same stable compaction as ldso_trace_compact, :602-645).  Only KRKi / Kt / host_flagged go up.  Whatever n_win: one upload
+ * (the tables of the kernels and the pose arrays), four launches (k_act_select_batch, k_activate_batch, k_compact_count_group, k_compact_move_group over the windows
+ * that compact), one download (decisions, lists, records and the compactions' counts) and one wait on the batch's stream.  tracer == NULL: window i takes no part and
+ * keeps its outputs, its handle and its map.  A tracer without records builds its window's map only.  decision_out / selected_out / out: n = the tracer's count before
+ * the call; n_selected and n_left (the tracer's count afterwards) are written by the call.  A tracer may be a member of a ldso_trace_group_t; it must be idle, as for
+ * ldso_ba_select_activate_tracer.  Refused (LDSO_E_INVALID, nothing enqueued, no output or tracer touched): everything ldso_ba_batch_select_activate_points refuses,
+ * a tracer on another device than the batch, the same tracer in two jobs, a sharded handle, n_hosts != F_i, missing outputs where the tracer holds records. */
+typedef struct {                      /* one window's share; tracer == NULL: the window takes no part */
+    struct ldso_tracer *tracer;       /* a ldso_tracer_t (the immature-point tracer, below) */
+    int n_hosts; const float *KRKi, *Kt; const int32_t *host_flagged;
+    float currentMinActDist; int compact;
+    int32_t *decision_out /*n*/, *selected_out /*n*/; int n_selected /*out*/;
+    ldso_activation_t *out /*n*/; int n_left /*out*/;        /* n = the tracer's count before the call */
+} ldso_act_tracer_job_t;
+int ldso_ba_batch_select_activate_tracers(ldso_ba_batch_t *b, ldso_act_tracer_job_t *jobs /*n_win*/, float minTraceQuality, int min_obs, float min_idepth_hessian,
+                                          int gn_iterations);
 /* The step that closes the key-frame loop: every window of the batch becomes the next one, with a number of launches, copies and host synchronisations that does not
  * depend on n, and the batch stays usable (it re-cuts itself).
  * ldso_ba_batch_update_windows = ldso_ba_update_window(handle_i, <jobs[i]>) for every window with jobs[i].frame_from != NULL: the arguments of the single-window entry in a
@@ -622,6 +642,16 @@ int ldso_trace_group_destroy(ldso_trace_group_t *g);
  * record of any member changes. */
 int ldso_trace_group_on(ldso_trace_group_t *g, const uint8_t *active /* n or NULL = all */, const int *n_hosts /* n */, const float *const *KRKi /* n pointers */,
                         const float *const *Kt /* n pointers */, const float *const *aff /* n pointers */, int *counts_out /* n*6 or NULL */);
+/* ldso_trace_group_compact = ldso_trace_compact(member_i, keep[i], n_hosts[i], host_map[i], &n_out[i]) for every member with active[i] != 0 (NULL: all): what leaves the immature sets of many
+ * sequences when each marginalises a frame (FullSystem.cc:602-645: its records go, the host indices behind it shift) or host code released points
+ * (FullSystem.cc:1052-1189).  keep: n pointers to the members' keep bytes (an entry or the array NULL: all kept); host_map: n pointers to n_hosts[i] entries (an entry
+ * or the array NULL: the identity).  A member's records, types and count afterwards are those of its own ldso_trace_compact, byte for byte.  One upload (job table,
+ * prefix table, host maps, keep bytes), two launches, one download of the counts and one wait on the group's stream, whatever n.  n_out: n or NULL; rows of inactive
+ * members are left alone, an active member without records reports 0.  Everything is checked before anything is enqueued: an n_hosts outside 1..LDSO_MAX_FRAMES or
+ * a map entry >= LDSO_MAX_FRAMES (the member's index in the message), or members that no longer share the stream, give LDSO_E_INVALID and no member's records,
+ * types or count change. */
+int ldso_trace_group_compact(ldso_trace_group_t *g, const uint8_t *active /* n or NULL = all */, const uint8_t *const *keep /* n pointers or NULL */,
+                             const int *n_hosts /* n */, const int32_t *const *host_map /* n pointers or NULL */, int *n_out /* n or NULL */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * New features of a key frame: FullSystem::makeNewTraces (FullSystem.cc:1272-1325) for setting_pointSelection == 1 (the default, Setting.cc:125) =

@@ -781,6 +781,12 @@ class ActJob(C.Structure):
                 ("n_selected", C.c_int), ("out", C.c_void_p)]
 
 
+class ActTracerJob(C.Structure):
+    """ldso_act_tracer_job_t (ldso_hip.h): one window's share of ldso_ba_batch_select_activate_tracers"""
+    _fields_ = [("tracer", C.c_void_p), ("n_hosts", C.c_int), ("KRKi", C.c_void_p), ("Kt", C.c_void_p), ("host_flagged", C.c_void_p), ("currentMinActDist", C.c_float),
+                ("compact", C.c_int), ("decision_out", C.c_void_p), ("selected_out", C.c_void_p), ("n_selected", C.c_int), ("out", C.c_void_p), ("n_left", C.c_int)]
+
+
 class WinJob(C.Structure):
     """ldso_win_job_t (ldso_hip.h): one window's share of ldso_ba_batch_update_windows = the arguments of ldso_ba_update_window"""
     _fields_ = [("F", C.c_int), ("image_slot", C.c_void_p), ("frame_from", C.c_void_p), ("P", C.c_int), ("point_from", C.c_void_p), ("res_mask", C.c_void_p),
@@ -907,6 +913,44 @@ class BABatch:
         J, keep = self._jobs(jobs, True)
         _chk(self.L.ldso_ba_batch_select_activate_points(self.h, J, C.c_float(min_trace_quality), C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations)))
         return [None if k is None else (k[6], k[7][:J[i].n_selected].copy(), k[8][:J[i].n_selected].copy()) for i, k in enumerate(keep)]
+
+    def _tracer_jobs(self, jobs):
+        """the ldso_act_tracer_job_t array of select_activate_tracers and the arrays it points into (per window: tracer, KRKi, Kt, flagged, decision, selected,
+        records, or None)"""
+        n = len(self.handles)
+        assert len(jobs) == n
+        J = (ActTracerJob * n)()
+        keep = []
+        for i, job in enumerate(jobs):
+            if job is None:
+                keep.append(None)
+                continue
+            T = job["tracer"]
+            K1 = None if job.get("KRKi") is None else np.ascontiguousarray(job["KRKi"], np.float32).reshape(-1, 9)
+            K2 = None if job.get("Kt") is None else np.ascontiguousarray(job["Kt"], np.float32).reshape(-1, 3)
+            fl = np.ascontiguousarray(job["flagged"], np.int32)
+            dec = np.zeros(T.n, np.int32); sel = np.zeros(T.n, np.int32); rec = np.zeros(T.n, synth.ACTIVATION_DTYPE)
+            keep.append((T, K1, K2, fl, dec, sel, rec))
+            j = J[i]
+            j.tracer, j.n_hosts, j.KRKi, j.Kt, j.host_flagged = T.h, len(fl), (None if K1 is None else K1.ctypes.data), (None if K2 is None else K2.ctypes.data), fl.ctypes.data
+            j.currentMinActDist, j.compact = float(job["min_act_dist"]), 1 if job.get("compact", True) else 0
+            j.decision_out, j.selected_out, j.out, j.n_left = dec.ctypes.data, sel.ctypes.data, rec.ctypes.data, T.n
+        return J, keep
+
+    def select_activate_tracers(self, jobs, min_trace_quality=3.0, min_obs=1, min_idepth_hessian=100.0, gn_iterations=3):
+        """BA.select_activate_tracer for every window of the batch in one enqueue (ldso_ba_batch_select_activate_tracers).  jobs[i]: a dict with the keys tracer (a Tracer),
+        KRKi, Kt, flagged, min_act_dist and optionally compact (default True), or None for a window that takes no part -> [(decision, selected, activation records of
+        the selected) or None]; the tracers' counts are refreshed"""
+        J, keep = self._tracer_jobs(jobs)
+        _chk(self.L.ldso_ba_batch_select_activate_tracers(self.h, J, C.c_float(min_trace_quality), C.c_int(min_obs), C.c_float(min_idepth_hessian), C.c_int(gn_iterations)))
+        out = []
+        for i, k in enumerate(keep):
+            if k is None:
+                out.append(None)
+                continue
+            k[0].n = J[i].n_left
+            out.append((k[4], k[5][:J[i].n_selected].copy(), k[6][:J[i].n_selected].copy()))
+        return out
 
     def update_windows(self, jobs):
         """ldso_ba_batch_update_windows: every window of the batch becomes its next one in one call.  jobs[i]: the arguments of BA.update_window as a tuple / list
@@ -1341,6 +1385,32 @@ class TracerGroup(_Group):
         counts = np.zeros((n, 6), np.int32)
         _chk(self.L.ldso_trace_group_on(self.h, _p(act), _p(nh), ptrs[0], ptrs[1], ptrs[2], _p(counts)))
         return counts
+
+
+    def compact(self, keeps=None, host_maps=None, n_hosts=None, active=None):
+        """ldso_trace_group_compact: Tracer.compact of every active member in one call -> the members' new counts (n) int32; rows of inactive members hold their
+        unchanged counts.  keeps / host_maps: per member the arguments of Tracer.compact (None, or a None entry: all kept / the identity); n_hosts: per member, default as
+        Tracer.compact"""
+        n = len(self.tracers)
+        act, idx = _active_mask(active, n)
+        hold = []
+        PK, PM = (C.c_void_p * n)(), (C.c_void_p * n)()
+        nh = np.zeros(n, np.int32)
+        for i in idx:
+            k = None if keeps is None or keeps[i] is None else np.ascontiguousarray(np.asarray(keeps[i]) != 0, np.uint8)
+            m = None if host_maps is None or host_maps[i] is None else np.ascontiguousarray(host_maps[i], np.int32)
+            assert k is None or len(k) == self.tracers[i].n
+            nh[i] = n_hosts[i] if n_hosts is not None and n_hosts[i] is not None else (len(m) if m is not None else MAX_FRAMES)
+            hold.append((k, m))
+            if k is not None and len(k):
+                PK[i] = k.ctypes.data
+            if m is not None:
+                PM[i] = m.ctypes.data
+        left = np.array([t.n for t in self.tracers], np.int32)
+        _chk(self.L.ldso_trace_group_compact(self.h, _p(act), PK, _p(nh), PM, _p(left)))
+        for i in idx:
+            self.tracers[i].n = int(left[i])
+        return left
 
 
 class PyramidGroup(_Group):

@@ -10,10 +10,10 @@
 //   phase B (wave 0)     the pending candidates in order; an accepted one is inserted as addIntoDistFinal does: cell = 0, then the pruned BFS from that single
 //                        seed over a frontier list (a cell joins the next frontier only when the round lowered it), until the frontier is empty.
 // Float projections in the reference's operation order, no contraction, IEEE division, int conversion by truncation after + 0.5f (as trace.hip, ba_activate.hip).
-// For a batch of windows (ldso_ba_batch_select_candidates / _select_activate_points / _activate_points, at the end of the file) the same body runs as one workgroup per
-// window in one launch, k_act_select_batch, each window with its own sizes and map placement.
+// For a batch of windows (ldso_ba_batch_select_candidates / _select_activate_points / _select_activate_tracers / _activate_points, at the end of the file) the same body
+// runs as one workgroup per window in one launch, k_act_select_batch, each window with its own sizes and map placement.
 //
-// The host side, behind the kernels: all seven entries of point activation (ldso_ba_activate_points, the three single-window selections, the three batched calls).  What
+// The host side, behind the kernels: all eight entries of point activation (ldso_ba_activate_points, the three single-window selections, the four batched calls).  What
 // can be said of a selection without a device - the job, its checks, the layout of its arenas, packing and unpacking - is act_stage.h, once for both paths; this file
 // adds the device: sel_args (regions -> pointers), sel_arena (growth of ldso_ba::d_sel), sel_lds_rule (the map in LDS or not), act_preconditions, then sel_run for one window
 // and batch_select_run for a batch, each: check every job, lay out, stage, fill SelArgs, launch, download, unpack.
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_act_select_batch(const SelArgs 
     // pointers that come out of a table are generic to the compiler; all of these lie in global memory, and saying so keeps the body on global_load / global_store
 #define SEL_GLOBAL(p) p = (decltype(p)) (__attribute__((address_space(1))) void *) (uintptr_t) (p)
     SEL_GLOBAL(A.seeds); SEL_GLOBAL(A.pts); SEL_GLOBAL(A.myType); SEL_GLOBAL(A.KRKi); SEL_GLOBAL(A.Kt); SEL_GLOBAL(A.flagged); SEL_GLOBAL(A.gmap); SEL_GLOBAL(A.decision);
-    SEL_GLOBAL(A.selected); SEL_GLOBAL(A.nSelected); SEL_GLOBAL(A.cell); SEL_GLOBAL(A.frac); SEL_GLOBAL(A.thr);
+    SEL_GLOBAL(A.selected); SEL_GLOBAL(A.nSelected); SEL_GLOBAL(A.cell); SEL_GLOBAL(A.frac); SEL_GLOBAL(A.thr); SEL_GLOBAL(A.pgeo); SEL_GLOBAL(A.phost);
 #undef SEL_GLOBAL
     if (A.ldsMap) act_select_body<true>(A, sel_lds);
     else act_select_body<false>(A, sel_lds);
@@ -434,31 +434,39 @@ int batch_act_window_checks(const ldso_ba *H, const std::string &w, bool window,
     return window ? act_preconditions(H, w, n_hosts) : LDSO_OK;
 }
 
-struct SelPart { int win; ActJob J; ActRegions R; };          // a participating window, its job and its share of the call's arenas
+// a participating window, its job and its share of the call's arenas; T: the tracer of a resident job, `compact`: its set is compacted by the decisions
+struct SelPart { int win; ActJob J; ActRegions R; ldso_tracer *T = nullptr; bool compact = false; };
 
-// The arenas of a batched call lie in the batch's staging pair (batch_stage): [nPart SelArgs | nAct ActWin | nAct + 1 wavefront offsets | every window's upload] go up,
-// [every window's download] comes down, the scratch lies behind it on the device; a window's map lies in its own d_sel at offset 0, where ldso_ba_get_distance_map reads it.
-int batch_select_run(ldso_ba_batch *Bt, const char *who, const char *solo, ldso_act_job_t *jobs, float minTraceQuality, bool activate, int min_obs, float min_idepth_hessian,
-                     int gn_iterations) {
+// The arenas of a batched call lie in the batch's staging pair (batch_stage): [the tables of act_batch_tables | every window's upload] go up, [every window's download |
+// the counts of the compactions] come down, the scratch lies behind them on the device; a window's map lies in its own d_sel at offset 0, where ldso_ba_get_distance_map
+// reads it.  jobOf(i, H, p, takes): window i's job into p (J, and T / compact of a resident one) with the entry's own refusals, takes = false: it sits out;
+// done(p, nSelected): the window's results are unpacked, behind the wait (a compacted tracer has its new count).
+template <class JobOf, class Done>
+int batch_select_run(ldso_ba_batch *Bt, const char *who, const char *solo, bool haveJobs, const char *missing, float minTraceQuality, bool activate, int min_obs,
+                     float min_idepth_hessian, int gn_iterations, JobOf jobOf, Done done) {
     const std::string w(who);
     REQ(Bt, w + ": null batch");
-    REQ(jobs && gn_iterations >= 0, w + ": bad arguments (null jobs)");
+    REQ(haveJobs && gn_iterations >= 0, w + ": bad arguments (null jobs)");
     RUN(batch_act_checks(Bt, w, solo));
     ldso_ba *H0 = Bt->h[0];
     // ---- every refusal, before anything is enqueued or written; the regions of the arenas on the way ----
     std::vector<SelPart> part;
     ActBases at;
     size_t cands = 0;
-    int nAct = 0;
+    int nAct = 0, nCmp = 0;
     for (int i = 0; i < (int) Bt->h.size(); i++) {
-        if (jobs[i].n_hosts == 0) continue;
         const ldso_ba *H = Bt->h[(size_t) i];
         SelPart p;
-        p.win = i; p.J = act_job(jobs[i], H->w, H->h, activate);
-        RUN(act_job_check(p.J, w, ACT_MISSING_BATCH));
+        bool takes = false;
+        p.win = i;
+        RUN(jobOf(i, H, p, takes));
+        if (!takes) continue;
+        RUN(act_job_check(p.J, w, missing));
         RUN(batch_act_window_checks(H, w, activate, p.J.nHosts));
         p.R = act_layout(p.J, at);
+        p.compact = p.compact && p.J.n > 0;
         if (activate && p.J.n > 0) nAct++;
+        if (p.compact) nCmp++;
         cands += (size_t) p.J.n;
         part.push_back(p);
     }
@@ -467,37 +475,57 @@ int batch_select_run(ldso_ba_batch *Bt, const char *who, const char *solo, ldso_
     if (nPart == 0) return LDSO_OK;
     CHK(hipSetDevice(H0->device));
     if (activate) RUN(batch_refresh(Bt));
-    const size_t oTab = 0, oAct = oTab + up16((size_t) nPart * sizeof(SelArgs)), oWave = oAct + up16((size_t) nAct * sizeof(ActWin)), oIn = oWave + up16(((size_t) nAct + 1) * 4), up = oIn + at.up;
-    RUN(batch_stage(Bt, up, at.down + at.scratch));
+    const ActBatchTables O = act_batch_tables((size_t) nPart, (size_t) nAct, (size_t) nCmp, sizeof(SelArgs), sizeof(ActWin), sizeof(CompactArgs));
+    const size_t up = O.in + at.up, oCnt = at.down, down = oCnt + act_batch_counts((size_t) nCmp);
+    RUN(batch_stage(Bt, up, down + at.scratch));
     char *hs = Bt->h_stage, *d = Bt->d_stage, *dOut = d + up;
-    SelArgs *tab = (SelArgs *) (hs + oTab);
-    ActWin *act = (ActWin *) (hs + oAct);
-    int32_t *wave = (int32_t *) (hs + oWave);
+    SelArgs *tab = (SelArgs *) (hs + O.sel);
+    ActWin *act = (ActWin *) (hs + O.act);
+    int32_t *wave = (int32_t *) (hs + O.wave);
+    CompactArgs *cmp = (CompactArgs *) (hs + O.cmp);
     size_t ldsBytes = SEL_LIST_BYTES;
-    int waves = 0, ia = 0;
+    int waves = 0, ia = 0, ic = 0;
     for (int k = 0; k < nPart; k++) {
         const SelPart &p = part[(size_t) k];
         ldso_ba *H = Bt->h[(size_t) p.win];
-        act_pack(p.J, p.R, hs + oIn);
+        act_pack(p.J, p.R, hs + O.in);
         RUN(sel_arena(H, p.R.mapBytes, p.R.mapBytes));
         SelArgs &A = tab[k];
-        A = sel_args(p.J, p.R, d + oIn, dOut, dOut + at.down, (unsigned char *) H->d_sel, minTraceQuality);
+        A = sel_args(p.J, p.R, d + O.in, dOut, dOut + down, (unsigned char *) H->d_sel, minTraceQuality);
+        // the candidates where the tracer holds them, the seeds straight from the resident window: every point whose host is not the newest frame (as sel_run)
+        if (p.J.resident) { A.pts = p.T->d_pts; A.myType = p.T->d_type; A.pgeo = H->B.pgeo; A.phost = H->B.phost; A.nWin = H->D.P; A.newestHost = p.J.nHosts - 1; }
         RUN(sel_lds_rule((const void *) k_act_select_batch, H0->device, Bt->selLdsLimit, Bt->selLdsSet, p.R.mapBytes, ldsBytes, A.ldsMap));
         if (activate && p.J.n > 0) {
             act[ia] = act_win(A.pts, (ldso_activation_t *) (dOut + p.R.act), p.J.n, min_obs, min_idepth_hessian, gn_iterations, A.selected, A.nSelected, p.win);
             wave[ia++] = waves; waves += p.J.n;
         }
+        if (p.compact) { cmp[ic] = trace_compact_job(p.T, nullptr, A.decision, LDSO_ACT_KEEP, p.J.nHosts, nullptr, (int32_t *) (dOut + oCnt) + ic); ic++; }
     }
     wave[ia] = waves;
+    const int cmpBlocks = nCmp ? group_prefix(nCmp, (int *) (hs + O.first), [&](int c) { return compact_blocks(cmp[c].n); }) : 0;
     CHK(hipMemcpyAsync(d, hs, up, hipMemcpyHostToDevice, H0->stream));
-    hipLaunchKernelGGL(k_act_select_batch, dim3(nPart), dim3(SEL_THREADS), ldsBytes, H0->stream, (const SelArgs *) (d + oTab));
+    hipLaunchKernelGGL(k_act_select_batch, dim3(nPart), dim3(SEL_THREADS), ldsBytes, H0->stream, (const SelArgs *) (d + O.sel));
     CHK(hipGetLastError());
     for (const SelPart &p : part) { ldso_ba *H = Bt->h[(size_t) p.win]; H->selW1 = p.J.w1; H->selH1 = p.J.h1; H->selMapOffset = 0; }
-    if (activate) CHK(ba_launch_activate_batch(Bt->d_items, (const ActWin *) (d + oAct), (const int32_t *) (d + oWave), nAct, waves, Bt->Dmax.nsg, H0->settings, H0->stream));
-    CHK(hipMemcpyAsync(hs + up, dOut, at.down, hipMemcpyDeviceToHost, H0->stream));
+    if (activate) CHK(ba_launch_activate_batch(Bt->d_items, (const ActWin *) (d + O.act), (const int32_t *) (d + O.wave), nAct, waves, Bt->Dmax.nsg, H0->settings, H0->stream));
+    if (cmpBlocks > 0) CHK(trace_launch_compact_group((const CompactArgs *) (d + O.cmp), (const int *) (d + O.first), nCmp, cmpBlocks, H0->stream));
+    CHK(hipMemcpyAsync(hs + up, dOut, down, hipMemcpyDeviceToHost, H0->stream));
     CHK(hipStreamSynchronize(H0->stream));
-    for (const SelPart &p : part) jobs[p.win].n_selected = act_unpack(p.J, p.R, hs + up);
+    const int32_t *cnt = (const int32_t *) (hs + up + oCnt);
+    ic = 0;
+    for (const SelPart &p : part) {
+        if (p.compact) trace_compact_finish_group(p.T, cnt[ic++]);
+        done(p, act_unpack(p.J, p.R, hs + up));
+    }
     return LDSO_OK;
+}
+
+// the explicit-array entries: jobs[i].n_hosts == 0: window i takes no part
+int batch_select_arrays(ldso_ba_batch *Bt, const char *who, const char *solo, ldso_act_job_t *jobs, float minTraceQuality, bool activate, int min_obs, float min_idepth_hessian,
+                        int gn_iterations) {
+    return batch_select_run(Bt, who, solo, jobs != nullptr, ACT_MISSING_BATCH, minTraceQuality, activate, min_obs, min_idepth_hessian, gn_iterations,
+        [&](int i, const ldso_ba *H, SelPart &p, bool &takes) -> int { takes = jobs[i].n_hosts != 0; if (takes) p.J = act_job(jobs[i], H->w, H->h, activate); return LDSO_OK; },
+        [&](const SelPart &p, int ns) { jobs[p.win].n_selected = ns; });
 }
 
 }  // namespace
@@ -560,13 +588,34 @@ int ldso_ba_batch_activate_points(ldso_ba_batch_t *Bt, const int *n_pts, const l
 // jobs[i].n_hosts != 0: per window what ldso_ba_select_candidates gives on its handle alone, its final map where ldso_ba_get_distance_map(handle_i) reads it.  One
 // upload (the argument table and all inputs), one launch (k_act_select_batch: a workgroup per window), one download, one wait.
 int ldso_ba_batch_select_candidates(ldso_ba_batch_t *Bt, ldso_act_job_t *jobs, float minTraceQuality) {
-    return batch_select_run(Bt, "ldso_ba_batch_select_candidates", "ldso_ba_select_candidates", jobs, minTraceQuality, false, 0, 0.0f, 0);
+    return batch_select_arrays(Bt, "ldso_ba_batch_select_candidates", "ldso_ba_select_candidates", jobs, minTraceQuality, false, 0, 0.0f, 0);
 }
 
 // ... followed by the optimizeImmaturePoint loop (FullSystem.cc:1154-1164, 892-1010) on every window's selected list where the selection left it (k_activate_batch:
 // the wavefronts beyond a window's count leave at once): per window what ldso_ba_select_activate_points gives.  Two launches, one wait.
 int ldso_ba_batch_select_activate_points(ldso_ba_batch_t *Bt, ldso_act_job_t *jobs, float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations) {
-    return batch_select_run(Bt, "ldso_ba_batch_select_activate_points", "ldso_ba_select_activate_points", jobs, minTraceQuality, true, min_obs, min_idepth_hessian, gn_iterations);
+    return batch_select_arrays(Bt, "ldso_ba_batch_select_activate_points", "ldso_ba_select_activate_points", jobs, minTraceQuality, true, min_obs, min_idepth_hessian, gn_iterations);
+}
+
+// The same with every window's immature set where it lives (ldso_ba_select_activate_tracer, per window): the candidates are the records and types of jobs[i].tracer,
+// the seeds the points of the resident window i, and with jobs[i].compact != 0 whatever the loop did not KEEP leaves that tracer's set in the same enqueue
+// (FullSystem.cc:1105-1188).  One upload (the tables of the three kernels and KRKi / Kt / flags), four launches (k_act_select_batch, k_activate_batch,
+// k_compact_count_group, k_compact_move_group over the windows that compact: keep32 = the window's decisions), one download (decisions, lists, records and the
+// compactions' counts), one wait, whatever the number of windows.  jobs[i].tracer == NULL: window i takes no part.
+int ldso_ba_batch_select_activate_tracers(ldso_ba_batch_t *Bt, ldso_act_tracer_job_t *jobs, float minTraceQuality, int min_obs, float min_idepth_hessian, int gn_iterations) {
+    const std::string w("ldso_ba_batch_select_activate_tracers");
+    return batch_select_run(Bt, w.c_str(), "ldso_ba_select_activate_tracer", jobs != nullptr, ACT_MISSING_TRACERS, minTraceQuality, true, min_obs, min_idepth_hessian, gn_iterations,
+        [&](int i, const ldso_ba *H, SelPart &p, bool &takes) -> int {
+            const ldso_act_tracer_job_t &j = jobs[i];
+            takes = j.tracer != nullptr;
+            if (!takes) return LDSO_OK;
+            REQ(j.tracer->device == H->device, w + ": window " + std::to_string(i) + ": the tracer and the batch live on different devices");
+            for (int k = 0; k < i; k++) REQ(jobs[k].tracer != j.tracer, w + ": window " + std::to_string(i) + ": the same tracer in two jobs");
+            p.J = act_job(0, nullptr, j.tracer->n, nullptr, nullptr, j.n_hosts, j.KRKi, j.Kt, j.host_flagged, j.currentMinActDist, H->w, H->h, true, j.decision_out, j.selected_out, j.out);
+            p.J.resident = true; p.T = j.tracer; p.compact = j.compact != 0;
+            return LDSO_OK;
+        },
+        [&](const SelPart &p, int ns) { jobs[p.win].n_selected = ns; jobs[p.win].n_left = p.T->n; });
 }
 
 // debug: CoarseDistanceMap::fwdWarpedIDDistFinal as the last selection left it, (w >> 1) * (h >> 1) floats, 0..39 and 1000

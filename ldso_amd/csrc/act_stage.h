@@ -34,6 +34,7 @@ inline ActJob act_job(const ldso_act_job_t &j, int w, int h, bool records) {
 // what an entry says of a job without its arrays: a single-window one, a batched one
 constexpr const char *ACT_MISSING_SOLO = "bad arguments";
 constexpr const char *ACT_MISSING_BATCH = "a window that takes part needs its arrays (seeds, points, my_type, KRKi, Kt, host_flagged and the outputs)";
+constexpr const char *ACT_MISSING_TRACERS = "a window that takes part needs KRKi, Kt, host_flagged and, where its tracer holds records, the outputs";
 
 // The checks of one job; `who` names the entry.  Device data cannot be range-checked here: the kernel drops a candidate and skips a seed whose host is not a frame of the window.
 inline int act_job_check(const ActJob &J, const std::string &who, const char *missing) {
@@ -65,6 +66,18 @@ inline ActRegions act_layout(const ActJob &J, ActBases &at) {
     R.mapBytes = up16((size_t) J.w1 * J.h1);
     return R;
 }
+
+// The tables of a batched call, in front of the windows' uploads: [nPart selection rows | nAct activation rows | nAct + 1 wavefront offsets | nCmp compaction rows |
+// nCmp + 1 workgroup prefixes, where nCmp > 0], every region 16-byte aligned; `in` = where the first window's upload begins.  A call that compacts (the resident
+// tracers of ldso_ba_batch_select_activate_tracers) gets its nCmp counts back behind the windows' downloads: act_batch_counts.
+struct ActBatchTables { size_t sel, act, wave, cmp, first, in; };
+inline ActBatchTables act_batch_tables(size_t nPart, size_t nAct, size_t nCmp, size_t selBytes, size_t actBytes, size_t cmpBytes) {
+    ActBatchTables T;
+    T.sel = 0; T.act = T.sel + up16(nPart * selBytes); T.wave = T.act + up16(nAct * actBytes); T.cmp = T.wave + up16((nAct + 1) * 4); T.first = T.cmp + up16(nCmp * cmpBytes);
+    T.in = T.first + (nCmp ? up16((nCmp + 1) * 4) : 0);
+    return T;
+}
+inline size_t act_batch_counts(size_t nCmp) { return up16(nCmp * 4); }
 
 // the job's inputs into the host copy of the upload arena; the bytes between the regions are left as they are
 inline void act_pack(const ActJob &J, const ActRegions &R, char *up) {

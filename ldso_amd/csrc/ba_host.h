@@ -222,6 +222,25 @@ struct TraceJob {
 };
 hipError_t trace_launch_group(const TraceJob *d_jobs, const int *d_first, int nJobs, int totalWaves, hipStream_t st);      // trace.hip: totalWaves = first[nJobs] > 0
 
+// One stable compaction of a tracer's records as the kernels of trace.hip read it: the by-value argument of k_compact_count / k_compact_move, one row of the job table of
+// k_compact_count_group / k_compact_move_group (device memory there, every pointer a device pointer or null).  A workgroup serves CMP_THREADS records.
+constexpr int CMP_THREADS = 256;
+struct CompactArgs {
+    const ldso_immature_t *src; ldso_immature_t *dst;
+    const float *srcType; float *dstType;
+    int n, nHosts;
+    const unsigned char *keep8;      // keep flags as bytes, or
+    const int32_t *keep32;           // ... record i is kept where keep32[i] == keepValue, or (both null) every record
+    int keepValue;
+    const int32_t *hostMap;          // [nHosts] new host index, < 0: the frame left; null: identity
+    unsigned char *flag;             // [n]
+    int32_t *blockCount;             // [ceil(n / 256)]
+    int32_t *nOut;
+};
+inline int compact_blocks(int n) { return n > 0 ? (n + CMP_THREADS - 1) / CMP_THREADS : 0; }
+// trace.hip: the two launches over a job table; first[j] = the workgroups in front of job j (compact_blocks of its records), totalBlocks = first[nJobs] > 0
+hipError_t trace_launch_compact_group(const CompactArgs *d_jobs, const int *d_first, int nJobs, int totalBlocks, hipStream_t st);
+
 // the immature-point tracer (trace.hip)
 struct ldso_tracer {
     int device = 0, w = 0, h = 0, maxPoints = 0, n = 0;
@@ -366,6 +385,10 @@ int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const st
 // trace_compact_finish swaps the buffers and takes the new count once the caller has synchronised `st`.
 int trace_compact_enqueue(ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, bool haveMap, hipStream_t st);
 void trace_compact_finish(ldso_tracer *T);
+// The same compaction as a row of a grouped launch (T->n > 0): the map and the count lie where the caller says (its arena), the flags and workgroup counts are the
+// tracer's own.  Behind the caller's wait: trace_compact_finish_group with the count that came down.
+CompactArgs trace_compact_job(const ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, const int32_t *d_hostMap, int32_t *d_nOut);
+void trace_compact_finish_group(ldso_tracer *T, int nOut);
 // ba_batch.hip: the windows' descriptors as they are now into ldso_ba_batch::d_items; the batch's staging arena with room for `up` + `down` bytes
 int batch_refresh(ldso_ba_batch *Bt);
 int batch_stage(ldso_ba_batch *Bt, size_t up, size_t down);

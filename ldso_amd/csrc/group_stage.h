@@ -1,7 +1,7 @@
 // group_stage.h — what the grouped calls (ldso_tr_group_*, ldso_trace_group_*, ldso_pyr_group_*, ldso_undist_group_*) share as far as it can be said without a
 // device: who may be a member, which members take part in a call, the prefix table that group_member_of searches, and where the regions of each group's staging
 // arena lie.  The device side of an arena (GroupArena, AsyncArena) is in ba_host.h.  No HIP header: it compiles with a plain C++ compiler
-// (tests/test_group_stage_cpu.py runs it under the sanitizers).  A further group starts here: a rule, a layout, and its entries on top of both.
+// (tests/test_group_stage_cpu.py and tests/test_compact_group_stage_cpu.py run it under the sanitizers).  A further group starts here: a rule, a layout, and its entries on top of both.
 #pragma once
 #include <string>
 #include <vector>
@@ -90,6 +90,19 @@ inline TraceGroupLayout trace_group_layout(size_t poseFloats, size_t nj, size_t 
     TraceGroupLayout L;
     L.poses = 0; L.jobs = align_up(poseFloats * 4, 16); L.first = align_up(L.jobs + nj * jobBytes, 16); L.down = align_up(L.first + (nj + 1) * 4, 16);
     L.downBytes = nj * 8 * 4; L.total = L.down + L.downBytes;
+    return L;
+}
+
+// tracer group, compaction: [CompactArgs x nj | first, nj + 1 | host maps, mapInts per job | the keep bytes of every job | counts, nj ints], every region and every
+// job's keep bytes 16-byte aligned; the counts come down.  keepBytes(j) = the keep flags job j uploads (0: it keeps every record, or has none)
+struct CompactGroupLayout { size_t jobs, first, maps; std::vector<size_t> keep; size_t down, downBytes, total; };
+template <class KeepBytes> CompactGroupLayout compact_group_layout(size_t nj, size_t jobBytes, size_t mapInts, KeepBytes keepBytes) {
+    CompactGroupLayout L;
+    L.jobs = 0; L.first = align_up(nj * jobBytes, 16); L.maps = align_up(L.first + (nj + 1) * 4, 16);
+    size_t at = align_up(L.maps + nj * mapInts * 4, 16);
+    L.keep.resize(nj);
+    for (size_t j = 0; j < nj; j++) { L.keep[j] = at; at = align_up(at + keepBytes(j), 16); }
+    L.down = at; L.downBytes = nj * 4; L.total = L.down + L.downBytes;
     return L;
 }
 

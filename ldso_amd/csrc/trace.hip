@@ -287,25 +287,13 @@ hipError_t trace_launch_group(const TraceJob *d_jobs, const int *d_first, int nJ
 //   k_compact_count  one flag per record, one count per workgroup of 256 records
 //   k_compact_move   every workgroup sums the counts in front of it (<= max_points / 256 words), ranks its own records, then moves them: 8 lanes x 16 B per
 //                    128-byte record, the lane that holds `host` rewrites it
+// CompactArgs (ba_host.h) is one compaction; the bodies are device functions of (job, block, blocks of the job), shared with the grouped kernels below.
 // ---------------------------------------------------------------------------------------------------------
-constexpr int CMP_THREADS = 256;
-
-struct CompactArgs {
-    const ldso_immature_t *src; ldso_immature_t *dst;
-    const float *srcType; float *dstType;
-    int n, nHosts;
-    const unsigned char *keep8;      // keep flags as bytes, or
-    const int32_t *keep32;           // ... record i is kept where keep32[i] == keepValue, or (both null) every record
-    int keepValue;
-    const int32_t *hostMap;          // [nHosts] new host index, < 0: the frame left; null: identity
-    unsigned char *flag;             // [n]
-    int32_t *blockCount;             // [ceil(n / 256)]
-    int32_t *nOut;
-};
-
-__global__ __launch_bounds__(CMP_THREADS) void k_compact_count(CompactArgs A) {
+// the body of k_compact_count for workgroup `block` of the nBlocks that serve A
+static __device__ __forceinline__ void compact_count(const CompactArgs &A, int block, int nBlocks) {
     __shared__ int s_cnt[CMP_THREADS / 64];
-    const int i = blockIdx.x * CMP_THREADS + threadIdx.x;
+    (void) nBlocks;
+    const int i = block * CMP_THREADS + threadIdx.x;
     bool keep = false;
     if (i < A.n) {
         const int host = A.src[i].host;
@@ -316,24 +304,25 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_count(CompactArgs A) {
     const int c = __popcll(__ballot(keep));
     if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) A.blockCount[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    if (threadIdx.x == 0) A.blockCount[block] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-__global__ __launch_bounds__(CMP_THREADS) void k_compact_move(CompactArgs A) {
+// the body of k_compact_move for workgroup `block` of the nBlocks that serve A
+static __device__ __forceinline__ void compact_move(const CompactArgs &A, int block, int nBlocks) {
     __shared__ int s_part[2][CMP_THREADS / 64], s_wave[CMP_THREADS / 64], s_dest[CMP_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nBlocks = gridDim.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the workgroups in front of this one, and all of them
     int before = 0, total = 0;
-    for (int j = tid; j < nBlocks; j += CMP_THREADS) { const int c = A.blockCount[j]; total += c; if (j < (int) blockIdx.x) before += c; }
+    for (int j = tid; j < nBlocks; j += CMP_THREADS) { const int c = A.blockCount[j]; total += c; if (j < block) before += c; }
     before = wave_sum(before); total = wave_sum(total);
-    const int i = blockIdx.x * CMP_THREADS + tid;
+    const int i = block * CMP_THREADS + tid;
     const bool keep = i < A.n && A.flag[i] != 0;
     const unsigned long long bm = __ballot(keep);
     if (lane == 0) { s_part[0][wave] = before; s_part[1][wave] = total; s_wave[wave] = __popcll(bm); }
     __syncthreads();
     before = s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3];
     total = s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3];
-    if (blockIdx.x == 0 && tid == 0) *A.nOut = total;
+    if (block == 0 && tid == 0) *A.nOut = total;
     int rank = before + __popcll(bm & ((1ull << lane) - 1ull));
     for (int wv = 0; wv < wave; wv++) rank += s_wave[wv];
     s_dest[tid] = keep ? rank : -1;
@@ -344,10 +333,66 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_move(CompactArgs A) {
     for (int r = tid >> 3; r < CMP_THREADS; r += CMP_THREADS / 8) {
         const int d = s_dest[r];
         if (d < 0) continue;                       // covers r beyond n: s_dest is -1 there
-        uint4 q = ((const uint4 *) (A.src + blockIdx.x * CMP_THREADS + r))[part];
+        uint4 q = ((const uint4 *) (A.src + block * CMP_THREADS + r))[part];
         if (part == 7 && A.hostMap) q.z = (unsigned) A.hostMap[(int) q.z];            // the count pass kept only hosts in [0, nHosts)
         ((uint4 *) (A.dst + d))[part] = q;
     }
+}
+
+__global__ __launch_bounds__(CMP_THREADS) void k_compact_count(CompactArgs A) { compact_count(A, (int) blockIdx.x, (int) gridDim.x); }
+__global__ __launch_bounds__(CMP_THREADS) void k_compact_move(CompactArgs A) { compact_move(A, (int) blockIdx.x, (int) gridDim.x); }
+
+// a row of the compaction table as the kernels read it: CompactArgs with its pointers typed as device memory (group_member.h: LD_GLOBAL)
+struct CompactArgsDev {
+    LD_GLOBAL const ldso_immature_t *src; LD_GLOBAL ldso_immature_t *dst;
+    LD_GLOBAL const float *srcType; LD_GLOBAL float *dstType;
+    int n, nHosts;
+    LD_GLOBAL const unsigned char *keep8;
+    LD_GLOBAL const int32_t *keep32;
+    int keepValue;
+    LD_GLOBAL const int32_t *hostMap;
+    LD_GLOBAL unsigned char *flag;
+    LD_GLOBAL int32_t *blockCount;
+    LD_GLOBAL int32_t *nOut;
+};
+static_assert(sizeof(CompactArgsDev) == sizeof(CompactArgs) && offsetof(CompactArgsDev, n) == offsetof(CompactArgs, n) && offsetof(CompactArgsDev, keep8) == offsetof(CompactArgs, keep8) &&
+              offsetof(CompactArgsDev, keepValue) == offsetof(CompactArgs, keepValue) && offsetof(CompactArgsDev, nOut) == offsetof(CompactArgs, nOut), "CompactArgsDev is CompactArgs");
+
+// The compactions of many tracers in two launches (ldso_trace_group_compact, trace_group.hip; ldso_ba_batch_select_activate_tracers, act_select.hip): first[j] = the
+// workgroups in front of job j, first[nJobs] = the grid.  Workgroup u serves the job group_member_of finds as that job's block u - first[j] of first[j + 1] - first[j]:
+// the same body on the same bytes as the job's own k_compact_count / k_compact_move.  A job without records has no workgroup.  Job index and block are uniform
+// (blockIdx), and the row is copied before the first store of the kernel, so its pointers stay in scalar registers.
+static __device__ __forceinline__ CompactArgs compact_job_of(const CompactArgs *jobs, const int *first, int nJobs, int &block, int &nBlocks) {
+    const int u = (int) blockIdx.x;
+    const int j = group_member_of(first, nJobs, u);
+    const int f0 = first[j];
+    block = u - f0; nBlocks = first[j + 1] - f0;
+    const CompactArgsDev D = ((const CompactArgsDev *) jobs)[j];
+    CompactArgs A;
+    A.src = (const ldso_immature_t *) D.src; A.dst = (ldso_immature_t *) D.dst; A.srcType = (const float *) D.srcType; A.dstType = (float *) D.dstType; A.n = D.n; A.nHosts = D.nHosts;
+    A.keep8 = (const unsigned char *) D.keep8; A.keep32 = (const int32_t *) D.keep32; A.keepValue = D.keepValue; A.hostMap = (const int32_t *) D.hostMap;
+    A.flag = (unsigned char *) D.flag; A.blockCount = (int32_t *) D.blockCount; A.nOut = (int32_t *) D.nOut;
+    return A;
+}
+
+__global__ __launch_bounds__(CMP_THREADS) void k_compact_count_group(const CompactArgs *__restrict__ jobs, const int *__restrict__ first, int nJobs) {
+    int block, nBlocks;
+    const CompactArgs A = compact_job_of(jobs, first, nJobs, block, nBlocks);
+    compact_count(A, block, nBlocks);
+}
+
+__global__ __launch_bounds__(CMP_THREADS) void k_compact_move_group(const CompactArgs *__restrict__ jobs, const int *__restrict__ first, int nJobs) {
+    int block, nBlocks;
+    const CompactArgs A = compact_job_of(jobs, first, nJobs, block, nBlocks);
+    compact_move(A, block, nBlocks);
+}
+
+hipError_t trace_launch_compact_group(const CompactArgs *d_jobs, const int *d_first, int nJobs, int totalBlocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_compact_count_group, dim3(totalBlocks), dim3(CMP_THREADS), 0, st, d_jobs, d_first, nJobs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_compact_move_group, dim3(totalBlocks), dim3(CMP_THREADS), 0, st, d_jobs, d_first, nJobs);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -358,14 +403,20 @@ static constexpr int TYPE_ONE = 0x3f800000;      // 1.0f as the word hipMemsetD3
 
 // The compaction on stream `st` (the tracer's own, or the stream of the BA handle whose selection produced keep32: the tracer is idle then).  The host map, when
 // there is one, lies in d_cmp already.  Nothing of the tracer's host state changes until trace_compact_finish, which the caller runs behind its synchronisation.
+CompactArgs trace_compact_job(const ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, const int32_t *d_hostMap, int32_t *d_nOut) {
+    CompactArgs A;
+    memset(&A, 0, sizeof(A));          // a row of a table crosses PCIe: every byte set
+    A.src = T->d_pts; A.dst = T->d_alt; A.srcType = T->d_type; A.dstType = T->d_typeAlt; A.n = T->n; A.nHosts = n_hosts;
+    A.keep8 = d_keep8; A.keep32 = d_keep32; A.keepValue = keepValue; A.hostMap = d_hostMap;
+    A.flag = T->d_flag; A.nOut = d_nOut; A.blockCount = T->d_cmp + LDSO_MAX_FRAMES + 4;
+    return A;
+}
+
 int trace_compact_enqueue(ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, bool haveMap, hipStream_t st) {
     T->nAfterCompact = T->n;
     if (T->n <= 0) return LDSO_OK;
-    CompactArgs A;
-    A.src = T->d_pts; A.dst = T->d_alt; A.srcType = T->d_type; A.dstType = T->d_typeAlt; A.n = T->n; A.nHosts = n_hosts;
-    A.keep8 = d_keep8; A.keep32 = d_keep32; A.keepValue = keepValue; A.hostMap = haveMap ? T->d_cmp : nullptr;
-    A.flag = T->d_flag; A.nOut = T->d_cmp + LDSO_MAX_FRAMES; A.blockCount = T->d_cmp + LDSO_MAX_FRAMES + 4;
-    const int blocks = (T->n + CMP_THREADS - 1) / CMP_THREADS;
+    const CompactArgs A = trace_compact_job(T, d_keep8, d_keep32, keepValue, n_hosts, haveMap ? T->d_cmp : nullptr, T->d_cmp + LDSO_MAX_FRAMES);
+    const int blocks = compact_blocks(T->n);
     hipLaunchKernelGGL(k_compact_count, dim3(blocks), dim3(CMP_THREADS), 0, st, A);
     CHK(hipGetLastError());
     hipLaunchKernelGGL(k_compact_move, dim3(blocks), dim3(CMP_THREADS), 0, st, A);
@@ -379,6 +430,8 @@ void trace_compact_finish(ldso_tracer *T) {
     std::swap(T->d_pts, T->d_alt); std::swap(T->d_type, T->d_typeAlt);
     T->n = std::min(std::max(T->nAfterCompact, 0), T->n);
 }
+
+void trace_compact_finish_group(ldso_tracer *T, int nOut) { T->nAfterCompact = nOut; trace_compact_finish(T); }
 
 extern "C" {
 
