@@ -684,6 +684,42 @@ int ldso_feat_device(ldso_features_t *f, const void **features_dev, const void *
 int ldso_feat_profile(ldso_features_t *f, int enable, float us_out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * A group of detectors: FullSystem::makeNewTraces (FullSystem.cc:1272-1325) for setting_pointSelection == 1 = FeatureDetector::DetectCorners
+ * (src/frontend/FeatureDetector.cc:34-130) and the ImmaturePoint constructors (src/internal/ImmaturePoint.cc:14-38) of the key frames that many sequences on one
+ * card make in the same step.  One ldso_feat_detect is a memset, five launches (most of its time on a handful of workgroups), a download and a wait, and
+ * ldso_trace_append_points_device waits once more; a group call runs the same kernel bodies for all active members in five launches, six with the append, with one
+ * upload, one download and one wait, whatever n.  A member's features, records, counts and appended records are those of its own solo calls from the same input,
+ * byte for byte.  All arrays are member-major.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct ldso_feat_group ldso_feat_group_t;
+/* 1 <= n <= 128 detectors on one device and one stream (ldso_feat_set_stream); image size, max_features, response table and pattern may differ.  A detector
+ * belongs to at most one group and stays usable on its own between group calls (ldso_feat_set_response, ldso_feat_detect, ldso_feat_get, ldso_feat_device, ...): the
+ * group reads every member's current state at each call and writes every result but the control words into the member's own buffers, and every call checks that
+ * the members still share their stream.  ldso_feat_destroy of a member is refused while the group lives. */
+int ldso_feat_group_create(ldso_features_t *const *members, int n, ldso_feat_group_t **out);
+int ldso_feat_group_destroy(ldso_feat_group_t *g);
+/* ldso_feat_detect(member_i, pyr[i], n_features[i], host_index[i], ...) for every member with active[i] != 0 (NULL: all; entries of inactive members are not
+ * read).  tracers: NULL, or n pointers of which an entry may be NULL; member i's fresh records are appended to tracers[i] with my_type = 1 in the same enqueue, as
+ * ldso_trace_append_points_device(tracers[i], n_i, member i's records) would, and the tracer's count grows behind the call's wait.  Everything is checked before
+ * anything is enqueued, every refusal names the member's index, and nothing of any member or tracer changes: LDSO_E_INVALID for an n_features out of range, a
+ * grid's capacity above max_features, a pyramid that does not fit the member or holds no image, a tracer that is not on the group's device and stream, the same
+ * tracer for two members, or a tracer with max_points - n below the GRID'S CAPACITY (ldso_feat_grid) - the count is not known before the wait, so this is stricter
+ * than the solo append, which needs room for the features found only; LDSO_E_UNSUPPORTED for a gridsize above 64.
+ * n_features_out, n_corners_out, status_out: n each or NULL; rows of inactive members are left untouched.  A non-finite pixel, score, angle or colour in member i
+ * sets status_out[i] = LDSO_E_NONFINITE (LDSO_OK otherwise); the call then returns LDSO_E_NONFINITE and the message names the first such member.  As in the solo
+ * call every member's results are there to be fetched, and the appends have happened: such records carry energyTH = NaN, and FullSystem.cc:1298 drops them. */
+int ldso_feat_group_detect(ldso_feat_group_t *g, const uint8_t *active /* n or NULL = all */, ldso_pyramid_t *const *pyr /* n */, const int *n_features /* n */,
+                           const int *host_index /* n */, ldso_tracer_t *const *tracers /* n pointers or NULL */, int *n_features_out, int *n_corners_out,
+                           int *status_out /* each n or NULL */);
+/* ldso_feat_get of every active member: features_out[i] / immature_out[i] take the member's last count of records (an entry or an array NULL: not fetched);
+ * exactly-sized copies, one wait.  A member's own ldso_feat_get and ldso_feat_device give the same after a group call. */
+int ldso_feat_group_get(ldso_feat_group_t *g, const uint8_t *active /* n or NULL = all */, ldso_feature_t *const *features_out /* n pointers or NULL */,
+                        ldso_immature_t *const *immature_out /* n pointers or NULL */);
+/* enable != 0: ldso_feat_group_detect brackets its launches with HIP events; us_out[5] (optional) = microseconds of the last profiled call:
+ * cells + compaction, corners, angle + descriptor, records, append */
+int ldso_feat_group_profile(ldso_feat_group_t *g, int enable, float us_out[5]);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DSO's gradient pixels of a key frame: FullSystem::makeNewTraces for setting_pointSelection == 0 (FullSystem.cc:1284-1304) = PixelSelector::makeMaps
  * (src/frontend/PixelSelector2.cc:111-168; makeHists :36-109, computeHistQuantil :27-34, select :170-315), the raster scan of the map and one ImmaturePoint
  * constructor per hit (src/internal/ImmaturePoint.cc:14-38), on levels 0-2 of a resident pyramid.  Maps, counts, potentials and thresholds are exactly the

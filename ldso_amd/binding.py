@@ -1194,7 +1194,7 @@ def _active_mask(active, n):
 
 
 class _Group:
-    """what the four groups share: the members are kept alive (the group dereferences them), the handle comes from the entry named by _create and goes back
+    """what the groups share: the members are kept alive (the group dereferences them), the handle comes from the entry named by _create and goes back
     through the one named by _destroy - unchecked, unlike a member's close: a group's destroy has nothing that refuses it"""
     _create = _destroy = None
 
@@ -1488,6 +1488,69 @@ class UndistorterGroup(_Group):
         """microseconds of the last profiled call: the one copy, the undistortion kernel, the grouped pyramid build"""
         us = np.zeros(3, np.float32)
         _chk(self.L.ldso_undist_group_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
+        return us
+
+
+class FeaturesGroup(_Group):
+    """ldso_feat_group_*: the corner features and immature points of the key frames of several detectors (independent sequences on one device and one stream) in
+    five launches, six when the records are appended to the sequences' tracers.  Arguments and results are per member, in the order of `detectors`; the members stay
+    usable on their own between group calls."""
+
+    _create, _destroy = "ldso_feat_group_create", "ldso_feat_group_destroy"
+
+    def __init__(self, detectors):
+        super().__init__(detectors)
+        self.detectors = self.members
+
+    def detect(self, pyramids, n_features, host_indices=None, tracers=None, active=None):
+        """ldso_feat_group_detect -> (n, n_corners, status) int32 arrays of one entry per member; entries of inactive members are -1.  pyramids: one Pyramid per
+        member (None for an inactive one), n_features: n values or one for all, tracers: None or one Tracer / None per member.  Raises LdsoError; with the code
+        E_NONFINITE the results are there all the same: Features.n / n_corners, Tracer.n and `last` = the three arrays."""
+        n = len(self.detectors)
+        assert len(pyramids) == n and (tracers is None or len(tracers) == n)
+        act, idx = _active_mask(active, n)
+        P = (C.c_void_p * n)()
+        for i in idx:
+            if pyramids[i] is not None:          # a missing one is refused by the library, with the member's index
+                P[i] = pyramids[i].h
+        T = None
+        if tracers is not None:
+            T = (C.c_void_p * n)()
+            for i in idx:
+                if tracers[i] is not None:
+                    T[i] = tracers[i].h
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_features, np.int32), (n,)), np.int32)
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(0 if host_indices is None else host_indices, np.int32), (n,)), np.int32)
+        cnt = np.full(n, -1, np.int32); cor = np.full(n, -1, np.int32); sta = np.full(n, -1, np.int32)
+        code = self.L.ldso_feat_group_detect(self.h, _p(act), P, _p(nf), _p(hi), T, _p(cnt), _p(cor), _p(sta))
+        if code in (0, E_NONFINITE):
+            for i in idx:
+                self.detectors[i].n, self.detectors[i].n_corners = int(cnt[i]), int(cor[i])
+                if tracers is not None and tracers[i] is not None:
+                    tracers[i].n += int(cnt[i])
+        self.last = (cnt, cor, sta)
+        _chk(code)
+        return cnt, cor, sta
+
+    def get(self, active=None):
+        """ldso_feat_group_get -> per member (features, immature records) of its last detection, None for an inactive member"""
+        n = len(self.detectors)
+        act, idx = _active_mask(active, n)
+        PF, PQ = (C.c_void_p * n)(), (C.c_void_p * n)()
+        out = [None] * n
+        for i in idx:
+            f = np.zeros(self.detectors[i].n, synth.FEATURE_DTYPE)
+            q = np.zeros(self.detectors[i].n, synth.IMMATURE_DTYPE)
+            out[i] = (f, q)
+            if len(f):
+                PF[i] = f.ctypes.data; PQ[i] = q.ctypes.data
+        _chk(self.L.ldso_feat_group_get(self.h, _p(act), PF, PQ))
+        return out
+
+    def profile(self, enable=True):
+        """microseconds of the last profiled call: cells + compaction, corners, angle + descriptor, records, append"""
+        us = np.zeros(5, np.float32)
+        _chk(self.L.ldso_feat_group_profile(self.h, C.c_int(1 if enable else 0), _p(us)))
         return us
 
 

@@ -1,7 +1,7 @@
-// group_stage.h — what the grouped calls (ldso_tr_group_*, ldso_trace_group_*, ldso_pyr_group_*, ldso_undist_group_*) share as far as it can be said without a
+// group_stage.h — what the grouped calls (ldso_tr_group_*, ldso_trace_group_*, ldso_pyr_group_*, ldso_undist_group_*, ldso_feat_group_*) share as far as it can be said without a
 // device: who may be a member, which members take part in a call, the prefix table that group_member_of searches, and where the regions of each group's staging
 // arena lie.  The device side of an arena (GroupArena, AsyncArena) is in ba_host.h.  No HIP header: it compiles with a plain C++ compiler
-// (tests/test_group_stage_cpu.py and tests/test_compact_group_stage_cpu.py run it under the sanitizers).  A further group starts here: a rule, a layout, and its entries on top of both.
+// (tests/test_group_stage_cpu.py, tests/test_compact_group_stage_cpu.py and tests/test_feat_group_abi_cpu.py run it under the sanitizers).  A further group starts here: a rule, a layout, and its entries on top of both.
 #pragma once
 #include <string>
 #include <vector>
@@ -103,6 +103,17 @@ template <class KeepBytes> CompactGroupLayout compact_group_layout(size_t nj, si
     L.keep.resize(nj);
     for (size_t j = 0; j < nj; j++) { L.keep[j] = at; at = align_up(at + keepBytes(j), 16); }
     L.down = at; L.downBytes = nj * 4; L.total = L.down + L.downBytes;
+    return L;
+}
+
+// features group: [FeatArgs x nj | four prefix tables of nj + 1: cells, compaction, corners and records (they share one), angle + descriptor | ctl rows, nj x 8 ints],
+// each region 16-byte aligned; the ctl rows go up zeroed and come down
+struct FeatGroupLayout { size_t jobs, firstCells, firstCompact, firstCorners, firstDescribe, down, downBytes, total; };
+inline FeatGroupLayout feat_group_layout(size_t nj, size_t jobBytes) {
+    FeatGroupLayout L;
+    const size_t table = align_up((nj + 1) * 4, 16);
+    L.jobs = 0; L.firstCells = align_up(nj * jobBytes, 16); L.firstCompact = L.firstCells + table; L.firstCorners = L.firstCompact + table; L.firstDescribe = L.firstCorners + table;
+    L.down = L.firstDescribe + table; L.downBytes = nj * 8 * 4; L.total = L.down + L.downBytes;
     return L;
 }
 
