@@ -1,23 +1,11 @@
-// ba_host.h — what the host-side translation units of the library share: the error channel, the launcher prototypes of the kernel files, the
-// handle structs, and the host helpers that cross files (hidden: none of them is part of the library's interface).
+// ba_host.h — what the host-side translation units of the bundle adjustment share (the ba_*.hip units and act_select.hip, which also compacts tracers): the
+// launcher prototypes of its kernel files, the handle and the batch, and the host helpers of the BA that cross files (hidden: none of them is part of the
+// library's interface).  What every host-side unit shares is hip_host.h; a stage unit includes that, never this file.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include "host_only.h"          // ldso_set_error, REQ, RUN
-#include "group_stage.h"        // align_up; membership, active list, prefix table and arena layouts of the grouped calls
+#include "hip_host.h"           // CHK, launch_lds, the create / allocation / stream / arena helpers
+#include "trace.h"              // ldso_tracer, CompactArgs, trace_compact_* (act_select.hip)
 #include "ba_dev.h"
-#include "pyramid.h"
 #include "ba_solve.h"
-
-#define CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ldso_set_error(std::string(#call) + ": " + hipGetErrorString(e_)); return LDSO_E_HIP; } } while (0)
-
-// A launch with dynamic LDS: above 48 KB the kernel's limit is raised first; the status of that call is no reason to skip the launch, whose own error the caller sees
-template <class Kernel, class... Args>
-hipError_t launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t ldsBytes, hipStream_t st, const Args &... args) {
-    if (ldsBytes > 48 * 1024) (void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes);
-    hipLaunchKernelGGL(kernel, grid, block, ldsBytes, st, args...);
-    return hipGetLastError();
-}
 
 // k_activate's view of a call (ba_activate.hip), and one window's share of a batched one (k_activate_batch): `item` = the window's BatchItem in ldso_ba_batch::d_items
 struct ActArgs {
@@ -208,187 +196,7 @@ struct BatchCuts {
     std::vector<int32_t> wg[3];
 };
 
-// One trace as the kernels of trace.hip read it: the by-value argument of k_trace_on, one row of the job table of k_trace_group (device memory there, every pointer
-// a device pointer; the rows of a launch share nothing)
-struct TraceJob {
-    ldso_immature_t *pts;
-    int n;
-    const float *img;       // level-0 image of the new frame, 12-byte AoS (I, dx, dy)
-    int w, h;
-    const float *KRKi, *Kt, *aff;      // per host: 9, 3, 2 floats
-    int nHosts;
-    ldso_trace_settings_t s;
-    int *counts;            // [6] per resulting status (a row of 8 ints)
-};
-hipError_t trace_launch_group(const TraceJob *d_jobs, const int *d_first, int nJobs, int totalWaves, hipStream_t st);      // trace.hip: totalWaves = first[nJobs] > 0
-
-// One stable compaction of a tracer's records as the kernels of trace.hip read it: the by-value argument of k_compact_count / k_compact_move, one row of the job table of
-// k_compact_count_group / k_compact_move_group (device memory there, every pointer a device pointer or null).  A workgroup serves CMP_THREADS records.
-constexpr int CMP_THREADS = 256;
-struct CompactArgs {
-    const ldso_immature_t *src; ldso_immature_t *dst;
-    const float *srcType; float *dstType;
-    int n, nHosts;
-    const unsigned char *keep8;      // keep flags as bytes, or
-    const int32_t *keep32;           // ... record i is kept where keep32[i] == keepValue, or (both null) every record
-    int keepValue;
-    const int32_t *hostMap;          // [nHosts] new host index, < 0: the frame left; null: identity
-    unsigned char *flag;             // [n]
-    int32_t *blockCount;             // [ceil(n / 256)]
-    int32_t *nOut;
-};
-inline int compact_blocks(int n) { return n > 0 ? (n + CMP_THREADS - 1) / CMP_THREADS : 0; }
-// trace.hip: the two launches over a job table; first[j] = the workgroups in front of job j (compact_blocks of its records), totalBlocks = first[nJobs] > 0
-hipError_t trace_launch_compact_group(const CompactArgs *d_jobs, const int *d_first, int nJobs, int totalBlocks, hipStream_t st);
-
-// the immature-point tracer (trace.hip)
-struct ldso_tracer {
-    int device = 0, w = 0, h = 0, maxPoints = 0, n = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    const void *inGroup = nullptr;    // the ldso_trace_group this tracer belongs to (at most one; ldso_trace_destroy refuses while set: the group dereferences its members)
-    ldso_trace_settings_t settings;
-    ldso_immature_t *d_pts = nullptr, *d_alt = nullptr;     // the resident records; the buffer the next compaction writes (the two swap)
-    float *d_type = nullptr, *d_typeAlt = nullptr;          // ImmaturePoint::my_type of every record (ImmaturePoint.h:114), beside d_pts / d_alt
-    unsigned char *d_keep = nullptr, *d_flag = nullptr;     // [maxPoints] compaction: the caller's keep flags, the flags of the count pass
-    int32_t *d_cmp = nullptr;                               // [LDSO_MAX_FRAMES host map | 4: the new count | maxPoints / 256 workgroup counts]
-    int nAfterCompact = 0;                                  // where an enqueued compaction's count lands (trace_compact_finish)
-    float *d_img = nullptr, *d_color = nullptr, *d_pose = nullptr;      // pose: [LDSO_MAX_FRAMES][14]
-    const float *img = nullptr;       // the frame traced on: d_img, or level 0 of a shared ldso_pyramid_t
-    int *d_counts = nullptr;
-    bool haveFrame = false;
-};
-
-// The staging arena of a grouped call (group_stage.h: the layouts): one pinned arena and its device twin, grown on demand.  The tracker and tracer groups end every
-// call with a host wait, so the next call finds both sides free.
-struct GroupArena { char *h_stage = nullptr, *d_stage = nullptr; size_t stageCap = 0; };
-// The same for a group whose calls do NOT wait on the host (pyramid and undistorter groups).  The pinned side is free once the last upload has been read: `uploaded`,
-// recorded behind the copy, guards it against the next call's writes.  The device side is free once the last call's kernels are through: in stream order on the
-// same stream, behind `done` (recorded behind the last launch) on another.  A replacement of the pair waits for `done` on the host.
-struct AsyncArena : GroupArena {
-    hipEvent_t uploaded = nullptr, done = nullptr;
-    hipStream_t lastStream = nullptr;
-    bool used = false;
-};
-
-// a group of tracers whose traces share one launch (trace_group.hip)
-struct ldso_trace_group {
-    std::vector<ldso_tracer *> m;
-    int device = 0;
-    GroupArena arena;
-};
-
-// a group of pyramids whose builds share launches (images.hip)
-struct ldso_pyr_group {
-    std::vector<ldso_pyramid *> m;
-    int device = 0;
-    AsyncArena arena;
-};
-
 #pragma GCC visibility push(hidden)
-// The head of a create function: a device must be visible, `device` must name one, and it becomes the current one.
-inline int open_device(int device, const char *who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ldso_set_error("no HIP device visible"); return LDSO_E_NODEVICE; }
-    REQ(device >= 0 && device < ndev, std::string(who) + ": device index out of range");
-    CHK(hipSetDevice(device));
-    return LDSO_OK;
-}
-// The tail of a create function whose body may fail half-way: the handle's own destroy frees whatever a half-built handle holds, the error text of the failure is kept.
-template <class Handle, class Destroy> int finish_create(int r, Handle *H, Handle **out, Destroy destroy) {
-    if (r != LDSO_OK) { const std::string keep = ldso_last_error(); destroy(H); ldso_set_error(keep); return r; }
-    *out = H; return LDSO_OK;
-}
-// Zero-fill of fresh device memory, waited for: hipMemset on device memory is asynchronous (legacy null stream) and the handles work on NON-BLOCKING streams,
-// which do not order themselves behind it: without the wait a zero-fill that is still queued (the null stream busy with another library's work, e.g. torch's)
-// could land on top of data the handle's first uploads / kernels have already written
-inline int zero_fill(void *p, size_t bytes) { CHK(hipMemset(p, 0, bytes)); CHK(hipStreamSynchronize(nullptr)); return LDSO_OK; }
-// n zeroed elements of device memory, recorded in `allocs` (what the handle's destroy frees)
-template <class T> int dalloc(std::vector<void *> &allocs, T **p, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    CHK(hipMalloc((void **) p, bytes));
-    allocs.push_back(*p);
-    return zero_fill(*p, bytes);
-}
-#define DALLOC(allocs, ptr, n) RUN(dalloc(allocs, &(ptr), (n)))
-// *_set_stream: the caller's stream `s` instead of the handle's own non-blocking one (which is drained and destroyed), or, with s == nullptr, an own one again
-inline int swap_stream(hipStream_t &stream, bool &ownStream, void *s) {
-    if (ownStream && stream) { hipStreamSynchronize(stream); if (s) { hipStreamDestroy(stream); ownStream = false; } }
-    if (s) { stream = (hipStream_t) s; ownStream = false; }
-    else if (!ownStream) { CHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)); ownStream = true; }
-    return LDSO_OK;
-}
-// A pinned arena and its device twin (the handle's h_stage / d_stage, the batch's) with room for `need` bytes.  A pair that is too small is replaced by one of
-// need + need / slackDiv bytes once `st`, the stream whose work may still read the old pair, has drained.
-inline int grow_arena(char *&h, char *&d, size_t &cap, size_t need, size_t slackDiv, hipStream_t st) {
-    if (need <= cap) return LDSO_OK;
-    CHK(hipStreamSynchronize(st));
-    if (h) (void) hipHostFree(h);
-    if (d) (void) hipFree(d);
-    h = nullptr; d = nullptr; cap = 0;
-    const size_t room = need + need / slackDiv;
-    CHK(hipHostMalloc((void **) &h, room));
-    CHK(hipMalloc((void **) &d, room));
-    cap = room;
-    return LDSO_OK;
-}
-// the arena of a group with room for `need` bytes; `st` = the stream of the group's calls
-inline int group_arena_grow(GroupArena &A, size_t need, hipStream_t st) { return grow_arena(A.h_stage, A.d_stage, A.stageCap, need, 2, st); }
-inline void group_arena_free(GroupArena &A) {          // at destroy
-    if (A.h_stage) (void) hipHostFree(A.h_stage);
-    if (A.d_stage) (void) hipFree(A.d_stage);
-}
-inline int async_arena_create(AsyncArena &A) {
-    CHK(hipEventCreateWithFlags(&A.uploaded, hipEventDisableTiming));
-    CHK(hipEventCreateWithFlags(&A.done, hipEventDisableTiming));
-    return LDSO_OK;
-}
-// both sides of the arena free for a call of `total` bytes on `st` (the rule beside AsyncArena), and large enough
-inline int async_arena_acquire(AsyncArena &A, size_t total, hipStream_t st) {
-    if (A.used) CHK(hipEventSynchronize(A.uploaded));
-    if (A.used && (total > A.stageCap || st != A.lastStream)) CHK(hipStreamWaitEvent(st, A.done, 0));
-    if (A.used && total > A.stageCap) CHK(hipEventSynchronize(A.done));
-    return group_arena_grow(A, total, st);
-}
-inline int async_arena_mark_uploaded(AsyncArena &A, hipStream_t st) { CHK(hipEventRecord(A.uploaded, st)); return LDSO_OK; }          // behind the call's one copy
-inline int async_arena_mark_done(AsyncArena &A, hipStream_t st) {          // behind the last launch that reads the device side
-    CHK(hipEventRecord(A.done, st));
-    A.used = true; A.lastStream = st;
-    return LDSO_OK;
-}
-inline void async_arena_release(AsyncArena &A) {          // at destroy
-    if (A.used) (void) hipEventSynchronize(A.done);          // the last call's kernels read the device side
-    if (A.uploaded) (void) hipEventDestroy(A.uploaded);
-    if (A.done) (void) hipEventDestroy(A.done);
-    group_arena_free(A);
-}
-// A resident pyramid handed to a consumer `what` (named in the message): it holds an image and matches in device, size and levels; then `st` waits for its build.
-inline int pyramid_wait(const ldso_pyramid *pyr, int device, int w, int h, int minLevels, hipStream_t st, const char *who, const char *what) {
-    REQ(pyr->built && pyr->device == device && pyr->w == w && pyr->h == h && pyr->levels >= minLevels, std::string(who) + ": pyramid does not match " + what + " or holds no image");
-    CHK(hipSetDevice(device));
-    CHK(hipStreamWaitEvent(st, pyr->ready, 0));
-    return LDSO_OK;
-}
-// Raw level-0 irradiance on the host (w * h floats) -> `levels` images (images.hip): staging buffer on first use, upload, kernels, all on `st`; the caller waits or not.
-inline int raw_to_images(float *&d_color, const float *irradiance, int w, int h, int levels, float *const *d_levels, hipStream_t st) {
-    if (!d_color) CHK(hipMalloc(&d_color, (size_t) w * h * sizeof(float)));
-    CHK(hipMemcpyAsync(d_color, irradiance, (size_t) w * h * sizeof(float), hipMemcpyHostToDevice, st));
-    CHK(img_launch_make_images(d_color, w, h, levels, d_levels, st));
-    return LDSO_OK;
-}
-
-// images.hip: the grouped FrameHessian::makeImages of the members `members` of g (indices into g->m) from src[k] = the level-0 irradiance of members[k] in device
-// memory, enqueued on `st` without a host wait; records the members' `ready` events and `built` flags (ldso_pyr_group_make_images*, ldso_undist_group_frames)
-int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const std::vector<const float *> &src, hipStream_t st);
-// trace.hip: the compaction of the tracer's resident immature set with keep flags that lie in device memory (ldso_ba_select_activate_tracer, act_select.hip):
-// record i stays where d_keep8[i] != 0 / d_keep32[i] == keepValue (both null: everywhere) and its host is a frame of the window.  Enqueued on `st`;
-// trace_compact_finish swaps the buffers and takes the new count once the caller has synchronised `st`.
-int trace_compact_enqueue(ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, bool haveMap, hipStream_t st);
-void trace_compact_finish(ldso_tracer *T);
-// The same compaction as a row of a grouped launch (T->n > 0): the map and the count lie where the caller says (its arena), the flags and workgroup counts are the
-// tracer's own.  Behind the caller's wait: trace_compact_finish_group with the count that came down.
-CompactArgs trace_compact_job(const ldso_tracer *T, const unsigned char *d_keep8, const int32_t *d_keep32, int keepValue, int n_hosts, const int32_t *d_hostMap, int32_t *d_nOut);
-void trace_compact_finish_group(ldso_tracer *T, int nOut);
 // ba_batch.hip: the windows' descriptors as they are now into ldso_ba_batch::d_items; the batch's staging arena with room for `up` + `down` bytes
 int batch_refresh(ldso_ba_batch *Bt);
 int batch_stage(ldso_ba_batch *Bt, size_t up, size_t down);
@@ -429,19 +237,4 @@ struct Damping { double lam, l1, il; };
 Damping damping(const ldso_settings_t &St, double lambda);
 GnInit gn_init(const ldso_ba *H, int itCheck);
 int lend_acc(ldso_ba *H, double *buf);
-// one warm launch, then `reps` launches between ONE pair of HIP events on `st` (the event overhead is amortised over them): microseconds per launch
-template <class Launch> int time_launches(hipStream_t st, int reps, double *avg_us, Launch launch) {
-    hipEvent_t a, b;
-    CHK(hipEventCreate(&a)); CHK(hipEventCreate(&b));
-    RUN(launch());          // warm
-    CHK(hipEventRecord(a, st));
-    for (int i = 0; i < reps; i++) RUN(launch());
-    CHK(hipEventRecord(b, st));
-    CHK(hipEventSynchronize(b));
-    float ms = 0;
-    CHK(hipEventElapsedTime(&ms, a, b));
-    (void) hipEventDestroy(a); (void) hipEventDestroy(b);
-    *avg_us = (double) ms * 1e3 / reps;
-    return LDSO_OK;
-}
 #pragma GCC visibility pop

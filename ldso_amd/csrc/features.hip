@@ -19,7 +19,7 @@
 // Every float expression keeps the reference's operand order and width (the library is built with -ffp-contract=off).  Where the reference would read
 // outside the image (descriptor / moment taps of a feature near the right or bottom border, possible at gridsize 16..18 and from 31 on; it has no check) a tap reads 0 here, and
 // an immature record whose taps leave the image gets a NaN colour and energyTH = NaN.  Rows 0 and h-1 have zero gradients (images.hip).
-#include "ba_host.h"
+#include "trace.h"
 #include "immature_record.h"
 #include "lane.h"
 #include "select_dev.h"
@@ -368,15 +368,14 @@ __global__ __launch_bounds__(256) void k_feat_append_group(const FeatArgs *__res
 struct ldso_features {
     int device = 0, w = 0, h = 0, maxFeat = 0, n = 0, nCorners = 0;
     hipStream_t stream = nullptr;
-    bool ownStream = false, hasPattern = false, hasB = false, profile = false;
+    bool ownStream = false, hasPattern = false, hasB = false;
     const void *inGroup = nullptr;      // the ldso_feat_group this detector belongs to (at most one; ldso_feat_destroy refuses while set: the group dereferences its members)
     int32_t *d_pattern = nullptr, *d_cellCount = nullptr, *d_ctl = nullptr;
     float *d_B = nullptr;
     ldso_feature_t *d_cellFeat = nullptr, *d_feat = nullptr;
     ldso_immature_t *d_imm = nullptr;
     FeatUmax umax;
-    hipEvent_t ev[5] = {};
-    float us[4] = {0, 0, 0, 0};
+    StageClock<4> clock;                // cells + compaction, corners, angle + descriptor, records
 };
 
 // FeatureDetector::FeatureDetector (FeatureDetector.cc:10-28); cvFloor / cvCeil / cvRound = floor / ceil / round-half-even of a double
@@ -426,7 +425,7 @@ int ldso_feat_destroy(ldso_features_t *F) {
     hipSetDevice(F->device);
     hipDeviceSynchronize();
     hipFree(F->d_pattern); hipFree(F->d_cellCount); hipFree(F->d_ctl); hipFree(F->d_B); hipFree(F->d_cellFeat); hipFree(F->d_feat); hipFree(F->d_imm);
-    for (hipEvent_t e : F->ev) if (e) hipEventDestroy(e);
+    F->clock.destroy();
     if (F->ownStream && F->stream) hipStreamDestroy(F->stream);
     delete F;
     return LDSO_OK;
@@ -443,7 +442,7 @@ int ldso_feat_create(int device, int w, int h, int max_features, const int32_t *
     ok = ok && hipMalloc(&F->d_pattern, 1024 * 4) == hipSuccess && hipMalloc(&F->d_B, 256 * 4) == hipSuccess && hipMalloc(&F->d_ctl, 8 * 4) == hipSuccess
          && hipMalloc(&F->d_cellCount, m * 4) == hipSuccess && hipMalloc(&F->d_cellFeat, m * sizeof(ldso_feature_t)) == hipSuccess
          && hipMalloc(&F->d_feat, m * sizeof(ldso_feature_t)) == hipSuccess && hipMalloc(&F->d_imm, m * sizeof(ldso_immature_t)) == hipSuccess;
-    for (hipEvent_t &e : F->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && F->clock.create() == LDSO_OK;
     if (ok && orb_pattern) { ok = hipMemcpy(F->d_pattern, orb_pattern, 1024 * 4, hipMemcpyHostToDevice) == hipSuccess; F->hasPattern = true; }
     if (!ok) { ldso_feat_destroy(F); ldso_set_error("ldso_feat_create: out of device memory"); return LDSO_E_HIP; }
     *out = F;
@@ -465,9 +464,7 @@ int ldso_feat_set_response(ldso_features_t *F, const float *B) {
 
 int ldso_feat_profile(ldso_features_t *F, int enable, float us_out[4]) {
     REQ(F, "ldso_feat_profile: null handle");
-    F->profile = enable != 0;
-    if (us_out) for (int i = 0; i < 4; i++) us_out[i] = F->us[i];
-    return LDSO_OK;
+    return F->clock.report(F->device, enable, us_out);
 }
 
 int ldso_feat_detect(ldso_features_t *F, ldso_pyramid_t *pyr, int n_features, int host_index, int *n_features_out, int *n_corners_out) {
@@ -481,31 +478,31 @@ int ldso_feat_detect(ldso_features_t *F, ldso_pyramid_t *pyr, int n_features, in
     RUN(pyramid_wait(pyr, F->device, F->w, F->h, 1, st, "ldso_feat_detect", "the detector (device, size)"));
     CHK(hipMemsetAsync(F->d_ctl, 0, 8 * 4, st));
     const FeatArgs A = feat_args(F, pyr, G, host_index, F->d_ctl);
-    const bool prof = F->profile;
-    if (prof) CHK(hipEventRecord(F->ev[0], st));
+    StageClock<4> &clk = F->clock.begin();
+    RUN(clk.mark(0, st));
     if (nCells > 0) {
         CHK(launch_lds(k_feat_cells, dim3(nCells), dim3(256), feat_cells_lds(G), st, A));
         hipLaunchKernelGGL(k_feat_compact, dim3(1), dim3(256), 0, st, A, nCells);
         CHK(hipGetLastError());
     }
-    if (prof) CHK(hipEventRecord(F->ev[1], st));
+    RUN(clk.mark(1, st));
     // the launches below are sized for the capacity; the kernels read the count from the device
     const int cap = nCells * G.perCell;
     if (cap > 0) {
         hipLaunchKernelGGL(k_feat_corners, dim3((cap + 255) / 256), dim3(256), 0, st, A);
         CHK(hipGetLastError());
-        if (prof) CHK(hipEventRecord(F->ev[2], st));
+        RUN(clk.mark(2, st));
         hipLaunchKernelGGL(k_feat_describe, dim3((cap + 3) / 4), dim3(256), 0, st, A, F->umax);
         CHK(hipGetLastError());
-        if (prof) CHK(hipEventRecord(F->ev[3], st));
+        RUN(clk.mark(3, st));
         hipLaunchKernelGGL(k_feat_records, dim3((cap + 255) / 256), dim3(256), 0, st, A);
         CHK(hipGetLastError());
-    } else if (prof) { CHK(hipEventRecord(F->ev[2], st)); CHK(hipEventRecord(F->ev[3], st)); }
-    if (prof) CHK(hipEventRecord(F->ev[4], st));
+    } else { RUN(clk.mark(2, st)); RUN(clk.mark(3, st)); }
+    RUN(clk.mark(4, st));
     int ctl[8] = {0};
     CHK(hipMemcpyAsync(ctl, F->d_ctl, 8 * 4, hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
-    if (prof) for (int i = 0; i < 4; i++) { float ms = 0; CHK(hipEventElapsedTime(&ms, F->ev[i], F->ev[i + 1])); F->us[i] = ms * 1e3f; }
+    RUN(clk.read());
     F->n = ctl[2]; F->nCorners = ctl[3];
     if (n_features_out) *n_features_out = F->n;
     if (n_corners_out) *n_corners_out = F->nCorners;
@@ -544,9 +541,7 @@ struct ldso_feat_group {
     int device = 0;
     GroupArena arena;
     FeatUmax umax;
-    bool profile = false;
-    hipEvent_t ev[6] = {};
-    float us[5] = {0, 0, 0, 0, 0};
+    StageClock<5> clock;                // the four stages of a detector, then the append
 };
 
 namespace {
@@ -570,7 +565,7 @@ int ldso_feat_group_destroy(ldso_feat_group_t *g) {
     if (g->arena.h_stage && !g->m.empty()) hipStreamSynchronize(g->m[0]->stream);
     group_leave(g);
     group_arena_free(g->arena);
-    for (hipEvent_t e : g->ev) if (e) hipEventDestroy(e);
+    g->clock.destroy();
     delete g;
     return LDSO_OK;
 }
@@ -580,8 +575,7 @@ int ldso_feat_group_create(ldso_features_t *const *members, int n, ldso_feat_gro
     CHK(hipSetDevice(members[0]->device));
     ldso_feat_group *g = new ldso_feat_group();
     g->device = members[0]->device; g->umax = feat_umax();
-    bool ok = true;
-    for (hipEvent_t &e : g->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    const bool ok = g->clock.create() == LDSO_OK;
     if (!ok) ldso_set_error("ldso_feat_group_create: hipEventCreate failed");
     RUN(finish_create(ok ? LDSO_OK : LDSO_E_HIP, g, out, ldso_feat_group_destroy));          // the arena comes with the first call
     g->m.assign(members, members + n);
@@ -591,9 +585,7 @@ int ldso_feat_group_create(ldso_features_t *const *members, int n, ldso_feat_gro
 
 int ldso_feat_group_profile(ldso_feat_group_t *g, int enable, float us_out[5]) {
     REQ(g, "ldso_feat_group_profile: null group");
-    g->profile = enable != 0;
-    if (us_out) for (int i = 0; i < 5; i++) us_out[i] = g->us[i];
-    return LDSO_OK;
+    return g->clock.report(g->device, enable, us_out);
 }
 
 // ldso_feat_detect (+ ldso_trace_append_points_device) of every active member: ONE upload of [FeatArgs table | four prefix tables | zeroed control rows], five or
@@ -660,24 +652,24 @@ int ldso_feat_group_detect(ldso_feat_group_t *g, const uint8_t *active, ldso_pyr
     const FeatArgs *dJ = (const FeatArgs *) (d_stage + L.jobs);
     const int *dCells = (const int *) (d_stage + L.firstCells), *dCompact = (const int *) (d_stage + L.firstCompact), *dCorners = (const int *) (d_stage + L.firstCorners),
               *dDescribe = (const int *) (d_stage + L.firstDescribe);
-    const bool prof = g->profile;
+    StageClock<5> &clk = g->clock.begin();
     const int J = (int) nj;
-    if (prof) CHK(hipEventRecord(g->ev[0], st));
+    RUN(clk.mark(0, st));
     if (uCells > 0) CHK(launch_lds(k_feat_cells_group, dim3(uCells), dim3(256), ldsBytes, st, dJ, dCells, J));
     CHK(feat_launch_group(k_feat_compact_group, uCompact, st, dJ, dCompact, J));
-    if (prof) CHK(hipEventRecord(g->ev[1], st));
+    RUN(clk.mark(1, st));
     // the launches below are sized for the capacities; the kernels read the counts from the device
     CHK(feat_launch_group(k_feat_corners_group, uCorners, st, dJ, dCorners, J));
-    if (prof) CHK(hipEventRecord(g->ev[2], st));
+    RUN(clk.mark(2, st));
     CHK(feat_launch_group(k_feat_describe_group, uDescribe, st, dJ, dDescribe, J, g->umax));
-    if (prof) CHK(hipEventRecord(g->ev[3], st));
+    RUN(clk.mark(3, st));
     CHK(feat_launch_group(k_feat_records_group, uCorners, st, dJ, dCorners, J));
-    if (prof) CHK(hipEventRecord(g->ev[4], st));
+    RUN(clk.mark(4, st));
     if (append) CHK(feat_launch_group(k_feat_append_group, uCorners, st, dJ, dCorners, J));
-    if (prof) CHK(hipEventRecord(g->ev[5], st));
+    RUN(clk.mark(5, st));
     CHK(hipMemcpyAsync(hC, d_stage + L.down, L.downBytes, hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
-    if (prof) for (int k = 0; k < 5; k++) { float ms = 0; CHK(hipEventElapsedTime(&ms, g->ev[k], g->ev[k + 1])); g->us[k] = ms * 1e3f; }
+    RUN(clk.read());
     int firstBad = -1;
     for (size_t j = 0; j < nj; j++) {
         const int i = members[j], *ctl = hC + 8 * j;

@@ -1,6 +1,6 @@
 // group_stage.h — what the grouped calls (ldso_tr_group_*, ldso_trace_group_*, ldso_pyr_group_*, ldso_undist_group_*, ldso_feat_group_*) share as far as it can be said without a
 // device: who may be a member, which members take part in a call, the prefix table that group_member_of searches, and where the regions of each group's staging
-// arena lie.  The device side of an arena (GroupArena, AsyncArena) is in ba_host.h.  No HIP header: it compiles with a plain C++ compiler
+// arena lie.  The device side of an arena (GroupArena, AsyncArena) is in hip_host.h.  No HIP header: it compiles with a plain C++ compiler
 // (tests/test_group_stage_cpu.py, tests/test_compact_group_stage_cpu.py and tests/test_feat_group_abi_cpu.py run it under the sanitizers).  A further group starts here: a rule, a layout, and its entries on top of both.
 #pragma once
 #include <string>

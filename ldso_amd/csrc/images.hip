@@ -4,7 +4,7 @@
 // the flat index range [w, w(h-1)) including the row wrap at x = 0 / w-1 (:81-89); rows 0 and h-1 keep zero gradients (the
 // reference leaves them uninitialised and never samples them).  Pure streaming: 4 B in / 12 B out per pixel at level 0.
 // absSquaredGrad (pixel selector only) is not produced.
-#include "ba_host.h"
+#include "hip_host.h"
 #include "group_member.h"
 
 // channel 0 of a level (copy of the input or 2x2 mean of the level below), gradients zeroed
@@ -173,7 +173,7 @@ int ldso_pyr_group_destroy(ldso_pyr_group_t *g) {
 }
 
 // the build of every active member from src[i] (device memory: the member's own d_color behind an upload or behind ldso_undist_group_frames' kernel, or the
-// caller's image); declared in ba_host.h
+// caller's image); declared in hip_host.h
 extern "C++" int pyr_group_build(ldso_pyr_group *g, const std::vector<int> &members, const std::vector<const float *> &src, hipStream_t st) {
     const size_t nm = members.size();
     int Lmax = 0;

@@ -1,7 +1,7 @@
 // initializer.h — what the translation units of the monocular initialiser share: the records the kernels read, the handle, and the launchers that cross files
 // (initializer.hip: the kernels; initializer_api.hip: handle, ldso_init_*, point record conversion; initializer_sched.cpp: the host-only optReg sweep schedule).
 #pragma once
-#include "ba_host.h"
+#include "hip_host.h"
 
 #define INI_MAXL 5            // maxIterations[] has five entries (CoarseInitializer.cc:43)
 #define INI_NT 256            // threads of an eval block: 32 points x 8 pattern pixels

@@ -19,7 +19,7 @@
 // block its level-3 result only if nothing inside selected; the one sequential quantity is n2.  Every float expression keeps the reference's operand order
 // and width (-ffp-contract=off); no floating-point sum crosses lanes.  Three reads the reference leaves undefined are defined (ldso_hip.h): the last row of
 // absSquaredGrad[2] is 0, sizes that are no multiples of 32 are refused, a non-finite pixel gives LDSO_E_NONFINITE (and never wins a comparison).
-#include "ba_host.h"
+#include "hip_host.h"
 #include "immature_record.h"
 #include "raster_scan.h"
 
@@ -289,15 +289,14 @@ __global__ __launch_bounds__(256) void k_pix_points(PixArgs A, ScanRect r, int h
 struct ldso_pixsel {
     int device = 0, w = 0, h = 0, potential = 3, n = 0, cap = 0;
     hipStream_t stream = nullptr;
-    bool ownStream = false, hasB = false, profile = false;
+    bool ownStream = false, hasB = false;
     float cut = 0.5f, add = 7.0f, dw1 = 0.75f; int sdd = 1;          // Setting.cc:83-87
     unsigned char *d_rp = nullptr, *d_dir = nullptr, *d_map = nullptr;
     unsigned short *d_mask = nullptr;
     float *d_B = nullptr, *d_ths = nullptr, *d_thsSmoothed = nullptr, *d_type = nullptr;
     int32_t *d_rowCount = nullptr, *d_rowStart = nullptr, *d_ctl = nullptr;
     ldso_immature_t *d_imm = nullptr;
-    hipEvent_t ev[6] = {};
-    float us[5] = {0, 0, 0, 0, 0};
+    StageClock<5> clock;                // make_maps: histogram, masks + scan, select, thinning (1 and 2 summed over the recursion rounds); make_points: the records
 };
 
 static int pix_size_ok(int w, int h) { return w % 32 == 0 && h % 32 == 0; }
@@ -352,7 +351,7 @@ int ldso_pixsel_destroy(ldso_pixsel_t *P) {
     (void) hipDeviceSynchronize();
     for (void *d : {(void *) P->d_rp, (void *) P->d_dir, (void *) P->d_map, (void *) P->d_mask, (void *) P->d_B, (void *) P->d_ths, (void *) P->d_thsSmoothed, (void *) P->d_type,
                     (void *) P->d_rowCount, (void *) P->d_rowStart, (void *) P->d_ctl, (void *) P->d_imm}) if (d) (void) hipFree(d);
-    for (hipEvent_t e : P->ev) if (e) (void) hipEventDestroy(e);
+    P->clock.destroy();
     if (P->ownStream && P->stream) (void) hipStreamDestroy(P->stream);
     delete P;
     return LDSO_OK;
@@ -366,7 +365,7 @@ static int pix_create_body(ldso_pixsel *P, const unsigned char *random_pattern) 
     CHK(hipMalloc(&P->d_rp, wh)); CHK(hipMalloc(&P->d_dir, wh)); CHK(hipMalloc(&P->d_map, wh)); CHK(hipMalloc(&P->d_mask, wh * 2));
     CHK(hipMalloc(&P->d_B, 256 * 4)); CHK(hipMalloc(&P->d_ths, cells * 4)); CHK(hipMalloc(&P->d_thsSmoothed, cells * 4));
     CHK(hipMalloc(&P->d_rowCount, (size_t) P->h * 4)); CHK(hipMalloc(&P->d_rowStart, (size_t) P->h * 4)); CHK(hipMalloc(&P->d_ctl, 8 * 4));
-    for (hipEvent_t &e : P->ev) CHK(hipEventCreate(&e));
+    RUN(P->clock.create());
     CHK(hipMemcpy(P->d_rp, random_pattern, wh, hipMemcpyHostToDevice));
     return zero_fill(P->d_map, wh);
 }
@@ -413,9 +412,7 @@ int ldso_pixsel_get_potential(ldso_pixsel_t *P, int *potential) {
 
 int ldso_pixsel_profile(ldso_pixsel_t *P, int enable, float us_out[5]) {
     REQ(P, "ldso_pixsel_profile: null handle");
-    P->profile = enable != 0;
-    if (us_out) for (int i = 0; i < 5; i++) us_out[i] = P->us[i];
-    return LDSO_OK;
+    return P->clock.report(P->device, enable, us_out);
 }
 
 int ldso_pixsel_make_maps(ldso_pixsel_t *P, ldso_pyramid_t *pyr, float density, int recursions_left, float th_factor, int *n_out, int counts_out[3], int *potential_used) {
@@ -424,36 +421,36 @@ int ldso_pixsel_make_maps(ldso_pixsel_t *P, ldso_pyramid_t *pyr, float density, 
     hipStream_t st = P->stream;
     RUN(pyramid_wait(pyr, P->device, P->w, P->h, 3, st, "ldso_pixsel_make_maps", "the selector (device, size, three levels)"));
     const size_t wh = (size_t) P->w * P->h;
-    const bool prof = P->profile;
+    StageClock<5> &clk = P->clock.begin();
     float usAcc[5] = {0, 0, 0, 0, 0};
     int pot = P->potential, ctl[8] = {0}, flags = 0;
     PixArgs A = pix_args(P, pyr, pot, th_factor);
     CHK(hipMemsetAsync(P->d_ctl, 0, 8 * 4, st));
     // one histogram pass per call: the recursion reuses it (gradHistFrame, :119)
-    if (prof) CHK(hipEventRecord(P->ev[0], st));
+    RUN(clk.mark(0, st));
     hipLaunchKernelGGL(k_pix_hist, dim3(A.w32 * A.h32), dim3(256), 0, st, A);
     CHK(hipGetLastError());
     hipLaunchKernelGGL(k_pix_smooth, dim3((A.w32 * A.h32 + 255) / 256), dim3(256), 0, st, A);
     CHK(hipGetLastError());
-    if (prof) CHK(hipEventRecord(P->ev[1], st));
+    RUN(clk.mark(1, st));
     const int rpn = (int) std::min<size_t>(wh, PIX_RP_LDS);
     int act = 0, ideal = pot, charTH = -1, counts[3] = {0, 0, 0};
     for (bool first = true;; first = false) {
         A = pix_args(P, pyr, pot, th_factor);
         const int NB = A.nbx * A.nby, L = lanes_per_block(pot);
-        if (!first) { CHK(hipMemsetAsync(P->d_ctl + PIX_N2, 0, 3 * 4, st)); if (prof) CHK(hipEventRecord(P->ev[1], st)); }
+        if (!first) { CHK(hipMemsetAsync(P->d_ctl + PIX_N2, 0, 3 * 4, st)); RUN(clk.mark(1, st)); }
         CHK(hipMemsetAsync(P->d_map, 0, wh, st));
         hipLaunchKernelGGL(k_pix_masks, dim3((unsigned) (((long long) NB * L + 255) / 256)), dim3(256), 0, st, A, L);
         CHK(hipGetLastError());
         CHK(launch_lds(k_pix_scan, dim3(1), dim3(1024), (size_t) rpn, st, A, NB, rpn));
-        if (prof) CHK(hipEventRecord(P->ev[2], st));
+        RUN(clk.mark(2, st));
         hipLaunchKernelGGL(k_pix_select, dim3((((A.nbx + 3) / 4) * ((A.nby + 3) / 4) + 3) / 4), dim3(256), 0, st, A);
         CHK(hipGetLastError());
-        if (prof) CHK(hipEventRecord(P->ev[3], st));
+        RUN(clk.mark(3, st));
         // the recursion decision needs the three counts: one wait per select pass
         CHK(hipMemcpyAsync(ctl, P->d_ctl, 8 * 4, hipMemcpyDeviceToHost, st));
         CHK(hipStreamSynchronize(st));
-        if (prof) for (int i = first ? 0 : 1; i < 3; i++) { float ms = 0; CHK(hipEventElapsedTime(&ms, P->ev[i], P->ev[i + 1])); usAcc[i] += ms * 1e3f; }
+        for (int i = first ? 0 : 1; i < 3; i++) { float us = 0; RUN(clk.lap(i, us)); usAcc[i] += us; }
         flags |= ctl[PIX_FLAGS];
         counts[0] = ctl[PIX_N2]; counts[1] = ctl[PIX_N3]; counts[2] = ctl[PIX_N4];
         // two kernels count the level-1 selections: the scan from the masks, the select pass from the pixels it marked
@@ -464,17 +461,17 @@ int ldso_pixsel_make_maps(ldso_pixsel_t *P, ldso_pyramid_t *pyr, float density, 
     }
     int n = counts[0] + counts[1] + counts[2];
     if (charTH >= 0 && n > 0) {
-        if (prof) CHK(hipEventRecord(P->ev[3], st));
+        RUN(clk.mark(3, st));
         RUN(raster_count(P->d_map, P->w, P->h, ScanRect{0, P->w, 0, P->h}, P->d_rowCount, P->d_rowStart, P->d_ctl + PIX_TOTAL, st, nullptr));          // the whole image; no total on the host
         hipLaunchKernelGGL(k_pix_thin, raster_grid(P->h), dim3(256), 0, st, A, charTH);
         CHK(hipGetLastError());
-        if (prof) CHK(hipEventRecord(P->ev[4], st));
+        RUN(clk.mark(4, st));
         CHK(hipMemcpyAsync(ctl, P->d_ctl, 8 * 4, hipMemcpyDeviceToHost, st));
         CHK(hipStreamSynchronize(st));
-        if (prof) { float ms = 0; CHK(hipEventElapsedTime(&ms, P->ev[3], P->ev[4])); usAcc[3] = ms * 1e3f; }
+        RUN(clk.lap(3, usAcc[3]));
         n -= ctl[PIX_REMOVED];
     }
-    if (prof) for (int i = 0; i < 4; i++) P->us[i] = usAcc[i];
+    for (int i = 0; i < 4; i++) clk.set(i, usAcc[i]);
     P->potential = ideal;                                          // :165
     if (n_out) *n_out = n;
     if (counts_out) for (int i = 0; i < 3; i++) counts_out[i] = counts[i];
@@ -510,9 +507,9 @@ int ldso_pixsel_make_points(ldso_pixsel_t *P, ldso_pyramid_t *pyr, int host_inde
     RUN(pyramid_wait(pyr, P->device, P->w, P->h, 1, st, "ldso_pixsel_make_points", "the selector (device, size)"));
     PixArgs A = pix_args(P, pyr, 1, 1.0f);
     const ScanRect r = scan_rect(P->w, P->h);
-    const bool prof = P->profile;
+    StageClock<5> &clk = P->clock.begin();
     CHK(hipMemsetAsync(P->d_ctl, 0, 8 * 4, st));
-    if (prof) CHK(hipEventRecord(P->ev[4], st));
+    RUN(clk.mark(4, st));
     int n = 0, ctl[8] = {0};
     RUN(raster_count(P->d_map, P->w, P->h, r, P->d_rowCount, P->d_rowStart, P->d_ctl + PIX_TOTAL, st, &n));
     if (n > P->cap) {                                              // the record buffers grow to what a call needs
@@ -528,10 +525,10 @@ int ldso_pixsel_make_points(ldso_pixsel_t *P, ldso_pyramid_t *pyr, int host_inde
         hipLaunchKernelGGL(k_pix_points, raster_grid(P->h), dim3(256), 0, st, A, r, host_index, P->d_imm, P->d_type, P->cap);
         CHK(hipGetLastError());
     }
-    if (prof) CHK(hipEventRecord(P->ev[5], st));
+    RUN(clk.mark(5, st));
     CHK(hipMemcpyAsync(ctl, P->d_ctl, 8 * 4, hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
-    if (prof) { float ms = 0; CHK(hipEventElapsedTime(&ms, P->ev[4], P->ev[5])); P->us[4] = ms * 1e3f; }
+    RUN(clk.read(4));
     P->n = n;
     if (n_out) *n_out = n;
     if (ctl[PIX_FLAGS] & SEL_FLAG_NONFINITE) { ldso_set_error("ldso_pixsel_make_points: non-finite colour"); return LDSO_E_NONFINITE; }

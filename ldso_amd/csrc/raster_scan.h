@@ -3,7 +3,7 @@
 // caller's statement with its rank = row start + set pixels before it in the row.  The library is built without relocatable device code, so the two kernels are
 // static (each including file gets its own copy) and the walk is instantiated beside its statement.
 #pragma once
-#include "ba_host.h"
+#include "hip_host.h"
 #include "lane.h"
 #include "select_dev.h"
 

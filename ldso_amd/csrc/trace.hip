@@ -8,7 +8,7 @@
 // to the CPU path; the best step (first minimum) and the second-best outside the +-radius window are wave reductions.  The
 // short Gauss-Newton refinement (<= 3 iterations of 8 samples) and the scalar bookkeeping run uniformly in all lanes.
 // Memory: per point 128 B record in / out + 4-byte taps of the level-0 image along the epipolar line (L2 resident).
-#include "ba_host.h"
+#include "trace.h"
 #include "lane.h"
 #include "group_member.h"
 
@@ -287,7 +287,7 @@ hipError_t trace_launch_group(const TraceJob *d_jobs, const int *d_first, int nJ
 //   k_compact_count  one flag per record, one count per workgroup of 256 records
 //   k_compact_move   every workgroup sums the counts in front of it (<= max_points / 256 words), ranks its own records, then moves them: 8 lanes x 16 B per
 //                    128-byte record, the lane that holds `host` rewrites it
-// CompactArgs (ba_host.h) is one compaction; the bodies are device functions of (job, block, blocks of the job), shared with the grouped kernels below.
+// CompactArgs (trace.h) is one compaction; the bodies are device functions of (job, block, blocks of the job), shared with the grouped kernels below.
 // ---------------------------------------------------------------------------------------------------------
 // the body of k_compact_count for workgroup `block` of the nBlocks that serve A
 static __device__ __forceinline__ void compact_count(const CompactArgs &A, int block, int nBlocks) {

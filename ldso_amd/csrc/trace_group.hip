@@ -3,7 +3,7 @@
 // launch, a download and a wait; k_trace_group (trace.hip) runs the same body for the points of all members, one wavefront per point, packed wave-granular.  The
 // members stay ordinary tracers; the group reads their current records, frame and settings at every call and owns only the staging arena of its launch.
 // ldso_trace_group_compact is ldso_trace_compact of the members (the records of a marginalised frame leave every sequence's set, FullSystem.cc:602-645) in two launches.
-#include "ba_host.h"
+#include "trace.h"
 #include "group_member.h"
 
 namespace {

@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <vector>
-#include "ba_host.h"
+#include "hip_host.h"
 
 #define TR_NT 256          // 4 wavefronts, one per SIMD: 512 registers (VGPR + AGPR) per lane - tr_eval keeps 4 points per lane in flight without scratch spills
 #define TR_MAXL LDSO_PYR_LEVELS

@@ -12,7 +12,7 @@
 // The result is bit for bit what the reference returns (float arithmetic in its operand order, -ffp-contract=off), with the one deliberate difference that
 // undistort_px.h states: a pixel whose four taps are not all inside the source image is 0 and nothing outside the raw buffer is read, where the reference
 // over-reads one row for the table entry xxi == 0 && yyi == hOrg - 1.  benchmark_varNoise / benchmark_varBlurNoise (:376-413, :468-555) are out of scope.
-#include "ba_host.h"
+#include "hip_host.h"
 #include "group_member.h"
 #include "undistort_px.h"
 
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_undist_group(const UndistJob *__restric
 struct ldso_undistorter {
     int device = 0, w = 0, h = 0, wOrg = 0, hOrg = 0;
     hipStream_t stream = nullptr;
-    bool ownStream = false, hasRemap = false, remapSet = false, hasG = false, useExposure = true, profile = false, profPending = false;
+    bool ownStream = false, hasRemap = false, remapSet = false, hasG = false, useExposure = true;
     int GDepth = 0, photometricCalibration = 2;
     float *d_remap = nullptr;           // remapX, then remapY
     float *d_G = nullptr, *d_vig = nullptr, *d_out = nullptr;
@@ -100,8 +100,7 @@ struct ldso_undistorter {
     int turn = 0;
     const float *last = nullptr;        // where the last frame's irradiance lies (a pyramid's d_color or d_out)
     hipEvent_t done = nullptr;          // recorded behind the last frame's kernel
-    hipEvent_t ev[4] = {};
-    float us[3] = {0, 0, 0};
+    StageClock<3> clock;                // copy, undistortion kernel, pyramid build; a frame does not wait: ldso_undist_profile settles it
     const void *inGroup = nullptr;      // the ldso_undist_group this undistorter belongs to (at most one; ldso_undist_destroy refuses while set: the group dereferences its members)
 };
 
@@ -110,9 +109,7 @@ struct ldso_undist_group {
     std::vector<ldso_undistorter *> m;
     int device = 0;
     AsyncArena arena;                   // undist_group_layout
-    bool profile = false, profPending = false;
-    hipEvent_t ev[4] = {};
-    float us[3] = {0, 0, 0};
+    StageClock<3> clock;                // the one copy, the undistortion kernel, the grouped pyramid build; settled by ldso_undist_group_profile
 };
 
 namespace {
@@ -136,13 +133,6 @@ UndistArgs frame_args(const ldso_undistorter *U, const void *d_raw, float *out, 
     return A;
 }
 
-// microseconds between the four events of a profiled call (copy, undistortion kernel, pyramid build); waits for that call
-int read_profile(const hipEvent_t ev[4], float us[3]) {
-    CHK(hipEventSynchronize(ev[3]));
-    for (int i = 0; i < 3; i++) { float ms = 0; CHK(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); us[i] = ms * 1e3f; }
-    return LDSO_OK;
-}
-
 constexpr GroupRule GROUP_RULE = {"an undistorter", "ldso_undist_set_stream", GROUP_MAX_MEMBERS};
 static_assert(sizeof(UndistJob) == 80, "the row of undist_group_layout as tests/test_group_stage_cpu.py sizes it");
 
@@ -158,7 +148,7 @@ int ldso_undist_destroy(ldso_undistorter_t *U) {
     hipFree(U->d_remap); hipFree(U->d_G); hipFree(U->d_vig); hipFree(U->d_out); hipFree(U->d_raw);
     for (void *p : U->h_raw) if (p) hipHostFree(p);
     for (hipEvent_t e : U->copied) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : U->ev) if (e) hipEventDestroy(e);
+    U->clock.destroy();
     if (U->done) hipEventDestroy(U->done);
     if (U->ownStream && U->stream) hipStreamDestroy(U->stream);
     delete U;
@@ -177,7 +167,7 @@ int ldso_undist_create(int device, int wOrg, int hOrg, int w, int h, ldso_undist
          && hipMalloc(&U->d_out, n * 4) == hipSuccess && hipMalloc(&U->d_raw, nOrg * 2) == hipSuccess;
     for (void *&p : U->h_raw) ok = ok && hipHostMalloc(&p, nOrg * 2, hipHostMallocDefault) == hipSuccess;
     for (hipEvent_t &e : U->copied) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    for (hipEvent_t &e : U->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    ok = ok && U->clock.create() == LDSO_OK;
     ok = ok && hipEventCreateWithFlags(&U->done, hipEventDisableTiming) == hipSuccess;
     if (!ok) { ldso_undist_destroy(U); ldso_set_error("ldso_undist_create: out of device or pinned memory"); return LDSO_E_HIP; }
     *out = U;
@@ -221,14 +211,7 @@ int ldso_undist_set_photometric(ldso_undistorter_t *U, const float *G, int GDept
 
 int ldso_undist_profile(ldso_undistorter_t *U, int enable, float us_out[3]) {
     REQ(U, "ldso_undist_profile: null handle");
-    if (U->profPending) {
-        CHK(hipSetDevice(U->device));
-        RUN(read_profile(U->ev, U->us));
-        U->profPending = false;
-    }
-    U->profile = enable != 0;
-    if (us_out) for (int i = 0; i < 3; i++) us_out[i] = U->us[i];
-    return LDSO_OK;
+    return U->clock.report(U->device, enable, us_out);
 }
 
 int ldso_undist_frame(ldso_undistorter_t *U, const void *raw, int bytes_per_pixel, float exposure, float factor, ldso_pyramid_t *pyr, float *exposure_out) {
@@ -245,11 +228,11 @@ int ldso_undist_frame(ldso_undistorter_t *U, const void *raw, int bytes_per_pixe
     U->turn ^= 1;
     CHK(hipEventSynchronize(U->copied[t]));          // the copy of the frame before last out of this staging buffer: long done
     memcpy(U->h_raw[t], raw, bytes);
-    const bool prof = U->profile;
-    if (prof) CHK(hipEventRecord(U->ev[0], st));
+    StageClock<3> &clk = U->clock.begin();
+    RUN(clk.mark(0, st));
     CHK(hipMemcpyAsync(U->d_raw, U->h_raw[t], bytes, hipMemcpyHostToDevice, st));
     CHK(hipEventRecord(U->copied[t], st));
-    if (prof) CHK(hipEventRecord(U->ev[1], st));
+    RUN(clk.mark(1, st));
     const UndistArgs A = frame_args(U, U->d_raw, pyr ? pyr->d_color : U->d_out, mode, factor);
     const size_t n = (size_t) U->w * U->h;
     const dim3 grid((unsigned) ((n + 255) / 256));
@@ -257,14 +240,14 @@ int ldso_undist_frame(ldso_undistorter_t *U, const void *raw, int bytes_per_pixe
     else hipLaunchKernelGGL(k_undist_frame<2>, grid, dim3(256), 0, st, A);
     CHK(hipGetLastError());
     CHK(hipEventRecord(U->done, st));
-    if (prof) CHK(hipEventRecord(U->ev[2], st));
+    RUN(clk.mark(2, st));
     U->last = A.out;
     if (pyr) {
         CHK(img_launch_make_images(pyr->d_color, pyr->w, pyr->h, pyr->levels, pyr->lv, st));
         CHK(hipEventRecord(pyr->ready, st));
         pyr->built = true;
     }
-    if (prof) { CHK(hipEventRecord(U->ev[3], st)); U->profPending = true; }
+    RUN(clk.mark(3, st)); clk.defer();
     if (exposure_out) *exposure_out = rule.exposureOut;
     return LDSO_OK;
 }
@@ -294,7 +277,7 @@ int ldso_undist_group_destroy(ldso_undist_group_t *g) {
     hipSetDevice(g->device);
     group_leave(g);
     async_arena_release(g->arena);          // waits for the last call's kernel
-    for (hipEvent_t e : g->ev) if (e) hipEventDestroy(e);
+    g->clock.destroy();
     delete g;
     return LDSO_OK;
 }
@@ -306,8 +289,7 @@ int ldso_undist_group_create(ldso_undistorter_t *const *u, int n, ldso_undist_gr
     g->device = u[0]->device;
     auto body = [&]() -> int {
         RUN(async_arena_create(g->arena));
-        for (hipEvent_t &e : g->ev) CHK(hipEventCreate(&e));
-        return LDSO_OK;
+        return g->clock.create();
     };
     RUN(finish_create(body(), g, out, ldso_undist_group_destroy));
     g->m.assign(u, u + n);
@@ -317,14 +299,7 @@ int ldso_undist_group_create(ldso_undistorter_t *const *u, int n, ldso_undist_gr
 
 int ldso_undist_group_profile(ldso_undist_group_t *g, int enable, float us_out[3]) {
     REQ(g, "ldso_undist_group_profile: null group");
-    if (g->profPending) {
-        CHK(hipSetDevice(g->device));
-        RUN(read_profile(g->ev, g->us));
-        g->profPending = false;
-    }
-    g->profile = enable != 0;
-    if (us_out) for (int i = 0; i < 3; i++) us_out[i] = g->us[i];
-    return LDSO_OK;
+    return g->clock.report(g->device, enable, us_out);
 }
 
 int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active, const void *const *raw, const int *bytes_per_pixel, const float *exposure, const float *factor,
@@ -366,15 +341,15 @@ int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active, cons
         J.w = A.w; J.h = A.h; J.wOrg = A.wOrg; J.hOrg = A.hOrg; J.mode = A.mode; J.bpp = bytes_per_pixel[i]; J.factor = A.factor; J.pad_ = 0;
     }
     const int wgs = group_prefix((int) nj, (int *) (h_stage + L.first), [&](int j) { return (int) (((size_t) hJ[j].w * hJ[j].h + 255) / 256); });          // 256 pixels per workgroup
-    const bool prof = g->profile;
-    if (prof) CHK(hipEventRecord(g->ev[0], st));
+    StageClock<3> &clk = g->clock.begin();
+    RUN(clk.mark(0, st));
     CHK(hipMemcpyAsync(d_stage, h_stage, L.total, hipMemcpyHostToDevice, st));
     RUN(async_arena_mark_uploaded(g->arena, st));
-    if (prof) CHK(hipEventRecord(g->ev[1], st));
+    RUN(clk.mark(1, st));
     hipLaunchKernelGGL(k_undist_group, dim3((unsigned) wgs), dim3(256), 0, st, (const UndistJob *) (d_stage + L.jobs), (const int *) (d_stage + L.first), (int) nj);
     CHK(hipGetLastError());
     RUN(async_arena_mark_done(g->arena, st));
-    if (prof) CHK(hipEventRecord(g->ev[2], st));
+    RUN(clk.mark(2, st));
     for (size_t j = 0; j < nj; j++) {
         ldso_undistorter *U = g->m[(size_t) members[j]];
         U->last = hJ[j].out;
@@ -385,7 +360,7 @@ int ldso_undist_group_frames(ldso_undist_group_t *g, const uint8_t *active, cons
         for (int i : members) src.push_back(pg->m[(size_t) i]->d_color);
         RUN(pyr_group_build(pg, members, src, st));
     }
-    if (prof) { CHK(hipEventRecord(g->ev[3], st)); g->profPending = true; }
+    RUN(clk.mark(3, st)); clk.defer();
     if (exposure_out) for (size_t j = 0; j < nj; j++) exposure_out[members[j]] = rule[j].exposureOut;
     return LDSO_OK;
 }

@@ -45,7 +45,7 @@ static void check_arena(const std::vector<Region> &R, size_t total, size_t downA
     free(blk);
 }
 
-constexpr size_t COMPACTJOB = 96;          // sizeof(CompactArgs): nine pointers and three ints with their padding (ba_host.h)
+constexpr size_t COMPACTJOB = 96;          // sizeof(CompactArgs): nine pointers and three ints with their padding (trace.h)
 
 // keep bytes per job: the record counts of the GPU test and friends, cycled; mode 1: nobody uploads keep bytes; mode 2: every other job
 static void layouts() {

@@ -1,5 +1,5 @@
 """The three routes of a window onto a handle (ldso_ba_set_window, ldso_ba_update_window, ldso_ba_batch_update_windows) share one description of the window's image
-(stage_image), one derivation of the dimensions (adopt_dims) and one way to grow a staging arena (grow_arena, csrc/ba_host.h).  What those shared pieces could break
+(stage_image), one derivation of the dimensions (adopt_dims) and one way to grow a staging arena (grow_arena, csrc/hip_host.h).  What those shared pieces could break
 and tests/test_resident_gpu.py / test_batch_update_window_gpu.py do not reach: a handle after a REFUSED upload, the handle's arena growing and being reused across
 windows of different sizes and kinds, the batch's arena growing between two key-frame steps of one batch.
 
